@@ -4,11 +4,16 @@ on synthetic LibriSpeech-shaped batches, 80-dim features resident in HBM, SpecAu
 bf16 MFMA compute, fused Adam, one RCCL all-reduce of the flat gradient arena per step.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
-`roofline` (dominant kernel family: algorithmic FLOPs / HIP-event time over the timed region)
-and `cpu_baseline` (the CPU oracle, oracle/model.py, timed on the host cores on a bounded sample).
+Prints ONE JSON line on rank 0: `metric`, `value` (training frames/s of the --steps timed optimizer steps), `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's configuration.  A plain run does only that: set-up, --warmup
+untimed steps, the timed steps, the line.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds the secondary measurements to the line: `roofline` (dominant kernel family: algorithmic FLOPs / HIP-event time
+over the timed region, whose launches are then timed inside the library) with the per-family tables of an instrumented
+warm-up step, the host-input, decode, log-mel, L4 and parity legs, `cpu_baseline` (the CPU oracle, oracle/model.py, timed
+on the host cores on a bounded sample) and, with N > 1 ranks, the data-parallel self-check `dp`.
 """
 import argparse
 import json
@@ -644,21 +649,48 @@ def parity_mode(dev, batches, steps=4, warmup=2):
     return out
 
 
+DUMP_SAMPLE = 1 << 22   # positions of each flat arena written by --dump-outputs (16 MB per file)
+
+
+def dump_outputs(path, losses, arena):
+    """what the timed path hands its caller after its last optimizer step, as float32 .npy files: the step's per-micro-batch
+    CTC losses (loss.npy), and the parameters it updated (params.npy) and the gradients it applied (grads.npy) -- both flat
+    arenas are larger than a dump should be, so each is sampled at the same fixed, seeded DUMP_SAMPLE positions (ascending)"""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, "loss.npy"), losses.detach().float().cpu().numpy())
+    n = arena.flat.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(DUMP_SAMPLE, n)].sort().values
+    idx = idx.to(arena.flat.device)
+    np.save(os.path.join(path, "params.npy"), arena.flat[idx].cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), arena.grad[idx].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed optimizer steps")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed optimizer steps before them")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--accum", type=int, default=5,
                     help="micro-batches per optimizer step (the reference trains with accum_grad: 5, asr/correct/exps/csj/asr.yaml:52, "
                          "asr/train_asr.py:106-128); a `step` of this benchmark is one optimizer step = this many micro-batches")
     ap.add_argument("--timer-stride", type=int, default=17,
-                    help="in the timed region every n-th launch of the dominant kernel family is timed with a HIP event pair")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--breakdown", action="store_true", help="print a per-entry-point GPU time table to stderr")
+                    help="(--full) in the timed region every n-th launch of the dominant kernel family is timed with a HIP event pair")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: family timers + roofline, host-input, decode, log-mel, L4 and parity "
+                         "legs, the CPU baseline, and with N > 1 ranks the data-parallel self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, updated parameters and gradients to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the CPU baseline")
+    ap.add_argument("--no-decode", action="store_true", help="(--full) without the host-input, decode, log-mel, L4 and parity legs")
+    ap.add_argument("--breakdown", action="store_true", help="(--full) print a per-entry-point GPU time table to stderr")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown instruments a warm-up step of the --full run: add --full")
+    full = args.full
 
     # the intra-op CPU pool must fit the container's CPU quota, or the kernel throttles the whole process -- the launching and
     # polling thread included -- for tens of milliseconds at a time (emoasr_amd/hostenv.py)
@@ -706,6 +738,7 @@ def main():
         eng.grad_hook = buckets.ready
 
     stacked = accum > 1 and dtype == torch.bfloat16 and eng.stacked_ok()
+    last_losses = [None]
 
     def step(group):
         """one optimizer step: `accum` micro-batches (SpecAugment on the device each), gradients of loss / accum summed -- through
@@ -720,11 +753,15 @@ def main():
             datas.append((xs, bt.xlens, bt.ys, bt.ylens))
         opt.zero_grad()
         if stacked:
-            loss = eng.ctc_train_stacked(datas, L2["blank_id"]).mean()
+            losses = eng.ctc_train_stacked(datas, L2["blank_id"])
+            loss = losses.mean()
         else:
+            losses = []
             for xs, xlens, ys, ylens in datas:
                 loss, _ = model(xs, xlens, ys, ylens, None, None)
                 (loss / accum).backward()
+                losses.append(loss.detach())
+        last_losses[0] = losses   # (what --dump-outputs writes of the last timed step)
         if buckets is not None:
             buckets.finish()   # the tail ranges went out during the backward sweep (train.GradBuckets)
         elif world > 1:
@@ -778,12 +815,13 @@ def main():
                 "attention_aux_side_stream": {"gflop": aux_fl / 1e9, "gbytes": aux_by / 1e9},
                 "optimizer": {"gflop": 0.0, "gbytes": nparams * 32.0 / 1e9}}
 
-    # warm-up; the LAST warm-up step is instrumented (every kernel family timed inside the library with HIP events on the launch
-    # stream): it gives the per-family table and picks the dominant family, which alone is then timed over the timed region
+    # warm-up; with --full the LAST warm-up step is instrumented (every kernel family timed inside the library with HIP events on
+    # the launch stream): it gives the per-family table and picks the dominant family, which alone is then timed over the timed
+    # region
     breakdown = None
     families, families_analytic = {}, {}
     for i in range(args.warmup):
-        if i == args.warmup - 1:
+        if full and i == args.warmup - 1:
             sync()
             emo_lib.set_option("timers", 1)
             for fam in FAMILIES:
@@ -803,23 +841,25 @@ def main():
             families_analytic = analytic_families(batches[i], sum(p.numel() for p in model.parameters()))
         else:
             step(batches[i])
-    # the roofline object is about ONE kernel family, chosen at run time: the one with the most device time in the instrumented
-    # step.  It is timed inside the library over exactly the timed region (only its own events are recorded there).
-    dominant = max(families, key=lambda k: families[k]["ms"]) if families else "gemm_nt_nn"
     sync()
     frames = sum(sum(b.xlens) for grp in batches[args.warmup:] for b in grp)
-    # an event pair per launch is not free (~10 us of lost overlap with the neighbouring kernels): families with hundreds of
-    # launches per step are SAMPLED, every 17th launch (17 is coprime with the per-step launch counts -- 208 = 16 x 13 for the
-    # GEMMs -- so over the timed steps every call site is sampled equally often)
-    stride = args.timer_stride if families.get(dominant, {}).get("calls", 0) > 48 else 1
-    emo_lib.set_option("timer_stride", stride)
-    emo_lib.set_option("timers", emo_lib.timer_mask(dominant))
-    emo_lib.timer_read_ex(dominant)
+    if full:
+        # the roofline object is about ONE kernel family, chosen at run time: the one with the most device time in the
+        # instrumented step.  It is timed inside the library over exactly the timed region (only its own events are recorded
+        # there).  An event pair per launch is not free (~10 us of lost overlap with the neighbouring kernels): families with
+        # hundreds of launches per step are SAMPLED, every 17th launch (17 is coprime with the per-step launch counts -- 208 =
+        # 16 x 13 for the GEMMs -- so over the timed steps every call site is sampled equally often)
+        dominant = max(families, key=lambda k: families[k]["ms"]) if families else "gemm_nt_nn"
+        stride = args.timer_stride if families.get(dominant, {}).get("calls", 0) > 48 else 1
+        emo_lib.set_option("timer_stride", stride)
+        emo_lib.set_option("timers", emo_lib.timer_mask(dominant))
+        emo_lib.timer_read_ex(dominant)
     stats0 = torch.cuda.memory_stats(dev) if os.environ.get("EMOASR_BENCH_TRACE") else None
     t0 = time.perf_counter()
     pairs = 0.0
     for bt in batches[args.warmup:]:
-        pairs += attn_pairs(bt)
+        if full:
+            pairs += attn_pairs(bt)
         loss = step(bt)
     sync()
     elapsed = time.perf_counter() - t0
@@ -831,9 +871,13 @@ def main():
     # a rate measured on broken arithmetic is no measurement: the last loss and every parameter must be finite after the timed steps
     if not (bool(torch.isfinite(loss.detach()).all()) and bool(torch.isfinite(eng.arena.flat).all())):
         raise SystemExit("bench.py: non-finite loss or parameters after the timed steps (loss %r)" % (float(loss.detach()),))
-    emo_lib.set_option("timers", 0)
-    emo_lib.set_option("timer_stride", 1)
-    dom = family_table(emo_lib, attn_work(pairs)).get(dominant, {"calls": 0, "ms": 0.0})
+    if full:
+        emo_lib.set_option("timers", 0)
+        emo_lib.set_option("timer_stride", 1)
+        dom = family_table(emo_lib, attn_work(pairs)).get(dominant, {"calls": 0, "ms": 0.0})
+    if args.dump_outputs and rank == 0:
+        ll = last_losses[0]
+        dump_outputs(args.dump_outputs, ll if torch.is_tensor(ll) else torch.stack(ll), eng.arena)
     tt = torch.tensor([elapsed, float(frames)], device=dev, dtype=torch.float64)
     if world > 1:
         tmax = tt.clone()
@@ -842,7 +886,7 @@ def main():
         elapsed, frames = tmax[0].item(), tt[1].item()
     value = frames / elapsed
     dp_info = None
-    if world > 1:
+    if full and world > 1:
         # the N > 1 line validates itself: what the collective backend reports, every rank's own frame count, and -- data-parallel
         # replicas apply the SAME reduced gradient with the same fused Adam -- the parameters must be bit-identical on all ranks
         # after the timed steps (a checksum over the raw bits of the flat f32 arena + its f64 sum, gathered from every rank)
@@ -896,7 +940,7 @@ def main():
         mean_T = frames / world / args.steps / accum / max(1, np.mean([len(b.xlens) for grp in batches[args.warmup:] for b in grp]))
         train_flops = 3.0 * fwd_flops_per_utt(int(mean_T)) / max(mean_T, 1) * frames
         res["model_mfma_frac"] = train_flops / elapsed / (MFMA_PEAK_TFLOPS[args.dtype] * 1e12 * world)
-        if dom["calls"]:
+        if full and dom["calls"]:
             # which roof bounds the family: its algorithmic intensity against the ridge of the two peaks
             ai = (dom.get("gflop", 0.0) / dom["gbytes"]) if dom.get("gbytes") else None
             bound = "hbm" if (ai is not None and ai < RIDGE_FLOP_PER_BYTE) or "tflops" not in dom else "mfma"
@@ -916,12 +960,14 @@ def main():
                                "flop_per_launch": 1e9 * dom.get("gflop", 0.0) / dom["calls"],
                                "bytes_per_launch": 1e9 * dom.get("gbytes", 0.0) / dom["calls"],
                                "share_of_step": stride * dom["ms"] * 1e-3 / elapsed}
-        else:
+        elif full:
             res["roofline"] = {"kernel": dominant, "bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": None, "traffic": None, "launches": 0}
-        res["families"] = {"step": "the last warm-up step, every family timed (HIP events inside the library)", **families}
-        res["families_analytic"] = {"what": "algorithmic GFLOP / GB per optimizer step of the families without in-library counters "
-                                            "(formulas: bench.py analytic_families; times: the kernel table)", **families_analytic}
+        if full:
+            res["families"] = {"step": "the last warm-up step, every family timed (HIP events inside the library)", **families}
+            res["families_analytic"] = {"what": "algorithmic GFLOP / GB per optimizer step of the families without in-library "
+                                                "counters (formulas: bench.py analytic_families; times: the kernel table)",
+                                        **families_analytic}
         if args.breakdown and breakdown:
             tot = sum(v["ms"] for v in breakdown.values())
             for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"]):
@@ -929,7 +975,7 @@ def main():
                 print(f"  {k:28s} calls {v['calls']:5d}  {v['ms']:9.3f} ms  {100 * v['ms'] / tot:5.1f}%  {tf:7.1f} TF/s",
                       file=sys.stderr)
             print(f"  total instrumented GPU time {tot:.2f} ms (one step, {accum} micro-batches)", file=sys.stderr)
-        if world == 1 and not args.no_decode:
+        if full and world == 1 and not args.no_decode:
             # the same optimizer steps with the features handed over as HOST buffers (pinned, as a DataLoader with pin_memory
             # yields them): the H2D copies are inside the timed region.  Never `value`; noted in DESIGN.md section 4.
             host_steps = batches[args.warmup:args.warmup + 4]
@@ -949,7 +995,7 @@ def main():
                                   "steps": len(host_steps) - 1,
                                   "MB_per_step": sum(px.numel() * 4 for px in pinned[1]) / 1e6,
                                   "note": "features start in pinned host memory, H2D inside the timed region (PCIe-inclusive rate)"}
-        if world == 1 and not args.no_decode:
+        if full and world == 1 and not args.no_decode:
             import tempfile
             with tempfile.TemporaryDirectory() as tmpdir:
                 res["decode_rtf"] = decode_rtf(model, dev, tmpdir)
@@ -992,7 +1038,7 @@ def main():
             torch.cuda.empty_cache()
             if args.dtype == "bf16":
                 res.update(parity_mode(dev, [b for grp in batches for b in grp]))
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(model)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -25,6 +25,20 @@ from asr.modeling.asr import ASR  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
+
+def save_npz(name, out):
+    """a fixture larger than tests/util.py SHARD_BYTES is written in parts <name>.part<k>.npz (save_golden_npz; golden_npz reads
+    either form back)"""
+    sys.path.insert(1, os.path.dirname(os.path.dirname(OUT)))
+    from tests.util import save_golden_npz
+    save_golden_npz(name, out, OUT)
+
+
+def load_npz(name):
+    sys.path.insert(1, os.path.dirname(os.path.dirname(OUT)))
+    from tests.util import golden_npz
+    return golden_npz(name)
+
 COMMON = dict(input_layer="conv2d", feat_dim=40, num_framestacks=1, enc_hidden_size=128,
               enc_num_attention_heads=2, enc_num_layers=2, enc_intermediate_size=256,
               dropout_enc_rate=0.0, dropout_attn_rate=0.0, dropout_dec_rate=0.0, vocab_size=40,
@@ -104,7 +118,7 @@ def run_ctc(name, cfg):
     out["eval/hyp_lens"] = np.array([len(h) for h in hyps])
     out["eval/hyps"] = np.array(sum(hyps, []), dtype=np.int64)
     out["eval/aligns"] = np.array(sum(aligns, []), dtype=np.int64)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    save_npz(name, out)
     print(name, "loss", float(loss), "eval loss", float(loss_eval), "hyp lens", [len(h) for h in hyps],
           "params", sum(p.numel() for p in model.parameters()))
 
@@ -175,7 +189,7 @@ def run_l3():
                 out[f"decode/{si}/{b}/hyps"] = np.array(sum(hyps, []), dtype=np.int64)
                 out[f"decode/{si}/{b}/scores"] = np.array(scores, dtype=np.float64)
                 print("decode", si, b, [len(h) for h in hyps], [round(s, 3) for s in scores])
-    np.savez_compressed(os.path.join(OUT, "l3_tiny.npz"), **out)
+    save_npz("l3_tiny", out)
     print("l3_tiny loss", float(loss.detach()), {k: float(v) for k, v in loss_dict.items()})
 
 
@@ -238,7 +252,7 @@ def run_l4():
     out["eval/hyps"] = np.array(sum(hyps, []), dtype=np.int64)
     out["eval/align_lens"] = np.array([len(a) for a in aligns])
     out["eval/aligns"] = np.array(sum(aligns, []), dtype=np.int64)
-    np.savez_compressed(os.path.join(OUT, "l4_tiny.npz"), **out)
+    save_npz("l4_tiny", out)
     print("l4_tiny loss", float(loss.detach()), {k: float(v) for k, v in loss_dict.items()}, "hyp lens",
           [len(h) for h in hyps], "align lens", [len(a) for a in aligns])
 
@@ -253,12 +267,12 @@ def run_ctc_beam():
     model and the l3_tiny LM; weights are read back from those fixtures (not stored twice) except the
     sharpened output layer (a random-init CTC head is near-uniform: every beam decision would be a tie)."""
     from lm.modeling.lm import LM
-    ctc = np.load(os.path.join(OUT, "l2_tiny.npz"))
-    l3 = np.load(os.path.join(OUT, "l3_tiny.npz"))
+    ctc = load_npz("l2_tiny")
+    l3 = load_npz("l3_tiny")
     model = ASR(make_params(CONFIGS["l2_tiny"]), phase="test")
-    model.load_state_dict({k[3:]: torch.from_numpy(ctc[k]) for k in ctc.files if k.startswith("sd/")})
+    model.load_state_dict({k[3:]: torch.from_numpy(ctc[k]) for k in ctc if k.startswith("sd/")})
     lm = LM(make_params(LM_CFG))
-    lm.load_state_dict({k[3:]: torch.from_numpy(l3[k]) for k in l3.files if k.startswith("lm/")})
+    lm.load_state_dict({k[3:]: torch.from_numpy(l3[k]) for k in l3 if k.startswith("lm/")})
     model.eval()
     lm.eval()
     torch.manual_seed(3)
@@ -363,7 +377,7 @@ def run_hostio():
     # ---- decode result rows (test_asr.py:96-117: strip <eos>, ids -> string, ids -> text through the vocab)
     # for the greedy hypotheses the reference produced on l2_tiny (tests/golden/l2_tiny.npz)
     from utils.converters import ints2str, strip_eos
-    g2 = np.load(os.path.join(OUT, "l2_tiny.npz"))
+    g2 = load_npz("l2_tiny")
     toks = ["<blank>", "<unk>", "<eos>"] + [("\u2581" if i % 3 == 0 else "") + "w%d" % i for i in range(3, 40)]
     with tempfile.TemporaryDirectory() as tmp:
         vp = os.path.join(tmp, "vocab.txt")
@@ -390,9 +404,9 @@ RNNT_BEAM_WIDTHS = [2, 4]
 def run_rnnt_beam():
     """RNN-T alignment-length synchronous beam search (rnn_transducer.py:242-325) on the fitted l4_tiny
     weights, one utterance at a time (the reference asserts batch size 1) -> rnntbeam_tiny.npz."""
-    g = np.load(os.path.join(OUT, "l4_tiny.npz"))
+    g = load_npz("l4_tiny")
     model = ASR(make_params(L4), phase="test")
-    model.load_state_dict({k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd/")})
+    model.load_state_dict({k[3:]: torch.from_numpy(g[k]) for k in g if k.startswith("sd/")})
     model.eval()
     xs, xlens = torch.from_numpy(g["xs"]), torch.from_numpy(g["xlens"])
     out = {}
@@ -507,8 +521,8 @@ def run_kd():
     out["loss/rnnt_align_grad"] = z.grad.numpy()
     out.update({"loss/rnnt_logits": z4.numpy(), "loss/rnnt_xlens": xl4.numpy(), "loss/rnnt_aligns": al4.numpy()})
     # ---- CTC decoder with kd_weight > 0 on the l2_tiny weights
-    g2 = np.load(os.path.join(OUT, "l2_tiny.npz"))
-    sd2 = {k[3:]: torch.from_numpy(g2[k]) for k in g2.files if k.startswith("sd/")}
+    g2 = load_npz("l2_tiny")
+    sd2 = {k[3:]: torch.from_numpy(g2[k]) for k in g2 if k.startswith("sd/")}
     xs, xlens, ys2, ylens2, ys_in, ys_out = make_batch(1, COMMON["feat_dim"], COMMON["vocab_size"])
     soft2 = _soft_labels(5, 4, ys2.shape[1], COMMON["vocab_size"])
     out["model/soft_ctc"] = soft2.numpy()
@@ -557,8 +571,8 @@ def run_kd():
         out[f"model/{name}/gnorms"] = np.array([float(v.norm()) for v in grads.values()])
         print("kd", name, float(loss), {k: float(v) for k, v in ld.items()})
     # ---- Transformer decoder with kd_weight > 0 (DistillLoss on ys_out, aux CTC without KD) on l3_tiny
-    g3 = np.load(os.path.join(OUT, "l3_tiny.npz"))
-    sd3 = {k[3:]: torch.from_numpy(g3[k]) for k in g3.files if k.startswith("sd/") and not k.startswith("sd/lm.")}
+    g3 = load_npz("l3_tiny")
+    sd3 = {k[3:]: torch.from_numpy(g3[k]) for k in g3 if k.startswith("sd/") and not k.startswith("sd/lm.")}
     sd3 = {k: v for k, v in sd3.items() if k.startswith("encoder.") or k.startswith("decoder.")}
     soft3 = _soft_labels(6, 4, ys_out.shape[1], COMMON["vocab_size"])
     out["model/soft_att"] = soft3.numpy()
@@ -584,8 +598,8 @@ def run_kd():
     sys.modules["warp_rnnt"].__version__ = "oracle-restatement"
     import asr.modeling.decoders.rnn_transducer as rt
     rt.warp_rnnt = sys.modules["warp_rnnt"]
-    g4 = np.load(os.path.join(OUT, "l4_tiny.npz"))
-    sd4 = {k[3:]: torch.from_numpy(g4[k]) for k in g4.files if k.startswith("sd/")}
+    g4 = load_npz("l4_tiny")
+    sd4 = {k[3:]: torch.from_numpy(g4[k]) for k in g4 if k.startswith("sd/")}
     soft4 = _soft_labels(8, 4, ys2.shape[1], COMMON["vocab_size"])
     out["model/soft_rnnt"] = soft4.numpy()
     for name, extra in (("rnnt_word", dict(kd_weight=0.3, kd_type="word", reduce_main_loss_kd=False)),
@@ -604,7 +618,7 @@ def run_kd():
             out[f"model/{name}/grad/{k}"] = grads[k].numpy()
         out[f"model/{name}/gnorms"] = np.array([float(v.norm()) for v in grads.values()])
         print("kd", name, float(loss), {k: float(v) for k, v in ld.items()})
-    np.savez_compressed(os.path.join(OUT, "kd_tiny.npz"), **out)
+    save_npz("kd_tiny", out)
 
 
 TRAIN_TRACE = dict(lr_schedule_type="noam", learning_rate=0.02, num_warmup_steps=4, accum_grad=2, clip_grad_norm=5.0,
@@ -618,8 +632,8 @@ def run_train_trace():
     (train_asr.py itself imports GitPython, which is absent: its train_step sequence is driven from here)."""
     import math
     from asr.optimizers import ScheduledOptimizer
-    g2 = np.load(os.path.join(OUT, "l2_tiny.npz"))
-    sd2 = {k[3:]: torch.from_numpy(g2[k]) for k in g2.files if k.startswith("sd/")}
+    g2 = load_npz("l2_tiny")
+    sd2 = {k[3:]: torch.from_numpy(g2[k]) for k in g2 if k.startswith("sd/")}
     params = make_params(dict(CONFIGS["l2_tiny"], **TRAIN_TRACE))
     model = ASR(params, phase="train")
     model.load_state_dict(sd2)

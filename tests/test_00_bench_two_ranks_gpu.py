@@ -4,8 +4,8 @@ needs one GPU per rank); everything above the collective backend -- per-rank bat
 bucketed asynchronous all-reduce released layer by layer, 1 / world in the fused Adam, the max-over-ranks timing, the JSON line
 -- is the code the 8-GPU run executes (asr/train_asr.py:67-71,236-243 replaced by data parallelism).
 
-The line must validate itself: `dp.nranks` = 2, both ranks' frame counts, and bit-identical parameters on both ranks after the
-steps.  This process makes no GPU call (it sorts first in the suite for that reason) and never re-executes itself."""
+With --full the line must validate itself: `dp.nranks` = 2, both ranks' frame counts, and bit-identical parameters on both ranks
+after the steps.  This process makes no GPU call (it sorts first in the suite for that reason) and never re-executes itself."""
 import json
 import os
 import socket
@@ -36,8 +36,8 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         out = open(str(tmp_path / f"rank{r}.out"), "w")
         err = open(str(tmp_path / f"rank{r}.err"), "w")
         files += [out, err]
-        procs.append(subprocess.Popen([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "2", "--no-decode",
-                                       "--no-cpu-baseline"], cwd=ROOT, env=env, stdout=out, stderr=err))
+        procs.append(subprocess.Popen([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "2", "--full",
+                                       "--no-decode", "--no-cpu-baseline"], cwd=ROOT, env=env, stdout=out, stderr=err))
     try:
         for p in procs:
             p.wait(timeout=840)

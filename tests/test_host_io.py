@@ -117,11 +117,11 @@ def test_checkpoint_average_and_resume(tmp_path):
 def test_parameter_order_matches_reference():
     """torch optimizers index parameters by position in model.parameters(); the golden fixtures keep the
     reference's state_dict key order, so equal parameter-name order means optim.ep{N} files map 1:1"""
-    from tests.util import CONFIGS
+    from tests.util import CONFIGS, golden_npz
     from emoasr_amd.modeling.asr import ASR
     for name in ("l1_tiny", "l2_tiny", "l3_tiny", "l4_tiny"):
-        z = np.load(os.path.join(os.path.dirname(__file__), "golden", name + ".npz"))
-        ref_keys = [k[3:] for k in z.files if k.startswith("sd/")]
+        z = golden_npz(name)
+        ref_keys = [k[3:] for k in z if k.startswith("sd/")]
         model = ASR(SimpleNamespace(**CONFIGS[name]), compute_dtype=torch.float32)
         assert list(model.state_dict().keys()) == ref_keys, name
         ref_params = [k for k in ref_keys if "running_" not in k and "num_batches_tracked" not in k]

@@ -34,9 +34,47 @@ DECODE_SETTINGS = [dict(beam_width=4, len_weight=0.0, lm_weight=0.0, decode_ctc_
                    dict(beam_width=3, len_weight=0.2, lm_weight=0.5, decode_ctc_weight=0.0)]
 
 
+SHARD_BYTES = 960 << 10   # a fixture whose arrays hold more is stored in parts: every committed file stays below 1 MiB
+
+
+def golden_npz(name):
+    """tests/golden/<name>.npz, or the parts <name>.part0.npz, <name>.part1.npz, ... that save_golden_npz wrote
+    -> {array name: numpy array} in the order the arrays were saved"""
+    paths = [os.path.join(GOLDEN, name + ".npz")]
+    if not os.path.exists(paths[0]):
+        paths = []
+        while os.path.exists(os.path.join(GOLDEN, f"{name}.part{len(paths)}.npz")):
+            paths.append(os.path.join(GOLDEN, f"{name}.part{len(paths)}.npz"))
+    assert paths, f"no golden fixture {name}"
+    out = {}
+    for p in paths:
+        with np.load(p) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
+def save_golden_npz(name, arrays, out_dir=GOLDEN):
+    """np.savez_compressed as <name>.npz, or, past SHARD_BYTES of array data, as consecutive runs of the arrays (their order kept)
+    in <name>.part0.npz, <name>.part1.npz, ... (golden_npz reads either form back)"""
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if cur and size + v.nbytes > SHARD_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    parts.append(cur)
+    if len(parts) == 1:
+        np.savez_compressed(os.path.join(out_dir, name + ".npz"), **parts[0])
+        return
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(out_dir, f"{name}.part{i}.npz"), **part)
+
+
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    g = {k: torch.from_numpy(z[k]) for k in z.files}
+    z = golden_npz(name)
+    g = {k: torch.from_numpy(v) for k, v in z.items()}
     sd = {k[3:]: v for k, v in g.items() if k.startswith("sd/")}
     return SimpleNamespace(**CONFIGS[name]), sd, g
 
@@ -114,8 +152,7 @@ DISTILL_CASES = {"distill": dict(soft_label_weight=0.3, lsm_prob=0.1),
 
 
 def load_kd_golden():
-    z = np.load(os.path.join(GOLDEN, "kd_tiny.npz"))
-    return {k: torch.from_numpy(z[k]) for k in z.files}
+    return {k: torch.from_numpy(v) for k, v in golden_npz("kd_tiny").items()}
 
 
 def synthetic_state(shapes, seed=1234):

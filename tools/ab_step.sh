@@ -16,7 +16,7 @@ run() {  # $1 = option string
   opts="$lo"
   ( [ -n "$envs" ] && export $envs
     [ -n "$libv" ] && export EMOASR_HIP_LIB=$GRAFT_REPO_ROOT/emoasr_amd/build/libemoasr_hip_$libv.so
-    EMOASR_OPTIONS="$opts" python3 bench.py --steps 10 --warmup 3 --no-decode --no-cpu-baseline 2>/dev/null |
+    EMOASR_OPTIONS="$opts" python3 bench.py --steps 10 --warmup 3 --full --no-decode --no-cpu-baseline 2>/dev/null |
     python3 -c "import json,sys;d=json.loads(sys.stdin.read());f=d['families'];print('%.3f ms/step  %.3f M/s  '%(d['ms_per_step'],d['value']/1e6)+' '.join('%s %.2f'%(k.replace('_kernel',''),v['ms']) for k,v in f.items() if isinstance(v,dict)))" )
 }
 for i in $(seq $N); do

@@ -1,7 +1,7 @@
 """ONE table for the final code -- kernel family -> launches, ms per step, algorithmic flop / bytes, achieved
 rate, fraction of the MFMA / HBM peak, bound, counter traffic over algorithmic bytes -- from the round's committed evidence:
     profiles/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace of `bench.py --steps 6 --warmup 2` (tools/kstats.py: us per step)
-    profiles/<tag>_bench.json         the bench line (families: in-library timers, algorithmic flop / bytes as the entry points were called)
+    profiles/<tag>_bench.json         the `bench.py --full` line (families: in-library timers, algorithmic flop / bytes as the entry points were called)
     profiles/<tag>_pmc.json           three separate rocprofv3 --pmc passes (tools/pmc_summary.py)
 usage: python tools/evidence_table.py r05"""
 import csv

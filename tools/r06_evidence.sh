@@ -4,7 +4,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=r06; O=gpurun_out/${TAG}_ev; mkdir -p $O
-CMD="python3 bench.py --steps 6 --warmup 2 --no-decode --no-cpu-baseline"
+CMD="python3 bench.py --steps 6 --warmup 2 --full --no-decode --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- $CMD > $O/kt.log 2>&1
 python3 tools/kstats.py $O/kt/kt_results.db 8 $O/${TAG}_kernel_stats.csv > $O/kstats.txt 2>&1
 python3 tools/kseq.py $O/kt/kt_results.db $O/${TAG}_kseq.txt > /dev/null 2>&1
@@ -40,5 +40,5 @@ fi
 MODES=fused python3 tools/attn_bench.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_attn_bench.txt
 BLAS=1 EPI=1 M=35145 python3 tools/gemm_bench.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_gemm_35k_rows.txt
 ( time python3 -m pytest tests -m gpu -q ) > $O/${TAG}_gputest.log 2>&1
-python3 bench.py > $O/${TAG}_bench.json 2> $O/bench.err
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
 tail -3 $O/${TAG}_gputest.log
