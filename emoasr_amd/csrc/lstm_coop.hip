@@ -482,3 +482,339 @@ extern "C" long emoasr_lstm_coop_status(void) {
   }
   return any;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The RNN encoder's bidirectional, length-aware recurrence (encoder_type "rnn", engine._RNNEncMixin) as ONE cooperative launch per
+// layer for BOTH directions: the barrier group is (direction, 64-row batch group), so 2 * ceil(B / 64) <= 8 groups of H / 16
+// workgroups run concurrently (B <= 256); the per-step chain (csrc/bilstm.hip) takes everything else.  Same scheme as the kernels
+// above (own 16 units per workgroup, W_hh rows in LDS, c in registers, one grid barrier per step), with the frame map of
+// csrc/bilstm.hip: step s of row b works on frame t = s (direction 0) or elens[b] - 1 - s (direction 1); a row with s >= elens[b] is
+// inactive and writes zeros to its frame s (padded outputs exact zeros, no negative t).  Outputs and layouts are the chain's
+// ([2][B][T][.], hprev included), so the weight-gradient products after the recurrence are shared.
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct BiFwdArgs {
+  int T, B, H, nb;            // nb = ceil(B / 64): batch groups per direction
+  const int* elens;           // [B], 1 .. T
+  const bf16* pre; long ldp;  // [B][T][8H] (row stride ldp): direction d's gates at columns 4H d ..
+  const bf16* w_hh[2];        // [4H][H] per direction
+  bf16* hseq; bf16* hprev;    // [2][B][T][H]
+  float* cseq;                // [2][B][T][H]
+  bf16* gact;                 // [2][B][T][4H]
+  unsigned* counter; int* err; unsigned base[L_MAXGRP];
+  int G;
+};
+
+__device__ __forceinline__ int bi_frame(int dir, int s, int len) { return s >= len ? s : (dir == 0 ? s : len - 1 - s); }
+
+// LDS: as lstm_seq_fwd_kernel
+__global__ __launch_bounds__(LT) void bilstm_seq_fwd_kernel(const BiFwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H = a.H, ld = H + 8, G = a.G, gi = blockIdx.x / G, g = blockIdx.x - gi * G;
+  const int dir = gi / a.nb, bg = gi - dir * a.nb;
+  const int m0 = bg * L_MAXB, Bs = a.B, B = min(L_MAXB, Bs - m0), Tn = a.T;
+  bf16* Ws = reinterpret_cast<bf16*>(smem);
+  bf16* hs = Ws + 64 * ld;
+  float* gat = reinterpret_cast<float*>(hs + 64 * ld);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  LBar bar;
+  lbar_init(bar, a.counter + 16 * gi, a.err, (unsigned)G, a.base[gi]);
+  const bf16* w_hh = a.w_hh[dir];
+  for (int i = tid; i < 64 * (H / 8); i += LT) {
+    const int r = i / (H / 8), c = (i - r * (H / 8)) * 8;
+    *reinterpret_cast<bf16x8*>(Ws + r * ld + c) = *reinterpret_cast<const bf16x8*>(w_hh + ((long)(r >> 4) * H + 16 * g + (r & 15)) * H + c);
+  }
+  for (int i = tid; i < 64 * ld / 2; i += LT) reinterpret_cast<unsigned*>(hs)[i] = 0u;   // rows >= B stay zero
+  __syncthreads();
+  float c_reg[2] = {0.f, 0.f};
+  int len_reg[2];
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {
+    const int m = (tid + LT * o) >> 4;
+    len_reg[o] = m < B ? min(a.elens[m0 + m], Tn) : 0;
+  }
+  const long dbase = (long)dir * Bs * Tn;   // (dir, b = 0, t = 0) row of the sequence buffers
+  const int gate = wave & 3, mt0 = 2 * (wave >> 2);
+  for (int s = 0; s < Tn; ++s) {
+    int t = tid;
+    EMO_FRESH(t);
+    float pv[2][4];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int p = t + LT * o, m = p >> 4, n = p & 15;
+      const bool act = m < B && s < len_reg[o];
+      const int fr = bi_frame(dir, s, len_reg[o]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        pv[o][q] = act ? (float)a.pre[((long)(m0 + m) * Tn + fr) * a.ldp + (long)dir * 4 * H + q * H + 16 * g + n] : 0.f;
+    }
+    if (s > 0) {
+      lgrid_sync(bar);   // h of step s - 1 complete on every workgroup of this group
+      // row m's previous h: frame s - 1 (forward) / len - s (reverse) -- rows inactive now get zeros
+      for (int i = t; i < B * (H / 8); i += LT) {
+        const int m = i / (H / 8), c = (i - m * (H / 8)) * 8;
+        const int len = min(a.elens[m0 + m], Tn);
+        bf16x8 v = bf16x8{};
+        if (s < len) {
+          const int tp = dir == 0 ? s - 1 : len - s;
+          v = *reinterpret_cast<const bf16x8*>(a.hseq + (dbase + (long)(m0 + m) * Tn + tp) * H + c);
+        }
+        *reinterpret_cast<bf16x8*>(hs + m * ld + c) = v;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int mt = mt0 + mi;
+        if (16 * mt < B) {
+          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+          const bf16* xrow = hs + (16 * mt + (lane & 15)) * ld + 8 * (lane >> 4);
+          const bf16* wrow = Ws + (16 * gate + (lane & 15)) * ld + 8 * (lane >> 4);
+          for (int ks = 0; ks < H / 32; ++ks)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(xrow + 32 * ks),
+                                                          *reinterpret_cast<const bf16x8*>(wrow + 32 * ks), acc, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gat[(gate * 64 + 16 * mt + 4 * (lane >> 4) + r) * 17 + (lane & 15)] = acc[r];
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int p = t + LT * o, m = p >> 4, n = p & 15;
+      if (m < B) {
+        const int len = len_reg[o], fr = bi_frame(dir, s, len);
+        const long row = dbase + (long)(m0 + m) * Tn + fr, col = 16 * g + n;
+        bf16* ga = a.gact + row * 4 * H + col;
+        if (s >= len) {
+          c_reg[o] = 0.f;
+          a.hseq[row * H + col] = (bf16)0.f; a.hprev[row * H + col] = (bf16)0.f; a.cseq[row * H + col] = 0.f;
+          ga[0] = ga[H] = ga[2 * H] = ga[3 * H] = (bf16)0.f;
+          continue;
+        }
+        float z[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) z[q] = pv[o][q] + (s > 0 ? rbf(gat[(q * 64 + m) * 17 + n]) : 0.f);   // the chain's product was bf16
+        const float ig = sigmoidf_(z[0]), fg = sigmoidf_(z[1]), gg = tanh_fast(z[2]), og = sigmoidf_(z[3]);
+        const float cn = fg * c_reg[o] + ig * gg;
+        c_reg[o] = cn;
+        a.cseq[row * H + col] = cn;
+        a.hseq[row * H + col] = (bf16)(og * tanh_fast(cn));
+        a.hprev[row * H + col] = s > 0 ? hs[m * ld + col] : (bf16)0.f;
+        ga[0] = (bf16)ig; ga[H] = (bf16)fg; ga[2 * H] = (bf16)gg; ga[3 * H] = (bf16)og;
+      }
+    }
+  }
+  if (lbar_failed(bar)) {   // (see lstm_seq_fwd_kernel)
+    const float qnan = __builtin_nanf("");
+    for (long i = threadIdx.x; i < (long)Tn * B * 16; i += LT) {
+      const long r = i >> 4, m = r / Tn, tt = r - m * Tn;
+      a.hseq[(dbase + (m0 + m) * Tn + tt) * H + 16 * g + (i & 15)] = (bf16)qnan;
+    }
+  }
+}
+
+struct BiBwdArgs {
+  int T, B, H, nb;
+  const int* elens;
+  const bf16* dy;        // [B][T][H]: gradient w.r.t. the summed output, both directions take it
+  const bf16* gact;      // [2][B][T][4H]
+  const float* cseq;     // [2][B][T][H]
+  const bf16* w_hh[2];
+  bf16* dg;              // [2][B][T][4H] out
+  float* part;           // [2 nb][2][G][64][H] f32 scratch
+  unsigned* counter; int* err; unsigned base[L_MAXGRP];
+  int G;
+};
+
+// LDS: as lstm_seq_bwd_kernel
+__global__ __launch_bounds__(LT) void bilstm_seq_bwd_kernel(const BiBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H = a.H, G = a.G, gi = blockIdx.x / G, g = blockIdx.x - gi * G;
+  const int dir = gi / a.nb, bg = gi - dir * a.nb;
+  const int m0 = bg * L_MAXB, Bs = a.B, B = min(L_MAXB, Bs - m0), Tn = a.T;
+  constexpr int LDK = 72;
+  bf16* WT = reinterpret_cast<bf16*>(smem);
+  bf16* dgl = WT + H * LDK;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  LBar bar;
+  lbar_init(bar, a.counter + 16 * gi, a.err, (unsigned)G, a.base[gi]);
+  const bf16* w_hh = a.w_hh[dir];
+  for (int i = tid; i < 64 * H; i += LT) {
+    const int k = i / H, n = i - k * H;
+    WT[n * LDK + k] = w_hh[((long)(k >> 4) * H + 16 * g + (k & 15)) * H + n];
+  }
+  for (int i = tid; i < 64 * LDK / 2; i += LT) reinterpret_cast<unsigned*>(dgl)[i] = 0u;   // rows >= B stay zero
+  __syncthreads();
+  float dc_reg[2] = {0.f, 0.f};
+  int len_reg[2];
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {
+    const int m = (tid + LT * o) >> 4;
+    len_reg[o] = m < B ? min(a.elens[m0 + m], Tn) : 0;
+  }
+  const long dbase = (long)dir * Bs * Tn;
+  const long slab = (long)64 * H;
+  float* const part = a.part + (long)gi * 2 * G * slab;
+  for (int s = Tn - 1; s >= 0; --s) {
+    int t = tid;
+    EMO_FRESH(t);
+    float dho[2], gv[2][4], cu[2], cp[2];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int p = t + LT * o, m = p >> 4, n = p & 15;
+      const int len = len_reg[o], fr = bi_frame(dir, s, len);
+      const long row = dbase + (long)(m0 + m) * Tn + fr, col = 16 * g + n;
+      const bool ok = m < B && s < len;
+      dho[o] = ok ? (float)a.dy[((long)(m0 + m) * Tn + fr) * H + col] : 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gv[o][q] = ok ? (float)a.gact[row * 4 * H + q * H + col] : 0.f;
+      cu[o] = ok ? a.cseq[row * H + col] : 0.f;
+      const bool first = dir == 0 ? fr == 0 : fr == len - 1;
+      cp[o] = (!ok || first) ? 0.f : a.cseq[(row + (dir == 0 ? -1 : 1)) * H + col];
+    }
+    const bool rec = s < Tn - 1;   // step s + 1 contributed to this step's dh
+    if (rec) lgrid_sync(bar);
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int p = t + LT * o, m = p >> 4, n = p & 15;
+      if (m < B) {
+        const int len = len_reg[o], fr = bi_frame(dir, s, len);
+        bf16* dst = a.dg + (dbase + (long)(m0 + m) * Tn + fr) * 4 * H + 16 * g + n;
+        if (s >= len) {   // inactive: zero gate gradients (frame s is padding), zero state, zero row for the partial product
+          dc_reg[o] = 0.f;
+          dst[0] = dst[H] = dst[2 * H] = dst[3 * H] = (bf16)0.f;
+          dgl[m * LDK + n] = dgl[m * LDK + 16 + n] = dgl[m * LDK + 32 + n] = dgl[m * LDK + 48 + n] = (bf16)0.f;
+          continue;
+        }
+        float dh = dho[o];
+        if (rec) {
+          const float* src = part + ((long)((s + 1) & 1) * G) * slab + (long)m * H + 16 * g + n;
+          float acc = 0.f;
+          for (int w0 = 0; w0 < G; w0 += 8) {
+            float pv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pv[e] = w0 + e < G ? src[(long)(w0 + e) * slab] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc += pv[e];
+          }
+          dh += acc;
+        }
+        const float ig = gv[o][0], fg = gv[o][1], gg = gv[o][2], og = gv[o][3];
+        const float tc = tanh_fast(cu[o]);
+        const float dct = dc_reg[o] + dh * og * (1.f - tc * tc);
+        const bf16 d0 = (bf16)(dct * gg * ig * (1.f - ig)), d1 = (bf16)(dct * cp[o] * fg * (1.f - fg));
+        const bf16 d2 = (bf16)(dct * ig * (1.f - gg * gg)), d3 = (bf16)(dh * tc * og * (1.f - og));
+        dc_reg[o] = dct * fg;
+        dst[0] = d0; dst[H] = d1; dst[2 * H] = d2; dst[3 * H] = d3;
+        dgl[m * LDK + n] = d0; dgl[m * LDK + 16 + n] = d1; dgl[m * LDK + 32 + n] = d2; dgl[m * LDK + 48 + n] = d3;
+      }
+    }
+    if (s > 0) {
+      __syncthreads();
+      float* dstp = part + ((long)(s & 1) * G + g) * slab;
+      const int MT = (B + 15) / 16;
+      for (int st = wave; st < H / 16; st += LW) {
+        bf16x8 wf[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) wf[ks] = *reinterpret_cast<const bf16x8*>(WT + (16 * st + (lane & 15)) * LDK + 32 * ks + 8 * (lane >> 4));
+        for (int mt = 0; mt < MT; ++mt) {
+          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(dgl + (16 * mt + (lane & 15)) * LDK + 32 * ks + 8 * (lane >> 4)),
+                                                          wf[ks], acc, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int m = 16 * mt + 4 * (lane >> 4) + r;
+            if (m < B) dstp[(long)m * H + 16 * st + (lane & 15)] = acc[r];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (lbar_failed(bar)) {
+    const float qnan = __builtin_nanf("");
+    for (long i = threadIdx.x; i < (long)Tn * B * 64; i += LT) {
+      const long r = i >> 6, m = r / Tn, tt = r - m * Tn; const int k = (int)(i & 63);
+      a.dg[(dbase + (m0 + m) * Tn + tt) * 4 * H + (long)(k >> 4) * H + 16 * g + (k & 15)] = (bf16)qnan;
+    }
+  }
+}
+
+long bilstm_cap_of(int which, int H) {
+  static size_t set_bytes[2] = {0, 0}, cap_bytes[2] = {0, 0};
+  static long cap[2] = {0, 0};
+  const void* k = which ? (const void*)bilstm_seq_bwd_kernel : (const void*)bilstm_seq_fwd_kernel;
+  const size_t smem = which ? lstm_bwd_smem(H) : lstm_fwd_smem(H);
+  if (smem > set_bytes[which]) {
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return 0;
+    set_bytes[which] = smem;
+  }
+  if (smem != cap_bytes[which]) { cap[which] = lstm_capacity(k, smem); cap_bytes[which] = smem; }
+  return cap[which];
+}
+int bilstm_groups(int B) { return 2 * lstm_groups(B); }
+
+}  // namespace
+
+// Can the cooperative bidirectional recurrence take this layer?  bf16, 2 * ceil(B / 64) <= 8 barrier groups (B <= 256), H a multiple
+// of 32 up to 512, and every workgroup of BOTH kernels resident at once by the occupancy query with one CU's worth of workgroups
+// to spare (never a grid at the edge of residency)
+extern "C" int emoasr_bilstm_seq_supported(int dtype, int B, int H) {
+  if (!(g_lstm_coop && dtype == EMO_BF16 && B >= 1 && bilstm_groups(B) <= L_MAXGRP && H % 32 == 0 && H >= 32 && H <= L_MAXH)) return 0;
+  const long need = (long)bilstm_groups(B) * (H / 16);
+  const long cf = bilstm_cap_of(0, H), cb = bilstm_cap_of(1, H);
+  const long spare_f = cf / std::max(1, lstm_cus()), spare_b = cb / std::max(1, lstm_cus());
+  return cf >= need + spare_f && cb >= need + spare_b;
+}
+
+// scratch of emoasr_bilstm_seq_bwd: [2 ceil(B / 64)][2][H / 16][64][H] f32
+extern "C" long emoasr_bilstm_seq_bwd_ws_bytes(int B, int H) { return (long)bilstm_groups(B) * 2 * (H / 16) * 64 * H * 4; }
+
+extern "C" int emoasr_bilstm_seq_fwd(int dtype, int B, int T_, int H, const int* elens, const void* pre, long ldp, const void* w_hh_f,
+                                     const void* w_hh_r, void* hseq, void* hprev, float* cseq, void* gact, void* stream) {
+  EMO_CHECK(emoasr_bilstm_seq_supported(dtype, B, H), "bilstm_seq_fwd: unsupported shape (dtype %d, B %d, H %d)", dtype, B, H);
+  EMO_CHECK(T_ >= 1 && ldp >= 8L * H && ldp % 8 == 0, "bilstm_seq_fwd: bad shape (T %d, ldp %ld)", T_, ldp);
+  EMO_CHECK(!lstm_capturing(stream), "bilstm_seq_fwd: the cooperative recurrence cannot be captured into a graph (host-tracked barrier values)");
+  BiFwdArgs a{};
+  a.T = T_; a.B = B; a.H = H; a.nb = lstm_groups(B); a.elens = elens; a.pre = (const bf16*)pre; a.ldp = ldp;
+  a.w_hh[0] = (const bf16*)w_hh_f; a.w_hh[1] = (const bf16*)w_hh_r;
+  a.hseq = (bf16*)hseq; a.hprev = (bf16*)hprev; a.cseq = cseq; a.gact = (bf16*)gact;
+  EmoScratch* sc = lstm_area(stream);
+  if (!sc) return 1;
+  a.counter = lstm_counter(sc, 0, &a.err);
+  const int ngrp = bilstm_groups(B);
+  a.G = H / 16;
+  lstm_base(sc, 0, a.G, T_, ngrp, a.base);
+  {
+    CoopOrder order(stream);
+    bilstm_seq_fwd_kernel<<<a.G * ngrp, LT, lstm_fwd_smem(H), (hipStream_t)stream>>>(a);
+  }
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_bilstm_seq_bwd(int dtype, int B, int T_, int H, const int* elens, const void* dy, const void* gact, const float* cseq,
+                                     const void* w_hh_f, const void* w_hh_r, void* dg, void* ws, long ws_bytes, void* stream) {
+  EMO_CHECK(emoasr_bilstm_seq_supported(dtype, B, H), "bilstm_seq_bwd: unsupported shape (dtype %d, B %d, H %d)", dtype, B, H);
+  EMO_CHECK(T_ >= 1, "bilstm_seq_bwd: bad T %d", T_);
+  EMO_CHECK(ws && ws_bytes >= emoasr_bilstm_seq_bwd_ws_bytes(B, H), "bilstm_seq_bwd: scratch too small");
+  EMO_CHECK(!lstm_capturing(stream), "bilstm_seq_bwd: the cooperative recurrence cannot be captured into a graph (host-tracked barrier values)");
+  BiBwdArgs a{};
+  a.T = T_; a.B = B; a.H = H; a.nb = lstm_groups(B); a.elens = elens; a.dy = (const bf16*)dy; a.gact = (const bf16*)gact; a.cseq = cseq;
+  a.w_hh[0] = (const bf16*)w_hh_f; a.w_hh[1] = (const bf16*)w_hh_r; a.dg = (bf16*)dg; a.part = (float*)ws;
+  EmoScratch* sc = lstm_area(stream);
+  if (!sc) return 1;
+  a.counter = lstm_counter(sc, 1, &a.err);
+  const int ngrp = bilstm_groups(B);
+  a.G = H / 16;
+  lstm_base(sc, 1, a.G, T_, ngrp, a.base);
+  {
+    CoopOrder order(stream);
+    bilstm_seq_bwd_kernel<<<a.G * ngrp, LT, lstm_bwd_smem(H), (hipStream_t)stream>>>(a);
+  }
+  EMO_LAUNCH_CHECK();
+  return 0;
+}

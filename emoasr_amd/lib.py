@@ -267,6 +267,11 @@ SIGNATURES = {
     "emoasr_lstm_cell_bwd": [I, I, I, P, L, P, P, P, P, P, P, P],
     "emoasr_lstm_seq_fwd": [I, I, I, I, P, P, P, P, P, P, P, P],
     "emoasr_lstm_seq_bwd": [I, I, I, I, P, P, P, P, P, P, P, L, P],
+    "emoasr_bilstm_cell_fwd": [I, I, I, I, I, P, P, L, P, P, P, P, P, P, P, P],
+    "emoasr_bilstm_cell_bwd": [I, I, I, I, I, P, P, P, P, P, P, P, P, P],
+    "emoasr_bilstm_out": [I, I, I, I, P, P, P, P, F, U64, P],
+    "emoasr_bilstm_seq_fwd": [I, I, I, I, P, P, L, P, P, P, P, P, P, P],
+    "emoasr_bilstm_seq_bwd": [I, I, I, I, P, P, P, P, P, P, P, P, L, P],
     "emoasr_joint_tanh": [I, I, I, I, I, P, P, P, P],
     "emoasr_joint_reduce": [I, I, I, I, I, P, P, P, P],
     "emoasr_rnnt_forward": [I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, P, P, P],

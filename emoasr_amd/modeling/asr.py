@@ -43,9 +43,13 @@ class ASR(nn.Module):
         self.decoder_type = params.decoder_type
         self.params = params
         self.compute_dtype = compute_dtype   # (property: "f32x3" -> torch.float32 + f32_split)
-        if self.encoder_type not in ("transformer", "conformer"):
+        if self.encoder_type == "rnn":
+            from .encoders.rnn import RNNEncoder
+            self.encoder = RNNEncoder(params)
+        elif self.encoder_type in ("transformer", "conformer"):
+            self.encoder = TransformerEncoder(params, is_conformer=(self.encoder_type == "conformer"))
+        else:
             raise NotImplementedError(f"emoasr_amd: encoder_type={self.encoder_type!r} is outside the HIP hot path")
-        self.encoder = TransformerEncoder(params, is_conformer=(self.encoder_type == "conformer"))
         if self.decoder_type == "ctc":
             self.decoder = CTCDecoder(params)
         elif self.decoder_type == "transformer":

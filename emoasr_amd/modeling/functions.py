@@ -63,6 +63,24 @@ def encoder_apply(enc, xs, xlens):
     return eouts, elens, inter
 
 
+def rnn_encoder_apply(enc, xs, xlens):
+    """RNNEncoder.forward on the engine (engine._RNNEncMixin) -> (eouts [B, max elens, H], elens, None); the output length and the
+    lengths are pad_packed_sequence's (input_layer "none": elens = xlens)"""
+    eng = _engine_of(enc)
+    xs = xs.to(torch.float32).contiguous()
+    host = _host_list(xlens)
+    if torch.is_grad_enabled():
+        eng.step_count += 1
+        eouts, elens_dev, _ = _EncoderFn.apply(eng, enc.training, xs, host, *eng.arena.params)
+    else:
+        eouts, _, elens_dev, _ = eng.forward(xs, host, enc.training, stash=False)
+    elens = torch.tensor(eng._rnn_elens(host), dtype=torch.int64)
+    if torch.is_tensor(xlens):
+        elens = elens.to(xlens.device)
+    eouts._emo_elens_dev = elens_dev
+    return eouts, elens, None
+
+
 class _EncoderStackedFn(torch.autograd.Function):
     """the encoder over several micro-batches in ONE stacked pass (engine.encoder_forward_stacked): outputs one eouts tensor per
     micro-batch (views of the stacked rows); the backward waits for all of their gradients and runs one stacked sweep"""

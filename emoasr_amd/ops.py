@@ -872,6 +872,79 @@ def lstm_cell_bwd(dh_out, dh_rec, dc, gates_act, c_prev, c, dgates_pre):
              _p(gates_act), _p(c_prev), _p(c), _p(dgates_pre), _stream())
 
 
+def bilstm_cell_fwd(s, elens, pre, rec, hstate, cstate, hseq, hprev, cseq, gact):
+    """step s of both directions of a length-aware bidirectional LSTM layer (csrc/bilstm.hip): pre [B,T,8H] (row stride allowed),
+    rec [2,B,4H] | None (s = 0), hstate [2,B,H] / cstate f32 [2,B,H] in-out, outputs hseq / hprev [2,B,T,H], cseq f32, gact [2,B,T,4H]"""
+    _, B, T, H = hseq.shape
+    assert pre.stride(-1) == 1 and pre.stride(0) == T * pre.stride(1) and elens.dtype == torch.int32
+    for t in (hstate, cstate, hseq, hprev, cseq, gact) + ((rec,) if rec is not None else ()):
+        assert t.is_contiguous()
+    for t in (pre, hstate, hprev, gact) + ((rec,) if rec is not None else ()):
+        assert t.dtype == hseq.dtype, (t.dtype, hseq.dtype)
+    assert cseq.dtype == cstate.dtype == torch.float32
+    lib.call("emoasr_bilstm_cell_fwd", dt(hseq), B, T, H, s, _p(elens), _p(pre), pre.stride(1), _p(rec), _p(hstate), _p(cstate),
+             _p(hseq), _p(hprev), _p(cseq), _p(gact), _stream())
+
+
+def bilstm_cell_bwd(s, elens, dy, dh_rec, dcstate, gact, cseq, dg, dgc):
+    """backward step s (T - 1 .. 0): dy [B,T,H], dh_rec [2,B,H] | None (s = T - 1), dcstate f32 [2,B,H] in-out ->
+    dg [2,B,T,4H] at this step's frames, dgc [2,B,4H]"""
+    _, B, T, H4 = dg.shape
+    for t in (dy, dcstate, gact, cseq, dg, dgc) + ((dh_rec,) if dh_rec is not None else ()):
+        assert t.is_contiguous()
+    for t in (dy, gact, dgc) + ((dh_rec,) if dh_rec is not None else ()):
+        assert t.dtype == dg.dtype, (t.dtype, dg.dtype)
+    assert cseq.dtype == dcstate.dtype == torch.float32 and elens.dtype == torch.int32
+    lib.call("emoasr_bilstm_cell_bwd", dt(dg), B, T, H4 // 4, s, _p(elens), _p(dy), _p(dh_rec), _p(dcstate), _p(gact), _p(cseq),
+             _p(dg), _p(dgc), _stream())
+
+
+def bilstm_out(elens, x0, x1=None, drop_p=0.0, seed=0):
+    """y [B,T,H] = dropout(x0 + x1) at t < elens[b], exact zeros beyond (x1 None: masked dropout of x0)"""
+    B, T, H = x0.shape
+    assert x0.is_contiguous() and (x1 is None or (x1.is_contiguous() and x1.shape == x0.shape and x1.dtype == x0.dtype))
+    assert elens.dtype == torch.int32
+    y = torch.empty_like(x0)
+    lib.call("emoasr_bilstm_out", dt(x0), B, T, H, _p(elens), _p(x0), _p(x1), _p(y), drop_p, seed, _stream())
+    return y
+
+
+def bilstm_seq_supported(x, B, H):
+    """does the cooperative bidirectional recurrence (csrc/lstm_coop.hip) take this layer?"""
+    return lib.size_query("emoasr_bilstm_seq_supported", dt(x), B, H) == 1
+
+
+def bilstm_seq_fwd(elens, pre, w_hh_f, w_hh_r, hseq, hprev, cseq, gact):
+    """the whole recurrence of both directions in one cooperative launch: same operands as bilstm_cell_fwd over all steps"""
+    _, B, T, H = hseq.shape
+    assert pre.stride(-1) == 1 and pre.stride(0) == T * pre.stride(1) and elens.dtype == torch.int32
+    for t in (pre, w_hh_f, w_hh_r, hprev, gact):
+        assert t.dtype == hseq.dtype, (t.dtype, hseq.dtype)
+    for t in (w_hh_f, w_hh_r, hseq, hprev, cseq, gact):
+        assert t.is_contiguous()
+    assert cseq.dtype == torch.float32
+    lib.call("emoasr_bilstm_seq_fwd", dt(hseq), B, T, H, _p(elens), _p(pre), pre.stride(1), _p(w_hh_f), _p(w_hh_r), _p(hseq),
+             _p(hprev), _p(cseq), _p(gact), _stream())
+
+
+def bilstm_seq_bwd(elens, dy, gact, cseq, w_hh_f, w_hh_r, dg):
+    """dy [B,T,H] -> dg [2,B,T,4H] over all steps in one cooperative launch"""
+    _, B, T, H4 = dg.shape
+    H = H4 // 4
+    for t in (dy, gact, w_hh_f, w_hh_r):
+        assert t.dtype == dg.dtype, (t.dtype, dg.dtype)
+    for t in (dy, gact, cseq, w_hh_f, w_hh_r, dg):
+        assert t.is_contiguous()
+    assert cseq.dtype == torch.float32 and elens.dtype == torch.int32
+    need = lib.size_query("emoasr_bilstm_seq_bwd_ws_bytes", B, H)
+    key = ("bilstm", dg.device, need)
+    ws = _lstm_ws.get(key)
+    if ws is None:
+        ws = _lstm_ws[key] = torch.empty(need, device=dg.device, dtype=torch.uint8)
+    lib.call("emoasr_bilstm_seq_bwd", dt(dg), B, T, H, _p(elens), _p(dy), _p(gact), _p(cseq), _p(w_hh_f), _p(w_hh_r), _p(dg), _p(ws),
+             need, _stream())
+
+
 def joint_tanh(e, g):
     """e [B,T,J], g [B,U,J] -> tanh(e[:, :, None] + g[:, None]) [B,T,U,J]"""
     B, T, J = e.shape

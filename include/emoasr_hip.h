@@ -491,6 +491,38 @@ long emoasr_lstm_seq_bwd_ws_bytes(int B, int H);
 int emoasr_lstm_seq_bwd(int dtype, int U, int B, int H, const void* dh_seq, const void* gact, const float* cseq, const float* c0,
                         const void* w_hh, void* dgp, void* ws, long ws_bytes, void* stream);
 long emoasr_lstm_coop_status(void);
+/* The RNN encoder's bidirectional LSTM layer with per-utterance lengths (csrc/bilstm.hip; engine._RNNEncMixin is the call site):
+ * nn.LSTM(bidirectional=True, batch_first=True) over pack_padded_sequence(x, elens) as a per-step chain.  Step s = 0 .. T - 1
+ * (T = max elens) of row b works on frame t = s (direction 0, forward) or t = elens[b] - 1 - s (direction 1, reverse); a row with
+ * s >= elens[b] is inactive and writes zeros to its frame s (so padded frames of every output are exact zeros, every frame is
+ * written once per direction, and no negative t is ever formed).  elens int32 [B] on the device, every entry in 1 .. T.
+ * emoasr_bilstm_cell_fwd: pre [B][T][8H] (row stride ldp >= 8H: x . W_ih^T + b_ih + b_hh, direction d's i | f | g | o at columns
+ *   4H d ..); rec [2][B][4H] = hstate . W_hh^T of the step (NULL at s = 0: zero state); hstate [2][B][H] in: h of step s - 1, out: of
+ *   step s; cstate f32 [2][B][H] likewise; outputs at (d, b, t): hseq [2][B][T][H], hprev [2][B][T][H] (the h the cell started from:
+ *   the W_hh gradient is hprev^T-paired with dg, row for row), cseq f32 [2][B][T][H], gact [2][B][T][4H] (activated gates).
+ * emoasr_bilstm_cell_bwd: steps s = T - 1 .. 0; dy [B][T][H] is the gradient w.r.t. the summed output (both directions take it);
+ *   dh_rec [2][B][H] = dgc of step s + 1 . W_hh (NULL at s = T - 1: dh_rec = dc = 0); dcstate f32 [2][B][H] in/out; outputs
+ *   dg [2][B][T][4H] (gradient w.r.t. the gate pre-activations, zero at padded frames) and dgc [2][B][4H] (this step's rows).
+ * emoasr_bilstm_out: y [B][T][H] = dropout(x0 + x1) at t < elens[b], 0 beyond (x1 may be NULL: the backward's masked dropout); the
+ *   keep mask is emoasr_scale_dropout's of the flat index. */
+int emoasr_bilstm_cell_fwd(int dtype, int B, int T, int H, int s, const int* elens, const void* pre, long ldp, const void* rec,
+                           void* hstate, float* cstate, void* hseq, void* hprev, float* cseq, void* gact, void* stream);
+int emoasr_bilstm_cell_bwd(int dtype, int B, int T, int H, int s, const int* elens, const void* dy, const void* dh_rec,
+                           float* dcstate, const void* gact, const float* cseq, void* dg, void* dgc, void* stream);
+int emoasr_bilstm_out(int dtype, int B, int T, int H, const int* elens, const void* x0, const void* x1, void* y, float drop_p,
+                      uint64_t seed, void* stream);
+/* The same layer's recurrence as ONE cooperative launch for both directions (csrc/lstm_coop.hip; the call site is
+ * engine._RNNEncMixin, option "lstm_coop"): barrier group = (direction, 64-row batch group), H / 16 workgroups each; same frame map,
+ * inputs and outputs as the chain above (pre, hseq, hprev, cseq, gact forward; dy, gact, cseq -> dg backward), w_hh_f / w_hh_r
+ * [4H][H].  emoasr_bilstm_seq_supported() -> 1 for bf16, B <= 256, H % 32 == 0, H <= 512 when every workgroup of both kernels
+ * is resident by the occupancy query with one CU's worth to spare; otherwise the chain runs.  ws: emoasr_bilstm_seq_bwd_ws_bytes(B, H)
+ * bytes of scratch.  A barrier that gave up is reported by emoasr_lstm_coop_status().  Not capturable into a graph. */
+int emoasr_bilstm_seq_supported(int dtype, int B, int H);
+long emoasr_bilstm_seq_bwd_ws_bytes(int B, int H);
+int emoasr_bilstm_seq_fwd(int dtype, int B, int T, int H, const int* elens, const void* pre, long ldp, const void* w_hh_f,
+                          const void* w_hh_r, void* hseq, void* hprev, float* cseq, void* gact, void* stream);
+int emoasr_bilstm_seq_bwd(int dtype, int B, int T, int H, const int* elens, const void* dy, const void* gact, const float* cseq,
+                          const void* w_hh_f, const void* w_hh_r, void* dg, void* ws, long ws_bytes, void* stream);
 /* joint network: h[b,t,u,:] = tanh(e[b,t,:] + g[b,u,:]) ; reductions of d(pre-tanh) back to de / dg */
 int emoasr_joint_tanh(int dtype, int B, int T, int U, int J, const void* e, const void* g, void* h, void* stream);
 int emoasr_joint_reduce(int dtype, int B, int T, int U, int J, const void* d, void* de, void* dg, void* stream);
