@@ -4,7 +4,8 @@
 // the 128x64-tile kernel of gemm.hip (LDS-read-bound at ~20 % of the MFMA peak).
 //
 //   big_nt : C[M,N] = epilogue(A[M,K] . B[N,K]^T), A plain / gathered through the conv geometry (forward) / gathered
-//            per output-parity class (data gradient; all four classes in one launch)
+//            per output-parity class (data gradient; all four classes in one launch; optionally with the first
+//            convolution's weight gradient as the epilogue instead of the stored data gradient)
 //
 // Structure (one workgroup per CU):
 //   * 512 threads = 8 waves as 2 (M) x 4 (N); block tile BM x 256 with BM = 256 / 192 / 128 chosen by the host so that
@@ -41,6 +42,11 @@ struct BigDgrad {  // data gradient, one entry per output-parity class (pt, pf)
   int tile0[5];            // first tile of each class
   int pt[4], pf[4], nI[4], nJ[4], ntap[4], M[4];
   int dh[4][4], dw[4][4], wtap[4][4];
+  // MODE 6 (the first convolution's weight gradient folded into the epilogue): its f32 input x [B, Tn, Fx] and the per-tile
+  // partial sums part[tile row][C][10] (nine taps, then the bias)
+  const float* x;
+  int Tn, Fx;
+  float* part;
 };
 // Transducer joint head without the [B,T,U,V] logits (rnn_transducer.py:101-115,147-156): epilogue modes of the plain product
 // z = h . W^T + bias over rows n = lattice cells (b, t, u).
@@ -114,9 +120,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // parameter: with the mode a run-time field every instantiation carried all four fully unrolled epilogues (20 k instructions
 // for TMW = 4; a wave runs the epilogue once per tile, straight through: SQ_WAIT_INST_ANY was 43 % of the wave cycles of the
 // head-gradient launch, i.e. instruction fetch).
+// MODE 6 (AMODE 2 only): the data gradient dy1 is never stored; the epilogue folds it into the first convolution's weight
+// gradient (see the FUSE epilogue below).
 template <int TMW, int AMODE, int NW, int MODE>
 __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
-  static_assert(AMODE == 0 || MODE == 0, "epilogue modes belong to the plain product");
+  static_assert(AMODE == 0 || MODE == 0 || (AMODE == 2 && MODE == 6 && NW == 8), "epilogue modes belong to the plain product");
+  constexpr bool FUSE = AMODE == 2 && MODE == 6;
   constexpr int BM = TMW * 32, BN = 256;
   constexpr int NJ = BN / (NW / 2) / 16;           // 16-column groups per wave: 4 (64 columns) or 8 (128)
   constexpr int WCOLS = NJ * 16;
@@ -135,8 +144,10 @@ __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
   // ---- which tile -----------------------------------------------------------------------------------
   int cls = 0, tm, tn;
   int M = g.M;
+  int trow = 0;   // AMODE 2: tile row over all classes
   if constexpr (AMODE == 2) {
     const int t = bid / g.tiles_n;
+    trow = t;
     tn = bid - t * g.tiles_n;
     while (cls + 1 < g.dg.ncls && t >= g.dg.tile0[cls + 1]) ++cls;
     tm = t - g.dg.tile0[cls];
@@ -331,8 +342,13 @@ __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[2 * pr + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[ks][j], aq[sidx & 1][i], acc[2 * pr + i][j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) {
+          // (FUSE keeps D itself: a lane holds 4 consecutive ROWS of one column -- the k layout of the folded product below)
+          if constexpr (FUSE)
+            acc[2 * pr + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[sidx & 1][i], bq[ks][j], acc[2 * pr + i][j], 0, 0, 0);
+          else
+            acc[2 * pr + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[ks][j], aq[sidx & 1][i], acc[2 * pr + i][j], 0, 0, 0);
+        }
         const int grp = ks * TMW + 2 * pr + i;
 #pragma unroll
         for (int p = 0; p < N_PCS; ++p)
@@ -350,6 +366,130 @@ __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();  // every wave is done with the staging buffers
   const int ncol0 = n0 + wc * WCOLS;
+  if constexpr (FUSE) {
+    // The first convolution's weight gradient (asr/modeling/encoders/conv.py:9-11), folded into this epilogue:
+    //   dw1[c][q] = sum_rows dy1[row][c] * X[row][q],  X[row] = the nine input samples under output position row (q = kh*3 + kw)
+    //   and a 1 for the bias (q = 9).
+    // dy1 = relu'(y1) * acc is exactly the bf16 value the plain epilogue stores; it never leaves the CU (the separate weight-gradient
+    // kernel read all of it back).  acc[i][j][r] = dy1[row i*16 + 4*(lane >> 4) + r][col j*16 + (lane & 15)] (D layout) IS the A
+    // operand of a 16x16x32 MFMA whose k runs over the 32 rows of two row groups, with X as the B operand in the same k order.  X
+    // enters as three bf16 pieces hi + mid + lo (exact for f32): every product is the one the f32 kernel formed.  Per wave
+    // TMW / 2 x NJ x 3 MFMAs; the two wave rows are summed through LDS and each tile writes its [256][10] partial sums.
+    static_assert(NW == 8 && BN * 2 * BM + 9 * (BM + 4) * 4 + (NW / 2) * NJ * 4 * 64 * 4 <= (3 * BM + 2 * BN) * 128,
+                  "fused epilogue: LDS layout");
+    const BigDgrad& dg = g.dg;
+    const int pt = dg.pt[cls], pf = dg.pf[cls], nI = dg.nI[cls], nJ = dg.nJ[cls], per_b = nI * nJ;
+    constexpr int MROW = BN * 2;   // bytes per staged mask row
+    constexpr int XLD = BM + 4;    // row stride of X^T (floats)
+    char* mk = smem;                                                        // [BM][BN] bf16
+    float* xt = reinterpret_cast<float*>(smem + BM * MROW);                 // [9][XLD]
+    float* red = reinterpret_cast<float*>(smem + BM * MROW + 9 * XLD * 4);  // [NW / 2][NJ][4][64]
+    // (1) the ReLU-mask tile y1[row][n0 .. n0 + 255] by LDS-DMA: one wave instruction lands two 512-byte rows, lane-linear; chunk
+    // ch of row r holds source chunk ch ^ 2 (r & 3), so that the transposed reads of four consecutive rows hit distinct banks
+    {
+      const __amdgpu_buffer_rsrc_t rsM = make_rsrc(g.dmask);
+      constexpr int M_PCS = BM / (2 * NW);
+      const unsigned ch = lane & 31;
+      int row = 2 * wave + (lane >> 5);
+      int grow = m0 + row;
+      int b = grow / per_b, ii = grow - b * per_b;
+      int jj = ii % nJ;
+      ii /= nJ;
+#pragma unroll
+      for (int p = 0; p < M_PCS; ++p) {
+        unsigned voff = EMO_OOB;
+        if (grow < M)
+          voff = (unsigned)(((((long)b * dg.T1 + 2 * ii + pt) * dg.F1 + 2 * jj + pf) * dg.C + n0) * 2) +
+                 ((ch ^ ((unsigned)(row & 3) << 1)) << 4);
+        dma16(rsM, smem + (p * NW + wave) * 1024, voff, 0);
+        row += 2 * NW; grow += 2 * NW; jj += 2 * NW;   // (the next piece: 2 NW rows on)
+        while (jj >= nJ) { jj -= nJ; ++ii; }
+        while (ii >= nI) { ii -= nI; ++b; }
+      }
+    }
+    // (2) X^T of the tile's rows (zeros past the class's last row)
+    if (tid < BM) {
+      const int grow = m0 + tid;
+      float xv[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) xv[q] = 0.f;
+      if (grow < M) {
+        const int b = grow / per_b, r = grow - b * per_b;
+        const int ii = r / nJ, jj = r - ii * nJ;
+        const float* xp = dg.x + ((long)b * dg.Tn + 4 * ii + 2 * pt) * dg.Fx + 4 * jj + 2 * pf;   // x[b, 2 t1, 2 f1]
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) xv[kh * 3 + kw] = xp[kh * dg.Fx + kw];
+      }
+#pragma unroll
+      for (int q = 0; q < 9; ++q) xt[q * XLD + tid] = xv[q];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // (3) the folded product
+    const int g4 = lane >> 4, l15 = lane & 15, mw = wr * (BM / 2);
+    f32x4 gacc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) gacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TMW; i += 2) {
+      bf16x8 xh, xm, xl;   // k slot 4 h + s <-> row (i + h) * 16 + 4 * g4 + s, column q = l15
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (l15 < 9) xv = *reinterpret_cast<const f32x4*>(xt + l15 * XLD + mw + (i + h) * 16 + 4 * g4);
+        else if (l15 == 9) xv = f32x4{1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float v = xv[s];
+          const bf16 hi = (bf16)v;
+          const float r1 = v - (float)hi;
+          const bf16 mid = (bf16)r1;
+          xh[4 * h + s] = hi; xm[4 * h + s] = mid; xl[4 * h + s] = (bf16)(r1 - (float)mid);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        bf16x8 dv;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          // ds_read_b64_tr_b16: the 16 lanes of a group address rows mrow0 + (l15 >> 2), columns 4 (lane & 3) .. + 3; lane l15
+          // receives column l15 of the four rows -- the mask of acc[i + h][j][0 .. 3]
+          const int mrow = mw + (i + h) * 16 + 4 * g4 + (l15 >> 2);
+          const int col = wc * WCOLS + j * 16 + 4 * (lane & 3);
+          const unsigned addr = (unsigned)(mrow * MROW) + ((((unsigned)(col >> 3)) ^ ((unsigned)(mrow & 3) << 1)) << 4) + (unsigned)(col & 7) * 2;
+          const s16x4 mv = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(mk + addr));
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            const float y = __builtin_bit_cast(float, (unsigned)(unsigned short)mv[s] << 16);
+            dv[4 * h + s] = y > 0.f ? (bf16)acc[i + h][j][s] : (bf16)0.f;
+          }
+        }
+        gacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dv, xh, gacc[j], 0, 0, 0);
+        gacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dv, xm, gacc[j], 0, 0, 0);
+        gacc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dv, xl, gacc[j], 0, 0, 0);
+      }
+    }
+    // (4) gacc[j][r] = partial dw1[c = ncol0 + j*16 + 4*g4 + r][q = l15] of this wave's rows: the two wave rows summed, then one
+    // [C][10] slice per tile row
+    if (wr == 1) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[((wc * NJ + j) * 4 + r) * 64 + lane] = gacc[j][r];
+    }
+    __syncthreads();
+    if (wr == 0 && l15 < 10) {
+      float* pp = dg.part + (long)trow * dg.C * 10;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pp[(long)(ncol0 + j * 16 + 4 * g4 + r) * 10 + l15] = gacc[j][r] + red[((wc * NJ + j) * 4 + r) * 64 + lane];
+    }
+    return;
+  }
   if constexpr (AMODE == 0) {
     // general epilogue, in the order and precision of gemm_nt_kernel's: alpha, bias, pre_out, activation, dropout (mask
     // indexed by row * N + col).  16-row slabs go through wave-private LDS as f32 (row stride 68 floats), then every lane
@@ -855,16 +995,11 @@ int emo_conv2_fwd_big(int B, int T1, int F1, int C, const void* y1, const void* 
 // dy1[b,t1,f1,c] = relu'(y1[b,t1,f1,c]) * sum_{kh,kw,n} dy2[b,(t1-kh)/2,(f1-kw)/2,n] * W[n,c,kh,kw]: the four output-parity
 // classes (DgradGeom in gemm.hip) as ONE launch, heaviest class first.  wt: the weight as [c][kh][kw][n] (k-contiguous for
 // every tap), i.e. conv.2.weight.permute(1, 2, 3, 0).
-extern "C" int emoasr_conv2_dgrad_kc(int dtype, int B, int T1, int F1, int C, const void* dy2, const void* wt,
-                                     const void* y1, void* dy1, void* stream) {
-  EMO_CHECK(dtype == EMO_BF16, "conv2_dgrad_kc: bf16 only");
-  EMO_CHECK(T1 >= 3 && F1 >= 3, "conv2_dgrad_kc: input too small (T1=%d F1=%d)", T1, F1);
-  EMO_CHECK(C % 256 == 0, "conv2_dgrad_kc: C must be a multiple of 256");
+// the four parity classes of the data gradient in a.dg, tiles in a.tiles_m / a.tiles_n; returns the tile height
+static int dgrad_plan(int B, int T1, int F1, int C, BigArgs& a) {
   const int T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
-  EMO_CHECK((long)B * T1 * F1 * C * 2 < (1L << 32), "conv2_dgrad_kc: tensors must be < 4 GiB");
-  BigArgs a{};
   a.korder = g_big_korder;
-  a.N = C; a.K = 4 * C; a.A = dy2; a.B = wt; a.ldb = 9 * C; a.C = dy1; a.ldc = C; a.dmask = y1;
+  a.N = C; a.K = 4 * C; a.ldb = 9 * C; a.ldc = C;
   BigDgrad& g = a.dg;
   g.T1 = T1; g.F1 = F1; g.T2 = T2; g.F2 = F2; g.C = C;
   long rows = 0;
@@ -888,5 +1023,74 @@ extern "C" int emoasr_conv2_dgrad_kc(int dtype, int B, int T1, int F1, int C, co
   for (int c = 0; c < g.ncls; ++c) { g.tile0[c] = t0; t0 += cdiv(g.M[c], bm); }
   g.tile0[g.ncls] = t0;
   a.tiles_m = t0; a.tiles_n = C / 256;
-  return launch_big_bm<2>(a, bm, t0 * a.tiles_n, (hipStream_t)stream);
+  return bm;
+}
+
+extern "C" int emoasr_conv2_dgrad_kc(int dtype, int B, int T1, int F1, int C, const void* dy2, const void* wt,
+                                     const void* y1, void* dy1, void* stream) {
+  EMO_CHECK(dtype == EMO_BF16, "conv2_dgrad_kc: bf16 only");
+  EMO_CHECK(T1 >= 3 && F1 >= 3, "conv2_dgrad_kc: input too small (T1=%d F1=%d)", T1, F1);
+  EMO_CHECK(C % 256 == 0, "conv2_dgrad_kc: C must be a multiple of 256");
+  EMO_CHECK((long)B * T1 * F1 * C * 2 < (1L << 32), "conv2_dgrad_kc: tensors must be < 4 GiB");
+  BigArgs a{};
+  const int bm = dgrad_plan(B, T1, F1, C, a);
+  a.A = dy2; a.B = wt; a.C = dy1; a.dmask = y1;
+  return launch_big_bm<2>(a, bm, a.tiles_m * a.tiles_n, (hipStream_t)stream);
+}
+
+int emo_conv1_wgrad_reduce(int nblk, int C, const float* part, float* dw, float* db, int accumulate, hipStream_t s);
+
+// part[nblk][n] -> out[s][n] = sum of the s-th of gridDim.y row ranges (the first fold of the per-tile partials: 2 000+ tile rows)
+__global__ __launch_bounds__(256) void w1_fold_kernel(int nblk, int n, const float* __restrict__ part, float* __restrict__ out) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= n) return;
+  const int per = (nblk + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int k0 = blockIdx.y * per, k1 = min(nblk, k0 + per);
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = k0; k < k1; ++k) acc += part[(long)k * n + col];
+  out[(long)blockIdx.y * n + col] = acc;
+}
+constexpr int W1_SLICES = 64;
+
+extern "C" long emoasr_conv2_dgrad_w1_scratch_floats(int B, int T, int F, int C) {
+  const int T1 = (T - 3) / 2 + 1, F1 = (F - 3) / 2 + 1;
+  if (B <= 0 || T1 < 3 || F1 < 3 || C <= 0) return 1;
+  BigArgs a{};
+  dgrad_plan(B, T1, F1, C, a);
+  return ((long)a.tiles_m + W1_SLICES) * C * 10;
+}
+
+// emoasr_conv2_dgrad_kc with the first convolution's weight gradient folded into its epilogue (see big_nt_kernel, FUSE): dy1 is
+// never stored.  x f32 [B, T, F] (conv1's input), dw1 [C][9], db1 [C] (+)= as emoasr_conv1_wgrad on the dy1 that
+// emoasr_conv2_dgrad_kc would have written; scratch: emoasr_conv2_dgrad_w1_scratch_floats(B, T, F, C) floats.
+extern "C" int emoasr_conv2_dgrad_w1(int dtype, int B, int T, int F, int C, const void* dy2, const void* wt, const void* y1,
+                                     const float* x, float* dw1, float* db1, int accumulate, float* scratch, void* stream) {
+  EMO_CHECK(dtype == EMO_BF16, "conv2_dgrad_w1: bf16 only");
+  const int T1 = (T - 3) / 2 + 1, F1 = (F - 3) / 2 + 1;
+  EMO_CHECK(T >= 3 && F >= 3 && T1 >= 3 && F1 >= 3, "conv2_dgrad_w1: input too small (T=%d F=%d)", T, F);
+  EMO_CHECK(C % 256 == 0, "conv2_dgrad_w1: C must be a multiple of 256");
+  hipStream_t s = (hipStream_t)stream;
+  if (B == 0) {
+    if (!accumulate) {
+      hipMemsetAsync(dw1, 0, sizeof(float) * C * 9, s);
+      hipMemsetAsync(db1, 0, sizeof(float) * C, s);
+    }
+    return 0;
+  }
+  EMO_CHECK((long)B * T1 * F1 * C * 2 < (1L << 32), "conv2_dgrad_w1: tensors must be < 4 GiB");
+  EMO_CHECK(scratch, "conv2_dgrad_w1: scratch of emoasr_conv2_dgrad_w1_scratch_floats(B, T, F, C) floats required");
+  BigArgs a{};
+  const int bm = dgrad_plan(B, T1, F1, C, a);
+  a.A = dy2; a.B = wt; a.C = nullptr; a.dmask = y1;
+  a.dg.x = x; a.dg.Tn = T; a.dg.Fx = F; a.dg.part = scratch;
+  int rc;
+  if (bm == 256) rc = launch_big_t<8, 2, 8, 6>(a, a.tiles_m * a.tiles_n, s);
+  else if (bm == 192) rc = launch_big_t<6, 2, 8, 6>(a, a.tiles_m * a.tiles_n, s);
+  else rc = launch_big_t<4, 2, 8, 6>(a, a.tiles_m * a.tiles_n, s);
+  if (rc) return rc;
+  float* part2 = scratch + (long)a.tiles_m * C * 10;
+  w1_fold_kernel<<<dim3(cdiv(C * 10, 256), W1_SLICES), 256, 0, s>>>(a.tiles_m, C * 10, scratch, part2);
+  EMO_LAUNCH_CHECK();
+  return emo_conv1_wgrad_reduce(W1_SLICES, C, part2, dw1, db1, accumulate, s);
 }

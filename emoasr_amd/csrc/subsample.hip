@@ -253,6 +253,13 @@ inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 16384 ? 
 
 void emo_conv1_set_pair(int v) { g_conv1_pair = v ? 1 : 0; }
 
+// the fold of [nblk][C][10] partial sums into dw1 / db1 (also behind emoasr_conv2_dgrad_w1, gemm_big.hip)
+int emo_conv1_wgrad_reduce(int nblk, int C, const float* part, float* dw, float* db, int accumulate, hipStream_t s) {
+  conv1_wgrad_reduce_kernel<<<cdiv(C * 10, 64), 256, 0, s>>>(nblk, C, part, dw, db, accumulate);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int emoasr_conv1_fwd(int dtype, int B, int Tn, int F, int C, const float* x, const float* w1,
                                 const float* b1, void* y1, void* stream) {
   EMO_CHECK(Tn >= 3 && F >= 3, "conv1: input too small (T=%d F=%d)", Tn, F);

@@ -261,6 +261,8 @@ class CTCEngine(_DecoderMixinPlaceholder):
         self.inter_layer = int(cfg.inter_ctc_layer_id) if inter_on else 0
         self.eouts_inter = None
         self._implicit_dgrad = os.environ.get("EMOASR_CONV2_DGRAD", "implicit") == "implicit"
+        # the first convolution's weight gradient folded into the large-tile data gradient (emoasr_conv2_dgrad_w1; A/B switch)
+        self._conv1_fold = os.environ.get("EMOASR_CONV1_FOLD", "1") != "0"
         self._conv_fused = os.environ.get("EMOASR_CONV_FUSED", "1") != "0"  # csrc/convfused.hip (bit-identical; A/B switch)
         if not self._conv_fused:
             from . import lib as _lib
@@ -739,11 +741,15 @@ class CTCEngine(_DecoderMixinPlaceholder):
             wt = ops.strided_copy(A.p(pre + "conv.2.weight").permute(1, 2, 3, 0), out_dtype=dt).view(C, 9 * C)
         else:
             w2r = ops.strided_copy(A.p(pre + "conv.2.weight").permute(0, 2, 3, 1), out_dtype=dt).view(C, 9 * C)
+        dw1, db1 = A.g(pre + "conv.0.weight").view(C, 9), A.g(pre + "conv.0.bias")
         for k, xs in enumerate(st.xs_list):
             dy2_k = dy2[rows[k]:rows[k + 1]].view(-1, C)
             ops.conv2_wgrad(dy2_k, st.y1s[k], dw2, dbias=A.g(pre + "conv.2.bias"), accumulate=True)
+            if kc and self._conv1_fold:   # conv1's weight gradient in the data gradient's epilogue: dy1 never reaches HBM
+                ops.conv2_dgrad_w1(dy2_k, wt, st.y1s[k], xs, dw1, db1, accumulate=True)
+                continue
             dy1 = ops.conv2_dgrad_kc(dy2_k, wt, st.y1s[k]) if kc else ops.conv2_dgrad(dy2_k, w2r, st.y1s[k])
-            ops.conv1_wgrad(xs, dy1, A.g(pre + "conv.0.weight").view(C, 9), A.g(pre + "conv.0.bias"), accumulate=True)
+            ops.conv1_wgrad(xs, dy1, dw1, db1, accumulate=True)
         ops.strided_copy(dw2.view(C, 3, 3, C).permute(0, 3, 1, 2), out=A.g(pre + "conv.2.weight"), accumulate=True)
 
     def encoder_forward_stacked(self, xs_list, xlens_list):
@@ -1141,6 +1147,10 @@ class CTCEngine(_DecoderMixinPlaceholder):
         if self._implicit_dgrad and dy2.dtype == torch.bfloat16 and C % 256 == 0 and self._conv_big:
             # all four parity classes in one launch of the large-tile kernel; it wants the weight as [c, kh, kw, n]
             wt = ops.strided_copy(A.p(pre + "conv.2.weight").permute(1, 2, 3, 0), out_dtype=dy2.dtype).view(C, 9 * C)
+            if self._conv1_fold:   # conv1's weight gradient in the data gradient's epilogue: dy1 never reaches HBM
+                ops.conv2_dgrad_w1(dy2, wt, st.y1, st.xs, A.g(pre + "conv.0.weight").view(C, 9), A.g(pre + "conv.0.bias"),
+                                   accumulate=True)
+                return
             dy1 = ops.conv2_dgrad_kc(dy2, wt, st.y1)
         elif self._implicit_dgrad:
             dy1 = ops.conv2_dgrad(dy2, st.w2r, st.y1)  # four parity-class implicit GEMMs, no im2col buffer

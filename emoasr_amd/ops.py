@@ -240,6 +240,19 @@ def conv2_dgrad_kc(dy2, wt, y1):
     return dy1
 
 
+def conv2_dgrad_w1(dy2, wt, y1, x, dw1, db1, accumulate=False):
+    """conv2_dgrad_kc with conv1_wgrad(x, dy1, dw1, db1) folded into its epilogue: dy1 is never materialised.
+    x [B,T,F] f32 (conv1's input), dw1 [C,9], db1 [C] f32"""
+    B, T1, F1, C = y1.shape
+    Bx, T, Fd = x.shape
+    assert Bx == B and (T - 3) // 2 + 1 == T1 and (Fd - 3) // 2 + 1 == F1, (x.shape, y1.shape)
+    scratch = torch.empty(lib.size_query("emoasr_conv2_dgrad_w1_scratch_floats", B, T, Fd, C), device=x.device,
+                          dtype=torch.float32)
+    lib.call("emoasr_conv2_dgrad_w1", dt(y1), B, T, Fd, C, _p(_chk(dy2, y1.dtype)), _p(_chk(wt, y1.dtype)), _p(y1),
+             _p(_chk(x, torch.float32)), _p(_chk(dw1, torch.float32)), _p(_chk(db1, torch.float32)), int(accumulate),
+             _p(scratch), _stream())
+
+
 def gemm_nt_big(a, b, out=None, bias=None, relu=False):
     """out[M,N] = relu?(a[M,K] @ b[N,K]^T + bias) on the large-tile kernel (bf16, N % 8 == 0, K % 64 == 0)"""
     M, K, lda = _rows(_chk(a, torch.bfloat16))

@@ -155,6 +155,12 @@ int emoasr_conv2_col2im(int dtype, int B, int T1, int F1, int C, const void* dco
  * output channels n is contiguous. */
 int emoasr_conv2_dgrad_kc(int dtype, int B, int T1, int F1, int C, const void* dy2, const void* wt, const void* y1,
                           void* dy1, void* stream);
+/* emoasr_conv2_dgrad_kc with the first convolution's weight gradient in its epilogue: dy1 is never stored.  B, T, F: the shape
+ * of conv1's input x f32 [B,T,F]; dw1[C,9], db1[C] (+)= what emoasr_conv1_wgrad computes from the dy1 above.
+ * scratch: emoasr_conv2_dgrad_w1_scratch_floats(B, T, F, C) floats (per-tile partial sums). */
+int emoasr_conv2_dgrad_w1(int dtype, int B, int T, int F, int C, const void* dy2, const void* wt, const void* y1,
+                          const float* x, float* dw1, float* db1, int accumulate, float* scratch, void* stream);
+long emoasr_conv2_dgrad_w1_scratch_floats(int B, int T, int F, int C);
 /* Large-tile NT product for long, wide shapes (bf16; N % 8 == 0, K % 64 == 0): C = relu?(A . B^T + bias).  The kernel
  * behind emoasr_conv2_fwd / _dgrad_kc on a plain row-major A (nn.Linear with >= 256 outputs over >= 10^5 rows). */
 int emoasr_gemm_nt_big(int dtype, int M, int N, int K, const void* A, long lda, const void* B, long ldb, void* C, long ldc,
