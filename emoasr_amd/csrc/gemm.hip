@@ -18,6 +18,7 @@
 #include <vector>
 #include "mma.h"
 #include "../../include/emoasr_hip.h"
+#include "gemm_big_tn.h"
 
 namespace {
 
@@ -65,6 +66,8 @@ __device__ __forceinline__ void dgrad_row(const DgradGeom& g, int m, int& b, int
 int g_tr_read = 1;
 int g_gemm_wholek = 1;   // option "gemm_wholek"
 int g_gemm_tile = 0, g_gemm_kb = 0, g_gemm_xcd = 1, g_tn_group_kb = 0, g_tn_place = 0, g_gemm_wide128 = 0;
+int g_tn_big = 1;         // bf16 TN products with N2 % 256 == 0, N1 >= 256 on the eight-wave 256x256 tile (gemm_big_tn.hip); "tn_big"
+int g_tn_big_blocks = 0;  // block budget of a 256-tile launch ("tn_big_blocks": 64..1024; 0 = default)
 int g_tn_group_blocks = 0;  // override of a grouped TN launch's block budget (emoasr_set_option "tn_group_blocks"; 0 = auto)
 // f32 products as three bf16 MFMAs over (hi, lo) operand pairs (see SplitCfg): asked for PER CALL by the dtype code EMO_F32X3.  The
 // entry points of this file note it here for the launch helpers below them (thread-local, for the duration of the call: two engines
@@ -915,6 +918,18 @@ int launch_nn(const NtArgs& a, hipStream_t s, int nz = 1) {
   return g_tr_read ? launch_nt_<T, 0, true, true>(a, s, nz) : launch_nt_<T, 0, true, false>(a, s, nz);
 }
 
+// Most split-K slices one TN product may take (launch_tn and emoasr_gemm_tn_grouped): every slice adds the whole f32 output
+// once more through global float atomics, which run at ~1.3 TB/s chip-wide.  Keep that traffic around 8 MB ...
+// ... unless the reduction is so long that the atomics stay a small share (~10 % measured) of the product's own time,
+// estimated at 300 TFLOP/s: the Conv2d weight gradient (K = B*T'*F2 ~ 130 k) wants 15 slices, not 3,
+// and the vocabulary head's (10 000 x 256 = 10.2 MB of output, K ~ 35 k) several, not one.
+inline int tn_split_cap(long N1, long N2, long K) {
+  const long out_bytes = N1 * N2 * 4;
+  const double est_s = 2.0 * (double)N1 * (double)N2 * (double)K / 300e12;
+  const long cap_work = (long)(0.25 * est_s * 1.3e12 / (double)out_bytes);
+  return (int)std::max(std::max(1L, (8L << 20) / out_bytes), cap_work);
+}
+
 template <typename T, int BMODE, bool SP = false>
 int launch_tn(TnArgs a, hipStream_t s) {
   if constexpr (is_f32<T> && !SP) { if (t_f32_split) return launch_tn<T, BMODE, true>(a, s); }
@@ -926,17 +941,10 @@ int launch_tn(TnArgs a, hipStream_t s) {
   const int bn = big ? 128 : 64;
   const long tiles = (long)cdiv(a.N1, bn) * cdiv(a.N2, bn);
   // split-K: as many slices as fit ONE round of resident blocks (rounding up past it leaves a mostly empty
-  // second round) with at least 4 k-tiles each, but keep
-  // the f32 atomic traffic (output bytes x slices) around 8 MB: global float atomics run at
-  // ~1.3 TB/s chip-wide, so more slices than that make the kernel atomic-bound.
+  // second round) with at least 4 k-tiles each, but no more than the atomic traffic allows (tn_split_cap)
   const long slots_ = g_tn_group_blocks > 0 ? g_tn_group_blocks : ((big && kb == 2) || (big && SP) ? 512 : 768);   // (split, 128 tile: 80 KB of LDS)
   int splits = (int)std::max(1L, slots_ / tiles);  // one full round of resident blocks (2 per CU for the 128x128 BK=64 tile, else 3)
-  const long out_bytes = (long)a.N1 * a.N2 * 4;
-  // ... unless the reduction is so long that the atomics stay below ~10 % of the product's own time
-  // (estimated at 300 TFLOP/s): the Conv2d weight gradient (K = B*T'*F2 ~ 130 k) wants 15 slices, not 3
-  const double est_s = 2.0 * a.N1 * a.N2 * (double)a.K / 300e12;
-  const long cap_work = (long)(0.25 * est_s * 1.3e12 / (double)out_bytes);
-  const int cap = (int)std::max(std::max(1L, (8L << 20) / out_bytes), cap_work);
+  const int cap = tn_split_cap(a.N1, a.N2, a.K);
   const int floor_splits = (int)std::min((long)splits, (128 + tiles - 1) / tiles);  // never starve the chip
   splits = std::max(floor_splits, std::min(splits, cap));
   splits = std::max(1, std::min(splits, nk / 4 > 0 ? nk / 4 : 1));
@@ -985,6 +993,8 @@ void emo_gemm_set_tn_group_blocks(int v) { g_tn_group_blocks = v > 0 ? v : 0; }
 void emo_gemm_set_kb(int v) { g_gemm_kb = v; }
 void emo_gemm_set_wholek(int v) { g_gemm_wholek = v; }
 void emo_gemm_set_tn_place(int v) { g_tn_place = v != 0; }
+void emo_gemm_set_tn_big(int v) { g_tn_big = v != 0; }
+void emo_gemm_set_tn_big_blocks(int v) { g_tn_big_blocks = (v >= 64 && v <= 1024) ? v : 0; }
 void emo_gemm_set_tn_group_kb(int v) { g_tn_group_kb = (v == 1 || v == 2) ? v : 0; }
 void emo_gemm_set_xcd(int v) { g_gemm_xcd = v; }
 void emo_gemm_set_split_tile(int v) { g_split_tile = (v >= 1 && v <= 3) ? v : 0; }
@@ -1052,6 +1062,9 @@ extern "C" int emoasr_gemm_nn_batched(int dtype, int M, int N, int K, const void
   return 0;
 }
 
+static bool tn_big_takes(int dtype, int N1, int N2, int K, long lda, long ldb);
+static void tn_big_splits(int n, const BigTnProblem* q, int* splits);
+
 extern "C" int emoasr_gemm_tn(int dtype, int N1, int N2, int K, const void* A, long lda, const void* B,
                               long ldb, float* C, long ldc, float alpha, int accumulate, float* colsum,
                               float colsum_scale, void* stream) {
@@ -1070,17 +1083,23 @@ extern "C" int emoasr_gemm_tn(int dtype, int N1, int N2, int K, const void* A, l
   a.alpha = alpha; a.colsum = colsum; a.colsum_scale = colsum_scale;
   EmoTimerScope timer_(EMO_TIMER_GEMM_TN, (hipStream_t)stream, 2.0 * N1 * N2 * K,
                        ((double)K * N1 + (double)K * N2) * (dtype == EMO_BF16 ? 2.0 : 4.0) + 4.0 * N1 * N2);
+  if (tn_big_takes(dtype, N1, N2, K, lda, ldb)) {   // (the front-end Linear: 256 x 4864)
+    const BigTnProblem q{N1, N2, K, A, lda, B, ldb, C, ldc, alpha, 0, colsum, colsum_scale};
+    int splits = 1;
+    tn_big_splits(1, &q, &splits);
+    return emo_tn_big_launch(1, &q, &splits, (hipStream_t)stream);
+  }
   EMO_DISPATCH(dtype, return (launch_tn<T, 0>(a, (hipStream_t)stream)));
 }
 
-// Grouped weight-gradient products (always accumulating): see TnGroup.
-extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_t* probs, void* stream) {
+// Host-side plan of a grouped launch: tile edge bt, k extent kb (x 32 / 16), per-problem arguments with their k slices, and the
+// block list G.start (G.start[n] = blocks of the launch).  No device work: emoasr_gemm_tn_grouped_plan reports it as is.
+static int tn_group_plan(int dtype, int n, const emoasr_tn_problem_t* probs, TnGroup& G, int& bt, int& kb) {
   EMO_CHECK(n > 0 && n <= EMOASR_TN_GROUP_MAX, "gemm_tn_grouped: n=%d outside 1..%d", n, EMOASR_TN_GROUP_MAX);
-  TnGroup G{};
   G.n = n;
   long tiles = 0;
   // 128x128 tiles (16 MFMAs per wave and k step instead of 4) when every product is at least that large
-  int bt = 128;
+  bt = 128;
   for (int i = 0; i < n; ++i)
     if (probs[i].N1 < 128 || probs[i].N2 < 128) bt = 64;
   if (g_gemm_tile == 3) bt = 64;
@@ -1088,7 +1107,7 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
   // 128 tile is 80 KB: the 480-block launch of a layer then ran in TWO rounds, blocks sharing operand tiles were no longer
   // co-resident and the launch read 1.2-1.6x its operands from HBM; BK = 32 reads them once -- 216 -> 185 us at 35 k rows,
   // tools/tn_probe.py.)  Option "gemm_kb" overrides.
-  const int kb = dtype == EMO_BF16 ? (g_tn_group_kb ? g_tn_group_kb : g_gemm_kb ? g_gemm_kb : (bt == 128 ? 1 : 2)) : 1;
+  kb = dtype == EMO_BF16 ? (g_tn_group_kb ? g_tn_group_kb : g_gemm_kb ? g_gemm_kb : (bt == 128 ? 1 : 2)) : 1;
   const bool split = dtype == EMO_F32X3;
   const int BK = (dtype == EMO_BF16 || split ? 32 : 16) * kb;
   for (int i = 0; i < n; ++i) {
@@ -1099,7 +1118,8 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
               "gemm_tn_grouped: ragged N1 needs padded lda");
     tiles += (long)cdiv(q.N1, bt) * cdiv(q.N2, bt);
   }
-  // at least 4 k-tiles per slice, and per problem no more f32 atomic traffic than ~8 MB (see launch_tn)
+  // at least 4 k-tiles per slice, and per problem no more slices than its f32 atomic traffic allows (tn_split_cap: the same rule
+  // as launch_tn, so that a long reduction into one large output -- the vocabulary head alone in its launch -- is still split)
   // one split factor for the whole group, chosen so that the launch is ONE full round of resident blocks:
   // three blocks per CU for the 128x128 BK=32 tile (40 KB of LDS) and the 64x64 one (48 KB), two for 128x128 BK=64.  Rounding
   // the block count up past that measured slower every time (at 35 k rows: 768 blocks 185 us, 896 blocks 257 us).
@@ -1112,7 +1132,7 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
     a.N1 = q.N1; a.N2 = q.N2; a.K = q.K; a.A = q.A; a.lda = q.lda; a.B = q.B; a.ldb = q.ldb;
     a.C = q.C; a.ldc = q.ldc; a.alpha = q.alpha; a.colsum = q.colsum; a.colsum_scale = q.colsum_scale;
     const int nk = cdiv(q.K, BK);
-    const int cap = (int)std::max(1L, (8L << 20) / ((long)q.N1 * q.N2 * 4));
+    const int cap = tn_split_cap(q.N1, q.N2, q.K);
     int splits = std::max(1, std::min(std::min(want, cap), nk / 4 > 0 ? nk / 4 : 1));
     a.k_tiles_per_split = cdiv(nk, splits);
     splits = cdiv(nk, a.k_tiles_per_split);
@@ -1120,7 +1140,27 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
     start += cdiv(q.N1, bt) * cdiv(q.N2, bt) * splits;
   }
   G.start[n] = start;
-  hipStream_t s = (hipStream_t)stream;
+  return 0;
+}
+
+// The plan alone (no launch, no device): splits[i] = k slices of problem i, *tile = the tile edge, -> blocks of the launch in *blocks
+extern "C" int emoasr_gemm_tn_grouped_plan(int dtype, int n, const emoasr_tn_problem_t* probs, int* splits, int* tile, int* blocks) {
+  TnGroup G{};
+  int bt = 0, kb = 0;
+  if (int rc = tn_group_plan(dtype, n, probs, G, bt, kb)) return rc;
+  for (int i = 0; i < n; ++i) splits[i] = (G.start[i + 1] - G.start[i]) / (cdiv(probs[i].N1, bt) * cdiv(probs[i].N2, bt));
+  *tile = bt;
+  *blocks = G.start[n];
+  return 0;
+}
+
+// one launch of gemm_tn_grouped_kernel over the n products
+static int tn_grouped_launch(int dtype, int n, const emoasr_tn_problem_t* probs, hipStream_t s) {
+  TnGroup G{};
+  int bt = 0, kb = 0;
+  if (int rc = tn_group_plan(dtype, n, probs, G, bt, kb)) return rc;
+  const bool split = dtype == EMO_F32X3;
+  int start = G.start[n];
   G.xcd = g_tn_place ? 1 : (g_gemm_xcd ? 2 : 0);
   if (G.xcd == 1) {   // deal whole slices to the XCDs: largest first, each to the XCD with the fewest blocks so far
     struct Slice { int tiles, prob, split; };
@@ -1156,13 +1196,6 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
       G.xcd = 2;
     }
   }
-  double gfl = 0.0, gby = 0.0;
-  for (int i = 0; i < n; ++i) {
-    gfl += 2.0 * probs[i].N1 * probs[i].N2 * probs[i].K;
-    gby += ((double)probs[i].K * probs[i].N1 + (double)probs[i].K * probs[i].N2) * (dtype == EMO_BF16 ? 2.0 : 4.0) + 4.0 * probs[i].N1 * probs[i].N2;
-  }
-  EmoTimerScope timer_(EMO_TIMER_GEMM_TN, s, gfl, gby);
-  emo_timer_begin(EMO_TIMER_TN_GROUPED, s, gfl, gby);
   if (dtype == EMO_BF16) {
     if (bt == 128 && kb == 1) {
       if (g_tr_read) gemm_tn_grouped_kernel<bf16, true, 1, 128><<<start, 256, 0, s>>>(G);
@@ -1184,9 +1217,58 @@ extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_
     emo_set_error("bad dtype %d", dtype);
     return 1;
   }
-  emo_timer_end(EMO_TIMER_TN_GROUPED, s);
   EMO_LAUNCH_CHECK();
   return 0;
+}
+
+// Which TN products take the eight-wave 256x256 tile (gemm_big_tn.hip): bf16, N2 a multiple of 256, N1 >= 256 (ragged N1 where
+// lda is padded), option "tn_big" on, transposed LDS reads on.  Everything else -- small N, f32, f32x3 -- keeps tn_block.
+static bool tn_big_takes(int dtype, int N1, int N2, int K, long lda, long ldb) {
+  return dtype == EMO_BF16 && g_tn_big && g_tr_read && emo_tn_big_fits(N1, N2, K, lda, ldb);
+}
+// k slices of the products of one 256-tile launch: one split factor for the launch from its block budget (option
+// "tn_big_blocks"; the atomic bytes of a launch are blocks x 256 KB, so the budget is a tuning parameter, not "fill every CU"),
+// per product at most what tn_split_cap allows and at least 4 k-tiles of 32 per slice
+static void tn_big_splits(int n, const BigTnProblem* q, int* splits) {
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) tiles += (long)(q[i].N2 / 256) * cdiv(q[i].N1, 256);
+  const int want = (int)std::max(1L, (long)(g_tn_big_blocks > 0 ? g_tn_big_blocks : 192) / tiles);
+  for (int i = 0; i < n; ++i) {
+    const int nk = cdiv(q[i].K, 32);
+    splits[i] = std::max(1, std::min(std::min(want, tn_split_cap(q[i].N1, q[i].N2, q[i].K)), nk / 4 > 0 ? nk / 4 : 1));
+  }
+}
+
+// Grouped weight-gradient products (always accumulating): see TnGroup.  A mixed group runs as two launches: the products the
+// 256 tile takes (tn_big_takes), then the rest on gemm_tn_grouped_kernel.
+extern "C" int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_t* probs, void* stream) {
+  EMO_CHECK(n > 0 && n <= EMOASR_TN_GROUP_MAX, "gemm_tn_grouped: n=%d outside 1..%d", n, EMOASR_TN_GROUP_MAX);
+  hipStream_t s = (hipStream_t)stream;
+  double gfl = 0.0, gby = 0.0;
+  BigTnProblem big[EMOASR_TN_GROUP_MAX];
+  emoasr_tn_problem_t rest[EMOASR_TN_GROUP_MAX];
+  int nbig = 0, nrest = 0;
+  for (int i = 0; i < n; ++i) {
+    const emoasr_tn_problem_t& q = probs[i];
+    EMO_CHECK(q.N1 > 0 && q.N2 > 0 && q.K > 0, "gemm_tn_grouped: empty problem %d", i);
+    gfl += 2.0 * q.N1 * q.N2 * q.K;
+    gby += ((double)q.K * q.N1 + (double)q.K * q.N2) * (dtype == EMO_BF16 ? 2.0 : 4.0) + 4.0 * q.N1 * q.N2;
+    if (tn_big_takes(dtype, q.N1, q.N2, q.K, q.lda, q.ldb) && (q.N1 % 8 == 0 || q.lda >= (q.N1 + 7) / 8 * 8))
+      big[nbig++] = BigTnProblem{q.N1, q.N2, q.K, q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.alpha, 0, q.colsum, q.colsum_scale};
+    else
+      rest[nrest++] = q;
+  }
+  EmoTimerScope timer_(EMO_TIMER_GEMM_TN, s, gfl, gby);
+  emo_timer_begin(EMO_TIMER_TN_GROUPED, s, gfl, gby);
+  int rc = 0;
+  if (nbig) {
+    int splits[EMOASR_TN_GROUP_MAX];
+    tn_big_splits(nbig, big, splits);
+    rc = emo_tn_big_launch(nbig, big, splits, s);
+  }
+  if (!rc && nrest) rc = tn_grouped_launch(dtype, nrest, rest, s);
+  emo_timer_end(EMO_TIMER_TN_GROUPED, s);
+  return rc;
 }
 
 // Conv2d(C->C, k3, s2) over channels-last y1[B,T1,F1,C] as an implicit GEMM:
@@ -1258,4 +1340,33 @@ extern "C" int emoasr_conv2_wgrad(int dtype, int B, int T1, int F1, int C, const
   a.ldc = 9 * C; a.alpha = 1.f; a.colsum = dbias; a.colsum_scale = 1.f;
   a.cg = ConvGeom{T1, F1, T2, F2, C};
   EMO_DISPATCH(dtype, return (launch_tn<T, 1>(a, (hipStream_t)stream)));
+}
+
+// The Conv2d weight gradient on the 256x256 tile (gemm_big_tn.hip): bf16, C a multiple of 256, option "tn_big" on, and only
+// through the segmented entry point: what the tile gains is paying the split-K atomics once for all micro-batches.  One launch
+// per micro-batch (emoasr_conv2_wgrad) keeps gemm_tn_kernel's gathered mode -- measured at five micro-batches of K = 133 k:
+// 1064 us on gemm_tn_kernel, 1099 us as five launches of the 256 tile, 918 us as one -- and so do C = 128, f32 and f32x3.
+// Block budget: this product is compute-bound (157 GFLOP per micro-batch), so one block per CU unless "tn_big_blocks" says
+// otherwise (five micro-batches: 189 blocks 1100 us, 252 blocks 918 us, 315 blocks 1350 us, 504 blocks 966 us).
+static bool tn_big_conv_takes(int dtype, int C) { return dtype == EMO_BF16 && g_tn_big && g_tr_read && C % 256 == 0; }
+static int tn_big_conv(int nseg, const emoasr_conv2_wgrad_seg_t* segs, int F1, int C, float* dw, float* dbias, hipStream_t s) {
+  const int F2 = (F1 - 3) / 2 + 1;
+  long K = 0;
+  for (int i = 0; i < nseg; ++i) K += (long)segs[i].B * ((segs[i].T1 - 3) / 2 + 1) * F2;
+  return emo_tn_big_conv_launch(nseg, segs, F1, C, dw, dbias, g_tn_big_blocks > 0 ? g_tn_big_blocks : 256,
+                                tn_split_cap(C, 9L * C, K), s);
+}
+
+// The same over several micro-batches as one reduction (always accumulating): one launch of the 256-tile kernel where it
+// applies, else one emoasr_conv2_wgrad per segment.
+extern "C" int emoasr_conv2_wgrad_seg(int dtype, int nseg, const emoasr_conv2_wgrad_seg_t* segs, int F1, int C, float* dw,
+                                      float* dbias, void* stream) {
+  EMO_CHECK(nseg >= 1 && nseg <= EMOASR_CONV2_WGRAD_SEGMENTS, "conv2_wgrad_seg: nseg=%d outside 1..%d", nseg, EMOASR_CONV2_WGRAD_SEGMENTS);
+  EMO_CHECK(F1 >= 3 && C % 128 == 0, "conv2_wgrad_seg: F1=%d C=%d", F1, C);
+  for (int i = 0; i < nseg; ++i) EMO_CHECK(segs[i].B > 0 && segs[i].T1 >= 3, "conv2_wgrad_seg: segment %d is empty", i);
+  if (tn_big_conv_takes(dtype, C) && emo_tn_big_conv_fits(nseg, segs, F1, C))
+    return tn_big_conv(nseg, segs, F1, C, dw, dbias, (hipStream_t)stream);
+  for (int i = 0; i < nseg; ++i)
+    if (int rc = emoasr_conv2_wgrad(dtype, segs[i].B, segs[i].T1, F1, C, segs[i].dy2, segs[i].y1, dw, dbias, 1, stream)) return rc;
+  return 0;
 }

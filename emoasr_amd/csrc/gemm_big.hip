@@ -27,11 +27,10 @@
 //     epilogue packs them to 8 bytes, transposes 16-row slabs through wave-private LDS and stores full 128-byte rows.
 #include <algorithm>
 #include "mma.h"
+#include "lds_dma.h"
 #include "../../include/emoasr_hip.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 struct BigConv {   // forward gather: see ConvGeom in gemm.hip
   int T1, F1, T2, F2, C;
@@ -80,16 +79,6 @@ struct BigArgs {
   BigDgrad dg;
 };
 
-__device__ __forceinline__ int xcd_remap_big(int pid, int nblk) {
-  const int per = nblk / 8, rem = nblk - per * 8;
-  const int x = pid % 8, slot = pid / 8;
-  return x * per + min(x, rem) + slot;
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 16, voff, soff, 0, 0);
-}
-
 // exchange inside groups of 8 lanes on the VALU (DPP), for reductions: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
 // (lane i <-> 7 - i of its half-row: after the two quad steps every lane of a quad holds the quad's result, so the mirror pairs the
 // two quads' results).  __shfl_xor compiles to ds_bpermute_b32 -- an LDS-pipe round trip per step.
@@ -101,15 +90,6 @@ __device__ __forceinline__ float max8(float x) {
 }
 __device__ __forceinline__ float sum8(float x) {
   x += dpp8<0xB1>(x); x += dpp8<0x4E>(x); return x + dpp8<0x141>(x);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  static_assert(N == 8 || N == 6 || N == 4 || N == 3 || N == 2, "wait_vmcnt: unexpected piece count");
 }
 
 // AMODE 0: plain row-major A.  1: Conv2d forward gather.  2: Conv2d data gradient (parity classes).

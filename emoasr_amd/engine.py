@@ -742,9 +742,16 @@ class CTCEngine(_DecoderMixinPlaceholder):
         else:
             w2r = ops.strided_copy(A.p(pre + "conv.2.weight").permute(0, 2, 3, 1), out_dtype=dt).view(C, 9 * C)
         dw1, db1 = A.g(pre + "conv.0.weight").view(C, 9), A.g(pre + "conv.0.bias")
+        # conv2's weight gradient over all micro-batches as one reduction (bf16, C % 256 == 0: one launch of the 256-tile kernel
+        # pays the split-K atomics into dw2 once; the library falls back to one launch per micro-batch when "tn_big" is off)
+        seg_wgrad = kc and C % 256 == 0 and len(st.xs_list) <= ops.lib.CONV2_WGRAD_SEGMENTS
+        if seg_wgrad:
+            ops.conv2_wgrad_seg([(dy2[rows[k]:rows[k + 1]].view(-1, C), st.y1s[k]) for k in range(len(st.xs_list))], dw2,
+                                dbias=A.g(pre + "conv.2.bias"))
         for k, xs in enumerate(st.xs_list):
             dy2_k = dy2[rows[k]:rows[k + 1]].view(-1, C)
-            ops.conv2_wgrad(dy2_k, st.y1s[k], dw2, dbias=A.g(pre + "conv.2.bias"), accumulate=True)
+            if not seg_wgrad:
+                ops.conv2_wgrad(dy2_k, st.y1s[k], dw2, dbias=A.g(pre + "conv.2.bias"), accumulate=True)
             if kc and self._conv1_fold:   # conv1's weight gradient in the data gradient's epilogue: dy1 never reaches HBM
                 ops.conv2_dgrad_w1(dy2_k, wt, st.y1s[k], xs, dw1, db1, accumulate=True)
                 continue

@@ -46,6 +46,11 @@ class TnProblem(Structure):
                 ("colsum", c_void_p), ("colsum_scale", c_float)]
 
 
+class Conv2WgradSeg(Structure):
+    _fields_ = [("dy2", c_void_p), ("y1", c_void_p), ("B", c_int), ("T1", c_int)]
+
+
+CONV2_WGRAD_SEGMENTS = 8
 TN_GROUP_MAX = 16
 
 
@@ -188,11 +193,13 @@ SIGNATURES = {
     "emoasr_gemm_tn": [I, I, I, I, P, L, P, L, P, L, F, I, P, F, P],
     "emoasr_gemm_nn_batched": [I, I, I, I, P, L, L, L, P, L, L, L, P, L, L, L, I, I, F, I, P],
     "emoasr_gemm_tn_grouped": [I, I, POINTER(TnProblem), P],
+    "emoasr_gemm_tn_grouped_plan": [I, I, POINTER(TnProblem), POINTER(c_int), POINTER(c_int), POINTER(c_int)],
     "emoasr_colsum": [I, I, I, P, L, P, F, I, P],
     "emoasr_conv1_fwd": [I, I, I, I, I, P, P, P, P, P],
     "emoasr_conv1_wgrad": [I, I, I, I, I, P, P, P, P, I, P, P],
     "emoasr_conv2_fwd": [I, I, I, I, I, P, P, P, POINTER(Epilogue), P],
     "emoasr_conv2_wgrad": [I, I, I, I, I, P, P, P, P, I, P],
+    "emoasr_conv2_wgrad_seg": [I, I, POINTER(Conv2WgradSeg), I, I, P, P, P],
     "emoasr_conv2_col2im": [I, I, I, I, I, P, P, P, P],
     "emoasr_conv2_dgrad": [I, I, I, I, I, P, P, P, P, P],
     "emoasr_conv2_dgrad_kc": [I, I, I, I, I, P, P, P, P, P],

@@ -166,6 +166,17 @@ def gemm_tn_grouped(problems, stream=None):
         lib.call("emoasr_gemm_tn_grouped", dt(chunk[0][0]), len(chunk), arr, sptr)
 
 
+def gemm_tn_grouped_plan(shapes, dtype=torch.bfloat16):
+    """Launch plan of one grouped call for shapes = [(N1, N2, K), ...] (at most lib.TN_GROUP_MAX), host only:
+    -> (split-K slices per problem, tile edge, workgroups of the launch)"""
+    arr = (lib.TnProblem * len(shapes))()
+    for q, (N1, N2, K) in zip(arr, shapes):
+        q.N1, q.N2, q.K, q.lda, q.ldb, q.ldc, q.alpha = N1, N2, K, (N1 + 7) // 8 * 8, N2, N2, 1.0
+    splits, tile, blocks = (ctypes.c_int * len(shapes))(), ctypes.c_int(), ctypes.c_int()
+    lib.call("emoasr_gemm_tn_grouped_plan", _DT[dtype], len(shapes), arr, splits, byref(tile), byref(blocks))
+    return list(splits), tile.value, blocks.value
+
+
 def gemm_nn_batched(a, b, out, M, N, K, lda, sa, ldb, sb, ldc, sc, nb, nh, alpha=1.0, accumulate=False):
     """out[b,h] (+)= alpha * a[b,h] (M x K, k-contiguous) @ b[b,h] (K x N, k-major); s* = (outer, inner)
     batch strides in elements; base pointers are the tensors' data pointers."""
@@ -220,6 +231,20 @@ def conv2_wgrad(dy2, y1, dw, dbias=None, accumulate=False):
     B, T1, F1, C = y1.shape
     lib.call("emoasr_conv2_wgrad", dt(y1), B, T1, F1, C, _p(dy2), _p(y1), _p(_chk(dw, torch.float32)),
              _p(dbias), int(accumulate), _stream())
+
+
+def conv2_wgrad_seg(segs, dw, dbias=None):
+    """segs: up to lib.CONV2_WGRAD_SEGMENTS pairs (dy2 [B,T2,F2,C] or [B*T2*F2, C], y1 [B,T1,F1,C]) sharing F1 and C; dw (and
+    dbias) accumulate the weight gradient of all of them as ONE reduction -- one launch where the 256-tile kernel applies"""
+    assert 1 <= len(segs) <= lib.CONV2_WGRAD_SEGMENTS
+    _, _, F1, C = segs[0][1].shape
+    arr = (lib.Conv2WgradSeg * len(segs))()
+    for q, (dy2, y1) in zip(arr, segs):
+        B, T1, f1, c = y1.shape
+        assert (f1, c) == (F1, C) and y1.dtype == segs[0][1].dtype
+        _chk(dy2, y1.dtype)
+        q.dy2, q.y1, q.B, q.T1 = dy2.data_ptr(), _chk(y1).data_ptr(), B, T1
+    lib.call("emoasr_conv2_wgrad_seg", dt(segs[0][1]), len(segs), arr, F1, C, _p(_chk(dw, torch.float32)), _p(dbias), _stream())
 
 
 def conv2_dgrad(dy2, w, y1):

@@ -122,6 +122,9 @@ typedef struct emoasr_tn_problem {
   float colsum_scale;
 } emoasr_tn_problem_t;
 int emoasr_gemm_tn_grouped(int dtype, int n, const emoasr_tn_problem_t* probs, void* stream);
+/* The launch plan emoasr_gemm_tn_grouped would use for these shapes, without launching (host only; the pointer fields of
+ * probs are not read): splits[i] = split-K slices of problem i, *tile = the tile edge, *blocks = workgroups of the launch. */
+int emoasr_gemm_tn_grouped_plan(int dtype, int n, const emoasr_tn_problem_t* probs, int* splits, int* tile, int* blocks);
 /* out[N] (+)= scale * sum_rows X[M,N]   (bias gradients) */
 int emoasr_colsum(int dtype, int M, int N, const void* X, long ldx, float* out, float scale,
                   int accumulate, void* stream);
@@ -142,6 +145,18 @@ int emoasr_conv2_fwd(int dtype, int B, int T1, int F1, int C, const void* y1, co
 /* dw[n,(kh,kw,c)] (+)= dy2^T . im2col(y1);  dbias[n] (+)= sum dy2 (may be NULL) */
 int emoasr_conv2_wgrad(int dtype, int B, int T1, int F1, int C, const void* dy2, const void* y1,
                        float* dw, float* dbias, int accumulate, void* stream);
+/* The same over up to EMOASR_CONV2_WGRAD_SEGMENTS micro-batches (each with its own B and T1; F1, C shared) as ONE reduction:
+ * one launch pays the split-K atomics into dw once instead of once per micro-batch.  Always accumulates.  bf16 with C a
+ * multiple of 256 and option "tn_big" on runs as one launch of the 256x256-tile kernel; anything else as nseg calls of
+ * emoasr_conv2_wgrad. */
+#define EMOASR_CONV2_WGRAD_SEGMENTS 8
+typedef struct emoasr_conv2_wgrad_seg {
+  const void* dy2;   /* [B, T2, F2, C] */
+  const void* y1;    /* [B, T1, F1, C] */
+  int B, T1;
+} emoasr_conv2_wgrad_seg_t;
+int emoasr_conv2_wgrad_seg(int dtype, int nseg, const emoasr_conv2_wgrad_seg_t* segs, int F1, int C, float* dw,
+                           float* dbias, void* stream);
 /* dy1[b,t1,f1,c] = relu'(y1) * sum_{kh,kw} dcol[(b,t2,f2),(kh,kw,c)]  (col2im gather) */
 /* Data gradient of the same convolution without an im2col buffer (four implicit GEMMs, one per parity class of
  * the output position): dy1[b,t1,f1,c] = relu'(y1[b,t1,f1,c]) * sum_{kh,kw,n} dy2[b,(t1-kh)/2,(f1-kw)/2,n]*w[n,(kh,kw,c)];

@@ -26,7 +26,7 @@ def family(name):
     if "gemm_nt_kernel" in n:
         m = re.search(r"gemm_nt_kernelI\w+?Li(\d+)ELi(\d+)ELi(\d)E", n)
         return "front-end Conv2d" if m and m.group(3) in ("1", "2") else "products fwd / dgrad"
-    if "gemm_tn_grouped" in n:
+    if "gemm_tn_grouped" in n or "big_tn_kernel" in n:
         return "weight gradients"
     if "gemm_tn_kernel" in n:
         m = re.search(r"gemm_tn_kernelI\w+?Li(\d+)ELi(\d+)ELi(\d)E", n)

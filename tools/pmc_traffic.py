@@ -12,7 +12,7 @@ def family(name):
     if m:
         kind = {"1": "conv2_fwd", "2": "conv2_dgrad"}.get(m.group(4), "gemm_nn" if m.group(5) == "1" else "gemm_nt")
         return f"{kind}[{m.group(2)}x{m.group(3)}]"
-    m = re.search(r"(gemm_tn_grouped_kernel|gemm_tn_kernel|attn_bwd_dq2_kernel|attn_fwd_kernel|ln_bwd8_kernel|ln_fwd_kernel)", n)
+    m = re.search(r"(gemm_tn_grouped_kernel|gemm_tn_kernel|big_tn_kernel|attn_bwd_dq2_kernel|attn_fwd_kernel|ln_bwd8_kernel|ln_fwd_kernel)", n)
     if m:
         return m.group(1)
     m = re.search(r"N12_GLOBAL__N_1\d+([a-z0-9_]+_kernel)", n)
