@@ -99,6 +99,15 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(long n, int C, const T* __
   }
 }
 
+// dx = dy * act'(pre): the gradient through an activation that no product's epilogue can carry (the LM head's transform, whose
+// GELU is followed by a LayerNorm: modeling_bert.py:537-554)
+template <typename T>
+__global__ __launch_bounds__(256) void act_bwd_kernel(long n, int act, const T* __restrict__ dy, const T* __restrict__ pre,
+                                                      T* __restrict__ dx) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    dx[i] = from_f32<T>(to_f32(dy[i]) * apply_dact<T>(act, to_f32(pre[i])));
+}
+
 inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 }  // namespace
@@ -198,6 +207,14 @@ extern "C" int emoasr_posenc(int dtype, int B, int T_, int N, const void* x, con
   if (n == 0) return 0;
   EMO_DISPATCH(dtype, (posenc_kernel<T><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(
                           T_, N, n, (const T*)x, pe, scale, drop_p, seed, (T*)y)));
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_act_bwd(int dtype, long n, int act, const void* dy, const void* pre, void* dx, void* stream) {
+  if (n == 0) return 0;
+  EMO_DISPATCH(dtype, (act_bwd_kernel<T><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(n, act, (const T*)dy, (const T*)pre,
+                                                                                      (T*)dx)));
   EMO_LAUNCH_CHECK();
   return 0;
 }

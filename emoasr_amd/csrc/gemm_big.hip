@@ -957,6 +957,82 @@ extern "C" int emoasr_rnnt_head_grad(int dtype, int nrows, int V, int J, const v
   return rnnt_head_launch(nrows, V, J, h, w, bias, dz, lddz, rn, (hipStream_t)stream);
 }
 
+// ---- cross-entropy vocabulary head without the logits (lm/modeling/transformer.py:45-56,79-99) ----------------------------
+// The transducer head's two epilogues serve it unchanged: with occ = gamma_label = the row's weight and gamma_blank = 0 the
+// gradient exp(z - lse) occ - [label] gamma_y is w (softmax - onehot).  Only the row-wise kernels around them are new.
+namespace {
+// labels -> label columns (an ignored label, -100, is clamped into the vocabulary: its row carries weight 0)
+__global__ __launch_bounds__(256) void ce_ycol_kernel(int n, int V, const int* __restrict__ labels, int* __restrict__ ycol) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int y = labels[i];
+  ycol[i] = (y < 0 || y >= V) ? 0 : y;
+}
+
+// part [nchunk][rows][2] (chunk-major) -> lse; logp = z[label] - lse; loss = -w logp
+__global__ __launch_bounds__(64) void ce_fold_kernel(int rows, int nchunk, const float* __restrict__ part, const float* __restrict__ zy,
+                                                     const float* __restrict__ wrow, float* __restrict__ lse,
+                                                     float* __restrict__ logp, float* __restrict__ loss) {
+  const int row = blockIdx.x * 64 + threadIdx.x;
+  if (row >= rows) return;
+  const float2* pp = reinterpret_cast<const float2*>(part) + row;
+  float m = -INFINITY, s = 0.f;
+  for (int c = 0; c < nchunk; ++c) {
+    const float2 v = pp[(long)c * rows];
+    const float mn = fmaxf(m, v.x);
+    s = s * expf(m - mn) + v.y * expf(v.x - mn);
+    m = mn;
+  }
+  const float l = m + logf(s);
+  const float lp = zy[row] - l;
+  lse[row] = l;
+  if (logp) logp[row] = lp;
+  if (loss) loss[row] = wrow ? -wrow[row] * lp : -lp;
+}
+
+__global__ __launch_bounds__(256) void ce_coef_kernel(int n, const float* __restrict__ lse, const float* __restrict__ wrow,
+                                                      float gscale, const float* __restrict__ gscale_dev,
+                                                      float* __restrict__ coef) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float s = (wrow ? wrow[i] : 1.f) * gscale * (gscale_dev ? *gscale_dev : 1.f);
+  *reinterpret_cast<f32x4*>(coef + (long)i * 4) = f32x4{lse[i], s, 0.f, s};
+}
+}  // namespace
+
+extern "C" int emoasr_ce_head_fwd(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias,
+                                  const int* labels, const float* wrow, float* part, float* zscr, int* ycol, float* lse,
+                                  float* logp, float* loss, void* stream) {
+  EMO_CHECK(dtype == EMO_BF16, "ce_head_fwd: bf16 only");
+  if (nrows == 0) return 0;
+  EMO_CHECK(labels && part && zscr && ycol && lse, "ce_head_fwd: labels / part / zscr / ycol / lse required");
+  hipStream_t s = (hipStream_t)stream;
+  ce_ycol_kernel<<<cdiv(nrows, 256), 256, 0, s>>>(nrows, V, labels, ycol);
+  EMO_LAUNCH_CHECK();
+  BigRnnt rn{};
+  rn.mode = 1; rn.blank = 0; rn.nchunk = cdiv(V, 64); rn.row0 = 0;
+  rn.part = part; rn.part_rows = nrows; rn.part_row0 = 0; rn.zb = zscr; rn.zy = zscr + nrows; rn.ycol = ycol;
+  if (rnnt_head_launch(nrows, V, K, x, w, bias, nullptr, V, rn, s)) return 1;
+  ce_fold_kernel<<<cdiv(nrows, 64), 64, 0, s>>>(nrows, rn.nchunk, part, zscr + nrows, wrow, lse, logp, loss);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_ce_head_grad(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias,
+                                   const float* lse, const int* ycol, const float* wrow, float gscale, const float* gscale_dev,
+                                   float* coef, void* dz, long lddz, void* stream) {
+  EMO_CHECK(dtype == EMO_BF16, "ce_head_grad: bf16 only");
+  if (nrows == 0) return 0;
+  EMO_CHECK(lse && ycol && coef && dz, "ce_head_grad: lse / ycol / coef / dz required");
+  EMO_CHECK(lddz % 8 == 0 && lddz >= V, "ce_head_grad: bad row stride");
+  hipStream_t s = (hipStream_t)stream;
+  ce_coef_kernel<<<cdiv(nrows, 256), 256, 0, s>>>(nrows, lse, wrow, gscale, gscale_dev, coef);
+  EMO_LAUNCH_CHECK();
+  BigRnnt rn{};
+  rn.mode = 2; rn.blank = 0; rn.nchunk = cdiv(V, 64); rn.coef = coef; rn.ycol = ycol;
+  return rnnt_head_launch(nrows, V, K, x, w, bias, dz, lddz, rn, s);
+}
+
 // Conv2d forward through the large-tile kernel; called by emoasr_conv2_fwd (gemm.hip) for bf16, C % 256 == 0.
 int emo_conv2_fwd_big(int B, int T1, int F1, int C, const void* y1, const void* w, void* y2, const float* bias,
                       int relu, hipStream_t s) {

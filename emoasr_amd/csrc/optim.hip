@@ -79,6 +79,51 @@ __global__ __launch_bounds__(256) void adam_kernel(long n, float* __restrict__ p
   }
 }
 
+// torch.optim.AdamW over the arena: decoupled decay p *= 1 - lr * wd with the span's wd, then the Adam update.  One wave walks one
+// 64-element piece at a time (arena slots are 64-element aligned, so a piece lies in ONE span): the span is found by a binary search
+// that is uniform over the wave.  A span with wd < 0 is left bit-identical (parameter, moments).
+__global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, float lr,
+                                                    float beta1, float beta2, float eps, float bc1,
+                                                    float bc2_sqrt, const float* __restrict__ gnorm_sq,
+                                                    float clip, float grad_mult, int* __restrict__ skipped,
+                                                    const long* __restrict__ span_end, const float* __restrict__ span_wd,
+                                                    int nspans) {
+  float mult = grad_mult;
+  if (gnorm_sq) {
+    const float nsq = *gnorm_sq * grad_mult * grad_mult;
+    if (!isfinite(nsq)) {  // NaN / Inf gradient: skip the step (train_lm.py:75-76) and count it for the host's counters
+      if (skipped && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skipped, 1);
+      return;
+    }
+    if (clip > 0.f) {
+      const float c = clip / (sqrtf(nsq) + 1e-6f);
+      if (c < 1.f) mult *= c;
+    }
+  }
+  const long npieces = (n + 63) / 64;
+  const int lane = threadIdx.x & 63;
+  for (long piece = (long)blockIdx.x * 4 + (threadIdx.x >> 6); piece < npieces; piece += (long)gridDim.x * 4) {
+    const long first = piece * 64;
+    int lo = 0, hi = nspans - 1;   // the first span with span_end > first
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (span_end[mid] > first) hi = mid; else lo = mid + 1;
+    }
+    const float wd = span_wd[lo];
+    if (wd < 0.f) continue;
+    const long i = first + lane;
+    if (i >= n) continue;
+    const float pi = p[i] * (1.f - lr * wd);
+    const float gi = g[i] * mult;
+    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = pi - (lr / bc1) * (mi / denom);
+  }
+}
+
 inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 }  // namespace
@@ -115,6 +160,20 @@ extern "C" int emoasr_adam_step_ex(long n, float* p, const float* g, float* m, f
   const float bc2 = 1.f - powf(beta2, (float)step);
   adam_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(n, p, g, m, v, lr, beta1, beta2, eps, weight_decay,
                                                           bc1, sqrtf(bc2), gnorm_sq, clip, grad_mult, skipped);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_adamw_step(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                                 float eps, int step, const float* gnorm_sq, float clip, float grad_mult, int* skipped,
+                                 const long* span_end, const float* span_wd, int nspans, void* stream) {
+  if (n == 0) return 0;
+  EMO_CHECK(step >= 1, "adamw: step must be >= 1");
+  EMO_CHECK(span_end && span_wd && nspans >= 1, "adamw: span table required");
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2 = 1.f - powf(beta2, (float)step);
+  adamw_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(n, p, g, m, v, lr, beta1, beta2, eps, bc1, sqrtf(bc2), gnorm_sq, clip,
+                                                           grad_mult, skipped, span_end, span_wd, nspans);
   EMO_LAUNCH_CHECK();
   return 0;
 }

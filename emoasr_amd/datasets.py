@@ -233,3 +233,49 @@ def write_results_tsv(path, rows, comment=None):
             tok = r["token_id"]
             tok = tok if isinstance(tok, str) else " ".join(str(int(t)) for t in tok)
             f.write("\t".join([str(r["utt_id"]), tok, str(r["text"]), str(r["reftext"])] + [str(r[k]) for k in extra]) + "\n")
+
+
+class LMDataset:
+    """lm/datasets.py:24-120 for the Transformer LM: a TSV with columns utt_id / token_id (space-separated ids).
+    Items: (utt_id, y_in int64, ylen, label int64 | None).  phase "train": with params.add_sos_eos the ids are wrapped in <eos>,
+    then y_in = y[:-1] and label = y[1:] (next-token targets); any other phase: y_in = y, no label."""
+
+    def __init__(self, params, data_path, phase="train", size=-1):
+        if params.lm_type != "transformer":
+            raise NotImplementedError(f"emoasr_amd: LMDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
+        columns = ["utt_id", "token_id"] + (["ylen"] if getattr(params, "bucket_shuffle", False) else [])
+        data = _read_table(data_path)[columns]
+        n = len(data)
+        data = data.dropna().reset_index(drop=True)
+        if len(data) != n:
+            logging.warning(f"nan value in dataset is removed: {n:d} -> {len(data):d}")
+        self.add_sos_eos = params.add_sos_eos
+        self.eos_id = params.eos_id
+        self.phase = phase
+        self.data = data[:size] if size > 0 else data
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, idx):
+        row = self.data.loc[idx]
+        ids = [int(t) for t in str(row["token_id"]).split()]
+        if self.add_sos_eos:
+            ids = [self.eos_id] + ids + [self.eos_id]
+        y = torch.tensor(ids, dtype=torch.long)
+        if self.phase == "train":
+            assert len(y) > 1
+            y_in, label = y[:-1], y[1:]
+        else:
+            y_in, label = y, None
+        return row["utt_id"], y_in, y_in.size(0), label
+
+    def collate_fn(self, batch):
+        """dict with the reference's keys: ys_in padded with <eos>, ylens, labels padded with -100 (train phase only)"""
+        from torch.nn.utils.rnn import pad_sequence
+        utt_ids, ys_in, ylens, labels = zip(*batch)
+        ret = {"utt_ids": list(utt_ids), "ys_in": pad_sequence(ys_in, batch_first=True, padding_value=self.eos_id),
+               "ylens": torch.tensor(ylens)}
+        if labels[0] is not None:
+            ret["labels"] = pad_sequence(labels, batch_first=True, padding_value=-100)
+        return ret

@@ -289,11 +289,15 @@ SIGNATURES = {
     "emoasr_rnnt_forward_parts": [I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "emoasr_rnnt_coef": [I, I, I, I, P, P, P, P, P, P, P, P, P, F, P, P, P, P],
     "emoasr_rnnt_head_grad": [I, I, I, I, P, P, P, P, P, I, P, L, P],
+    "emoasr_ce_head_fwd": [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
+    "emoasr_ce_head_grad": [I, I, I, I, P, P, P, P, P, P, F, P, P, P, L, P],
+    "emoasr_act_bwd": [I, L, I, P, P, P, P],
     "emoasr_argmax_rows": [I, I, I, P, L, P, P],
     "emoasr_first_not_equal": [I, P, I, P, P],
     "emoasr_sqnorm": [L, P, P, P],
     "emoasr_adam_step": [L, P, P, P, P, F, F, F, F, F, I, P, F, F, P],
     "emoasr_adam_step_ex": [L, P, P, P, P, F, F, F, F, F, I, P, F, F, P, P],
+    "emoasr_adamw_step": [L, P, P, P, P, F, F, F, F, I, P, F, F, P, P, P, I, P],
     "emoasr_specaug_apply": [I, I, I, P, P, I, I, P, P, P],
     "emoasr_fbank": [P, L, I, I, I, I, F, P, P, P, I, P],
     "emoasr_cmvn": [I, I, P, P, P, P],

@@ -1,9 +1,20 @@
 """Transformer LM for shallow fusion -- module API of lm/modeling/lm.py:22-66 and
 lm/modeling/transformer.py:19-77 (a causal BERT, vendored HF v3.0.0 modeling_bert.py:159-554),
-inference only, on HIP kernels.
+on HIP kernels: shallow-fusion inference, training, N-best scoring and the row log-probabilities behind the perplexity.
 
     lm = LM(params).cuda();  lm.load_state_dict(reference_lm_state_dict)
     log_probs, states = lm.predict(ys [B,N] int64, ylens [B], states=None)     # [B, V], None
+    logits = lm(ys, ylens)                                                     # [B, max(ylens), V] f32
+    loss, loss_dict = lm(ys_in, ylens, labels);  loss.backward()               # CrossEntropyLoss(ignore_index=-100), mean
+    scores = lm.score(ys, ylens)                                               # list: sum_i log p(ys[b,i+1] | ys[b,:i+1])
+
+Training (forward / backward sequencing below, no autograd graph inside): post-LN BERT blocks with a causal + padding key mask,
+hidden dropout 0.1 after the embedding LayerNorm / attention.output.dense / output.dense and attention-probability dropout 0.1
+(the reference builds its config without dropout arguments, so train() mode always has both: `hidden_dropout_prob`,
+`attention_probs_dropout_prob` here, eval() turns them off).  Gradients land in the parameter arena; `bert.pooler.*` is never
+read and its .grad stays None.  In bf16 with V % 8 == 0, d % 64 == 0 and at least ops.CE_HEAD_MIN_ROWS rows the vocabulary head
+of the loss / score path never writes [rows, V] logits (ops.ce_head_fwd / ce_head_bwd); otherwise (and in f32 / f32x3, and
+in forward() without labels, which returns them) the logits are materialised.  token_logprobs / score always run without dropout.
 
 State-dict keys match the reference (`lm.transformer.bert.*`, `lm.transformer.cls.predictions.*`,
 output embedding tied to the word embedding).  Only `lm_type == "transformer"` is on the path.
@@ -18,6 +29,7 @@ import torch.nn as nn
 from .. import ops
 from ..engine import ParamArena, h2d_i32
 from ..ops import ACT_GELU
+from ..engine import _Stash
 from .blocks import _Holder
 
 
@@ -124,6 +136,13 @@ class LM(nn.Module):
         self.lm = TransformerLM(params)
         self._arena = None
         self._pe = None
+        # the reference's TransformersConfig defaults (lm/modeling/transformer.py:22-29 passes neither): active in train() mode
+        self.hidden_dropout_prob = 0.1
+        self.attention_probs_dropout_prob = 0.1
+        self.fused_head = os.environ.get("EMOASR_CE_HEAD_FUSED", "1") != "0"   # A/B switch of the logit-free head
+        self.last_head = None     # "fused" / "materialised": the path the last loss / score call took
+        self.seed = 0x5EED
+        self.step_count = 0
 
     def load_state_dict(self, state_dict, strict=True):
         try:
@@ -191,6 +210,8 @@ class LM(nn.Module):
         if A is not arena_before:
             self._graphs = {}     # (captured launches hold the old arena's addresses)
         A.refresh_shadow()
+        if getattr(self, "_pe_stale", False):   # a training step has moved the embeddings since the table was built
+            self._refresh_pe()
         ys = torch.as_tensor(ys)
         B, N = ys.shape
         dev = A.flat.device
@@ -253,3 +274,273 @@ class LM(nn.Module):
             ys_host = ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)
             yl = ylens.tolist() if torch.is_tensor(ylens) else list(ylens)
             return self.predict_device(ys_host, yl), states
+
+    # ---------------------------------------------------------------- training, scoring
+    _PRE = "lm.transformer.bert."
+    _CP = "lm.transformer.cls.predictions."
+    _NO_GRAD = ("lm.transformer.bert.pooler.dense.weight", "lm.transformer.bert.pooler.dense.bias")
+
+    def _seed(self, site):
+        return (self.seed * 1000003 + self.step_count * 4099 + site) & 0xFFFFFFFFFFFF
+
+    def _prepare(self):
+        """arena bound, compute-dtype weights and the additive position + token-type(0) table current (the parameters move
+        between training steps; the table is rebuilt IN PLACE, so captured predict graphs keep reading the right address)"""
+        arena_before = self._arena
+        A = self._bind()
+        if A is not arena_before:
+            self._graphs = {}
+        A.refresh_shadow()
+        self._refresh_pe()
+        return A
+
+    def _refresh_pe(self):
+        A, emb = self._arena, self._PRE + "embeddings."
+        pos, typ = A.p(emb + "position_embeddings.weight"), A.p(emb + "token_type_embeddings.weight")
+        ops.strided_copy(pos, out=self._pe)
+        ops.strided_copy(typ[0].expand(pos.shape[0], pos.shape[1]), out=self._pe, accumulate=True)
+        self._pe_stale = False
+
+    def _split(self):
+        return self.f32_split if self.compute_dtype == torch.float32 else None
+
+    def _encode(self, ids, klens, B, N, p_h, p_att, keep):
+        """ids int32 [B,N], klens int32 [B] on the device -> (hidden [B*N, d], stash | None): embeddings + the post-LN blocks
+        (modeling_bert.py:159-436), dropout by the seeded sites"""
+        A, P = self._arena, self.params
+        d, H, nl = P.hidden_size, P.num_attention_heads, P.num_layers
+        pre = self._PRE
+        e = ops.embed_fwd(ids, A.w(pre + "embeddings.word_embeddings.weight"), self._pe, 1.0).view(B * N, d)
+        x, m0, r0 = ops.layernorm_fwd(e, A.p(pre + "embeddings.LayerNorm.weight"), A.p(pre + "embeddings.LayerNorm.bias"),
+                                      1e-12, keep)
+        s_emb = self._seed(1)
+        if p_h > 0:
+            x = ops.scale_dropout(x, 1.0, p_h, s_emb)
+        scale = 1.0 / math.sqrt(d // H)
+        layers = []
+        for i in range(nl):
+            lay = f"{pre}encoder.layer.{i}."
+            s_att, s_o, s_f = self._seed(100 + 10 * i), self._seed(101 + 10 * i), self._seed(102 + 10 * i)
+            wqkv = A.w_span(lay + "attention.self.query.weight", lay + "attention.self.value.weight", (3 * d, d))
+            bqkv = A.p_span(lay + "attention.self.query.bias", lay + "attention.self.value.bias", (3 * d,))
+            qkv = ops.gemm_nt(x, wqkv, bias=bqkv).view(B, N, 3 * d)
+            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=True,
+                                  drop_p=p_att, seed=s_att)
+            y = ops.gemm_nt(o.view(B * N, d), A.w(lay + "attention.output.dense.weight"),
+                            bias=A.p(lay + "attention.output.dense.bias"), residual=x, res_scale=1.0, drop_p=p_h, seed=s_o)
+            x1, m1, r1 = ops.layernorm_fwd(y, A.p(lay + "attention.output.LayerNorm.weight"),
+                                           A.p(lay + "attention.output.LayerNorm.bias"), 1e-12, keep)
+            u = torch.empty(B * N, P.intermediate_size, device=x.device, dtype=x.dtype) if keep else None
+            a = ops.gemm_nt(x1, A.w(lay + "intermediate.dense.weight"), bias=A.p(lay + "intermediate.dense.bias"),
+                            act=ACT_GELU, pre_out=u)
+            y2 = ops.gemm_nt(a, A.w(lay + "output.dense.weight"), bias=A.p(lay + "output.dense.bias"), residual=x1,
+                             res_scale=1.0, drop_p=p_h, seed=s_f)
+            x2, m2, r2 = ops.layernorm_fwd(y2, A.p(lay + "output.LayerNorm.weight"), A.p(lay + "output.LayerNorm.bias"),
+                                           1e-12, keep)
+            if keep:
+                layers.append((x, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f))
+            x = x2
+        if not keep:
+            return x, None
+        st = _Stash()
+        st.B, st.N, st.ids, st.klens, st.p_h, st.p_att = B, N, ids, klens, p_h, p_att
+        st.e, st.m0, st.r0, st.s_emb, st.layers = e, m0, r0, s_emb, layers
+        return x, st
+
+    def _transform(self, x, keep):
+        """cls.predictions.transform (modeling_bert.py:537-554): dense + GELU + LayerNorm -> (t2, stash)"""
+        A, cp = self._arena, self._CP
+        tu = torch.empty_like(x) if keep else None
+        t = ops.gemm_nt(x, A.w(cp + "transform.dense.weight"), bias=A.p(cp + "transform.dense.bias"), act=ACT_GELU, pre_out=tu)
+        t2, mt, rt = ops.layernorm_fwd(t, A.p(cp + "transform.LayerNorm.weight"), A.p(cp + "transform.LayerNorm.bias"),
+                                       1e-12, keep)
+        return t2, (x, tu, t, mt, rt)
+
+    def _head_rows(self, t2, labels, w):
+        """the tied output projection + soft-max, reduced per row: labels int32 [M] (clamped), w f32 [M]
+        -> (rows f32 [M] = -w[m] * log p(labels[m] | row m), head stash)"""
+        A = self._arena
+        W, bias = A.w(self._PRE + "embeddings.word_embeddings.weight"), A.p(self._CP + "bias")
+        if self.fused_head and ops.ce_head_ok(t2, W):
+            rows, _, ctx = ops.ce_head_fwd(t2, W, bias, labels, w)
+            self.last_head = "fused"
+            return rows, ("fused", ctx)
+        logits = ops.gemm_nt(t2, W, bias=bias)
+        rows, _ = ops.lsm_loss(logits, labels, w, 0.0)
+        self.last_head = "materialised"
+        return rows, ("materialised", logits)
+
+    def _inputs(self, ys, ylens):
+        ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
+        if ylens is None:
+            yl = [ys.shape[1]] * ys.shape[0]      # (no mask: every position is a key)
+        else:
+            yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+            ys = ys[:, : max(yl)]
+        P = self.params
+        assert ys.shape[1] <= P.max_seq_len, f"sequence length {ys.shape[1]} exceeds max_seq_len {P.max_seq_len}"
+        assert len(yl) == ys.shape[0] and min(yl) >= 1, "ylens: one length >= 1 per row"
+        assert 0 <= int(ys.min()) and int(ys.max()) < P.vocab_size, "token id outside the vocabulary"
+        return ys.contiguous(), yl
+
+    def forward(self, ys, ylens=None, labels=None, ps=None, plens=None):
+        """lm/modeling/lm.py:45-46, transformer.py:35-56: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss})"""
+        ys, yl = self._inputs(ys, ylens)
+        A = self._prepare()
+        if labels is None:
+            B, N = ys.shape
+            if self.training:      # (the reference's logits in train() mode carry its dropout too)
+                self.step_count += 1
+            p_h = float(self.hidden_dropout_prob) if self.training else 0.0
+            p_att = float(self.attention_probs_dropout_prob) if self.training else 0.0
+            with torch.no_grad(), ops.stream_scope(self._split()):
+                dev = A.flat.device
+                x, _ = self._encode(h2d_i32(ys, dev), h2d_i32(yl, dev), B, N, p_h, p_att, False)
+                t2, _ = self._transform(x, False)
+                W = A.w(self._PRE + "embeddings.word_embeddings.weight")
+                logits = ops.gemm_nt(t2, W, bias=A.p(self._CP + "bias"), out_f32=t2.dtype != torch.float32)
+            return logits.view(B, N, -1)
+        labels = (labels.cpu() if torch.is_tensor(labels) else torch.as_tensor(labels)).to(torch.int64)
+        if ylens is not None:
+            labels = labels[:, : max(yl)]
+        loss = _LMLossFn.apply(self, ys, yl, labels.contiguous(), *A.params)
+        return loss, {"loss_total": loss}
+
+    def _loss_forward(self, ys, yl, labels, keep):
+        A = self._arena
+        dev = A.flat.device
+        B, N = ys.shape
+        training = self.training
+        if training:
+            self.step_count += 1
+        p_h = float(self.hidden_dropout_prob) if training else 0.0
+        p_att = float(self.attention_probs_dropout_prob) if training else 0.0
+        valid = labels != -100
+        assert labels.shape == ys.shape and int(labels.max()) < self.params.vocab_size, "labels: [B, N] ids below vocab_size or -100"
+        count = int(valid.sum())
+        w = valid.to(torch.float32) / max(count, 1)     # mean over the rows with a label (CrossEntropyLoss, ignore_index=-100)
+        with ops.stream_scope(self._split()):
+            ids, klens, lab = h2d_i32(ys, dev), h2d_i32(yl, dev), h2d_i32(labels.clamp(min=0).view(-1), dev)
+            w_dev = w.view(-1).pin_memory().to(dev, non_blocking=True)
+            x, st = self._encode(ids, klens, B, N, p_h, p_att, keep)
+            t2, tst = self._transform(x, keep)
+            rows, head = self._head_rows(t2, lab, w_dev)
+            loss = rows.sum()
+        if keep:
+            self._pe_stale = True     # (an update follows: predict() rebuilds the position table before its next use)
+            st.t2, st.tst, st.head, st.lab, st.w = t2, tst, head, lab, w_dev
+        return loss, st
+
+    def _loss_backward(self, st, g):
+        """g: the incoming gradient of the loss (0-dim, on the device).  Accumulates every parameter gradient into the arena."""
+        with ops.stream_scope(self._split()):
+            self._backward(st, g.to(torch.float32).reshape(1))
+
+    def _backward(self, st, g1):
+        A, P = self._arena, self.params
+        A.attach_grads()
+        d, H, nl = P.hidden_size, P.num_attention_heads, P.num_layers
+        B, N, p_h, p_att = st.B, st.N, st.p_h, st.p_att
+        pre, cp = self._PRE, self._CP
+        word = pre + "embeddings.word_embeddings.weight"
+
+        def lin_bwd(dy, x_in, wname, bname, **epi):   # gradients of y = x_in W^T + b; -> dy W with the epilogue
+            w = A.w(wname)
+            ops.gemm_tn(dy, x_in, out=A.g(wname), accumulate=True, colsum=A.g(bname))
+            return ops.gemm_nn(dy, w, **epi)
+
+        def ln_bwd(dy, x_in, name, mean, rstd):
+            return ops.layernorm_bwd(dy, x_in, A.p(name + ".weight"), mean, rstd, None, A.g(name + ".weight"), A.g(name + ".bias"))
+
+        drop = lambda t, seed: ops.scale_dropout(t, 1.0, p_h, seed) if p_h > 0 else t
+        # ---- vocabulary head (tied to the word embedding: its weight gradient lands in the embedding's slot)
+        kind, hctx = st.head
+        if kind == "fused":
+            dt2 = ops.ce_head_bwd(st.t2, A.w(word), A.p(cp + "bias"), hctx, A.g(word), A.g(cp + "bias"), 1.0, g1)
+        else:
+            _, dz = ops.lsm_loss(hctx, st.lab, st.w, 0.0, True, 1.0, g1)
+            dt2 = lin_bwd(dz, st.t2, word, cp + "bias")
+        x, tu, t, mt, rt = st.tst
+        dpre = ops.act_bwd(ln_bwd(dt2, t, cp + "transform.LayerNorm", mt, rt), tu, ACT_GELU)
+        dx = lin_bwd(dpre, x, cp + "transform.dense.weight", cp + "transform.dense.bias")
+        # ---- blocks, last to first.  Post-LN: LayerNorm backward first, then the branch and the residual together
+        scale = 1.0 / math.sqrt(d // H)
+        scratch = None
+        for i in reversed(range(nl)):
+            lay = f"{pre}encoder.layer.{i}."
+            xin, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f = st.layers[i]
+            dy2 = ln_bwd(dx, y2, lay + "output.LayerNorm", m2, r2)
+            du = lin_bwd(drop(dy2, s_f), a, lay + "output.dense.weight", lay + "output.dense.bias", dact_pre=u, dact=ACT_GELU)
+            dx1 = lin_bwd(du, x1, lay + "intermediate.dense.weight", lay + "intermediate.dense.bias", residual=dy2, res_scale=1.0)
+            dy = ln_bwd(dx1, y, lay + "attention.output.LayerNorm", m1, r1)
+            do = lin_bwd(drop(dy, s_o), o.view(B * N, d), lay + "attention.output.dense.weight", lay + "attention.output.dense.bias")
+            dqkv = torch.empty_like(qkv)
+            q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+            dq, dk, dv = dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]
+            # (the single-pass attention backward has no causal mask: the materialised path, as the ASR decoder's self-attention)
+            if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
+                scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
+            ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=True, drop_p=p_att,
+                         seed=s_att, scratch=scratch)
+            dqkv2 = dqkv.view(B * N, 3 * d)
+            qn, vn = lay + "attention.self.query.", lay + "attention.self.value."
+            ops.gemm_tn(dqkv2, xin, out=A.g_span(qn + "weight", vn + "weight", (3 * d, d)), accumulate=True,
+                        colsum=A.g_span(qn + "bias", vn + "bias", (3 * d,)))
+            dx = ops.gemm_nn(dqkv2, A.w_span(qn + "weight", vn + "weight", (3 * d, d)), residual=dy, res_scale=1.0)
+        # ---- embeddings (modeling_bert.py:159-201): word rows scattered, positions summed over the batch, token type 0 over all rows
+        emb = pre + "embeddings."
+        de = ln_bwd(drop(dx, st.s_emb), st.e, emb + "LayerNorm", st.m0, st.r0)
+        ops.embed_bwd(st.ids, de.view(B, N, d), 1.0, A.g(word))
+        ops.colsum(de.view(B, N * d), out=A.g(emb + "position_embeddings.weight").view(-1)[: N * d], accumulate=True)
+        ops.colsum(de, out=A.g(emb + "token_type_embeddings.weight")[0], accumulate=True)
+        for n in self._NO_GRAD:      # never read by the LM: .grad stays None as in the reference (AdamW then leaves them alone)
+            A.params[A.names.index(n)].grad = None
+
+    def token_logprobs(self, ys, ylens, labels):
+        """log p(labels[b,i] | ys[b,:i+1]) for every position with labels != -100 (zeros elsewhere) -> float64 [B, N] on the HOST:
+        the logit-free head forward (label logit minus log-sum-exp), ONE device-to-host copy of the row values"""
+        ys, yl = self._inputs(ys, ylens)
+        labels = (labels.cpu() if torch.is_tensor(labels) else torch.as_tensor(labels)).to(torch.int64)[:, : ys.shape[1]]
+        A = self._prepare()
+        dev = A.flat.device
+        B, N = ys.shape
+        valid = labels != -100
+        with torch.no_grad(), ops.stream_scope(self._split()):
+            ids, klens, lab = h2d_i32(ys, dev), h2d_i32(yl, dev), h2d_i32(labels.clamp(min=0).contiguous().view(-1), dev)
+            w_dev = valid.to(torch.float32).contiguous().view(-1).pin_memory().to(dev, non_blocking=True)
+            x, _ = self._encode(ids, klens, B, N, 0.0, 0.0, False)
+            t2, _ = self._transform(x, False)
+            rows, _ = self._head_rows(t2, lab, w_dev)
+        return -rows.cpu().to(torch.float64).view(B, N) * valid.to(torch.float64)
+
+    def score(self, ys, ylens, batch_size=100):
+        """lm/modeling/transformer.py:79-99: per row sum_{i < ylens[b]-1} log p(ys[b,i+1] | ys[b,:i+1]) -> Python list of floats
+        (summed on the host in double precision, as the reference sums Python floats)"""
+        ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        out = []
+        batch_size = batch_size or len(yl)
+        for b0 in range(0, len(yl), batch_size):
+            y, l = ys[b0:b0 + batch_size, : max(yl[b0:b0 + batch_size])], yl[b0:b0 + batch_size]
+            labels = torch.full_like(y, -100)
+            for b, n in enumerate(l):
+                labels[b, : n - 1] = y[b, 1:n]
+            out += self.token_logprobs(y, l, labels).sum(dim=1).tolist()
+        return out
+
+
+class _LMLossFn(torch.autograd.Function):
+    """the LM training loss as ONE autograd node over the parameters: backward() runs the hand-written gradient kernels"""
+
+    @staticmethod
+    def forward(ctx, lm, ys, yl, labels, *params):
+        keep = any(ctx.needs_input_grad)     # (False under torch.no_grad(): nothing is stashed)
+        loss, st = lm._loss_forward(ys, yl, labels, keep)
+        ctx.lm, ctx.st = lm, st
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.lm._loss_backward(ctx.st, g)
+        ctx.st = None
+        return (None, None, None, None) + (None,) * len(ctx.lm._arena.params)

@@ -647,6 +647,14 @@ def posenc(x, pe, scale, drop_p=0.0, seed=0):
     return y
 
 
+def act_bwd(dy, pre, act):
+    """dy * act'(pre), elementwise (same shape and dtype)"""
+    assert dy.shape == pre.shape and dy.dtype == pre.dtype and dy.is_contiguous() and pre.is_contiguous()
+    dx = torch.empty_like(dy)
+    lib.call("emoasr_act_bwd", dt(dy), dy.numel(), act, _p(_chk(dy)), _p(pre), _p(dx), _stream())
+    return dx
+
+
 def add(a, b):
     y = torch.empty_like(a)
     lib.call("emoasr_add", dt(a), a.numel(), _p(a), _p(b), _p(y), _stream())
@@ -1078,6 +1086,56 @@ def rnnt_grad(logits, ctx, nll, labels, elens, ylens, blank, gscale, gscale_dev=
     return dz
 
 
+# ---- cross-entropy vocabulary head without the logits (Transformer LM) -------------------------------------------------------
+CE_HEAD_MIN_ROWS = 1024    # below this the large-tile product leaves most CUs idle: the materialised path is taken
+CE_HEAD_CHUNK = 1024       # rows of dz alive at a time in the backward
+
+
+def ce_head_ok(x, w):
+    """does the logit-free head take this shape?  bf16, V % 8 == 0, K % 64 == 0, enough rows, operands below 4 GiB"""
+    M, K, lda = _rows(x)
+    V = w.shape[0]
+    return (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and V % 8 == 0 and V >= 256 and K % 64 == 0 and lda == K
+            and w.stride(0) == K and M >= CE_HEAD_MIN_ROWS and M * K * 2 < (1 << 32) and V * K * 2 < (1 << 32))
+
+
+def ce_head_fwd(x, w, bias, labels, wrow=None):
+    """x [M, K] bf16, w [V, K] bf16, bias f32 [V], labels int32 [M] (-100 = ignored), wrow f32 [M] | None
+    -> (loss rows f32 [M] = -wrow * logp, logp f32 [M] = log p(label | row), ctx for ce_head_bwd).  No [M, V] buffer."""
+    assert ce_head_ok(x, w), "ce_head_fwd: shape outside the fused head's gates (ops.ce_head_ok)"
+    M, K, _ = _rows(_chk(x))
+    V = w.shape[0]
+    dev = x.device
+    part = torch.empty((V + 63) // 64, M, 2, device=dev, dtype=torch.float32)
+    zscr = torch.empty(2 * M, device=dev, dtype=torch.float32)
+    ycol = torch.empty(M, device=dev, dtype=torch.int32)
+    out = torch.empty(3, M, device=dev, dtype=torch.float32)
+    lse, logp, loss = out[0], out[1], out[2]
+    lib.call("emoasr_ce_head_fwd", dt(x), M, V, K, _p(x), _p(w), _p(bias), _p(_chk(labels, torch.int32)), _p(wrow), _p(part),
+             _p(zscr), _p(ycol), _p(lse), _p(logp), _p(loss), _stream())
+    return loss, logp, (lse, ycol, wrow)
+
+
+def ce_head_bwd(x, w, bias, ctx, dw, dbias, gscale=1.0, gscale_dev=None, chunk=None, want_dx=True):
+    """gradients of sum(loss rows) * gscale [* gscale_dev]: dw f32 [V, K] and dbias f32 [V] are ACCUMULATED into, -> dx [M, K] bf16.
+    dz = w_row (softmax - onehot) is recomputed `chunk` rows at a time and fed to gemm_nn / gemm_tn."""
+    lse, ycol, wrow = ctx
+    M, K, _ = _rows(_chk(x))
+    V = w.shape[0]
+    chunk = min(M, chunk or CE_HEAD_CHUNK)
+    dz = torch.empty(chunk, V, device=x.device, dtype=x.dtype)
+    coef = torch.empty(chunk, 4, device=x.device, dtype=torch.float32)
+    dx = torch.empty(M, K, device=x.device, dtype=x.dtype) if want_dx else None
+    for r0 in range(0, M, chunk):
+        n = min(chunk, M - r0)
+        lib.call("emoasr_ce_head_grad", dt(x), n, V, K, _p(x[r0:r0 + n]), _p(w), _p(bias), _p(lse[r0:r0 + n]), _p(ycol[r0:r0 + n]),
+                 None if wrow is None else _p(wrow[r0:r0 + n]), gscale, _p(gscale_dev), _p(coef), _p(dz), V, _stream())
+        if want_dx:
+            gemm_nn(dz[:n], w, out=dx[r0:r0 + n])
+        gemm_tn(dz[:n], x[r0:r0 + n], out=dw, accumulate=True, colsum=dbias)
+    return dx
+
+
 def argmax_rows(x):
     M, V, ld = _rows(_chk(x))
     out = torch.empty(M, device=x.device, dtype=torch.int32)
@@ -1100,6 +1158,13 @@ def sqnorm(x, out):
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, gnorm_sq=None, clip=0.0, grad_mult=1.0, skipped=None):
     lib.call("emoasr_adam_step_ex", p.numel(), _p(p), _p(g), _p(m), _p(v), lr, beta1, beta2, eps, weight_decay,
              step, _p(gnorm_sq), clip, grad_mult, _p(skipped), _stream())
+
+
+def adamw_step(p, g, m, v, lr, beta1, beta2, eps, step, span_end, span_wd, gnorm_sq=None, clip=0.0, grad_mult=1.0, skipped=None):
+    """span_end int64 [S] / span_wd f32 [S] on the device: see emoasr_adamw_step (a negative span_wd leaves the span untouched)"""
+    assert span_end.dtype == torch.int64 and span_wd.dtype == torch.float32 and span_end.numel() == span_wd.numel()
+    lib.call("emoasr_adamw_step", p.numel(), _p(p), _p(g), _p(m), _p(v), lr, beta1, beta2, eps, step, _p(gnorm_sq), clip,
+             grad_mult, _p(skipped), _p(_chk(span_end)), _p(_chk(span_wd)), span_end.numel(), _stream())
 
 
 # ---- features --------------------------------------------------------------------------

@@ -111,6 +111,143 @@ class Adam:
         checkpoint.load_optimizer_state_dict(self._core, {"optimizer": sd, "_step": max(steps) if steps else 0})
 
 
+def get_optimizer_params_nodecay(model_named_params, weight_decay):
+    """asr/optimizers.py:128-146: two parameter groups -- names containing "bias", "LayerNorm.bias" or "LayerNorm.weight" get no
+    weight decay"""
+    nodecay_keys = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
+    named = list(model_named_params)
+    nodecay = lambda n: any(nd in n for nd in nodecay_keys)
+    return [{"params": [p for n, p in named if not nodecay(n)], "weight_decay": weight_decay},
+            {"params": [p for n, p in named if nodecay(n)], "weight_decay": 0.0}]
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW's interface over the arena (lm/train_lm.py:188-195): decoupled weight decay, any number of parameter
+    groups with their own `weight_decay` (the two of get_optimizer_params_nodecay), ONE learning rate (ScheduledOptimizer writes
+    the same rate into every group).  A parameter whose .grad is None when step() runs has never been part of the loss (the LM's
+    pooler): it is left bit-identical and gets no state entry, as torch skips it.  Once a parameter HAS had a gradient it takes part
+    in every later step (with a zero gradient where its .grad is None again: decay and moment decay still apply, where torch would
+    skip that one step) -- the fused update walks the arena, not a per-step list.  state_dict() / load_state_dict() speak torch's
+    layout: parameter indices run through group 0 first, then group 1."""
+
+    def __init__(self, params, lr=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        params = list(params)
+        if not (params and isinstance(params[0], dict)):
+            params = [{"params": params}]
+        self.param_groups = [dict({"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay, "amsgrad": False},
+                                  **dict(g, params=list(g["params"]))) for g in params]
+        for g in self.param_groups[1:]:
+            assert tuple(g["betas"]) == tuple(self.param_groups[0]["betas"]) and g["eps"] == self.param_groups[0]["eps"], \
+                "emoasr_amd.optimizers.AdamW: the groups share betas and eps (one fused update over the arena)"
+        self._core = None
+        self._pending = None
+        self.clip_grad_norm = 0.0
+        self.grad_mult = 1.0
+        self._unclaimed = 0
+        self._seen = set()     # ids of the parameters that have had a gradient at a step (they own optimizer state)
+
+    def _all_params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _can_bind(self):
+        from .engine import arena_of
+        try:
+            arena_of(self._all_params())
+            return True
+        except LookupError:
+            return False
+
+    def _bind(self):
+        from .engine import arena_of
+        from .train import ArenaAdamW
+        arena = arena_of(self._all_params())
+        if self._core is not None:
+            assert self._core.arena is arena, "the model was re-bound to a new arena after the optimizer took its first step"
+            return self._core
+        name_of = {id(p): n for n, p in zip(arena.names, arena.params)}
+        mine = self._all_params()
+        assert len(mine) == len(arena.params) and all(id(p) in name_of for p in mine), \
+            "emoasr_amd.optimizers.AdamW: the parameter groups must hold every parameter of the model exactly once"
+        self._name_of = name_of
+        decay_of = {name_of[id(p)]: g["weight_decay"] for g in self.param_groups for p in g["params"]}
+        g0 = self.param_groups[0]
+        self._core = ArenaAdamW(arena, lambda step: self.param_groups[0]["lr"], decay_of, betas=g0["betas"], eps=g0["eps"])
+        if self._pending is not None:
+            self._load(self._pending)
+            self._pending = None
+        return self._core
+
+    def step(self):
+        core = self._bind()
+        for p in self._all_params():
+            if p.grad is not None:
+                self._seen.add(id(p))
+        core.set_active(self._name_of[i] for i in self._seen)
+        core.clip = float(self.clip_grad_norm)
+        core.step(grad_mult=self.grad_mult)
+
+    def zero_grad(self, set_to_none=False):
+        if self._core is not None or self._can_bind():
+            self._bind().zero_grad()
+
+    def _groups_out(self):
+        out, k = [], 0
+        for g in self.param_groups:
+            n = len(g["params"])
+            out.append(dict({key: v for key, v in g.items() if key != "params"}, params=list(range(k, k + n))))
+            k += n
+        return out
+
+    def state_dict(self):
+        if self._core is None and not self._can_bind():
+            return self._pending or {"state": {}, "param_groups": self._groups_out()}
+        core = self._bind()
+        self.fold_skipped()     # (keeps the count pending for the wrapping scheduler: ScheduledOptimizer.fold_skipped)
+        arena, state = core.arena, {}
+        if core._step > 0:
+            for i, p in enumerate(self._all_params()):
+                if id(p) in self._seen:
+                    n = self._name_of[id(p)]
+                    o, v = arena.offsets[n], arena.pviews[n]
+                    state[i] = {"step": torch.tensor(float(core._step)),
+                                "exp_avg": core.m[o:o + v.numel()].view(v.shape).detach().cpu().clone(),
+                                "exp_avg_sq": core.v[o:o + v.numel()].view(v.shape).detach().cpu().clone()}
+        return {"state": state, "param_groups": self._groups_out()}
+
+    def load_state_dict(self, sd):
+        if self._core is None and not self._can_bind():
+            self._pending = sd
+        else:
+            self._bind()
+            self._load(sd)
+        for g, src in zip(self.param_groups, sd.get("param_groups") or []):
+            for k in ("lr", "betas", "eps", "weight_decay"):
+                if k in src:
+                    g[k] = tuple(src[k]) if k == "betas" else src[k]
+
+    def _load(self, sd):
+        core, arena = self._core, self._core.arena
+        mine = self._all_params()
+        st = sd.get("state", {})
+        bad = [i for i in st if not (isinstance(i, int) and 0 <= i < len(mine))]
+        assert not bad, f"optimizer state holds entries for parameters the model does not have: {bad[:5]}"
+        core.m.zero_()
+        core.v.zero_()
+        self._seen = set()
+        steps = []
+        for i, p in enumerate(mine):
+            if i in st:
+                n = self._name_of[id(p)]
+                o, v = arena.offsets[n], arena.pviews[n]
+                assert tuple(st[i]["exp_avg"].shape) == tuple(v.shape), f"optimizer state of {n}: shape {tuple(st[i]['exp_avg'].shape)}"
+                core.m[o:o + v.numel()].view(v.shape).copy_(st[i]["exp_avg"])
+                core.v[o:o + v.numel()].view(v.shape).copy_(st[i]["exp_avg_sq"])
+                self._seen.add(id(p))
+                steps.append(int(st[i]["step"]))
+        core._step = max(steps) if steps else 0
+        core._active = None
+
+
 def _warmup_ramp(peak, warm, step):
     return (peak / max(1.0, warm)) * step
 

@@ -112,6 +112,44 @@ class ArenaAdam:
         self.v.copy_(sd["v"])
 
 
+class ArenaAdamW(ArenaAdam):
+    """torch.optim.AdamW on the arena (lm/train_lm.py:188-195): decoupled decay per parameter from a span table on the device, one
+    norm launch and one update launch per step (csrc/optim.hip: adamw_kernel).  `decay_of`: {parameter name: weight decay};
+    `active`: names of the parameters that take part -- the others (never given a gradient) stay bit-identical, parameter and
+    moments, as torch skips `grad is None`."""
+
+    def __init__(self, arena, lr_fn, decay_of, betas=(0.9, 0.999), eps=1e-8, clip_grad_norm=0.0):
+        super().__init__(arena, lr_fn, betas=betas, eps=eps, weight_decay=0.0, clip_grad_norm=clip_grad_norm)
+        self.decay_of = dict(decay_of)
+        self._active = None
+        self._table = None
+
+    def set_active(self, names):
+        names = frozenset(names)
+        if names == self._active:
+            return
+        arena = self.arena
+        ends, wds = [], []
+        for k, n in enumerate(arena.names):      # arena order: slot k ends where slot k + 1 begins (64-element aligned)
+            ends.append(arena.offsets[arena.names[k + 1]] if k + 1 < len(arena.names) else arena.size)
+            wds.append(float(self.decay_of[n]) if n in names else -1.0)
+        assert ends[-1] == arena.flat.numel() and all(e % 64 == 0 for e in ends[:-1])
+        dev = arena.flat.device
+        self._table = (torch.tensor(ends, dtype=torch.int64).to(dev), torch.tensor(wds, dtype=torch.float32).to(dev))
+        self._active = names
+
+    def step(self, grad_mult=1.0):
+        assert self._table is not None, "ArenaAdamW.set_active(names) first"
+        self._step += 1
+        self.lr = self.lr_fn(self._step)
+        self.nsq.zero_()
+        from . import ops
+        ops.sqnorm(self.arena.grad, self.nsq)
+        ops.adamw_step(self.arena.flat, self.arena.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                       self._step, self._table[0], self._table[1], gnorm_sq=self.nsq, clip=self.clip, grad_mult=grad_mult,
+                       skipped=self.skipped)
+
+
 def _world(group=None):
     import torch.distributed as dist
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1

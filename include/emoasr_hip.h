@@ -377,6 +377,8 @@ int emoasr_scale_dropout(int dtype, long n, const void* x, void* y, float scale,
  * transformer.py:43-45); pe f32 [>=T, N] or NULL (conformer.py:49: scale only) */
 int emoasr_posenc(int dtype, int B, int T, int N, const void* x, const float* pe, float scale,
                   float drop_p, uint64_t seed, void* y, void* stream);
+/* dx[i] = dy[i] * act'(pre[i])  (act: EMOASR_ACT_*; pre = the saved pre-activation) */
+int emoasr_act_bwd(int dtype, long n, int act, const void* dy, const void* pre, void* dx, void* stream);
 /* y[i] = a[i] + b[i] */
 int emoasr_add(int dtype, long n, const void* a, const void* b, void* y, void* stream);
 
@@ -583,6 +585,21 @@ int emoasr_rnnt_coef(int B, int T, int U, int Lmax, const float* lse, const floa
                      const float* gscale_dev, float* coef, int* ycol, void* stream);
 int emoasr_rnnt_head_grad(int dtype, int nrows, int V, int J, const void* h, const void* w, const float* bias, const float* coef,
                           const int* ycol, int blank, void* dz, long lddz, void* stream);
+/* Cross-entropy vocabulary head WITHOUT the [rows, V] logits (the Transformer LM's output layer: lm/modeling/transformer.py:45-56,
+ * 79-99; bf16, V % 8 == 0, V >= 64, K % 64 == 0 -- the Python caller, ops.ce_head_ok, takes it from V >= 256 and 1 024 rows on).  The two epilogues of the transducer head above with occ = gamma_label = row
+ * weight and gamma_blank = 0:
+ *   emoasr_ce_head_fwd   z = x . w^T + bias is reduced in the product's epilogue: lse[n] = log sum_v exp z[n, v],
+ *                        logp[n] = z[n, y[n]] - lse[n] and (when loss != NULL) loss[n] = -wrow[n] * logp[n], with y[n] = labels[n]
+ *                        clamped into [0, V) -- rows with an ignored label (-100) carry wrow = 0.  ycol [nrows] receives y;
+ *                        part: scratch [ceil(V / 64), nrows, 2] f32; zscr: scratch [2 * nrows] f32.
+ *   emoasr_ce_head_grad  dz[n, :] = s[n] * (exp(z[n, :] - lse[n]) - [v == ycol[n]]), s[n] = wrow[n] * gscale [* *gscale_dev], for
+ *                        the nrows rows of one row chunk, z RECOMPUTED from x; coef: scratch [nrows, 4] f32.  The caller walks the
+ *                        rows in chunks (dz chunk -> emoasr_gemm_nn / emoasr_gemm_tn), so at most one chunk of dz exists. */
+int emoasr_ce_head_fwd(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias, const int* labels,
+                       const float* wrow, float* part, float* zscr, int* ycol, float* lse, float* logp, float* loss, void* stream);
+int emoasr_ce_head_grad(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias, const float* lse,
+                        const int* ycol, const float* wrow, float gscale, const float* gscale_dev, float* coef, void* dz, long lddz,
+                        void* stream);
 /* out[m] = argmax_v x[m,:V] (first maximum) */
 int emoasr_argmax_rows(int dtype, int M, int V, const void* x, long ldx, int* out, void* stream);
 /* out[0] = first i < n with x[i] != value (-1: none), out[1] = x[that i] (value: none) -- the windowed greedy
@@ -920,6 +937,14 @@ int emoasr_adam_step(long n, float* p, const float* g, float* m, float* v, float
 int emoasr_adam_step_ex(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, const float* gnorm_sq, float clip, float grad_mult, int* skipped,
                         void* stream);
+/* torch.optim.AdamW (lm/train_lm.py:188-195) over the flat arena: p *= 1 - lr * wd, then the Adam update without the coupled
+ * decay term; clip / NaN skip / skipped counter as emoasr_adam_step_ex.  The arena is described by a span table on the DEVICE:
+ * span_end [nspans] (ascending element offsets, every one a multiple of 64 except the last = n; span k is
+ * [span_end[k-1], span_end[k])) and span_wd [nspans]: the span's weight decay, or a NEGATIVE value for a span the update leaves
+ * bit-identical (a parameter that never received a gradient: no decay, no moments -- torch skips `grad is None`). */
+int emoasr_adamw_step(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps,
+                      int step, const float* gnorm_sq, float clip, float grad_mult, int* skipped, const long* span_end,
+                      const float* span_wd, int nspans, void* stream);
 
 /* ---- on-GPU features --------------------------------------------------------- */
 /* SpecAugment (asr/spec_augment.py:39-95): zero (or fill) bands.  spans int32

@@ -1,0 +1,113 @@
+"""Transformer-LM training throughput and the vocabulary head A/B (fused = no [rows, V] logits, against materialised).
+
+    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100]
+
+Prints one JSON line:
+  train_tokens_per_s   real (unpadded) tokens per second of a full training step (forward, backward, clip + AdamW) of the 12-layer
+                       LM of bench.py (LM12: V = 10 000, d = 256) in bf16 at `--batch` sequences with Libri-like lengths, with the
+                       head the gates select, and the same with the materialised head (EMOASR_CE_HEAD_FUSED=0's path);
+  head_*_us            the head alone (loss rows forward + dX / dW / dbias backward) on that batch's rows, as same-box A/B pairs in
+                       ONE process: fused, materialised, fused, ... -- the medians and every pair's ratio.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+from types import SimpleNamespace
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LM12 = dict(lm_type="transformer", vocab_size=10000, hidden_size=256, num_layers=12, num_attention_heads=4,
+            intermediate_size=1024, max_seq_len=256)     # bench.py: LM12
+
+
+def libri_like_batch(batch, vocab, seed=0):
+    """next-token batch with sentence lengths like LibriSpeech transcripts in a 10 k word-piece vocabulary (median ~40 tokens,
+    a tail to ~120)"""
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.exp(torch.randn(batch, generator=g) * 0.55 + 3.65).clamp(4, 160).to(torch.int64).tolist()
+    N = max(lens)
+    ys = torch.full((batch, N), 2, dtype=torch.int64)
+    labels = torch.full((batch, N), -100, dtype=torch.int64)
+    for b, n in enumerate(lens):
+        y = torch.randint(3, vocab, (n + 1,), generator=g)
+        ys[b, :n], labels[b, :n] = y[:-1], y[1:]
+    return {"ys_in": ys, "ylens": torch.tensor(lens), "labels": labels}, sum(lens)
+
+
+def timed(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3     # us per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=100)
+    args = ap.parse_args()
+    from emoasr_amd import ops
+    from emoasr_amd.modeling.lm import LM
+    from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
+    from emoasr_amd.train_lm import train_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    params = SimpleNamespace(**dict(LM12, learning_rate=1e-4, lr_schedule_type="lindecay", num_warmup_steps=100, weight_decay=0.01,
+                                    clip_grad_norm=1.0, accum_grad=1, log_step=10 ** 9))
+    lm = LM(params, compute_dtype=torch.bfloat16).to(dev).train()
+    opt = ScheduledOptimizer(AdamW(get_optimizer_params_nodecay(list(lm.named_parameters()), params.weight_decay), lr=0,
+                                   weight_decay=params.weight_decay), params, num_total_steps=10 ** 6)
+    data, tokens = libri_like_batch(args.batch, LM12["vocab_size"])
+    rows = data["ys_in"].numel()
+    out = {"batch": args.batch, "tokens": tokens, "rows_padded": rows, "dtype": "bf16"}
+    step = lambda: train_step(lm, opt, data, params, dev, sync=False)
+    for fused in (True, False, True, False):
+        lm.fused_head = fused
+        timed(step, args.warmup)
+        us = timed(step, args.steps)
+        key = "train_tokens_per_s" if fused else "train_tokens_per_s_materialised"
+        out.setdefault(key, []).append(round(tokens / us * 1e6))
+        out["head_taken" if fused else "head_taken_materialised"] = lm.last_head
+    # ---- the head alone on the same rows
+    d, V = LM12["hidden_size"], LM12["vocab_size"]
+    x = torch.randn(rows, d, device=dev).to(torch.bfloat16)
+    w = (torch.randn(V, d, device=dev) * 0.1).to(torch.bfloat16)
+    bias = torch.zeros(V, device=dev)
+    lab = data["labels"].clamp(min=0).to(torch.int32).view(-1).to(dev)
+    wrow = ((data["labels"] != -100).float() / tokens).view(-1).to(dev)
+    dw, db = torch.zeros(V, d, device=dev), torch.zeros(V, device=dev)
+
+    def fused_head():
+        _, _, ctx = ops.ce_head_fwd(x, w, bias, lab, wrow)
+        ops.ce_head_bwd(x, w, bias, ctx, dw, db)
+
+    def materialised_head():
+        logits, _ = ops.gemm_nt_lse(x, w, bias)
+        _, dz = ops.lsm_loss(logits, lab, wrow, 0.0, True)
+        ops.gemm_tn(dz, x, out=dw, accumulate=True, colsum=db)
+        ops.gemm_nn(dz, w)
+
+    out["head_fused_ok"] = bool(ops.ce_head_ok(x, w))
+    fu, ma = [], []
+    timed(fused_head, 3), timed(materialised_head, 3)
+    for _ in range(args.pairs):
+        fu.append(timed(fused_head, 10))
+        ma.append(timed(materialised_head, 10))
+    out["head_fused_us"], out["head_materialised_us"] = round(statistics.median(fu), 1), round(statistics.median(ma), 1)
+    out["head_pair_ratio_fused_over_materialised"] = [round(a / b, 3) for a, b in zip(fu, ma)]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
