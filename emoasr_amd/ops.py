@@ -1020,12 +1020,13 @@ def rnnt_forward(logits, labels, elens, ylens, blank):
     return (lse, lpb, lpy, alpha, beta), nll
 
 
-def rnnt_head_forward(h, w, bias, B, T, U, labels, elens, ylens, blank, lattice_stream=None):
+def rnnt_head_forward(h, w, bias, B, T, U, labels, elens, ylens, blank, lattice_stream=None, rows_per_launch=None):
     """the transducer's output layer + loss lattice WITHOUT the [B,T,U,V] logits: h [B*T*U, J] (bf16), w [V, J]
     -> ctx tuple (lse, lpb, lpy, alpha, beta) f32 [B,T,U], nll f32 [B]   (as rnnt_forward)
     lattice_stream: a torch side stream for the fold + lattice launches (2 B blocks of one wave row each: ~190 us of a mostly
     idle chip); -> (ctx, nll, event, keep) then -- the caller waits for `event` on its own stream before it reads ctx / nll and
-    holds `keep` (scratch the side stream still reads) until then"""
+    holds `keep` (scratch the side stream still reads) until then
+    rows_per_launch: a multiple of 256 that replaces the 4 GiB row step (tests: the launches with row0 > 0 at small sizes)"""
     N, J = h.shape
     V = w.shape[0]
     dev = h.device
@@ -1037,6 +1038,9 @@ def rnnt_head_forward(h, w, bias, B, T, U, labels, elens, ylens, blank, lattice_
     ycol = torch.empty(N, device=dev, dtype=torch.int32)
     lib.call("emoasr_rnnt_ycol", B, T, U, labels.shape[1], _p(labels), _p(ylens), _p(ycol), _stream())
     step = max(1, min(N, ((1 << 31) // (J * 2)) // 256 * 256))   # rows per launch: the operand stays below 4 GiB
+    if rows_per_launch is not None:
+        assert rows_per_launch > 0 and rows_per_launch % 256 == 0 and rows_per_launch * J * 2 < (1 << 32), rows_per_launch
+        step = rows_per_launch
     for r0 in range(0, N, step):
         n = min(step, N - r0)
         lib.call("emoasr_rnnt_head_fwd", dt(h), r0, n, T, U, V, J, labels.shape[1], _p(h[r0:r0 + n]), _p(w), _p(bias), _p(labels),
