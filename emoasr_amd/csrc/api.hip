@@ -63,6 +63,7 @@ void emo_gemm_set_big_bm(int v);
 void emo_gemm_set_big_korder(int v);
 void emo_gemm_set_big_min_tiles(int v);
 void emo_conv_set_dwconv_lds(int v);
+void emo_conv_set_strip(int v);
 void emo_layer_set_conv_fused(int v);
 void emo_layer_set_wgrad_side(int v);
 void emo_layer_set_stack_launch(int v);
@@ -177,6 +178,7 @@ extern "C" int emoasr_set_option(const char* name, int value) {
   if (strcmp(name, "big_korder") == 0) { emo_gemm_set_big_korder(value); return 0; }
   if (strcmp(name, "big_min_tiles") == 0) { emo_gemm_set_big_min_tiles(value); return 0; }
   if (strcmp(name, "dwconv_lds") == 0) { emo_conv_set_dwconv_lds(value); return 0; }
+  if (strcmp(name, "conv_strip") == 0) { emo_conv_set_strip(value); return 0; }
   if (strcmp(name, "conv_fused") == 0) { emo_layer_set_conv_fused(value); return 0; }
   if (strcmp(name, "wgrad_side") == 0) { emo_layer_set_wgrad_side(value); return 0; }
   if (strcmp(name, "stack_launch") == 0) { emo_layer_set_stack_launch(value); return 0; }

@@ -88,7 +88,7 @@ constexpr int BNF_CH = 16, BNF_G = 64;  // channels x groups of partial blocks p
   EmoScratch* tsc_ = emo_stream_scratch(EMO_SCRATCH_BN_TICKETS, (void*)(stream_), 2 * 64 * sizeof(unsigned)); \
   if (!tsc_) return 1;                                                                            \
   unsigned* tickets_ = static_cast<unsigned*>(tsc_->dev)
-__global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(int B_, int Tn_, int C, const float* __restrict__ part_,
+__global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(int B_, int Tn_, int C, float* __restrict__ part_,
                                                                  float* __restrict__ mean_, float* __restrict__ var_,
                                                                  float* __restrict__ running_mean,
                                                                  float* __restrict__ running_var, float momentum,
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(int B_, int Tn_
   // applies all segments' updates.  sg.n <= 1: the one dense batch (B_, Tn_).
   const int ns = sg.n > 1 ? sg.n : 1, si = blockIdx.y;
   const int B = sg.n > 1 ? sg.b0[si + 1] - sg.b0[si] : B_, Tn = sg.n > 1 ? sg.T[si] : Tn_;
-  const float* part = sg.n > 1 ? part_ + sg.part[si] : part_;
+  float* part = sg.n > 1 ? part_ + sg.part[si] : part_;
   float* mean = mean_ + (long)si * C;
   float* var = var_ + (long)si * C;
   const int nx = (Tn + DW_TT - 1) / DW_TT, nblk = B * nx;
@@ -141,6 +141,9 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(int B_, int Tn_
     for (int g = 0; g < BNF_G; ++g) m2sum += red[g][lane];
     mean[c] = mu;
     var[c] = m2sum / M;
+    // stacked: the exact sum for the block that applies the running update (var * M is a rounding away from it); this block
+    // was the only reader of its channels' partials and has finished with them
+    if (sg.n > 1) part[c] = m2sum;
   }
   if (!running_mean && !running_var && !num_batches_tracked) return;
   // ---- running statistics, in segment order, by the last block of this channel group ------------------------------------------------
@@ -157,9 +160,9 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(int B_, int Tn_
     for (int k = 0; k < ns; ++k) {
       const float Mk = sg.n > 1 ? (float)(sg.row[k + 1] - sg.row[k]) : M;
       const float mk = __hip_atomic_load(mean_ + (long)k * C + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float vk = __hip_atomic_load(var_ + (long)k * C + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // biased: M2 / M
-      // (the own segment's sum is at hand exactly -- a dense batch updates bit for bit as before; the others' come back from var)
-      const float m2k = k == si ? m2sum : vk * Mk;
+      // every segment's centred sum exactly (the others' from their blocks' stash in the partial table): each update is bit for
+      // bit the one of a separate dense pass
+      const float m2k = k == si ? m2sum : __hip_atomic_load(part_ + sg.part[k] + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       rm = (1.f - momentum) * rm + momentum * (k == si ? mu : mk);
       rv = (1.f - momentum) * rv + momentum * (Mk > 1.f ? m2k / (Mk - 1.f) : m2k / Mk);
     }
@@ -559,7 +562,7 @@ extern "C" int emoasr_bn_stats_finalize(int B, int Tn, int C, const float* part,
   EMO_CHECK(B * Tn > 0, "bn_stats_finalize: empty batch");
   EMO_CHECK(cdiv(C, BNF_CH) <= 64, "bn_stats_finalize: C=%d too wide for the ticket table", C);
   EMO_BN_TICKETS(stream);
-  bn_stats_finalize_kernel<<<cdiv(C, BNF_CH), 1024, 0, (hipStream_t)stream>>>(B, Tn, C, part, mean, var, running_mean,
+  bn_stats_finalize_kernel<<<cdiv(C, BNF_CH), 1024, 0, (hipStream_t)stream>>>(B, Tn, C, const_cast<float*>(part), mean, var, running_mean,
                                                                           running_var, momentum, num_batches_tracked, RowSegs{}, tickets_);
   EMO_LAUNCH_CHECK();
   return 0;
@@ -673,7 +676,7 @@ extern "C" int emoasr_bn_swish_bwd(int dtype, int M, int C, const void* dz, cons
 }
 
 // ---- stacked micro-batches: the BatchNorm kernels over all segments in one launch each (called by csrc/convfused.hip) -----------
-int emo_bn_stats_finalize_seg(const RowSegs& sg, int C, const float* part, float* mean, float* var, float* running_mean,
+int emo_bn_stats_finalize_seg(const RowSegs& sg, int C, float* part, float* mean, float* var, float* running_mean,
                               float* running_var, float momentum, long long* nbt, hipStream_t s) {
   EMO_CHECK(cdiv(C, BNF_CH) <= 64, "bn_stats_finalize: C=%d too wide for the ticket table", C);
   EMO_BN_TICKETS(s);

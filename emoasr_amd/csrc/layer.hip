@@ -17,7 +17,7 @@ void emo_attn_bwd_join(void* stream);
 int emo_attn_bwd_prelaunch(int dtype, const emoasr_attn_t* a, void* ws, size_t ws_bytes, float* zero, long zn, void* stream);
 
 // csrc/convmodule.hip: the BatchNorm kernels over ALL stacked micro-batches in one launch each (any dtype)
-int emo_bn_stats_finalize_seg(const RowSegs& sg, int C, const float* part, float* mean, float* var, float* running_mean,
+int emo_bn_stats_finalize_seg(const RowSegs& sg, int C, float* part, float* mean, float* var, float* running_mean,
                               float* running_var, float momentum, long long* nbt, hipStream_t s);
 int emo_bn_swish_fwd_seg_dt(int dtype, const RowSegs& sg, int C, const void* y, const float* mean, const float* var,
                             const float* gamma, const float* beta, float eps, void* z, hipStream_t s);

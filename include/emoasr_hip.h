@@ -49,6 +49,9 @@ int emoasr_version(void);
  * large-tile kernel: 0 off, 1 = N 512 from K 512 and N 256 from K 2048, 2 = N 256 from K 512 as well), "big_waves" (8 / 4),
  * "big_bm", "big_min_tiles", "gemm_wide128", "ln_fwd8", "ln_bwd_pf", "ln_bwd_blocks", "conv1_pair", "lstm_coop", "decode_coop",
  * "rnnt_greedy_coop" -- every default is what the training step (or the decode leg) measured fastest;
+ * "conv_strip" (32-frame tiles a workgroup of the fused convolution-module kernels walks, keeping the halo in LDS: 0 = by the
+ * number of live strips of the launch -- the smallest n <= 8 that leaves at most two workgroups per CU --, n >= 1 = n tiles
+ * (values above 65536 count as 65536), 1 = one tile per workgroup; a negative value counts as 0);
  * "timers" (see emoasr_timer_read) */
 int emoasr_set_option(const char* name, int value);
 /* Device time of selected kernels that sit behind composite entry points, measured with HIP events on the launch stream
@@ -758,7 +761,10 @@ size_t emoasr_conformer_layer_bwd_ws_bytes(int dtype, int B, int T, int d, int H
  * csrc/convfused.hip).  Same arithmetic as emoasr_glu_dwconv_fwd + emoasr_bn_stats_finalize + emoasr_bn_swish_fwd (forward) and
  * emoasr_bn_swish_bwd_sums + emoasr_conv_bwd_fused (backward) called once per segment, in order: the depthwise convolution sees each
  * segment's own zero padding, BatchNorm takes its batch statistics per segment (bmean / bvar [n, C]) and moves the running
- * statistics once per segment.  g / dg [M, 2C], c / z / dz [M, C]; part: the segments' emoasr_dwconv_stats_floats areas back to back;
+ * statistics once per segment, each update bit for bit the one of emoasr_bn_stats_finalize on that segment.  g / dg [M, 2C],
+ * c / z / dz [M, C]; part: the segments' emoasr_dwconv_stats_floats areas back to back -- scratch: with more than one segment the
+ * merge CONSUMES it (it leaves every segment's centred sum of squares in the first C floats of the segment's area; the dense
+ * emoasr_bn_stats_finalize leaves `part` as it found it);
  * scratch sizes from emoasr_conv_module_bwd_seg_scratch_floats (which = 0: BatchNorm sums, 1: depthwise weight-gradient partials).
  * Reference: conformer.py:126-133 and its autograd. */
 int emoasr_conv_module_fwd_seg(int dtype, const emoasr_segments_t* seg, int C, int K, const void* g, const float* w,
