@@ -1,4 +1,5 @@
 // Library-level plumbing: error strings, version, run-time options.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -45,54 +46,27 @@ void emo_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-void emo_gemm_set_tr_read(int v);
-void emo_gemm_set_tile(int v);
-void emo_gemm_set_tn_group_blocks(int v);
-void emo_gemm_set_tn_group_kb(int v);
-void emo_gemm_set_tn_place(int v);
-void emo_gemm_set_tn_big(int v);
-void emo_gemm_set_tn_big_blocks(int v);
-void emo_gemm_set_wholek(int v);
-void emo_gemm_set_kb(int v);
-void emo_gemm_set_xcd(int v);
-void emo_gemm_set_split_tile(int v);
-void emo_gemm_set_split_kb(int v);
-void emo_gemm_set_split_min128(int v);
-void emo_gemm_set_conv_big(int v);
-void emo_gemm_set_big_bm(int v);
-void emo_gemm_set_big_korder(int v);
-void emo_gemm_set_big_min_tiles(int v);
-void emo_conv_set_dwconv_lds(int v);
-void emo_conv_set_strip(int v);
-void emo_layer_set_conv_fused(int v);
-void emo_layer_set_wgrad_side(int v);
-void emo_layer_set_stack_launch(int v);
-void emo_layer_set_ffn_save_dact(int v);
-void emo_layer_set_att_bits(int v);
-void emo_ln_set_fwd8(int v);
-void emo_gemm_set_wide128(int v);
-void emo_gemm_set_big_n256(int v);
-void emo_gemm_set_big_waves(int v);
-void emo_conv1_set_pair(int v);
-void emo_attn_set_prelaunch(int v);
-void emo_ln_set_bwd_pf(int v);
-void emo_ln_set_bwd_blocks(int v);
-void emo_rnnt_set_greedy_coop(int v);
-void emo_rnnt_set_beam_mfma(int v);
-void emo_decode_set_coop(int v);
-void emo_lstm_set_coop(int v);
-void emo_decode_set_coop_merge(int v);
-void emo_attn_set_tr_read(int v);
-void emo_attn_set_fw(int v);
-void emo_attn_set_fwd4(int v);
-void emo_attn_set_q2(int v);
-void emo_attn_set_bwd_split(int v);
-void emo_attn_set_side(int v);
-void emo_attn_set_side_prio(int v);
-void emo_attn_set_lpt(int v);
-void emo_attn_set_fwd_split(int v);
-void emo_attn_set_xcd(int v);
-void emo_attn_set_fwd_waves(int v);
+// ---- run-time options: the list of common.h -------------------------------------------------------------------------------
+EmoOptions g_opt = {
+#define EMO_OPT_DEFAULT(name, def, norm, doc) def,
+    EMO_OPTIONS(EMO_OPT_DEFAULT)
+#undef EMO_OPT_DEFAULT
+};
+namespace {
+struct OptionEntry { const char* name; int EmoOptions::*field; int def; int (*norm)(int); };
+const OptionEntry kOptions[] = {
+#define EMO_OPT_ENTRY(name, def, norm, doc) {#name, &EmoOptions::name, def, [](int v) -> int { return norm; }},
+    EMO_OPTIONS(EMO_OPT_ENTRY)
+#undef EMO_OPT_ENTRY
+};
+constexpr int kOptionCount = sizeof(kOptions) / sizeof(kOptions[0]);
+const OptionEntry* find_option(const char* name) {
+  for (const OptionEntry& o : kOptions)
+    if (strcmp(name, o.name) == 0) return &o;
+  emo_set_error("unknown option '%s'", name);
+  return nullptr;
+}
+}  // namespace
 
 // ---- kernel timers: HIP-event pairs around selected launches, on the stream they are launched on -----------------------
 // (bench.py's roofline object needs the live device time of ONE kernel that sits behind a composite entry point;
@@ -103,15 +77,14 @@ const char* const kTimerNames[EMO_TIMER_COUNT] = {"attn_bwd_fused_kernel", "attn
                                                   "gemm_tn_grouped_kernel", "gemm_nt_nn", "gemm_tn", "layernorm", "conv_module"};
 struct TimerRec { hipEvent_t e0, e1; double flops, bytes; bool ended; };
 std::vector<TimerRec> g_rec[EMO_TIMER_COUNT];
-int g_timers_on = 0;
-int g_timer_stride = 1;              // record every n-th launch of a family only (option "timer_stride"): an event pair per launch
-long g_timer_seen[EMO_TIMER_COUNT];  // costs ~2 % of the step for the 208-launch GEMM family; 1 in 7 is a uniform sample of its shapes
+long g_timer_seen[EMO_TIMER_COUNT];  // option "timer_stride" records every n-th launch of a family only: an event pair per launch
+                                     // costs ~2 % of the step for the 208-launch GEMM family; 1 in 7 is a uniform sample of its shapes
 bool g_timer_open[EMO_TIMER_COUNT];
-bool timer_on(int id) { return g_timers_on == 1 || (g_timers_on > 1 && ((g_timers_on >> (id + 1)) & 1)); }
+bool timer_on(int id) { return g_opt.timers == 1 || (g_opt.timers > 1 && ((g_opt.timers >> (id + 1)) & 1)); }
 }  // namespace
 void emo_timer_begin(int id, hipStream_t s, double flops, double bytes) {
   if (!timer_on(id)) return;
-  g_timer_open[id] = (g_timer_seen[id]++ % g_timer_stride) == 0;
+  g_timer_open[id] = (g_timer_seen[id]++ % g_opt.timer_stride) == 0;
   if (!g_timer_open[id]) return;
   TimerRec r{};
   hipEventCreate(&r.e0);
@@ -156,59 +129,17 @@ extern "C" int emoasr_timer_read(const char* name, int* calls, double* ms, int r
 extern "C" const char* emoasr_last_error(void) { return g_err; }
 extern "C" int emoasr_version(void) { return 1; }
 extern "C" int emoasr_set_option(const char* name, int value) {
-  if (strcmp(name, "tr_read") == 0) {
-    emo_gemm_set_tr_read(value);
-    emo_attn_set_tr_read(value);
-    return 0;
-  }
-  if (strcmp(name, "gemm_tile") == 0) { emo_gemm_set_tile(value); return 0; }
-  if (strcmp(name, "tn_group_blocks") == 0) { emo_gemm_set_tn_group_blocks(value); return 0; }
-  if (strcmp(name, "tn_group_kb") == 0) { emo_gemm_set_tn_group_kb(value); return 0; }
-  if (strcmp(name, "tn_place") == 0) { emo_gemm_set_tn_place(value); return 0; }
-  if (strcmp(name, "tn_big") == 0) { emo_gemm_set_tn_big(value); return 0; }
-  if (strcmp(name, "tn_big_blocks") == 0) { emo_gemm_set_tn_big_blocks(value); return 0; }
-  if (strcmp(name, "gemm_wholek") == 0) { emo_gemm_set_wholek(value); return 0; }
-  if (strcmp(name, "gemm_kb") == 0) { emo_gemm_set_kb(value); return 0; }
-  if (strcmp(name, "gemm_xcd") == 0) { emo_gemm_set_xcd(value); return 0; }
-  if (strcmp(name, "split_tile") == 0) { emo_gemm_set_split_tile(value); return 0; }
-  if (strcmp(name, "split_kb") == 0) { emo_gemm_set_split_kb(value); return 0; }
-  if (strcmp(name, "split_min128") == 0) { emo_gemm_set_split_min128(value); return 0; }
-  if (strcmp(name, "conv_big") == 0) { emo_gemm_set_conv_big(value); return 0; }
-  if (strcmp(name, "big_bm") == 0) { emo_gemm_set_big_bm(value); return 0; }
-  if (strcmp(name, "big_korder") == 0) { emo_gemm_set_big_korder(value); return 0; }
-  if (strcmp(name, "big_min_tiles") == 0) { emo_gemm_set_big_min_tiles(value); return 0; }
-  if (strcmp(name, "dwconv_lds") == 0) { emo_conv_set_dwconv_lds(value); return 0; }
-  if (strcmp(name, "conv_strip") == 0) { emo_conv_set_strip(value); return 0; }
-  if (strcmp(name, "conv_fused") == 0) { emo_layer_set_conv_fused(value); return 0; }
-  if (strcmp(name, "wgrad_side") == 0) { emo_layer_set_wgrad_side(value); return 0; }
-  if (strcmp(name, "stack_launch") == 0) { emo_layer_set_stack_launch(value); return 0; }
-  if (strcmp(name, "ffn_save_dact") == 0) { emo_layer_set_ffn_save_dact(value); return 0; }
-  if (strcmp(name, "attn_mask_bits") == 0) { emo_layer_set_att_bits(value); return 0; }
-  if (strcmp(name, "attn_prelaunch") == 0) { emo_attn_set_prelaunch(value); return 0; }
-  if (strcmp(name, "conv1_pair") == 0) { emo_conv1_set_pair(value); return 0; }
-  if (strcmp(name, "big_waves") == 0) { emo_gemm_set_big_waves(value); return 0; }
-  if (strcmp(name, "big_n256") == 0) { emo_gemm_set_big_n256(value); return 0; }
-  if (strcmp(name, "gemm_wide128") == 0) { emo_gemm_set_wide128(value); return 0; }
-  if (strcmp(name, "ln_fwd8") == 0) { emo_ln_set_fwd8(value); return 0; }
-  if (strcmp(name, "ln_bwd_pf") == 0) { emo_ln_set_bwd_pf(value); return 0; }
-  if (strcmp(name, "ln_bwd_blocks") == 0) { emo_ln_set_bwd_blocks(value); return 0; }
-  if (strcmp(name, "rnnt_greedy_coop") == 0) { emo_rnnt_set_greedy_coop(value); return 0; }
-  if (strcmp(name, "rnnt_beam_mfma") == 0) { emo_rnnt_set_beam_mfma(value); return 0; }
-  if (strcmp(name, "decode_coop") == 0) { emo_decode_set_coop(value); return 0; }
-  if (strcmp(name, "lstm_coop") == 0) { emo_lstm_set_coop(value); return 0; }
-  if (strcmp(name, "decode_coop_merge") == 0) { emo_decode_set_coop_merge(value); return 0; }
-  if (strcmp(name, "attn_fw") == 0) { emo_attn_set_fw(value); return 0; }
-  if (strcmp(name, "attn_fwd4") == 0) { emo_attn_set_fwd4(value); return 0; }
-  if (strcmp(name, "attn_q2") == 0) { emo_attn_set_q2(value); return 0; }
-  if (strcmp(name, "attn_bwd_split") == 0) { emo_attn_set_bwd_split(value); return 0; }
-  if (strcmp(name, "attn_side") == 0) { emo_attn_set_side(value); return 0; }
-  if (strcmp(name, "attn_side_prio") == 0) { emo_attn_set_side_prio(value); return 0; }
-  if (strcmp(name, "attn_lpt") == 0) { emo_attn_set_lpt(value); return 0; }
-  if (strcmp(name, "attn_fwd_split") == 0) { emo_attn_set_fwd_split(value); return 0; }
-  if (strcmp(name, "attn_xcd") == 0) { emo_attn_set_xcd(value); return 0; }
-  if (strcmp(name, "attn_fwd_waves") == 0) { emo_attn_set_fwd_waves(value); return 0; }
-  if (strcmp(name, "timers") == 0) { g_timers_on = value; return 0; }
-  if (strcmp(name, "timer_stride") == 0) { g_timer_stride = value > 0 ? value : 1; return 0; }
-  emo_set_error("unknown option '%s'", name);
-  return 1;
+  const OptionEntry* o = find_option(name);
+  if (!o) return 1;
+  g_opt.*(o->field) = o->norm(value);
+  return 0;
 }
+extern "C" int emoasr_get_option(const char* name, int* value, int* default_value) {
+  const OptionEntry* o = find_option(name);
+  if (!o) return 1;
+  if (value) *value = g_opt.*(o->field);
+  if (default_value) *default_value = o->def;
+  return 0;
+}
+extern "C" int emoasr_option_count(void) { return kOptionCount; }
+extern "C" const char* emoasr_option_name(int index) { return index >= 0 && index < kOptionCount ? kOptions[index].name : nullptr; }

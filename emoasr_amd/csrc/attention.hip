@@ -3220,20 +3220,10 @@ int set_smem(K kernel, int bytes) {
   return 0;
 }
 
-int g_tr = 1;
-int g_q2 = 1;         // option "attn_q2": the query pass reads the dS image the key pass wrote (attn_bwd_q2_kernel) instead of recomputing it
-int g_bwd_split = 1;  // option "attn_bwd_split": the two-pass backward (attn_bwd_kv_kernel + attn_bwd_q_kernel); 0 = the single-pass kernel
-int g_fused_fw = 0;  // key tiles per workgroup of the single-pass backward (0 = by grid size; emoasr_set_option "attn_fw")
-
-int g_fwd4 = 1;       // option "attn_fwd4": the block-staged forward (attn_fwd4_kernel) for the training launches
-int g_fwd_split = 1;  // option "attn_fwd_split": key split for small launches
-int g_fwd_waves = 0;  // option "attn_fwd_waves": waves per workgroup of attn_fwd_kernel (0 = 1 for stacked launches, else 4)
-int g_attn_xcd = 1;   // option "attn_xcd": stacked forward / fused-backward launches keep a (head, utterance) group on one XCD
-int g_attn_lpt = 1;   // option "attn_lpt": 0 = segments in stacking order
 // dispatch order of a stacked launch's segments: longest first (stable), see seg_of_slot
 void fill_seg_order(emoasr_attn_t& a) {
   for (int k = 0; k < EMOASR_MAX_SEGMENTS; ++k) a.seg_order[k] = k;
-  if (a.nseg > 1 && g_attn_lpt)
+  if (a.nseg > 1 && g_opt.attn_lpt)
     std::stable_sort(a.seg_order, a.seg_order + a.nseg, [&](int x, int y) { return a.seg_T[x] > a.seg_T[y]; });
 }
 int check_args(const emoasr_attn_t* a, int dtype) {
@@ -3280,9 +3270,9 @@ int launch_fwd(const emoasr_attn_t& a_in, hipStream_t s) {
   if constexpr (std::is_same<TK, bf16>::value) {
     constexpr int FW = 4;
     const long ntile = (long)cdiv(a.Tq, 32) * a.H * a.B;
-    if (g_fwd4 && a.pos && !a.causal && !a.st && a.Tq == a.Tk && ((a.Tq >= 64 && ntile > 4L * n_cu) || g_fwd4 == 2)) {   // (option value 2: whenever eligible -- tests)
+    if (g_opt.attn_fwd4 && a.pos && !a.causal && !a.st && a.Tq == a.Tk && ((a.Tq >= 64 && ntile > 4L * n_cu) || g_opt.attn_fwd4 == 2)) {   // (option value 2: whenever eligible -- tests)
       dim3 g4(cdiv(a.Tq, 32 * FW), a.H, a.B);
-      const int nt4 = (g_attn_xcd && a.nseg > 1) ? (int)g4.x : 0;
+      const int nt4 = (g_opt.attn_xcd && a.nseg > 1) ? (int)g4.x : 0;
       if (nt4) g4 = dim3(8 * cdiv(a.H * a.B, 8) * nt4, 1, 1);
       emo_timer_begin(EMO_TIMER_ATTN_FWD, s);
 #define EMO_FWD4_LAUNCH(TR_, DM_)                                                                  \
@@ -3291,7 +3281,7 @@ int launch_fwd(const emoasr_attn_t& a_in, hipStream_t s) {
     attn_fwd4_kernel<TR_, FW, DM_><<<g4, 64 * FW, Fwd4Cfg<FW>::smem(), s>>>(a, nt4);                \
   } while (0)
       const int dm = a.drop_p > 0.f ? (a.keep_mask ? 1 : 2) : 0;   // no dropout / keep-mask bits / inline hash
-      if (g_tr) { if (dm == 1) EMO_FWD4_LAUNCH(true, 1); else if (dm == 2) EMO_FWD4_LAUNCH(true, 2); else EMO_FWD4_LAUNCH(true, 0); }
+      if (g_opt.tr_read) { if (dm == 1) EMO_FWD4_LAUNCH(true, 1); else if (dm == 2) EMO_FWD4_LAUNCH(true, 2); else EMO_FWD4_LAUNCH(true, 0); }
       else      { if (dm == 1) EMO_FWD4_LAUNCH(false, 1); else if (dm == 2) EMO_FWD4_LAUNCH(false, 2); else EMO_FWD4_LAUNCH(false, 0); }
 #undef EMO_FWD4_LAUNCH
       emo_timer_end(EMO_TIMER_ATTN_FWD, s);
@@ -3299,18 +3289,18 @@ int launch_fwd(const emoasr_attn_t& a_in, hipStream_t s) {
       return 0;
     }
   }
-  const bool split = g_fwd_split && a.nseg <= 1 && !a.st && (long)cdiv(a.Tq, 32) * a.H * a.B <= 2L * n_cu;
+  const bool split = g_opt.attn_fwd_split && a.nseg <= 1 && !a.st && (long)cdiv(a.Tq, 32) * a.H * a.B <= 2L * n_cu;
   const int ks = split ? 4 : 1;
-  const int nw = split ? 4 : (g_fwd_waves ? g_fwd_waves : (a.nseg > 1 ? 1 : 4));
+  const int nw = split ? 4 : (g_opt.attn_fwd_waves ? g_opt.attn_fwd_waves : (a.nseg > 1 ? 1 : 4));
   const int smem = nw * fwd_wave_bytes<TK>();
   dim3 grid(cdiv(a.Tq, split ? 32 : 32 * nw), a.H, a.B);   // (stacked micro-batches: Tq = the longest segment, B = all utterances)
   // stacked launches: 1-D, the query tiles of one (head, utterance) on one XCD (attn_block)
-  const int nt = (g_attn_xcd && a.nseg > 1) ? (int)grid.x : 0;
+  const int nt = (g_opt.attn_xcd && a.nseg > 1) ? (int)grid.x : 0;
   if (nt) grid = dim3(8 * cdiv(a.H * a.B, 8) * nt, 1, 1);
   // at most one wave per SIMD: see attn_fwd_kernel (not for the split type: two prefetch sets of (hi, lo) fragments spill)
   const bool one_round = !kSplit<TK> && (long)grid.x * grid.y * grid.z * nw <= 4L * n_cu;
   emo_timer_begin(EMO_TIMER_ATTN_FWD, s);
-  if (g_tr) {
+  if (g_opt.tr_read) {
     if (one_round) {
       if (set_smem(attn_fwd_kernel<TK, true, true>, smem)) return 1;
       attn_fwd_kernel<TK, true, true><<<grid, 64 * nw, smem, s>>>(a, nt, ks);
@@ -3463,23 +3453,21 @@ FusedExtras g_fused_extras{};
 //   emo_attn_bwd_defer_join(1)   that call leaves the table gradient running on the side stream; emo_attn_bwd_join(stream) makes
 //                                `stream` wait for it (csrc/layer.hip: right before the grouped weight-gradient launch)
 // Callers that know nothing of this (ops.attn_bwd) get the join inside the call: same stream semantics as before.
-int g_attn_side = 1;
-int g_side_prio = 0;
 hipStream_t g_side = nullptr;
 hipEvent_t g_ev_fork = nullptr, g_ev_join = nullptr, g_ev_mask = nullptr;
 bool g_join_pending = false, g_defer_join = false;
 struct MaskTag { const void* buf = nullptr; uint64_t seed = 0; long nrows = -1; float p = 0.f; } g_mask_tag;
 
 bool side_ready() {
-  if (!g_attn_side) return false;
+  if (!g_opt.attn_side) return false;
   if (g_side) return true;
   // option "attn_side_prio" = 1: the side stream at the LOWEST priority -- its launches (keep mask, Q + bias copies, table gradient)
   // are low-occupancy fillers that should take idle slots, not compete with the chain's kernels for dispatch
   int lo = 0, hi = 0;
   hipError_t ce = hipSuccess;
-  if (g_side_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) ce = hipStreamCreateWithPriority(&g_side, hipStreamNonBlocking, lo);
+  if (g_opt.attn_side_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) ce = hipStreamCreateWithPriority(&g_side, hipStreamNonBlocking, lo);
   else ce = hipStreamCreateWithFlags(&g_side, hipStreamNonBlocking);
-  if (ce != hipSuccess) { g_side = nullptr; g_attn_side = 0; return false; }
+  if (ce != hipSuccess) { g_side = nullptr; g_opt.attn_side = 0; return false; }   // (the option reads 0 from here on)
   hipEventCreateWithFlags(&g_ev_fork, hipEventDisableTiming);
   hipEventCreateWithFlags(&g_ev_join, hipEventDisableTiming);
   hipEventCreateWithFlags(&g_ev_mask, hipEventDisableTiming);
@@ -3536,7 +3524,7 @@ void launch_dpos3(const emoasr_attn_t& a, const FusedWs& ws, hipStream_t s) {
     const int T_ = a.nseg > 1 ? a.seg_T[k] : a.Tq, nt = cdiv(T_, 32);
     pl.wg0[k + 1] = pl.wg0[k] + a.H * (2 * nt - 1) * pl.nch;
   }
-  if (g_tr) attn_bwd_dpos3_kernel<T, true><<<pl.wg0[nseg], 256, 0, s>>>(a, ws, pl);
+  if (g_opt.tr_read) attn_bwd_dpos3_kernel<T, true><<<pl.wg0[nseg], 256, 0, s>>>(a, ws, pl);
   else attn_bwd_dpos3_kernel<T, false><<<pl.wg0[nseg], 256, 0, s>>>(a, ws, pl);
 }
 
@@ -3549,7 +3537,7 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
   const long nqd = nrows * a.H * DK;
   side_join(s);   // (a table gradient left on the side stream by a caller that never joined: it used this workspace)
   FusedWs ws{};
-  const bool want_mask = g_bwd_split && a.drop_p > 0.f && !a.keep_mask;
+  const bool want_mask = g_opt.attn_bwd_split && a.drop_p > 0.f && !a.keep_mask;
   const FusedLayout lay = fused_layout<T>(a, want_mask);
   EMO_CHECK(lay.total <= bytes, "attn_bwd_fused: workspace too small (%zu < %zu bytes)", bytes, lay.total);
   ws.dq_slab = nqd;
@@ -3565,7 +3553,7 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
     ws.qu = a.q; ws.qv = a.q; ws.ldqu = a.ldq;
   }
   unsigned* maskbuf = nullptr;
-  const bool ext_mask = a.keep_mask != nullptr && a.drop_p > 0.f && g_bwd_split;   // (the single-pass kernel hashes inline: same mask)   // the forward's bits (emoasr_attn_dropmask): nothing to hash here
+  const bool ext_mask = a.keep_mask != nullptr && a.drop_p > 0.f && g_opt.attn_bwd_split;   // (the single-pass kernel hashes inline: same mask)   // the forward's bits (emoasr_attn_dropmask): nothing to hash here
   if (ext_mask) {
     ws.mask_nw = a.keep_nw;
     ws.mask = a.keep_mask;
@@ -3584,7 +3572,7 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
   ws.stamp = stamp_calls++ == 0 ? d_stamp : nullptr;   // the first (eager) call only: later calls may be under stream capture
 #endif
   // prepared ahead of time on the side stream (emo_attn_bwd_prelaunch)?  Then this prologue computes delta only.
-  const bool prepared = g_bwd_split && g_mask_tag.buf == mem && g_mask_tag.seed == a.seed && g_mask_tag.nrows == nrows &&
+  const bool prepared = g_opt.attn_bwd_split && g_mask_tag.buf == mem && g_mask_tag.seed == a.seed && g_mask_tag.nrows == nrows &&
                         g_mask_tag.p == a.drop_p;
   if (prepared) {
     hipStreamWaitEvent(s, g_ev_mask, 0);
@@ -3602,13 +3590,13 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
   }
   const long nb4 = (long)cdiv(a.Tk, 128) * a.H * a.B, nb2 = (long)cdiv(a.Tk, 64) * a.H * a.B;
-  const int fw = g_fused_fw ? g_fused_fw : ((nb4 > n_cu && nb2 <= 2 * n_cu) ? 2 : 4);
-  if (g_bwd_split) {
+  const int fw = g_opt.attn_fw ? g_opt.attn_fw : ((nb4 > n_cu && nb2 <= 2 * n_cu) ? 2 : 4);
+  if (g_opt.attn_bwd_split) {
     // two passes, two workgroups per CU each (see attn_bwd_kv_kernel); no dQ partial slabs, no finalize launch
     constexpr int FW = 4;
     using SC = SplitCfg<T, FW>;
     dim3 gk(cdiv(a.Tk, 32 * FW), a.H, a.B), gq(cdiv(a.Tq, 32 * FW), a.H, a.B);
-    const int ntk = (g_attn_xcd && a.nseg > 1) ? (int)gk.x : 0, ntq = (g_attn_xcd && a.nseg > 1) ? (int)gq.x : 0;
+    const int ntk = (g_opt.attn_xcd && a.nseg > 1) ? (int)gk.x : 0, ntq = (g_opt.attn_xcd && a.nseg > 1) ? (int)gq.x : 0;
     if (ntk) gk = dim3(8 * cdiv(a.H * a.B, 8) * ntk, 1, 1);
     if (ntq) gq = dim3(8 * cdiv(a.H * a.B, 8) * ntq, 1, 1);
     emo_timer_begin(EMO_TIMER_ATTN_BWD_MAIN, s);
@@ -3629,10 +3617,10 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
       attn_bwd_q_kernel<T, TR_, REL_, FW><<<gq, 64 * FW, SC::q_smem(REL_), s>>>(a, ws, ntq);                        \
     }                                                                                                               \
   } while (0)
-    const bool use_q2 = g_q2 && rel && sizeof(T) == 2;
+    const bool use_q2 = g_opt.attn_q2 && rel && sizeof(T) == 2;
     ws.img_from_kv = use_q2 ? 1 : 0;
-    if (rel) { if (g_tr) EMO_KV_LAUNCH(true, true); else EMO_KV_LAUNCH(false, true); }
-    else     { if (g_tr) EMO_KV_LAUNCH(true, false); else EMO_KV_LAUNCH(false, false); }
+    if (rel) { if (g_opt.tr_read) EMO_KV_LAUNCH(true, true); else EMO_KV_LAUNCH(false, true); }
+    else     { if (g_opt.tr_read) EMO_KV_LAUNCH(true, false); else EMO_KV_LAUNCH(false, false); }
     // the position-table gradient (+ its cast for the weight-gradient product): on the side stream when there is one
     hipStream_t st2 = s;
     const bool forked = rel && a.dpos && side_ready();
@@ -3650,8 +3638,8 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
     };
     // (forked right behind the KEY pass -- which writes the dS image since R6 -- the table gradient ran beside the query pass and
     // both stretched by what was hidden: query pass 2.93 -> 3.51 ms per step, the step 26.19 against 26.27 ms; it stays behind both)
-    if (rel) { if (g_tr) EMO_Q_LAUNCH(true, true); else EMO_Q_LAUNCH(false, true); }
-    else     { if (g_tr) EMO_Q_LAUNCH(true, false); else EMO_Q_LAUNCH(false, false); }
+    if (rel) { if (g_opt.tr_read) EMO_Q_LAUNCH(true, true); else EMO_Q_LAUNCH(false, true); }
+    else     { if (g_opt.tr_read) EMO_Q_LAUNCH(true, false); else EMO_Q_LAUNCH(false, false); }
 #undef EMO_KV_LAUNCH
 #undef EMO_Q_LAUNCH
     emo_timer_end(EMO_TIMER_ATTN_BWD_MAIN, s);
@@ -3702,9 +3690,9 @@ int launch_bwd_fused(const emoasr_attn_t& a_in, char* mem, size_t bytes, hipStre
   do {                                                                                             \
     const int smem = FusedCfg<T, FW_>::smem_bytes(REL_);                                           \
     dim3 grid(cdiv(a.Tk, 32 * FW_), a.H, a.B);                                                     \
-    const int nt = (g_attn_xcd && a.nseg > 1) ? (int)grid.x : 0;   /* key blocks of one (head, utterance) on one XCD */ \
+    const int nt = (g_opt.attn_xcd && a.nseg > 1) ? (int)grid.x : 0;   /* key blocks of one (head, utterance) on one XCD */ \
     if (nt) grid = dim3(8 * cdiv(a.H * a.B, 8) * nt, 1, 1);                                        \
-    if (g_tr) { if (set_smem(attn_bwd_fused_kernel<T, true, REL_, FW_>, smem)) return 1;           \
+    if (g_opt.tr_read) { if (set_smem(attn_bwd_fused_kernel<T, true, REL_, FW_>, smem)) return 1;           \
                 attn_bwd_fused_kernel<T, true, REL_, FW_><<<grid, 64 * FW_, smem, s>>>(a, ws, nt); }   \
     else      { if (set_smem(attn_bwd_fused_kernel<T, false, REL_, FW_>, smem)) return 1;          \
                 attn_bwd_fused_kernel<T, false, REL_, FW_><<<grid, 64 * FW_, smem, s>>>(a, ws, nt); }  \
@@ -3762,25 +3750,21 @@ void emo_attn_bwd_fused_extras(float* zero, long zn, const float* cast_src, void
   g_fused_extras = FusedExtras{zero, zn, cast_src, cast_dst, cn};
 }
 
-void emo_attn_set_side(int v) { g_attn_side = v ? 1 : 0; }
-void emo_attn_set_side_prio(int v) { g_side_prio = v ? 1 : 0; }   // (takes effect when the side stream is created)
 void emo_attn_bwd_defer_join(int v) { g_defer_join = v != 0; }
 // With the keep mask handed over by the forward (round 6) the prelaunch has only the Q + bias copies left (~6 us of the call's own
 // prologue), and a fork + a join of the side stream cost the main queue ~6 us EACH (the kernel sequence of the step shows the bubbles):
-// 1 = prelaunch only when there is a mask to hash.  Option "attn_prelaunch" (value 1 = always prelaunch, as before).
-int g_prelaunch_mask_only = 1;
-void emo_attn_set_prelaunch(int v) { g_prelaunch_mask_only = v ? 0 : 1; }
+// option "attn_prelaunch" 0 = prelaunch only when there is a mask to hash (1 = always prelaunch, as before).
 void emo_attn_bwd_join(void* stream) { side_join((hipStream_t)stream); }
 // Everything of the next emoasr_attn_bwd_fused(a, ws) call that depends on FORWARD data only, now, on the side stream: the keep
 // mask (with dropout), the dense Q + pos_bias_u / Q + pos_bias_v copies, the clearing of the position-table gradient (zero, zn).
 // No-op without a side stream; the call itself does whatever was not prepared.
 int emo_attn_bwd_prelaunch(int dtype, const emoasr_attn_t* a_in, void* ws, size_t ws_bytes, float* zero, long zn, void* stream) {
-  if (dtype != EMO_BF16 || !g_bwd_split || !side_ready()) return 0;
+  if (dtype != EMO_BF16 || !g_opt.attn_bwd_split || !side_ready()) return 0;
   emoasr_attn_t a = *a_in;
   fill_seg_order(a);
   const bool rel = a.pos != nullptr, want_mask = a.drop_p > 0.f && !a.keep_mask;
   if (!rel && !want_mask) return 0;
-  if (!want_mask && g_prelaunch_mask_only) return 0;   // option "attn_prelaunch": see g_prelaunch_mask_only
+  if (!want_mask && !g_opt.attn_prelaunch) return 0;   // (see above emo_attn_bwd_join)
   const FusedLayout lay = fused_layout<bf16>(a, want_mask);
   if (lay.total > ws_bytes) return 0;
   const long nrows = a.nseg > 1 ? a.seg_row[a.nseg] : (long)a.B * a.Tq;
@@ -3800,15 +3784,6 @@ int emo_attn_bwd_prelaunch(int dtype, const emoasr_attn_t* a_in, void* ws, size_
   EMO_LAUNCH_CHECK();
   return 0;
 }
-void emo_attn_set_tr_read(int v) { g_tr = v; }
-void emo_attn_set_lpt(int v) { g_attn_lpt = v; }
-void emo_attn_set_fwd_split(int v) { g_fwd_split = v; }
-void emo_attn_set_fwd4(int v) { g_fwd4 = v; }
-void emo_attn_set_xcd(int v) { g_attn_xcd = v; }
-void emo_attn_set_fwd_waves(int v) { g_fwd_waves = (v == 1 || v == 2 || v == 4) ? v : 0; }
-void emo_attn_set_bwd_split(int v) { g_bwd_split = v ? 1 : 0; }
-void emo_attn_set_q2(int v) { g_q2 = v ? 1 : 0; }
-void emo_attn_set_fw(int v) { g_fused_fw = (v == 2 || v == 4) ? v : 0; }
 
 extern "C" long emoasr_attn_dropmask_words(int Tk) { return cdiv(Tk, 32); }
 // The keep mask of one attention launch as bits, for its forward AND its backward (emoasr_attn_t::keep_mask).  When the library has
@@ -3876,7 +3851,7 @@ extern "C" int emoasr_attn_bwd(int dtype, const emoasr_attn_t* a, void* stream) 
   // products split; the GEMMs behind it (dV, dK, dpos) follow the same option inside gemm.hip
   if (dtype == EMO_F32X3 && a->pdT && !a->st) return launch_bwd_tr<float, true, f32s>(*a, (hipStream_t)stream, dtype);
   EMO_DISPATCH(dtype, {
-    if (g_tr) return (launch_bwd_tr<T, true>(*a, (hipStream_t)stream, dtype));
+    if (g_opt.tr_read) return (launch_bwd_tr<T, true>(*a, (hipStream_t)stream, dtype));
     return (launch_bwd_tr<T, false>(*a, (hipStream_t)stream, dtype));
   });
   return 0;

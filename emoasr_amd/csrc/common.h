@@ -497,6 +497,73 @@ EmoScratch* emo_stream_scratch(int slot, void* stream, size_t bytes);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---------------------------------------------------------------------------
+// Run-time options: ONE list.  EMO_OPTIONS(X) calls X(name, default, normalisation, description) per option; the fields of
+// EmoOptions, the defaults of g_opt and the name table behind emoasr_set_option / emoasr_get_option / emoasr_option_name
+// (api.hip) are all expansions of it, so adding or retiring an option is one line here.  `normalisation` is an expression in
+// the value `v` a caller sets; what it yields is what is stored, what the use sites read as g_opt.<name> and what
+// emoasr_get_option reports.  Why a default is what it is stands next to the code that reads the option.
+// Options are process-wide plain ints, read at launch time without synchronisation: set them while no call of the library is
+// in flight on any thread.
+// ---------------------------------------------------------------------------
+constexpr int LN_BWD8_MAXBLK = 2048;  // layernorm.hip, N % 8 == 0 backward: 8 rows (one per half-wave) in flight each; 1024 blocks: 9.3 us + a 26 us fold per step, 512: 8.5 + 15, 256: 9.9 + 8
+#define EMO_OPTIONS(X)                                                                                                              \
+  X(tr_read, 1, v, "1 = ds_read_b64_tr_b16 operand reads (products and attention), 0 = the scalar fallback")                       \
+  X(gemm_tile, 0, v, "tile of the NT / NN / grouped TN products (1 = 128x128, 2 = 128x64, 3 = 64x64; 0 = rule)")                    \
+  X(gemm_kb, 0, v, "k depth of the bf16 products (1 = BK 32, 2 = BK 64; 0 = rule)")                                                \
+  X(gemm_xcd, 1, v, "XCD-aware block order of the products")                                                                       \
+  X(gemm_wholek, 1, v, "whole-K staging for M <= 2048, K % 256 == 0")                                                              \
+  X(gemm_wide128, 0, v ? 1 : 0, "stacked row counts: 64x64 tiles only below N = 512 (default: below 768)")                          \
+  X(tn_group_blocks, 0, v > 0 ? v : 0, "block budget of a grouped TN launch (0 = auto)")                                            \
+  X(tn_group_kb, 0, (v == 1 || v == 2) ? v : 0, "k depth of a grouped TN launch (0 = gemm_kb, else by tile)")                       \
+  X(tn_place, 0, v != 0, "grouped TN launch: whole k slices dealt to the XCDs, largest first")                                           \
+  X(tn_big, 1, v != 0, "bf16 TN products with N2 % 256 == 0, N1 >= 256 on the eight-wave 256x256 tile (gemm_big_tn.hip)")           \
+  X(tn_big_blocks, 0, (v >= 64 && v <= 1024) ? v : 0, "block budget of a 256-tile TN launch (64..1024; 0 = default)")               \
+  X(split_tile, 0, (v >= 1 && v <= 3) ? v : 0, "tile of the split (f32x3) NT / NN products (1 = 128x128, 2 = 128x64, 3 = 64x64; 0 = rule)") \
+  X(split_kb, 1, v == 2 ? 2 : 1, "2 = BK 64 for split reductions of K >= 512")                                                     \
+  X(split_min128, 512, v > 0 ? v : 512, "128x128 split tiles from this many tiles on")                                             \
+  X(conv_big, 1, v, "the large-tile NT kernel (gemm_big.hip) for the products and Conv2d launches it wants")                         \
+  X(big_bm, 0, v, "tile height of the large-tile kernel (0 = by round efficiency)")                                                \
+  X(big_korder, 1, v, "gathered Conv2d products of the large-tile kernel: 1 = channel chunk outermost, taps innermost; 0 = tap-major")\
+  X(big_min_tiles, 2000, v, "plain products go to the large-tile kernel from this many 128x256 tiles on")                           \
+  X(big_waves, 8, v == 4 ? 4 : 8, "8 (2 x 4 waves, 64 columns each) or 4 (2 x 2 waves, 128 columns each)")                          \
+  X(big_n256, 2, v < 0 ? 0 : v, "long reductions onto one / two 256-column tiles (0 off, 1, 2: gemm_big.hip)")                      \
+  X(dwconv_lds, 1, v, "depthwise stencil with the time tile staged through LDS (bf16)")                                            \
+  X(conv_strip, 0, v > 0 ? std::min(v, 1 << 16) : 0, "32-frame tiles per strip of the fused convolution-module kernels (0 = by live strips)") \
+  X(conv_fused, 1, v, "bf16: the fused convolution-module kernels (convfused.hip)")                                                \
+  X(conv1_pair, 1, v ? 1 : 0, "bf16, C = 256: the first Conv2d forward takes two output frames per workgroup")                                    \
+  X(wgrad_side, 0, v ? 1 : 0, "the layer backward's grouped weight-gradient launch on a side stream (layer.hip)")                   \
+  X(stack_launch, 1, v, "stacked micro-batches: all segments in one launch per kernel")                                            \
+  X(ffn_save_dact, 1, v ? 1 : 0, "feed-forward blocks save Swish'(u) * dropout_scale instead of u")                                 \
+  X(attn_mask_bits, 1, v ? 1 : 0, "the layer hashes its attention keep mask once, as bits, in the forward")                         \
+  X(attn_prelaunch, 0, v ? 1 : 0, "1 = the attention backward always prelaunches on the side stream, 0 = only to hash a mask")      \
+  X(attn_fw, 0, (v == 2 || v == 4) ? v : 0, "key tiles per workgroup of the single-pass attention backward (0 = by grid size)")     \
+  X(attn_fwd4, 1, v, "the block-staged forward (attn_fwd4_kernel) for the training launches (2 = whenever eligible)")              \
+  X(attn_fwd_split, 1, v, "key split for small forward launches")                                                                  \
+  X(attn_fwd_waves, 0, (v == 1 || v == 2 || v == 4) ? v : 0, "waves per workgroup of attn_fwd_kernel (0 = 1 for stacked launches, else 4)") \
+  X(attn_q2, 1, v ? 1 : 0, "the query pass reads the dS image the key pass wrote instead of recomputing it")                        \
+  X(attn_bwd_split, 1, v ? 1 : 0, "the two-pass backward; 0 = the single-pass kernel")                                             \
+  X(attn_side, 1, v ? 1 : 0, "side stream of the two-pass backward")                                                               \
+  X(attn_side_prio, 0, v ? 1 : 0, "the side stream at the lowest priority (takes effect when it is created)")                      \
+  X(attn_lpt, 1, v, "stacked launches dispatch the longest segment first (0 = stacking order)")                                    \
+  X(attn_xcd, 1, v, "stacked launches keep a (head, utterance) group on one XCD")                                                  \
+  X(ln_fwd8, 1, v ? 1 : 0, "the half-wave-per-row LayerNorm forward for M > 4096 rows")                                            \
+  X(ln_bwd_pf, 1, v ? 1 : 0, "the LayerNorm backward requests the next row before it reduces the current one")                      \
+  X(ln_bwd_blocks, 512, std::max(64, std::min(v, LN_BWD8_MAXBLK)), "persistent blocks of the N % 8 == 0 LayerNorm backward (64..LN_BWD8_MAXBLK)") \
+  X(rnnt_greedy_coop, 1, v, "the cooperative transducer greedy search")                                                            \
+  X(rnnt_beam_mfma, 1, v ? 1 : 0, "bf16 LSTM / joint steps of the transducer beam search on the matrix cores")                      \
+  X(decode_coop, 1, v, "the cooperative decoder / LM step kernels")                                                                \
+  X(decode_coop_merge, 1, v, "projection + self-attention in one stage: bit 0 the decoder stack, bit 1 the LM stack")              \
+  X(lstm_coop, 1, v, "the cooperative LSTM sequence kernels")                                                                      \
+  X(timers, 0, v, "HIP-event timers: 0 off, 1 every family, else a bit mask (1 << (id + 1))")                                      \
+  X(timer_stride, 1, v > 0 ? v : 1, "record every n-th launch of a timer family only")
+struct EmoOptions {
+#define EMO_OPT_FIELD(name, def, norm, doc) int name;
+  EMO_OPTIONS(EMO_OPT_FIELD)
+#undef EMO_OPT_FIELD
+};
+extern EmoOptions g_opt;   // (api.hip; constant-initialised with the defaults above)
+
 // HIP-event timers around selected kernels (api.hip; read with emoasr_timer_read, enabled by option "timers")
 enum { EMO_TIMER_ATTN_BWD_MAIN = 0, EMO_TIMER_ATTN_BWD_DPOS = 1, EMO_TIMER_ATTN_FWD = 2, EMO_TIMER_TN_GROUPED = 3,
        EMO_TIMER_GEMM_NT_NN = 4, EMO_TIMER_GEMM_TN = 5, EMO_TIMER_LAYERNORM = 6, EMO_TIMER_CONV_MODULE = 7,

@@ -405,8 +405,6 @@ int emo_dwconv_bwd_w_reduce(int nblk, int C, int K, const float* part, float* dw
 // Tiles per strip (option "conv_strip"): n >= 1 forces n, 1 is the one-tile-per-workgroup schedule; 0 = the smallest S <= 8
 // that brings the launch's live strips to at most two workgroups per CU (both kernels keep two resident; a longer strip
 // stages fewer halo rows and writes fewer partial rows, a shorter one leaves no CU without work).
-static int g_conv_strip = 0;
-void emo_conv_set_strip(int v) { g_conv_strip = v > 0 ? std::min(v, 1 << 16) : 0; }
 namespace {
 long live_strips(int n, const int* B, const int* T, int S) {
   long r = 0;
@@ -414,7 +412,7 @@ long live_strips(int n, const int* B, const int* T, int S) {
   return r;
 }
 int strip_tiles(int n, const int* B, const int* T, int cy) {
-  if (g_conv_strip > 0) return g_conv_strip;
+  if (g_opt.conv_strip > 0) return g_opt.conv_strip;
   static int cus = 0;
   if (!cus) {
     int dev = 0, v = 0;

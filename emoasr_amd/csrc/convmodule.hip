@@ -516,10 +516,8 @@ inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 8192 ? 8
 // convfused.hip: the same stencil with the time tile staged through LDS by 16-byte loads (bf16; bit-identical results)
 int emo_dwconv_lds(int B, int Tn, int C, int K, const void* x, const float* w, const float* bias, void* y, int flip,
                    float* part, hipStream_t s);
-static int g_dwconv_lds = 1;
-void emo_conv_set_dwconv_lds(int v) { g_dwconv_lds = v; }
 static bool use_lds(int dtype, int Tn, int C) {
-  return g_dwconv_lds && dtype == EMO_BF16 && C % 8 == 0 && (long)Tn * C * 2 < (1L << 32);
+  return g_opt.dwconv_lds && dtype == EMO_BF16 && C % 8 == 0 && (long)Tn * C * 2 < (1L << 32);
 }
 int emo_dwconv_bwd_w_reduce(int nblk, int C, int K, const float* part, float* dw, float* dbias, hipStream_t s) {
   dwconv_bwd_w_reduce_kernel<<<dim3(cdiv((K + 1) * C, 64), nblk >= 1024 ? 4 : 1), 256, 0, s>>>(nblk, C, K, part, dw, dbias);

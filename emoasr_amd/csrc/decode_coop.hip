@@ -804,10 +804,9 @@ __global__ __launch_bounds__(CT) void dec_step_coop_kernel(const DecCoopArgs a) 
   }
 }
 
-int g_decode_coop = 1;
-int g_coop_merge = 1;   // projection + self-attention in one stage where the shapes allow: bit 0 the decoder stack (339 -> 322 us),
-                        // bit 1 the LM stack (351 -> 351 us: the later arrival of 15 of the 16 weight fragments and the four-fold
-                        // projection eat the barrier it saves; off) -- option "decode_coop_merge"
+// option "decode_coop_merge": projection + self-attention in one stage where the shapes allow: bit 0 the decoder stack (339 -> 322 us),
+// bit 1 the LM stack (351 -> 351 us: the later arrival of 15 of the 16 weight fragments and the four-fold projection eat the
+// barrier it saves; off)
 
 // device scratch of the two chains (0: decoder, 1: LM), allocated on first use -- which must not be inside a stream capture: the
 // search's eager warm-up pass (modeling/beam_search_device.py) comes first
@@ -846,8 +845,6 @@ bool plan_ok(int N, int K) {
 }  // namespace
 
 static long g_coop_launches[2] = {0, 0};
-void emo_decode_set_coop(int v) { g_decode_coop = v; }
-void emo_decode_set_coop_merge(int v) { g_coop_merge = v; }
 
 // The kernels are launched with <<<>>> (they are replayed from HIP graphs), so the co-residency of the CG workgroups their grid
 // barrier assumes is verified once here: occupancy x compute units >= CG for all four instantiations.
@@ -870,7 +867,7 @@ static bool coop_resident() {
 
 // Can the cooperative kernels take this step?  (bf16, <= 16 hypotheses, <= 12 / 8 layers, shapes that fit the plans)
 bool emo_decode_coop_ok(int dtype, int nb, int nl, int max_layers, int d, int H, int F, int T) {
-  return g_decode_coop && coop_resident() && dtype == EMO_BF16 && nb >= 1 && nb <= 16 && nl >= 1 && nl <= max_layers && d <= C_MAXD && F <= C_MAXF &&
+  return g_opt.decode_coop && coop_resident() && dtype == EMO_BF16 && nb >= 1 && nb <= 16 && nl >= 1 && nl <= max_layers && d <= C_MAXD && F <= C_MAXF &&
          d % H == 0 && (d / H) % 8 == 0 && d / H <= 64 && nb * H <= C_MAXPAIR && (T + 63) / 64 <= C_MAXCHUNK && plan_ok(3 * d, d) &&
          plan_ok(d, d) && plan_ok(F, d) && plan_ok(d, F);
 }
@@ -885,7 +882,7 @@ int emo_bert_lm_step_coop(int nl, const emoasr_bert_layer_t* layers, const emoas
   a.kcache = (bf16*)io->kcache; a.vcache = (bf16*)io->vcache; a.transform = io->transform; a.out_hidden = (bf16*)out_hidden;
   a.B = *B;
   for (int i = 0; i < nl; ++i) a.layers[i] = layers[i];
-  if ((g_coop_merge & 2) && qkv_merge_ok(a.d, a.H)) lm_step_coop_kernel<true><<<CG, CT, 0, s>>>(a);
+  if ((g_opt.decode_coop_merge & 2) && qkv_merge_ok(a.d, a.H)) lm_step_coop_kernel<true><<<CG, CT, 0, s>>>(a);
   else lm_step_coop_kernel<false><<<CG, CT, 0, s>>>(a);
   EMO_LAUNCH_CHECK();
   ++g_coop_launches[1];
@@ -923,7 +920,7 @@ int emo_transformer_decoder_step_coop(int nl, const emoasr_decoder_layer_t* laye
   a.kcache = (bf16*)io->kcache; a.vcache = (bf16*)io->vcache; a.kmem = io->kmem; a.out_x = (bf16*)out_x;
   a.B = *B;
   for (int i = 0; i < nl; ++i) { a.layers[i] = layers[i]; a.kv[i] = io->kv[i]; }
-  if ((g_coop_merge & 1) && qkv_merge_ok(a.d, a.H)) dec_step_coop_kernel<true><<<CG, CT, 0, s>>>(a);
+  if ((g_opt.decode_coop_merge & 1) && qkv_merge_ok(a.d, a.H)) dec_step_coop_kernel<true><<<CG, CT, 0, s>>>(a);
   else dec_step_coop_kernel<false><<<CG, CT, 0, s>>>(a);
   EMO_LAUNCH_CHECK();
   ++g_coop_launches[0];

@@ -63,12 +63,6 @@ __device__ __forceinline__ void dgrad_row(const DgradGeom& g, int m, int& b, int
   j = r - i * g.nJ;
 }
 
-int g_tr_read = 1;
-int g_gemm_wholek = 1;   // option "gemm_wholek"
-int g_gemm_tile = 0, g_gemm_kb = 0, g_gemm_xcd = 1, g_tn_group_kb = 0, g_tn_place = 0, g_gemm_wide128 = 0;
-int g_tn_big = 1;         // bf16 TN products with N2 % 256 == 0, N1 >= 256 on the eight-wave 256x256 tile (gemm_big_tn.hip); "tn_big"
-int g_tn_big_blocks = 0;  // block budget of a 256-tile launch ("tn_big_blocks": 64..1024; 0 = default)
-int g_tn_group_blocks = 0;  // override of a grouped TN launch's block budget (emoasr_set_option "tn_group_blocks"; 0 = auto)
 // f32 products as three bf16 MFMAs over (hi, lo) operand pairs (see SplitCfg): asked for PER CALL by the dtype code EMO_F32X3.  The
 // entry points of this file note it here for the launch helpers below them (thread-local, for the duration of the call: two engines
 // in different modes on two streams, or an autograd thread, cannot see each other's mode)
@@ -78,9 +72,6 @@ struct SplitScope {
   explicit SplitScope(int dtype) : prev(t_f32_split) { t_f32_split = dtype == EMO_F32X3 ? 1 : 0; }
   ~SplitScope() { t_f32_split = prev; }
 };
-int g_split_tile = 0;       // option "split_tile": tile of the split NT / NN products (1 = 128x128 where it fills the chip twice, 2 = 128x64, 3 = 64x64; 0 = rule)
-int g_split_kb = 1;         // option "split_kb": 2 = BK 64 for split reductions of K >= 512
-int g_split_min128 = 512;   // option "split_min128": 128 x 128 split tiles from this many tiles on
 
 // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Reading
 // the linear id as (xcd, slot) makes XCD x work on ONE contiguous range of the logical block list, so
@@ -835,7 +826,7 @@ __global__ __launch_bounds__(256) void gemm_tn_grouped_kernel(const TnGroup G) {
 template <typename T, int AMODE, bool BKM, bool TR, bool SP = false>
 int launch_nt_(const NtArgs& a_in, hipStream_t s, int nz = 1) {
   NtArgs a = a_in;
-  a.xcd = g_gemm_xcd;
+  a.xcd = g_opt.gemm_xcd;
   if constexpr (SP) {
     // split products: the bf16 kernel's tile rule (128x64 while that fills the chip 1.5 times, else 64x64), BK = 32
     const long t12864 = (long)cdiv(a.M, 128) * cdiv(a.N, 64) * nz, t128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128) * nz;
@@ -844,10 +835,10 @@ int launch_nt_(const NtArgs& a_in, hipStream_t s, int nz = 1) {
     // ... and 128 x 128 with ONE register stage (two workgroups per CU; with the 3-deep ring it ran one wave per SIMD and lost)
     // where that tile still fills the chip: 16.70 against 17.12 ms per step
     (void)t12864;
-    int tile = (t128 >= g_split_min128 && a.N % 128 == 0) ? 1 : 3;
-    if (g_split_tile == 1 && a.N % 128 == 0) tile = 1;
-    else if (g_split_tile >= 2) tile = g_split_tile;
-    const int kb = (g_split_kb == 2 && a.K >= 512) ? 2 : 1;
+    int tile = (t128 >= g_opt.split_min128 && a.N % 128 == 0) ? 1 : 3;
+    if (g_opt.split_tile == 1 && a.N % 128 == 0) tile = 1;
+    else if (g_opt.split_tile >= 2) tile = g_opt.split_tile;
+    const int kb = (g_opt.split_kb == 2 && a.K >= 512) ? 2 : 1;
 #define EMO_SP_LAUNCH(BM_, BN_)                                                            \
   do {                                                                                     \
     dim3 grid(cdiv(a.N, BN_), cdiv(a.M, BM_), nz);                                         \
@@ -863,7 +854,7 @@ int launch_nt_(const NtArgs& a_in, hipStream_t s, int nz = 1) {
   }
   // Tile: 128x64 once that still gives >= 384 blocks (1.5 per CU), else 64x64.  (A 128x128 tile
   // was measured slower than 128x64 on every shape of the L2 model.)  k extent: BK = 64 for long
-  // bf16 reductions, 32 for K = 256.  g_gemm_tile / g_gemm_kb: tuning overrides (emoasr_set_option).
+  // bf16 reductions, 32 for K = 256.  g_opt.gemm_tile / g_opt.gemm_kb: tuning overrides (emoasr_set_option).
   const long t12864 = (long)cdiv(a.M, 128) * cdiv(a.N, 64) * nz;
   // ... and 64x64 again for the stacked row counts (M >= 16 k): with four to five rounds of blocks either way the smaller tile's
   // higher occupancy wins -- every instantiation of the training step 4-7 % faster in the kernel trace (6.92 -> 6.51 ms per step)
@@ -873,9 +864,9 @@ int launch_nt_(const NtArgs& a_in, hipStream_t s, int nz = 1) {
   // (round 6, after the attention kernels stopped hammering the CUs' vector-memory paths: the mixed rule IS faster inside the step --
   // 128-row tiles from N = 768 on, four A/B pairs on one box: 26.85 against 26.94 ms (N >= 512), 26.96 against 27.10 (all shapes);
   // one by one at 35 k rows: ffn1 with its epilogue 75.9 -> 72.6 us, qkv 40.5 -> 36.6, d_ffn2 48.8 -> 43.3, N = 256 products 8 % slower)
-  const bool stacked64 = AMODE == 0 && a.M >= 16384 && !(a.N >= (g_gemm_wide128 ? 512 : 768));
-  const int tile = g_gemm_tile ? g_gemm_tile : (stacked64 ? 3 : (t12864 >= 384 ? 2 : 3));
-  const int kb = sizeof(T) == 2 ? (g_gemm_kb ? g_gemm_kb : (a.K >= 512 ? 2 : 1)) : 1;
+  const bool stacked64 = AMODE == 0 && a.M >= 16384 && !(a.N >= (g_opt.gemm_wide128 ? 512 : 768));
+  const int tile = g_opt.gemm_tile ? g_opt.gemm_tile : (stacked64 ? 3 : (t12864 >= 384 ? 2 : 3));
+  const int kb = sizeof(T) == 2 ? (g_opt.gemm_kb ? g_opt.gemm_kb : (a.K >= 512 ? 2 : 1)) : 1;
 #define EMO_NT_LAUNCH(BM_, BN_)                                                           \
   do {                                                                                    \
     dim3 grid(cdiv(a.N, BN_), cdiv(a.M, BM_), nz);                                        \
@@ -888,7 +879,7 @@ int launch_nt_(const NtArgs& a_in, hipStream_t s, int nz = 1) {
   } while (0)
   if constexpr (sizeof(T) == 2 && AMODE == 0 && !BKM) {
     // a few workgroups only (decoding): 256-wide k tiles, one wait per 256 of K (see the kernel)
-    if (g_gemm_wholek && a.M <= 2048 && a.K % 256 == 0 && nz == 1) {
+    if (g_opt.gemm_wholek && a.M <= 2048 && a.K % 256 == 0 && nz == 1) {
       dim3 grid(cdiv(a.N, 64), cdiv(a.M, 64), 1);
       gemm_nt_kernel<T, 64, 64, AMODE, BKM, TR, 8><<<grid, 256, 0, s>>>(a);
       EMO_LAUNCH_CHECK();
@@ -915,7 +906,7 @@ int launch_nt(const NtArgs& a, hipStream_t s) {
 template <typename T>
 int launch_nn(const NtArgs& a, hipStream_t s, int nz = 1) {
   if constexpr (is_f32<T>) { if (t_f32_split) return launch_nt_<T, 0, true, true, true>(a, s, nz); }
-  return g_tr_read ? launch_nt_<T, 0, true, true>(a, s, nz) : launch_nt_<T, 0, true, false>(a, s, nz);
+  return g_opt.tr_read ? launch_nt_<T, 0, true, true>(a, s, nz) : launch_nt_<T, 0, true, false>(a, s, nz);
 }
 
 // Most split-K slices one TN product may take (launch_tn and emoasr_gemm_tn_grouped): every slice adds the whole f32 output
@@ -935,14 +926,14 @@ int launch_tn(TnArgs a, hipStream_t s) {
   if constexpr (is_f32<T> && !SP) { if (t_f32_split) return launch_tn<T, BMODE, true>(a, s); }
   const bool big = (long)cdiv(a.N1, 128) * cdiv(a.N2, 128) >= 32 && a.N1 >= 128 && a.N2 >= 128;
   // BK = 32 with the 128x128 tile (three resident blocks per CU instead of two; see emoasr_gemm_tn_grouped), 64 for long reductions on 64x64
-  const int kb = sizeof(T) == 2 ? (g_gemm_kb ? g_gemm_kb : (a.K >= 512 && !big ? 2 : 1)) : 1;
+  const int kb = sizeof(T) == 2 ? (g_opt.gemm_kb ? g_opt.gemm_kb : (a.K >= 512 && !big ? 2 : 1)) : 1;
   const int BK = (SP ? 32 : TileCfg<T>::BK) * kb;
   const int nk = cdiv(a.K, BK);
   const int bn = big ? 128 : 64;
   const long tiles = (long)cdiv(a.N1, bn) * cdiv(a.N2, bn);
   // split-K: as many slices as fit ONE round of resident blocks (rounding up past it leaves a mostly empty
   // second round) with at least 4 k-tiles each, but no more than the atomic traffic allows (tn_split_cap)
-  const long slots_ = g_tn_group_blocks > 0 ? g_tn_group_blocks : ((big && kb == 2) || (big && SP) ? 512 : 768);   // (split, 128 tile: 80 KB of LDS)
+  const long slots_ = g_opt.tn_group_blocks > 0 ? g_opt.tn_group_blocks : ((big && kb == 2) || (big && SP) ? 512 : 768);   // (split, 128 tile: 80 KB of LDS)
   int splits = (int)std::max(1L, slots_ / tiles);  // one full round of resident blocks (2 per CU for the 128x128 BK=64 tile, else 3)
   const int cap = tn_split_cap(a.N1, a.N2, a.K);
   const int floor_splits = (int)std::min((long)splits, (128 + tiles - 1) / tiles);  // never starve the chip
@@ -965,10 +956,10 @@ int launch_tn(TnArgs a, hipStream_t s) {
     else EMO_TN_LAUNCH(64, true);
   } else {
   if (big) {
-    if (g_tr_read) EMO_TN_LAUNCH(128, true);
+    if (g_opt.tr_read) EMO_TN_LAUNCH(128, true);
     else EMO_TN_LAUNCH(128, false);
   } else {
-    if (g_tr_read) EMO_TN_LAUNCH(64, true);
+    if (g_opt.tr_read) EMO_TN_LAUNCH(64, true);
     else EMO_TN_LAUNCH(64, false);
   }
   }
@@ -979,27 +970,12 @@ int launch_tn(TnArgs a, hipStream_t s) {
 
 }  // namespace
 
-int emo_conv_big_enabled();
 bool emo_gemm_nt_big_wants(int M, int N, int K, long lda, long ldb, long ldc, const emoasr_epilogue_t& ep);
 int emo_gemm_nt_big_ep(int M, int N, int K, const void* A, long lda, const void* B, long ldb, void* C, long ldc,
                        const emoasr_epilogue_t& ep, hipStream_t s);
 int emo_conv2_fwd_big(int B, int T1, int F1, int C, const void* y1, const void* w, void* y2, const float* bias,
                       int relu, hipStream_t s);
 
-void emo_gemm_set_tr_read(int v) { g_tr_read = v; }
-void emo_gemm_set_tile(int v) { g_gemm_tile = v; }
-void emo_gemm_set_wide128(int v) { g_gemm_wide128 = v ? 1 : 0; }
-void emo_gemm_set_tn_group_blocks(int v) { g_tn_group_blocks = v > 0 ? v : 0; }
-void emo_gemm_set_kb(int v) { g_gemm_kb = v; }
-void emo_gemm_set_wholek(int v) { g_gemm_wholek = v; }
-void emo_gemm_set_tn_place(int v) { g_tn_place = v != 0; }
-void emo_gemm_set_tn_big(int v) { g_tn_big = v != 0; }
-void emo_gemm_set_tn_big_blocks(int v) { g_tn_big_blocks = (v >= 64 && v <= 1024) ? v : 0; }
-void emo_gemm_set_tn_group_kb(int v) { g_tn_group_kb = (v == 1 || v == 2) ? v : 0; }
-void emo_gemm_set_xcd(int v) { g_gemm_xcd = v; }
-void emo_gemm_set_split_tile(int v) { g_split_tile = (v >= 1 && v <= 3) ? v : 0; }
-void emo_gemm_set_split_kb(int v) { g_split_kb = v == 2 ? 2 : 1; }
-void emo_gemm_set_split_min128(int v) { g_split_min128 = v > 0 ? v : 512; }
 
 static int check_vec(long ld, int dtype, const char* what) {
   const int vec = dtype == EMO_BF16 ? 8 : 4;
@@ -1102,12 +1078,12 @@ static int tn_group_plan(int dtype, int n, const emoasr_tn_problem_t* probs, TnG
   bt = 128;
   for (int i = 0; i < n; ++i)
     if (probs[i].N1 < 128 || probs[i].N2 < 128) bt = 64;
-  if (g_gemm_tile == 3) bt = 64;
+  if (g_opt.gemm_tile == 3) bt = 64;
   // k extent of a tile: 32 for the 128x128 bf16 tile (40 KB of LDS, three blocks per CU), 64 for the 64x64 one.  (BK = 64 with the
   // 128 tile is 80 KB: the 480-block launch of a layer then ran in TWO rounds, blocks sharing operand tiles were no longer
   // co-resident and the launch read 1.2-1.6x its operands from HBM; BK = 32 reads them once -- 216 -> 185 us at 35 k rows,
   // tools/tn_probe.py.)  Option "gemm_kb" overrides.
-  kb = dtype == EMO_BF16 ? (g_tn_group_kb ? g_tn_group_kb : g_gemm_kb ? g_gemm_kb : (bt == 128 ? 1 : 2)) : 1;
+  kb = dtype == EMO_BF16 ? (g_opt.tn_group_kb ? g_opt.tn_group_kb : g_opt.gemm_kb ? g_opt.gemm_kb : (bt == 128 ? 1 : 2)) : 1;
   const bool split = dtype == EMO_F32X3;
   const int BK = (dtype == EMO_BF16 || split ? 32 : 16) * kb;
   for (int i = 0; i < n; ++i) {
@@ -1123,7 +1099,7 @@ static int tn_group_plan(int dtype, int n, const emoasr_tn_problem_t* probs, TnG
   // one split factor for the whole group, chosen so that the launch is ONE full round of resident blocks:
   // three blocks per CU for the 128x128 BK=32 tile (40 KB of LDS) and the 64x64 one (48 KB), two for 128x128 BK=64.  Rounding
   // the block count up past that measured slower every time (at 35 k rows: 768 blocks 185 us, 896 blocks 257 us).
-  const long slots = g_tn_group_blocks > 0 ? g_tn_group_blocks : ((bt == 128 && kb == 2) || (bt == 128 && split) ? 512 : 768);
+  const long slots = g_opt.tn_group_blocks > 0 ? g_opt.tn_group_blocks : ((bt == 128 && kb == 2) || (bt == 128 && split) ? 512 : 768);
   const int want = (int)std::max(1L, slots / tiles);
   int start = 0;
   for (int i = 0; i < n; ++i) {
@@ -1161,7 +1137,7 @@ static int tn_grouped_launch(int dtype, int n, const emoasr_tn_problem_t* probs,
   if (int rc = tn_group_plan(dtype, n, probs, G, bt, kb)) return rc;
   const bool split = dtype == EMO_F32X3;
   int start = G.start[n];
-  G.xcd = g_tn_place ? 1 : (g_gemm_xcd ? 2 : 0);
+  G.xcd = g_opt.tn_place ? 1 : (g_opt.gemm_xcd ? 2 : 0);
   if (G.xcd == 1) {   // deal whole slices to the XCDs: largest first, each to the XCD with the fewest blocks so far
     struct Slice { int tiles, prob, split; };
     std::vector<Slice> sl;
@@ -1198,13 +1174,13 @@ static int tn_grouped_launch(int dtype, int n, const emoasr_tn_problem_t* probs,
   }
   if (dtype == EMO_BF16) {
     if (bt == 128 && kb == 1) {
-      if (g_tr_read) gemm_tn_grouped_kernel<bf16, true, 1, 128><<<start, 256, 0, s>>>(G);
+      if (g_opt.tr_read) gemm_tn_grouped_kernel<bf16, true, 1, 128><<<start, 256, 0, s>>>(G);
       else gemm_tn_grouped_kernel<bf16, false, 1, 128><<<start, 256, 0, s>>>(G);
     } else if (bt == 128) {
-      if (g_tr_read) gemm_tn_grouped_kernel<bf16, true, 2, 128><<<start, 256, 0, s>>>(G);
+      if (g_opt.tr_read) gemm_tn_grouped_kernel<bf16, true, 2, 128><<<start, 256, 0, s>>>(G);
       else gemm_tn_grouped_kernel<bf16, false, 2, 128><<<start, 256, 0, s>>>(G);
     } else {
-      if (g_tr_read) gemm_tn_grouped_kernel<bf16, true, 2, 64><<<start, 256, 0, s>>>(G);
+      if (g_opt.tr_read) gemm_tn_grouped_kernel<bf16, true, 2, 64><<<start, 256, 0, s>>>(G);
       else gemm_tn_grouped_kernel<bf16, false, 2, 64><<<start, 256, 0, s>>>(G);
     }
   } else if (split) {
@@ -1224,7 +1200,7 @@ static int tn_grouped_launch(int dtype, int n, const emoasr_tn_problem_t* probs,
 // Which TN products take the eight-wave 256x256 tile (gemm_big_tn.hip): bf16, N2 a multiple of 256, N1 >= 256 (ragged N1 where
 // lda is padded), option "tn_big" on, transposed LDS reads on.  Everything else -- small N, f32, f32x3 -- keeps tn_block.
 static bool tn_big_takes(int dtype, int N1, int N2, int K, long lda, long ldb) {
-  return dtype == EMO_BF16 && g_tn_big && g_tr_read && emo_tn_big_fits(N1, N2, K, lda, ldb);
+  return dtype == EMO_BF16 && g_opt.tn_big && g_opt.tr_read && emo_tn_big_fits(N1, N2, K, lda, ldb);
 }
 // k slices of the products of one 256-tile launch: one split factor for the launch from its block budget (option
 // "tn_big_blocks"; the atomic bytes of a launch are blocks x 256 KB, so the budget is a tuning parameter, not "fill every CU"),
@@ -1232,7 +1208,7 @@ static bool tn_big_takes(int dtype, int N1, int N2, int K, long lda, long ldb) {
 static void tn_big_splits(int n, const BigTnProblem* q, int* splits) {
   long tiles = 0;
   for (int i = 0; i < n; ++i) tiles += (long)(q[i].N2 / 256) * cdiv(q[i].N1, 256);
-  const int want = (int)std::max(1L, (long)(g_tn_big_blocks > 0 ? g_tn_big_blocks : 192) / tiles);
+  const int want = (int)std::max(1L, (long)(g_opt.tn_big_blocks > 0 ? g_opt.tn_big_blocks : 192) / tiles);
   for (int i = 0; i < n; ++i) {
     const int nk = cdiv(q[i].K, 32);
     splits[i] = std::max(1, std::min(std::min(want, tn_split_cap(q[i].N1, q[i].N2, q[i].K)), nk / 4 > 0 ? nk / 4 : 1));
@@ -1280,7 +1256,7 @@ extern "C" int emoasr_conv2_fwd(int dtype, int B, int T1, int F1, int C, const v
   const int T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
   EMO_CHECK(C % 32 == 0, "conv2: C must be a multiple of 32");
   // bias (+ ReLU) only, bf16, C % 256 == 0: the large-tile kernel (gemm_big.hip)
-  if (dtype == EMO_BF16 && C % 256 == 0 && emo_conv_big_enabled() && ep->alpha == 1.f && !ep->residual && !ep->dact_pre &&
+  if (dtype == EMO_BF16 && C % 256 == 0 && g_opt.conv_big && ep->alpha == 1.f && !ep->residual && !ep->dact_pre &&
       !ep->pre_out && ep->drop_p == 0.f && !ep->out_f32 && (ep->act == EMO_ACT_NONE || ep->act == EMO_ACT_RELU))
     return emo_conv2_fwd_big(B, T1, F1, C, y1, w, y2, ep->bias, ep->act == EMO_ACT_RELU, (hipStream_t)stream);
   NtArgs a{};
@@ -1317,7 +1293,7 @@ extern "C" int emoasr_conv2_dgrad(int dtype, int B, int T1, int F1, int C, const
       a.ep.alpha = 1.f; a.ep.dact_pre = y1; a.ep.dact = EMO_ACT_RELU; a.ep.res_scale = 1.f;
       int rc = 1;
       EMO_DISPATCH(dtype, rc = (is_f32<T> && t_f32_split ? launch_nt_<float, 2, true, true, true>(a, (hipStream_t)stream)
-                                : g_tr_read ? launch_nt_<T, 2, true, true>(a, (hipStream_t)stream)
+                                : g_opt.tr_read ? launch_nt_<T, 2, true, true>(a, (hipStream_t)stream)
                                             : launch_nt_<T, 2, true, false>(a, (hipStream_t)stream)));
       if (rc) return rc;
     }
@@ -1348,12 +1324,12 @@ extern "C" int emoasr_conv2_wgrad(int dtype, int B, int T1, int F1, int C, const
 // 1064 us on gemm_tn_kernel, 1099 us as five launches of the 256 tile, 918 us as one -- and so do C = 128, f32 and f32x3.
 // Block budget: this product is compute-bound (157 GFLOP per micro-batch), so one block per CU unless "tn_big_blocks" says
 // otherwise (five micro-batches: 189 blocks 1100 us, 252 blocks 918 us, 315 blocks 1350 us, 504 blocks 966 us).
-static bool tn_big_conv_takes(int dtype, int C) { return dtype == EMO_BF16 && g_tn_big && g_tr_read && C % 256 == 0; }
+static bool tn_big_conv_takes(int dtype, int C) { return dtype == EMO_BF16 && g_opt.tn_big && g_opt.tr_read && C % 256 == 0; }
 static int tn_big_conv(int nseg, const emoasr_conv2_wgrad_seg_t* segs, int F1, int C, float* dw, float* dbias, hipStream_t s) {
   const int F2 = (F1 - 3) / 2 + 1;
   long K = 0;
   for (int i = 0; i < nseg; ++i) K += (long)segs[i].B * ((segs[i].T1 - 3) / 2 + 1) * F2;
-  return emo_tn_big_conv_launch(nseg, segs, F1, C, dw, dbias, g_tn_big_blocks > 0 ? g_tn_big_blocks : 256,
+  return emo_tn_big_conv_launch(nseg, segs, F1, C, dw, dbias, g_opt.tn_big_blocks > 0 ? g_opt.tn_big_blocks : 256,
                                 tn_split_cap(C, 9L * C, K), s);
 }
 

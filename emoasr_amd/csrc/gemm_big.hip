@@ -722,8 +722,6 @@ __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
   }
 }
 
-int g_conv_big = 1;
-
 inline int pick_bm(long M, int n_cu) {
   // the tile height that wastes the fewest CU-rounds: efficiency = M / (rounds * n_cu * BM)
   int best = 256;
@@ -760,8 +758,6 @@ int n_cu_cached() {
   return n;
 }
 
-int g_big_waves = 8;   // option "big_waves": 8 (2 x 4 waves, 64 columns each) or 4 (2 x 2 waves, 128 columns each)
-
 template <int TMW, int AMODE, int NW, int MODE>
 int launch_big_t(const BigArgs& a, int tiles, hipStream_t s) {
   constexpr int bytes = (3 * TMW * 32 + 2 * 256) * 128;  // A ring of three stages + B ring of two
@@ -795,33 +791,23 @@ int launch_big_bm(const BigArgs& a, int bm, int tiles, hipStream_t s) {
     const emoasr_epilogue_t& ep = a.ep;
     const bool lean = (ep.act & 0xFF) == EMO_ACT_NONE && !(ep.act & EMO_ACT_SAVE_DACT) && !ep.pre_out &&
                       (!ep.dact_pre || ep.dact == EMO_DACT_MUL || ep.dact == EMO_DACT_TANH_OUT);
-    if (lean && g_big_waves != 4) return launch_big_bm_<0, 8, 4>(a, bm, tiles, s);
-    if (ep.act == (EMO_ACT_SWISH | EMO_ACT_SAVE_DACT) && !ep.dact_pre && !ep.residual && g_big_waves != 4)
+    if (lean && g_opt.big_waves != 4) return launch_big_bm_<0, 8, 4>(a, bm, tiles, s);
+    if (ep.act == (EMO_ACT_SWISH | EMO_ACT_SAVE_DACT) && !ep.dact_pre && !ep.residual && g_opt.big_waves != 4)
       return launch_big_bm_<0, 8, 5>(a, bm, tiles, s);
   }
   // (the 4-wave layout -- measured slower on every product, DESIGN.md section 7 -- is kept for the general epilogue only)
-  if (g_big_waves == 4) return launch_big_bm_<AMODE, 4, 0>(a, bm, tiles, s);
+  if (g_opt.big_waves == 4) return launch_big_bm_<AMODE, 4, 0>(a, bm, tiles, s);
   return launch_big_bm_<AMODE, 8, 0>(a, bm, tiles, s);
 }
 
-int g_big_bm = 0;  // tuning override
-int g_big_korder = 1;
-
 }  // namespace
-
-void emo_gemm_set_conv_big(int v) { g_conv_big = v; }
-void emo_gemm_set_big_bm(int v) { g_big_bm = v; }
-void emo_gemm_set_big_waves(int v) { g_big_waves = v == 4 ? 4 : 8; }
-void emo_gemm_set_big_korder(int v) { g_big_korder = v; }
-int emo_conv_big_enabled() { return g_conv_big; }
 
 // Measured in the L2 training step (M ~ 7 k rows): with the q/k/v, feed-forward w1 and pointwise-conv-1 products
 // (165 - 220 tiles of 128 x 256) on this kernel the step took 9.72 ms against 9.66 ms without -- those launches are
 // latency-bound either way -- so only products of at least two full rounds of tiles are taken.  Round 3, stacked rows
 // (M ~ 35 k): the same three products (550 - 1100 tiles) run FASTER on the 64 x 64 kernel of gemm.hip (step 31.44 -> 30.96 ms
 // with the threshold at 2000 tiles, 31.17 with this kernel off for plain products): what stays here is the vocabulary
-// projection (N = 10 000: 2 280 tiles at 7 k rows, 11 000 at 35 k) and the Conv2d products.
-int g_big_min_tiles = 2000;
+// projection (N = 10 000: 2 280 tiles at 7 k rows, 11 000 at 35 k) and the Conv2d products.  Option "big_min_tiles".
 
 // Does the large-tile kernel take this emoasr_gemm_nt call?  (bf16 product, full 256-column tiles, 64-deep k-tiles, an
 // epilogue without f32 output, and enough 128-row tiles to occupy most CUs.)
@@ -830,9 +816,8 @@ int g_big_min_tiles = 2000;
 // grid reads it four times; tools/big_n256_probe.py at 35 145 rows: 38.0 -> 29.5 us (K = 1024), 30.9 -> 24.7 (768),
 // 184.7 -> 108.3 (4864), 370.7 -> 223.8 (10 048), bit-identical results (vendor BLAS: 23.6 / 20.6 / 87.1 / 191.2).
 // Option "big_n256".
-int g_big_n256 = 2;
 bool emo_gemm_nt_big_wants(int M, int N, int K, long lda, long ldb, long ldc, const emoasr_epilogue_t& ep) {
-  if (!g_conv_big || N % 8 != 0 || N < 256 || K % 64 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0) return false;
+  if (!g_opt.conv_big || N % 8 != 0 || N < 256 || K % 64 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0) return false;
   if (ep.out_f32 || (ep.dact_pre && (ep.act & EMO_ACT_SAVE_DACT))) return false;
   if (ep.residual && ep.ldr % 8 != 0) return false;
   if ((long)M * lda * 2 >= (1L << 32) || (long)N * ldb * 2 >= (1L << 32)) return false;
@@ -840,21 +825,19 @@ bool emo_gemm_nt_big_wants(int M, int N, int K, long lda, long ldb, long ldc, co
   // (option big_n256: 1 = N = 512 from K = 512 on, N = 256 from K = 2048 on; 2 = N = 256 from K = 512 on as well -- the second
   // feed-forward product, K = 1024: 29.5 against 38 us alone, but 72 against 44 us INSIDE the step, where its operand was written by
   // the launch before: three same-box pairs 29.4 against 28.9 ms per step)
-  if (g_big_n256 && M >= 8192 && ((N == 512 && K >= 512) || (N == 256 && K >= (g_big_n256 >= 2 ? 512 : 2048)))) return true;
+  if (g_opt.big_n256 && M >= 8192 && ((N == 512 && K >= 512) || (N == 256 && K >= (g_opt.big_n256 >= 2 ? 512 : 2048)))) return true;
   if (ep.residual || ep.dact_pre) return false;   // (only measured for the shapes above)
-  return (long)cdiv(M, 128) * cdiv(N, 256) >= g_big_min_tiles;
+  return (long)cdiv(M, 128) * cdiv(N, 256) >= g_opt.big_min_tiles;
 }
-void emo_gemm_set_big_n256(int v) { g_big_n256 = v < 0 ? 0 : v; }
 int emo_gemm_nt_big_ep(int M, int N, int K, const void* A, long lda, const void* B, long ldb, void* C, long ldc,
                        const emoasr_epilogue_t& ep, hipStream_t s) {
   BigArgs a{};
   a.M = M; a.N = N; a.K = K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
   a.ep = ep;
-  const int bm = g_big_bm ? g_big_bm : pick_bm_plain(M, N, K);
+  const int bm = g_opt.big_bm ? g_opt.big_bm : pick_bm_plain(M, N, K);
   a.tiles_m = cdiv(M, bm); a.tiles_n = cdiv(N, 256);
   return launch_big_bm<0>(a, bm, a.tiles_m * a.tiles_n, s);
 }
-void emo_gemm_set_big_min_tiles(int v) { g_big_min_tiles = v; }
 
 // C[M,N] (bf16) = relu?(A[M,K] . B[N,K]^T + bias): N % 8 == 0, K % 64 == 0, 16-byte aligned rows.
 extern "C" int emoasr_gemm_nt_big(int dtype, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
@@ -876,7 +859,7 @@ static int rnnt_head_launch(int nrows, int V, int J, const void* h, const void* 
   a.M = nrows; a.N = V; a.K = J; a.A = h; a.lda = J; a.B = w; a.ldb = J; a.C = C; a.ldc = ldc;
   a.ep.alpha = 1.f; a.ep.bias = bias; a.ep.res_scale = 1.f;
   a.rn = rn;
-  const int bm = g_big_bm ? g_big_bm : pick_bm_plain(nrows, V, J);
+  const int bm = g_opt.big_bm ? g_opt.big_bm : pick_bm_plain(nrows, V, J);
   a.tiles_m = cdiv(nrows, bm); a.tiles_n = cdiv(V, 256);
   return launch_big_bm<0>(a, bm, a.tiles_m * a.tiles_n, s);
 }
@@ -937,7 +920,7 @@ extern "C" int emoasr_gemm_nt_lse(int dtype, int M, int N, int K, const void* A,
   a.M = M; a.N = N; a.K = K; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
   a.ep.alpha = 1.f; a.ep.bias = bias; a.ep.res_scale = 1.f;
   a.rn.mode = 3; a.rn.nchunk = cdiv(N, 64); a.rn.part = part; a.rn.part_rows = M; a.rn.part_row0 = 0;
-  const int bm = g_big_bm ? g_big_bm : pick_bm_plain(M, N, K);
+  const int bm = g_opt.big_bm ? g_opt.big_bm : pick_bm_plain(M, N, K);
   a.tiles_m = cdiv(M, bm); a.tiles_n = cdiv(N, 256);
   if (launch_big_bm<0>(a, bm, a.tiles_m * a.tiles_n, (hipStream_t)stream)) return 1;
   lse_parts_kernel<<<cdiv(M, 64), 64, 0, (hipStream_t)stream>>>(M, a.rn.nchunk, part, lse);
@@ -1042,8 +1025,8 @@ int emo_conv2_fwd_big(int B, int T1, int F1, int C, const void* y1, const void* 
   a.M = B * T2 * F2; a.N = C; a.K = 9 * C; a.A = y1; a.B = w; a.ldb = 9 * C; a.C = y2; a.ldc = C;
   a.bias = bias; a.relu = relu;
   a.cg = BigConv{T1, F1, T2, F2, C};
-  a.korder = g_big_korder;
-  const int bm = g_big_bm ? g_big_bm : pick_bm(a.M, n_cu_cached());
+  a.korder = g_opt.big_korder;
+  const int bm = g_opt.big_bm ? g_opt.big_bm : pick_bm(a.M, n_cu_cached());
   a.tiles_m = cdiv(a.M, bm); a.tiles_n = C / 256;
   return launch_big_bm<1>(a, bm, a.tiles_m * a.tiles_n, s);
 }
@@ -1054,7 +1037,7 @@ int emo_conv2_fwd_big(int B, int T1, int F1, int C, const void* y1, const void* 
 // the four parity classes of the data gradient in a.dg, tiles in a.tiles_m / a.tiles_n; returns the tile height
 static int dgrad_plan(int B, int T1, int F1, int C, BigArgs& a) {
   const int T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
-  a.korder = g_big_korder;
+  a.korder = g_opt.big_korder;
   a.N = C; a.K = 4 * C; a.ldb = 9 * C; a.ldc = C;
   BigDgrad& g = a.dg;
   g.T1 = T1; g.F1 = F1; g.T2 = T2; g.F2 = F2; g.C = C;
@@ -1074,7 +1057,7 @@ static int dgrad_plan(int B, int T1, int F1, int C, BigArgs& a) {
       rows += (long)g.M[c] * g.ntap[c];
     }
   // tile height from the work-weighted row count (a 4-tap tile runs 4x as long as a 1-tap tile)
-  const int bm = g_big_bm ? g_big_bm : pick_bm(rows / 4, n_cu_cached());
+  const int bm = g_opt.big_bm ? g_opt.big_bm : pick_bm(rows / 4, n_cu_cached());
   int t0 = 0;
   for (int c = 0; c < g.ncls; ++c) { g.tile0[c] = t0; t0 += cdiv(g.M[c], bm); }
   g.tile0[g.ncls] = t0;

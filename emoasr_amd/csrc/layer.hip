@@ -43,13 +43,12 @@ emoasr_epilogue_t plain_ep() {
 // x + res_scale * drop(W2 act(W1 LN(x) + b1) + b2): LayerNorm + two products.  (The block as ONE launch -- 64 rows per workgroup, the
 // F-wide intermediate consumed on chip -- was built in round 2 and measured again at the stacked size in round 4: 263 us against
 // 120 us at M = 35 145, 90 against 36 at M = 7 029; every CU streams both weight matrices for its 64 rows.  Deleted.)
-int g_att_bits = 1;       // option "attn_mask_bits": the layer hashes its attention keep mask once, as bits, in the forward
-int g_ffn_save_dact = 1;  // option "ffn_save_dact": the feed-forward blocks save Swish'(u) * dropout_scale instead of u (common.h:
-                          // EMO_ACT_SAVE_DACT); must not change between a forward and its backward
-int g_stack_launch = 1;  // stacked micro-batches: 1 = the per-utterance kernels take all segments in ONE launch (segment table in
-                         // their arguments), 0 = one launch per segment (same arithmetic; A/B switch, option "stack_launch")
-int g_conv_fused = 1;  // bf16: the fused convolution-module kernels of csrc/convfused.hip (bit-identical to the separate launches)
-bool conv_fused_ok(int dtype, int d) { return g_conv_fused && dtype == EMO_BF16 && d % 8 == 0; }
+// Options read here: "attn_mask_bits" (the layer hashes its attention keep mask once, as bits, in the forward); "ffn_save_dact"
+// (the feed-forward blocks save Swish'(u) * dropout_scale instead of u, common.h: EMO_ACT_SAVE_DACT; must not change between a
+// forward and its backward); "stack_launch" (stacked micro-batches: 1 = the per-utterance kernels take all segments in ONE launch,
+// segment table in their arguments, 0 = one launch per segment: same arithmetic, A/B switch); "conv_fused" (bf16: the fused
+// convolution-module kernels of csrc/convfused.hip, bit-identical to the separate launches)
+bool conv_fused_ok(int dtype, int d) { return g_opt.conv_fused && dtype == EMO_BF16 && d % 8 == 0; }
 
 // Option "wgrad_side": the layer backward's grouped weight-gradient launch (nine products, ~0.2 ms at the stacked row count, 0.7
 // rounds of workgroups) goes to a SIDE stream and runs under the NEXT layer's gradient chain, most of whose launches leave CUs
@@ -57,7 +56,6 @@ bool conv_fused_ok(int dtype, int d) { return g_conv_fused && dtype == EMO_BF16 
 // launch reads the layer's workspace, so callers alternate between TWO workspaces from call to call (emoasr_amd/layer_rt.py); a
 // call first waits for the launch issued two calls earlier (the last reader of its workspace).  emoasr_wgrad_side_join makes
 // the caller's stream wait for the launches still in flight (before the optimizer, a gradient hook or a workspace release).
-int g_wgrad_side = 0;
 struct WgSide {
   hipStream_t side = nullptr;
   hipEvent_t fork = nullptr, done[2] = {nullptr, nullptr};
@@ -89,7 +87,7 @@ int ffn_fwd(int dtype, int M, int d, int F, const emoasr_ffn_params_t& p, const 
             float p_enc, uint64_t s_in, uint64_t s_out, const emoasr_ffn_stash_t& st, void* stream) {
   if (emoasr_layernorm_fwd(dtype, M, d, x, p.ln_g, p.ln_b, 1e-5f, st.h, st.mean, st.rstd, stream)) return 1;
   emoasr_epilogue_t e1 = plain_ep();
-  e1.bias = p.b1; e1.act = EMOASR_ACT_SWISH | (g_ffn_save_dact ? EMOASR_ACT_SAVE_DACT : 0); e1.pre_out = st.u; e1.drop_p = p_enc; e1.seed = s_in;
+  e1.bias = p.b1; e1.act = EMOASR_ACT_SWISH | (g_opt.ffn_save_dact ? EMOASR_ACT_SAVE_DACT : 0); e1.pre_out = st.u; e1.drop_p = p_enc; e1.seed = s_in;
   if (emoasr_gemm_nt(dtype, M, F, d, st.h, d, p.w1, d, st.a, F, &e1, stream)) return 1;
   emoasr_epilogue_t e2 = plain_ep();
   e2.bias = p.b2; e2.residual = x; e2.ldr = d; e2.res_scale = res_scale; e2.drop_p = p_enc; e2.seed = s_out;
@@ -166,7 +164,6 @@ void attn_args_for(emoasr_attn_t& a, const SegView& sv, int s0, int s1, int H, i
 
 }  // namespace
 
-void emo_layer_set_wgrad_side(int v) { g_wgrad_side = v ? 1 : 0; }
 extern "C" int emoasr_wgrad_side_join(int keep, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   WgSide* w = wg_side_of(s, false);
@@ -181,10 +178,6 @@ extern "C" int emoasr_wgrad_side_join(int keep, void* stream) {
   }
   return 0;
 }
-void emo_layer_set_conv_fused(int v) { g_conv_fused = v; }
-void emo_layer_set_stack_launch(int v) { g_stack_launch = v; }
-void emo_layer_set_ffn_save_dact(int v) { g_ffn_save_dact = v ? 1 : 0; }
-void emo_layer_set_att_bits(int v) { g_att_bits = v ? 1 : 0; }
 
 extern "C" int emoasr_conformer_attn_masks(int dtype, int nl, const emoasr_segments_t* seg, int B, int T, int H, int d, const int* klens,
                                            float p_att, const uint64_t* seeds, unsigned* masks, long layer_stride_words, int nw,
@@ -196,7 +189,7 @@ extern "C" int emoasr_conformer_attn_masks(int dtype, int nl, const emoasr_segme
   SegView sv;
   EMO_CHECK(seg_view(&io, d, &sv), "conformer_attn_masks: bad batch / segment shapes");
   const size_t esz = dtype == EMO_BF16 ? 2 : 4;
-  const int astep = g_stack_launch ? sv.n : 1;
+  const int astep = g_opt.stack_launch ? sv.n : 1;
   for (int l = 0; l < nl; ++l)
     for (int si = 0; si < sv.n; si += astep) {
       emoasr_attn_t am{};
@@ -219,8 +212,8 @@ extern "C" int emoasr_conformer_layer_fwd(int dtype, const emoasr_conformer_laye
   const float p_enc = io->p_enc;
   // the attention-dropout keep mask of this layer as bits, hashed now (on the attention's side stream: it runs under the macaron
   // block's products) for the attention forward below and both passes of its backward
-  const bool att_bits = g_att_bits && io->att_mask && io->training && io->p_att > 0.f && dtype == EMO_BF16;
-  const int astep_m = g_stack_launch ? sv.n : 1;
+  const bool att_bits = g_opt.attn_mask_bits && io->att_mask && io->training && io->p_att > 0.f && dtype == EMO_BF16;
+  const int astep_m = g_opt.stack_launch ? sv.n : 1;
   for (int si = 0; si < sv.n && att_bits && !io->att_mask_ready; si += astep_m) {
     emoasr_attn_t am{};
     attn_args_for(am, sv, si, si + astep_m, H, d, esz, io->qkv, io->pp, io->klens, io->seed[2]);
@@ -240,7 +233,7 @@ extern "C" int emoasr_conformer_layer_fwd(int dtype, const emoasr_conformer_laye
     emoasr_epilogue_t ep = plain_ep();
     if (emoasr_gemm_nt(dtype, R, d, d, io->pos_t, d, L->wpos, d, io->pp, d, &ep, stream)) return 1;
     // attention is per utterance: all stacked micro-batches in one launch (segment table in the arguments), or one each
-    const int astep = g_stack_launch ? sv.n : 1;
+    const int astep = g_opt.stack_launch ? sv.n : 1;
     for (int si = 0; si < sv.n; si += astep) {
       const size_t ro = (size_t)sv.row[si];
       emoasr_attn_t a{};
@@ -266,14 +259,14 @@ extern "C" int emoasr_conformer_layer_fwd(int dtype, const emoasr_conformer_laye
     const bool fused = conv_fused_ok(dtype, d);
     if (!fused && emoasr_glu_fwd(dtype, M, d, io->g, io->gl, stream)) return 1;
     if (io->training) EMO_CHECK(io->bn_part && io->bmean && io->bvar, "conformer_layer_fwd: training needs the BatchNorm buffers");
-    const bool conv_one_launch = fused && sv.n > 1 && g_stack_launch;   // all stacked micro-batches in one launch per kernel
+    const bool conv_one_launch = fused && sv.n > 1 && g_opt.stack_launch;   // all stacked micro-batches in one launch per kernel
     if (conv_one_launch &&
         emoasr_conv_module_fwd_seg(dtype, &io->seg, d, L->K, io->g, L->dw_w, L->dw_b, io->c, io->bn_part, io->bmean, io->bvar,
                                    L->bn_rm, L->bn_rv, 0.1f, L->bn_nbt, L->bn_g, L->bn_b, 1e-5f, io->z, io->training, stream))
       return 1;
     // f32 / f32x3 (the separate kernels), training: the depthwise convolution per micro-batch, then the BatchNorm statistics'
     // finalize and the BatchNorm + Swish apply over all micro-batches in ONE launch each
-    const bool bn_one_launch = !fused && io->training && sv.n > 1 && g_stack_launch;
+    const bool bn_one_launch = !fused && io->training && sv.n > 1 && g_opt.stack_launch;
     if (bn_one_launch) {
       const RowSegs sg = row_segs_of(sv, d);
       int tmax = 0;
@@ -423,7 +416,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
   hipStream_t s = (hipStream_t)stream;
   emoasr_tn_problem_t pr[EMOASR_TN_GROUP_MAX];
   int npr = 0;
-  WgSide* wgs = g_wgrad_side ? wg_side_of(s, true) : nullptr;
+  WgSide* wgs = g_opt.wgrad_side ? wg_side_of(s, true) : nullptr;
   if (wgs && wgs->pending[wgs->n & 1]) {   // the launch of two calls ago read THIS workspace (callers alternate between two)
     if (hipStreamWaitEvent(s, wgs->done[wgs->n & 1], 0) != hipSuccess) return 1;
     wgs->pending[wgs->n & 1] = false;
@@ -456,7 +449,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
     wgrad(dy, d, d, S.a, F, F, M, Gp.w2, alpha, Gp.b2);
     emoasr_epilogue_t e = plain_ep();
     e.alpha = alpha; e.dact_pre = S.u; e.seed = s_in;
-    if (g_ffn_save_dact) { e.dact = EMOASR_DACT_MUL; e.drop_p = 0.f; }   // S.u holds Swish'(u) * dropout_scale (ffn_fwd)
+    if (g_opt.ffn_save_dact) { e.dact = EMOASR_DACT_MUL; e.drop_p = 0.f; }   // S.u holds Swish'(u) * dropout_scale (ffn_fwd)
     else { e.dact = EMOASR_ACT_SWISH; e.drop_p = p; }
     // du = (dy . W2) * factor: against the transposed copy W2^T [F, d] as an NT product when the layer carries one
     if (w2t ? emoasr_gemm_nt(dtype, M, F, d, dy, d, w2t, d, du, F, &e, stream)
@@ -468,11 +461,11 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
   // What the attention backward needs of FORWARD data only -- the dropout keep mask, the dense Q + pos_bias copies, the cleared
   // position-table gradient -- is prepared now, on the attention's side stream, under the feed-forward / convolution backward
   // that comes first (csrc/attention.hip: emo_attn_bwd_prelaunch)
-  if (g_stack_launch && dtype == EMO_BF16) {
+  if (g_opt.stack_launch && dtype == EMO_BF16) {
     emoasr_attn_t am{};
     attn_args_for(am, sv, 0, sv.n, H, d, esz, st->qkv, st->pp, st->klens, st->seed[2]);
     am.bias_u = L->bias_u; am.bias_v = L->bias_v; am.drop_p = st->p_att;
-    if (g_att_bits && st->att_mask && st->p_att > 0.f) { am.keep_mask = st->att_mask; am.keep_nw = st->att_mask_nw; }
+    if (g_opt.attn_mask_bits && st->att_mask && st->p_att > 0.f) { am.keep_mask = st->att_mask; am.keep_nw = st->att_mask_nw; }
     if (emo_attn_bwd_prelaunch(dtype, &am, ws + bb.attn_ws, bb.attn_ws_bytes, (float*)(ws + bb.dpos), (long)sv.R() * d, stream)) return 1;
   }
   // ---- final LayerNorm ------------------------------------------------------------------------------------------
@@ -492,7 +485,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
     if (conv_fused_ok(dtype, d)) {
       // BatchNorm sums + fold, then ONE launch for BatchNorm/Swish apply -> depthwise data gradient -> GLU backward and the
       // depthwise weight-gradient partials (the GLU output is recomputed from g)
-      const bool conv_one_launch = sv.n > 1 && g_stack_launch;   // all stacked micro-batches in one launch per kernel
+      const bool conv_one_launch = sv.n > 1 && g_opt.stack_launch;   // all stacked micro-batches in one launch per kernel
       if (conv_one_launch &&
           emoasr_conv_module_bwd_seg(dtype, &st->seg, d, K, ws + bb.dz, st->c, st->bmean, st->bvar, L->bn_g, L->bn_b, 1e-5f,
                                      (float*)G->bn_g, (float*)G->bn_b, st->g, L->dw_w, ws + bb.dg, (float*)G->dw_w, (float*)G->dw_b,
@@ -512,7 +505,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
     } else {
       // f32 / f32x3: the BatchNorm gradient sums + fold of all micro-batches in one launch each, then per micro-batch the apply
       // pass and the depthwise convolution's two gradients
-      const bool bn_one_launch = sv.n > 1 && g_stack_launch;
+      const bool bn_one_launch = sv.n > 1 && g_opt.stack_launch;
       if (bn_one_launch) {   // every kernel of the chain over all micro-batches in one launch
         const RowSegs sg = row_segs_of(sv, d);
         int tmax = 0;
@@ -569,7 +562,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
       }
     }
     // bf16: all stacked micro-batches in one set of launches (segment table in the arguments), or one set each (workspace reused)
-    const int astep = g_stack_launch ? sv.n : 1;
+    const int astep = g_opt.stack_launch ? sv.n : 1;
     for (int si = 0; si < sv.n && dtype == EMO_BF16; si += astep) {
       const size_t ro = (size_t)sv.row[si], po = (size_t)sv.prow[si];
       const long Rs = sv.prow[si + astep] - sv.prow[si];
@@ -578,7 +571,7 @@ extern "C" int emoasr_conformer_layer_bwd(int dtype, const emoasr_conformer_laye
       attn_args_for(a, sv, si, si + astep, H, d, esz, st->qkv, st->pp, st->klens, st->seed[2]);
       a.bias_u = L->bias_u; a.bias_v = L->bias_v; a.drop_p = st->p_att;
       a.out = (char*)st->o + ro * d * esz; a.lse = st->lse + ro * H;
-      if (g_att_bits && st->att_mask && st->p_att > 0.f) { a.keep_mask = st->att_mask + ro * H * st->att_mask_nw; a.keep_nw = st->att_mask_nw; }
+      if (g_opt.attn_mask_bits && st->att_mask && st->p_att > 0.f) { a.keep_mask = st->att_mask + ro * H * st->att_mask_nw; a.keep_nw = st->att_mask_nw; }
       a.dout = ws + bb.dout + ro * d * esz; a.delta = (float*)(ws + bb.delta) + ro * H;
       a.dq = dqkv; a.dk = dqkv + (size_t)d * esz; a.dv = dqkv + (size_t)2 * d * esz;
       float* dpos = (float*)(ws + bb.dpos) + po * d;

@@ -11,9 +11,6 @@
 namespace {
 
 constexpr int LN_MAXC = 4;  // chunks of 256 features -> N <= 1024
-int g_ln_fwd8 = 1;          // option "ln_fwd8": the half-wave-per-row forward kernel for M > 4096 rows
-int g_ln_bwd_pf = 1;        // option "ln_bwd_pf": the backward requests the next row before it reduces the current one
-int g_ln_bwd_blocks = 512;  // option "ln_bwd_blocks": persistent blocks of the N % 8 == 0 backward (<= LN_BWD8_MAXBLK)
 
 template <typename T>
 __device__ __forceinline__ void load4(const T* p, float (&o)[4]) {
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(int M, int N, const T* __re
 // per-feature dgamma / dbeta partial sums in registers; one LDS reduction and one
 // f32 atomic per feature per block at the end.
 constexpr int LN_BWD_MAXBLK = 256;   // general kernel: persistent blocks, 4 rows (one per wave) in flight each
-constexpr int LN_BWD8_MAXBLK = 2048;  // N % 8 == 0 kernel: 8 rows (one per half-wave) in flight each; 1024 blocks: 9.3 us + a 26 us fold per step, 512: 8.5 + 15, 256: 9.9 + 8
+// (LN_BWD8_MAXBLK, the N % 8 == 0 kernel's maximum: common.h, where option "ln_bwd_blocks" is clamped to it)
 
 template <typename T>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(int M, int N, const T* __restrict__ dy,
@@ -468,14 +465,10 @@ __global__ __launch_bounds__(256) void ln_bwd_finalize_grouped_kernel(const LnFi
 }
 
 int ln_bwd_nblk(int M, int N) {
-  return N % 8 == 0 ? std::min(cdiv(M, 8), g_ln_bwd_blocks) : std::min(cdiv(M, 4), LN_BWD_MAXBLK);
+  return N % 8 == 0 ? std::min(cdiv(M, 8), g_opt.ln_bwd_blocks) : std::min(cdiv(M, 4), LN_BWD_MAXBLK);
 }
 
 }  // namespace
-
-void emo_ln_set_fwd8(int v) { g_ln_fwd8 = v ? 1 : 0; }
-void emo_ln_set_bwd_pf(int v) { g_ln_bwd_pf = v ? 1 : 0; }
-void emo_ln_set_bwd_blocks(int v) { g_ln_bwd_blocks = std::max(64, std::min(v, LN_BWD8_MAXBLK)); }
 
 extern "C" int emoasr_layernorm_fwd(int dtype, int M, int N, const void* x, const float* gamma,
                                     const float* beta, float eps, void* y, float* mean, float* rstd,
@@ -486,7 +479,7 @@ extern "C" int emoasr_layernorm_fwd(int dtype, int M, int N, const void* x, cons
   if (M <= 4096) {
     EMO_DISPATCH(dtype, (ln_fwd_kernel<T, true><<<cdiv(M, 4), 256, 0, (hipStream_t)stream>>>(
                             M, N, (const T*)x, gamma, beta, eps, (T*)y, mean, rstd)));
-  } else if (N % 8 == 0 && g_ln_fwd8) {
+  } else if (N % 8 == 0 && g_opt.ln_fwd8) {
 #define EMO_LNF8(NC_)                                                                                      \
   EMO_DISPATCH(dtype, (ln_fwd8_kernel<T, NC_><<<cdiv(M, 8), 256, 0, (hipStream_t)stream>>>(M, N, (const T*)x, gamma, beta, \
                                                                                            eps, (T*)y, mean, rstd)))
@@ -529,7 +522,7 @@ extern "C" int emoasr_layernorm_bwd_ex(int dtype, int M, int N, const void* dy, 
   EMO_DISPATCH(dtype, (ln_bwd8_kernel<T, NC_, PF_><<<nblk, 256, smem, s>>>(M, N, (const T*)dy, (const T*)x, gamma, mean, \
                                                                            rstd, (const T*)dres, (T*)dx, part,          \
                                                                            (T*)dy2, scale2, p2, seed2)))
-#define EMO_LN8(NC_) do { if (g_ln_bwd_pf && nblk * 8 < M) EMO_LN8_(NC_, true); else EMO_LN8_(NC_, false); } while (0)
+#define EMO_LN8(NC_) do { if (g_opt.ln_bwd_pf && nblk * 8 < M) EMO_LN8_(NC_, true); else EMO_LN8_(NC_, false); } while (0)
     switch (cdiv(N, 256)) {
       case 1: EMO_LN8(1); break;
       case 2: EMO_LN8(2); break;

@@ -340,8 +340,6 @@ bool lstm_capturing(void* stream) {
   return hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
 }
 
-int g_lstm_coop = 1;
-
 // counter value at the start of the next launch, per counter (0 forward, 1 backward); launches are stream-ordered
 void lstm_base(EmoScratch* sc, int which, int G, int U, int ngrp, unsigned (&base)[L_MAXGRP]) {
   unsigned* tracked = sc->host + which * L_MAXGRP;
@@ -371,8 +369,6 @@ long lstm_capacity(const void* kernel, size_t smem) {
 
 }  // namespace
 
-void emo_lstm_set_coop(int v) { g_lstm_coop = v; }
-
 // dynamic LDS of the two kernels, and the workgroups of each the device holds at once (attribute set + occupancy query, cached per
 // size; 0 = the query failed).  emoasr_lstm_seq_supported and the two launches share these, so "supported" and the launch-time
 // residency check cannot disagree.
@@ -394,7 +390,7 @@ static long lstm_cap_of(int which, int H) {
 // Can the cooperative recurrence take this layer?  (bf16, B <= 8 groups of 64, H a multiple of 32 up to 512, and every group's
 // workgroups of BOTH kernels resident together by the occupancy query -- the same numbers the launches check)
 extern "C" int emoasr_lstm_seq_supported(int dtype, int B, int H) {
-  if (!(g_lstm_coop && dtype == EMO_BF16 && B >= 1 && B <= L_MAXB * L_MAXGRP && H % 32 == 0 && H >= 32 && H <= L_MAXH)) return 0;
+  if (!(g_opt.lstm_coop && dtype == EMO_BF16 && B >= 1 && B <= L_MAXB * L_MAXGRP && H % 32 == 0 && H >= 32 && H <= L_MAXH)) return 0;
   const long need = (long)lstm_groups(B) * (H / 16);
   return lstm_cap_of(0, H) >= need && lstm_cap_of(1, H) >= need;
 }
@@ -763,7 +759,7 @@ int bilstm_groups(int B) { return 2 * lstm_groups(B); }
 // of 32 up to 512, and every workgroup of BOTH kernels resident at once by the occupancy query with one CU's worth of workgroups
 // to spare (never a grid at the edge of residency)
 extern "C" int emoasr_bilstm_seq_supported(int dtype, int B, int H) {
-  if (!(g_lstm_coop && dtype == EMO_BF16 && B >= 1 && bilstm_groups(B) <= L_MAXGRP && H % 32 == 0 && H >= 32 && H <= L_MAXH)) return 0;
+  if (!(g_opt.lstm_coop && dtype == EMO_BF16 && B >= 1 && bilstm_groups(B) <= L_MAXGRP && H % 32 == 0 && H >= 32 && H <= L_MAXH)) return 0;
   const long need = (long)bilstm_groups(B) * (H / 16);
   const long cf = bilstm_cap_of(0, H), cb = bilstm_cap_of(1, H);
   const long spare_f = cf / std::max(1, lstm_cus()), spare_b = cb / std::max(1, lstm_cus());

@@ -26,7 +26,6 @@ namespace {
 constexpr int BT = 256;        // threads per workgroup
 constexpr int NBMAX = 16;      // hypotheses per round
 constexpr int UN = 8;          // hidden units per workgroup (4 UN = 32 gate rows = the 32 eight-lane row groups of a workgroup)
-int g_beam_mfma = 1;           // option "rnnt_beam_mfma": bf16 LSTM / joint steps on the matrix cores (0: the VALU kernels, as f32)
 
 template <typename T> __device__ __forceinline__ float rnd(float x) { return to_f32(from_f32<T>(x)); }
 
@@ -388,8 +387,6 @@ __global__ __launch_bounds__(BT) void rnnt_beam_joint_mfma_kernel(const BeamJoin
 
 }  // namespace
 
-void emo_rnnt_set_beam_mfma(int v) { g_beam_mfma = v ? 1 : 0; }
-
 extern "C" int emoasr_rnnt_beam_lstm(int dtype, int nb, int nin, int H, const void* xtab, long ldx, const long long* xidx,
                                      const void* w_ih, const void* w_hh, const float* bias, void* ph, float* pc,
                                      const long long* src, const long long* dst, const long long* copy_src, long long* copy_dst,
@@ -401,7 +398,7 @@ extern "C" int emoasr_rnnt_beam_lstm(int dtype, int nb, int nin, int H, const vo
   const size_t smem = ((size_t)NBMAX * (nin + H) + NBMAX * 4 * UN) * sizeof(float);
   EMO_CHECK(smem <= 150 * 1024, "rnnt_beam_lstm: nin + H = %d too wide for the LDS plan", nin + H);
   BeamLstmArgs a{nb, nin, H, xtab, ldx, xidx, w_ih, w_hh, bias, ph, pc, src, dst, copy_src, copy_dst, copy_n};
-  if (dtype == EMO_BF16 && g_beam_mfma && H % 32 == 0 && nin % 32 == 0) {
+  if (dtype == EMO_BF16 && g_opt.rnnt_beam_mfma && H % 32 == 0 && nin % 32 == 0) {
     const size_t sm = (size_t)NBMAX * (nin + 8 + H + 8) * 2 + NBMAX * 64 * sizeof(float);
     EMO_CHECK(sm <= 64 * 1024, "rnnt_beam_lstm: nin + H = %d too wide for the LDS plan", nin + H);
     rnnt_beam_lstm_mfma_kernel<<<H / 16, BT, sm, (hipStream_t)stream>>>(a);
@@ -430,7 +427,7 @@ extern "C" int emoasr_rnnt_beam_joint(int dtype, int nb, int H, int J, int Tmax,
   const size_t smem = (size_t)NBMAX * H * sizeof(float);
   EMO_CHECK(smem <= 64 * 1024, "rnnt_beam_joint: H=%d too wide", H);
   BeamJointArgs a{nb, H, J, Tmax, ph, dst, w_dec, b_dec, e_all, t, hj};
-  if (dtype == EMO_BF16 && g_beam_mfma && H % 32 == 0 && J % 16 == 0 && (size_t)NBMAX * (H + 8) * 2 <= 64 * 1024) {
+  if (dtype == EMO_BF16 && g_opt.rnnt_beam_mfma && H % 32 == 0 && J % 16 == 0 && (size_t)NBMAX * (H + 8) * 2 <= 64 * 1024) {
     rnnt_beam_joint_mfma_kernel<<<(J + 63) / 64, BT, (size_t)NBMAX * (H + 8) * 2, (hipStream_t)stream>>>(a);
     EMO_LAUNCH_CHECK();
     return 0;

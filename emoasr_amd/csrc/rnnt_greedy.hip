@@ -308,7 +308,6 @@ __global__ __launch_bounds__(GT) void rnnt_greedy_kernel(const GreedyArgs a) {
 
 struct GreedyState { char* buf; size_t bytes; };
 GreedyState g_greedy{nullptr, 0};
-int g_rnnt_greedy_coop = 1;
 
 int greedy_cus() {
   static int n = 0;
@@ -322,15 +321,13 @@ int greedy_cus() {
 
 }  // namespace
 
-void emo_rnnt_set_greedy_coop(int v) { g_rnnt_greedy_coop = v; }
-
 // Can the cooperative search take this model?  (two LSTM layers, every width a multiple of 8, 32 workgroups that own whole units)
 // workgroups of the search: 64 (half the rows per workgroup and phase) when every matrix has that many rows / units, else 32
 static int greedy_groups(int H, int V) { return (H % 64 == 0 && V >= 64 && 4 * (H / 64) <= 64) ? 64 : 32; }
 
 extern "C" long emoasr_rnnt_greedy_supported(int dtype, int E, int H, int J, int V, int nl) {
   const int G = greedy_groups(H, V);
-  return g_rnnt_greedy_coop && (dtype == EMO_BF16 || dtype == EMO_F32) && nl == 2 && E % 8 == 0 && H % 8 == 0 && J % 8 == 0 &&
+  return g_opt.rnnt_greedy_coop && (dtype == EMO_BF16 || dtype == EMO_F32) && nl == 2 && E % 8 == 0 && H % 8 == 0 && J % 8 == 0 &&
          H % G == 0 && 4 * (H / G) <= 64 && E <= G_MAXE && H <= G_MAXH && J <= 4 * GT && V >= G && J >= G;
 }
 

@@ -245,13 +245,9 @@ __global__ __launch_bounds__(256) void col2im_kernel(int T1, int F1, int T2, int
   }
 }
 
-int g_conv1_pair = 1;   // option "conv1_pair"
-
 inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
 
 }  // namespace
-
-void emo_conv1_set_pair(int v) { g_conv1_pair = v ? 1 : 0; }
 
 // the fold of [nblk][C][10] partial sums into dw1 / db1 (also behind emoasr_conv2_dgrad_w1, gemm_big.hip)
 int emo_conv1_wgrad_reduce(int nblk, int C, const float* part, float* dw, float* db, int accumulate, hipStream_t s) {
@@ -265,7 +261,7 @@ extern "C" int emoasr_conv1_fwd(int dtype, int B, int Tn, int F, int C, const fl
   EMO_CHECK(Tn >= 3 && F >= 3, "conv1: input too small (T=%d F=%d)", Tn, F);
   const int T1 = (Tn - 3) / 2 + 1, F1 = (F - 3) / 2 + 1;
   if (B == 0) return 0;
-  if (dtype == EMO_BF16 && C == 256 && g_conv1_pair) {
+  if (dtype == EMO_BF16 && C == 256 && g_opt.conv1_pair) {
     conv1_fwd2_kernel<<<B * ((T1 + 1) / 2), 256, 5 * F * sizeof(float), (hipStream_t)stream>>>(Tn, F, T1, F1, x, w1, b1, (bf16*)y1);
     EMO_LAUNCH_CHECK();
     return 0;

@@ -263,23 +263,13 @@ class CTCEngine(_DecoderMixinPlaceholder):
         self._implicit_dgrad = os.environ.get("EMOASR_CONV2_DGRAD", "implicit") == "implicit"
         # the first convolution's weight gradient folded into the large-tile data gradient (emoasr_conv2_dgrad_w1; A/B switch)
         self._conv1_fold = os.environ.get("EMOASR_CONV1_FOLD", "1") != "0"
-        self._conv_fused = os.environ.get("EMOASR_CONV_FUSED", "1") != "0"  # csrc/convfused.hip (bit-identical; A/B switch)
-        if not self._conv_fused:
-            from . import lib as _lib
-            _lib.set_option("conv_fused", 0)
-            _lib.set_option("dwconv_lds", 0)
-        # feed-forward blocks save act'(u) * dropout_scale instead of u (csrc/common.h: EMO_ACT_SAVE_DACT; process-wide A/B switch)
-        self._ffn_save_dact = os.environ.get("EMOASR_FFN_SAVE_DACT", "1") != "0"
-        if not self._ffn_save_dact:
-            from . import lib as _lib
-            _lib.set_option("ffn_save_dact", 0)
-        self._conv_big = os.environ.get("EMOASR_CONV_BIG", "1") != "0"  # A/B switch of csrc/gemm_big.hip (process-wide)
-        if not self._conv_big:
-            from . import lib as _lib
-            _lib.set_option("conv_big", 0)
-        if os.environ.get("EMOASR_BIG_MIN_TILES"):
-            from . import lib as _lib
-            _lib.set_option("big_min_tiles", int(os.environ["EMOASR_BIG_MIN_TILES"]))
+        # library options this engine's own launch sequence depends on, as they stand now (lib.load() applied the environment's
+        # overrides); fixed per engine: "conv_fused" (csrc/convfused.hip, bit-identical), "ffn_save_dact" (the feed-forward blocks
+        # save act'(u) * dropout_scale instead of u, csrc/common.h: EMO_ACT_SAVE_DACT), "conv_big" (csrc/gemm_big.hip)
+        from . import lib as _lib
+        self._conv_fused = _lib.get_option("conv_fused") != 0
+        self._ffn_save_dact = _lib.get_option("ffn_save_dact") != 0
+        self._conv_big = _lib.get_option("conv_big") != 0
         self.p_enc = float(_cfg(cfg, "dropout_enc_rate", 0.0))
         self.p_att = float(_cfg(cfg, "dropout_attn_rate", 0.0))
         self.dtype = compute_dtype

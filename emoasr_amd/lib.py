@@ -3,6 +3,7 @@
 The product path has no CPU fallback: if the shared library is missing or an entry
 point fails, an exception is raised.
 """
+import contextlib
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_long, c_uint64,
@@ -311,6 +312,21 @@ class EmoasrHipError(RuntimeError):
 _lib = None
 
 
+def _off(*names):
+    """alias of an on/off switch: "0" turns the named options off, anything else leaves them alone"""
+    return lambda value: [(n, 0) for n in names] if value == "0" else []
+
+
+# environment variable -> the (option, value) pairs it stands for (A/B switches that predate EMOASR_OPTIONS)
+ENV_ALIASES = {
+    "EMOASR_CONV_FUSED": _off("conv_fused", "dwconv_lds"),   # csrc/convfused.hip (bit-identical to the separate launches)
+    "EMOASR_FFN_SAVE_DACT": _off("ffn_save_dact"),
+    "EMOASR_CONV_BIG": _off("conv_big"),                     # csrc/gemm_big.hip
+    "EMOASR_BIG_MIN_TILES": lambda value: [("big_min_tiles", int(value))],
+    "EMOASR_DECODE_COOP": lambda value: [("decode_coop", int(value))],   # csrc/decode_coop.hip
+}
+
+
 def load():
     """Load the shared library (once).  Raises if it has not been built."""
     global _lib
@@ -330,16 +346,29 @@ def load():
     lib.emoasr_version.restype = c_int
     lib.emoasr_set_option.argtypes = [c_char_p, c_int]
     lib.emoasr_set_option.restype = c_int
+    lib.emoasr_get_option.argtypes = [c_char_p, POINTER(c_int), POINTER(c_int)]
+    lib.emoasr_get_option.restype = c_int
+    lib.emoasr_option_count.argtypes = []
+    lib.emoasr_option_count.restype = c_int
+    lib.emoasr_option_name.argtypes = [c_int]
+    lib.emoasr_option_name.restype = c_char_p
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = args
         fn.restype = c_int
     _lib = lib
-    # tuning overrides for measurements: EMOASR_OPTIONS="name=value,name=value" (the names of emoasr_set_option)
+    # tuning overrides for measurements, applied HERE and nowhere else (no later import or constructor touches an option): first
+    # the aliases of ENV_ALIASES, then EMOASR_OPTIONS="name=value,name=value" (the names of emoasr_set_option), which wins
+    pairs = []
+    for var, to_pairs in ENV_ALIASES.items():
+        if os.environ.get(var):
+            pairs += [(var, n, v) for n, v in to_pairs(os.environ[var])]
     for item in filter(None, os.environ.get("EMOASR_OPTIONS", "").split(",")):
         name, _, value = item.partition("=")
-        if lib.emoasr_set_option(name.strip().encode(), int(value)) != 0:
-            raise EmoasrHipError(f"EMOASR_OPTIONS: {lib.emoasr_last_error().decode()}")
+        pairs.append(("EMOASR_OPTIONS", name.strip(), int(value)))
+    for var, name, value in pairs:
+        if lib.emoasr_set_option(name.encode(), value) != 0:
+            raise EmoasrHipError(f"{var}: {lib.emoasr_last_error().decode()}")
     return lib
 
 
@@ -427,3 +456,41 @@ def set_option(name, value):
     lib = load()
     if lib.emoasr_set_option(name.encode(), int(value)) != 0:
         raise EmoasrHipError(lib.emoasr_last_error().decode())
+
+
+def _get_option(name):
+    lib = load()
+    value, default = c_int(0), c_int(0)
+    if lib.emoasr_get_option(name.encode(), ctypes.byref(value), ctypes.byref(default)) != 0:
+        raise EmoasrHipError(lib.emoasr_last_error().decode())
+    return value.value, default.value
+
+
+def get_option(name):
+    """the option's current value, as the library normalised it"""
+    return _get_option(name)[0]
+
+
+def option_default(name):
+    return _get_option(name)[1]
+
+
+def option_names():
+    lib = load()
+    return [lib.emoasr_option_name(i).decode() for i in range(lib.emoasr_option_count())]
+
+
+@contextlib.contextmanager
+def options(**values):
+    """with lib.options(name=value, ...): the options hold these values inside the block (set in the order given) and what they
+    held before after it, restored in reverse order, also when the block raises.  Nests.  Like set_option it is process-wide: use
+    it while no call of the library is in flight on another thread."""
+    saved = []
+    try:
+        for name, value in values.items():
+            saved.append((name, get_option(name)))   # (raises for an unknown name before anything of it is set)
+            set_option(name, value)
+        yield
+    finally:
+        for name, value in reversed(saved):
+            set_option(name, value)

@@ -72,8 +72,6 @@ def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=Non
     Lmax = max_steps + 1
     A = eng.arena
     timing = os.environ.get("EMOASR_BEAM_TIMING") == "1"
-    if os.environ.get("EMOASR_DECODE_COOP"):    # A/B switch of csrc/decode_coop.hip (one cooperative launch per network and step)
-        lib.set_option("decode_coop", int(os.environ["EMOASR_DECODE_COOP"]))
     if timing:
         torch.cuda.synchronize()
         t_start = time.perf_counter()
@@ -191,7 +189,7 @@ def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=Non
         # HIP graphs pay off for the launch chains (~185 kernels per step); with the cooperative step kernels a step is ~25 launches
         # and plain launches are ~3 % faster (no graph boundaries: 0.476-0.607 against 0.494-0.625 ms per step over T' 190-600)
         g_env = os.environ.get("EMOASR_BEAM_GRAPH", "auto")
-        use_graph = (os.environ.get("EMOASR_DECODE_COOP", "1") == "0") if g_env == "auto" else g_env != "0"
+        use_graph = (lib.get_option("decode_coop") == 0) if g_env == "auto" else g_env != "0"
         if use_graph:
             if not getattr(eng, "_beam_graph_warm", False):
                 # first use in this process: one eager pass with the search marked finished, so that every kernel's lazy

@@ -43,17 +43,18 @@ enum { EMOASR_ACT_NONE = 0, EMOASR_ACT_RELU = 1, EMOASR_ACT_SWISH = 2,
 
 const char* emoasr_last_error(void);
 int emoasr_version(void);
-/* options: "tr_read" (1 = ds_read_b64_tr_b16 operand reads, 0 = scalar fallback); tuning: "gemm_tile", "gemm_kb",
- * "gemm_xcd", "gemm_wholek", "tn_group_blocks", "tn_group_kb", "tn_place", "attn_lpt", "attn_xcd", "attn_fwd_waves", "attn_fwd_split", "attn_fw" (key tiles per workgroup of the single-pass attention backward: 2, 4, 0 = auto);
- * round 4: "attn_bwd_split", "attn_side", "ffn_save_dact", "big_n256" (long reductions onto one / two 256-column tiles on the
- * large-tile kernel: 0 off, 1 = N 512 from K 512 and N 256 from K 2048, 2 = N 256 from K 512 as well), "big_waves" (8 / 4),
- * "big_bm", "big_min_tiles", "gemm_wide128", "ln_fwd8", "ln_bwd_pf", "ln_bwd_blocks", "conv1_pair", "lstm_coop", "decode_coop",
- * "rnnt_greedy_coop" -- every default is what the training step (or the decode leg) measured fastest;
- * "conv_strip" (32-frame tiles a workgroup of the fused convolution-module kernels walks, keeping the halo in LDS: 0 = by the
- * number of live strips of the launch -- the smallest n <= 8 that leaves at most two workgroups per CU --, n >= 1 = n tiles
- * (values above 65536 count as 65536), 1 = one tile per workgroup; a negative value counts as 0);
- * "timers" (see emoasr_timer_read) */
+/* Run-time options: named process-wide ints that select kernel paths and tuning values (csrc/common.h, EMO_OPTIONS, lists every
+ * one with its default, its normalisation and a line of description; every default is what the training step or the decode leg
+ * measured fastest).  emoasr_set_option stores the NORMALISED value (an out-of-range value becomes the option's fallback: e.g.
+ * "attn_fwd_waves" 3 -> 0, "big_waves" 5 -> 8, "conv_strip" -1 -> 0 and above 65536 -> 65536); emoasr_get_option returns the stored
+ * value and the default (either pointer may be null); emoasr_option_count / emoasr_option_name enumerate the names (null when the
+ * index is out of range).  An unknown name is an error (emoasr_last_error: "unknown option '<name>'").
+ * Options are read at launch time without synchronisation: set them while no call of the library is in flight on any thread.
+ * "timers": see emoasr_timer_read. */
 int emoasr_set_option(const char* name, int value);
+int emoasr_get_option(const char* name, int* value, int* default_value);
+int emoasr_option_count(void);
+const char* emoasr_option_name(int index);
 /* Device time of selected kernels that sit behind composite entry points, measured with HIP events on the launch stream
  * while emoasr_set_option("timers", 1) is in effect.  name: "attn_bwd_fused_kernel", "attn_bwd_dpos_kernel",
  * "attn_fwd_kernel", "gemm_tn_grouped_kernel".  -> number of launches recorded and their summed milliseconds

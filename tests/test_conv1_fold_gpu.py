@@ -34,8 +34,7 @@ def test_conv1_wgrad_folded_into_conv2_dgrad(dev, bm, B, T, Fd, C):
     """every tile height, ragged class tiles, C = 512 (two column tiles), the smallest input; plain and accumulating calls"""
     from emoasr_amd import lib, ops
     x, y1, dy2, wt = _inputs(dev, B, T, Fd, C)
-    lib.set_option("big_bm", bm)
-    try:
+    with lib.options(big_bm=bm):
         dy1 = ops.conv2_dgrad_kc(dy2, wt, y1)
         dw_ref = torch.empty(C, 9, device=dev)
         db_ref = torch.empty(C, device=dev)
@@ -50,8 +49,6 @@ def test_conv1_wgrad_folded_into_conv2_dgrad(dev, bm, B, T, Fd, C):
         ops.conv2_dgrad_w1(dy2, wt, y1, x, dw2, db2, accumulate=True)
         _close(dw2 - base_w, dw_ref, 1e-4, "conv1 wgrad (folded, accumulate)")
         _close(db2 - base_b, db_ref, 1e-4, "conv1 bgrad (folded, accumulate)")
-    finally:
-        lib.set_option("big_bm", 0)
 
 
 def test_conv1_fold_matches_torch_autograd(dev):

@@ -55,11 +55,8 @@ def _dense_case(dev, shape):
         inp = dict(g=_rnd(gen, dev, B * T, 2 * C, dtype=bf), w=_rnd(gen, dev, C, K, scale=K ** -0.5),
                    bias=_rnd(gen, dev, C, scale=0.1), gamma=1 + 0.1 * _rnd(gen, dev, C), beta=0.1 * _rnd(gen, dev, C),
                    ds=_rnd(gen, dev, B * T, C, dtype=bf), nbt=torch.zeros((), device=dev, dtype=torch.int64))
-        try:
-            lib.set_option("dwconv_lds", 0)
+        with lib.options(dwconv_lds=0):
             ref = _unfused(dev, shape, inp)
-        finally:
-            lib.set_option("dwconv_lds", 1)
         _DENSE[shape] = (inp, ref)
     return _DENSE[shape]
 
@@ -101,12 +98,9 @@ def test_dense_entries_bit_identical_for_every_strip_length(dev, shape, S):
     weight-gradient sums once per tile."""
     from emoasr_amd import lib
     inp, ref = _dense_case(dev, shape)
-    try:
-        lib.set_option("conv_strip", S)
+    with lib.options(conv_strip=S):
         lds = _unfused(dev, shape, inp)
         got = _fused(dev, shape, inp)
-    finally:
-        lib.set_option("conv_strip", 0)
     for k, v in ref.items():
         assert torch.equal(lds[k], v), f"S={S}: LDS-staged dwconv: {k} differs"
         if k in got:
@@ -192,8 +186,7 @@ def _stacked_case(dev, idx):
     dw_u, db_u = torch.zeros(C, K, device=dev), torch.zeros(C, device=dev)
     dw_ref = torch.zeros(C, K, device=dev, dtype=torch.float64)
     db_ref = torch.zeros(C, device=dev, dtype=torch.float64)
-    try:
-        lib.set_option("conv_strip", 1)
+    with lib.options(conv_strip=1):
         r0 = 0
         for B, T in segs:
             gi, dzi = i["g"][r0:r0 + B * T], dz[r0:r0 + B * T]
@@ -214,8 +207,6 @@ def _stacked_case(dev, idx):
             db_ref += dcd.sum(dim=(0, 1))
             cs.append(c2), means.append(mean), vars_.append(var)
             r0 += B * T
-    finally:
-        lib.set_option("conv_strip", 0)
     ref = dict(c=torch.cat(cs), z=torch.cat(zs), bmean=torch.stack(means), bvar=torch.stack(vars_), rm=rm, rv=rv, nbt=nbt)
     _STACKED[idx] = (i, dz, ref, torch.cat(dgs), dw_u, db_u, dw_ref, db_ref)
     return _STACKED[idx]
@@ -232,12 +223,9 @@ def test_stacked_entries_against_dense_per_segment(dev, idx, S):
     from emoasr_amd import lib
     segs, C, K = SEGSETS[idx]
     i, dz, ref, dg_ref, dw_u, db_u, dw_ref, db_ref = _stacked_case(dev, idx)
-    try:
-        lib.set_option("conv_strip", S)
+    with lib.options(conv_strip=S):
         got = _stacked_fwd(dev, segs, C, K, i)
         dg, dw, db = _stacked_bwd(dev, segs, C, K, i, dz, got["c"], got["bmean"], got["bvar"])
-    finally:
-        lib.set_option("conv_strip", 0)
     for k, v in ref.items():
         assert torch.equal(got[k], v), f"S={S}: {k} differs (max {(got[k].double() - v.double()).abs().max().item():.3e})"
     assert torch.equal(dg, dg_ref), f"S={S}: dg differs (max {(dg.float() - dg_ref.float()).abs().max().item():.3e})"
@@ -272,10 +260,7 @@ def test_stacked_backward_drops_no_tile(dev, S):
     dc = ops.bn_swish_bwd(dz[r0:r0 + n1], c[r0:r0 + n1], bmean[one], bvar[one], i["gamma"], i["beta"], EPS, dgam, dbet)
     assert torch.equal(dc, torch.ones_like(dc)), "the construction does not give dc == 1"
     from emoasr_amd import lib
-    try:
-        lib.set_option("conv_strip", S)
+    with lib.options(conv_strip=S):
         _, dw, db = _stacked_bwd(dev, segs, C, K, i, dz, c, bmean, bvar)
-    finally:
-        lib.set_option("conv_strip", 0)
     assert torch.isfinite(dw).all()
     assert torch.equal(db, torch.full_like(db, float(n1))), f"S={S}: db {db.min().item()} .. {db.max().item()}, rows {n1}"

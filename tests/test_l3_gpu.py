@@ -222,24 +222,16 @@ def test_alternative_decode_step_kernels_agree(dev, option):
     lm = LM(SimpleNamespace(**LM_CFG), compute_dtype=torch.bfloat16)
     lm.load_state_dict(lm_state(g))
     lm = lm.to(dev).eval()
-    try:
-        for u in range(min(3, len(g["xlens"]))):
-            n = int(g["xlens"][u])
-            x, xl = g["xs"][u:u + 1, :n].to(dev), g["xlens"][u:u + 1]
-            lib.set_option("decode_coop", 0)
+    if option.startswith("decode_coop_merge"):   # projection + self-attention as one stage in both / in neither stack
+        variant = dict(decode_coop=1, decode_coop_merge=int(option[-1]))
+    else:
+        variant = {option: 1}
+    for u in range(min(3, len(g["xlens"]))):
+        n = int(g["xlens"][u])
+        x, xl = g["xs"][u:u + 1, :n].to(dev), g["xlens"][u:u + 1]
+        with lib.options(decode_coop=0):
             ref_h, ref_s, _, _ = model.decode(x, xl, lm=lm, **DECODE_SETTINGS[2])
-            if option.startswith("decode_coop_merge"):   # projection + self-attention as one stage in both / in neither stack
-                lib.set_option("decode_coop", 1)
-                lib.set_option("decode_coop_merge", int(option[-1]))
-            else:
-                lib.set_option(option, 1)
+        with lib.options(**variant):
             hyps, scores, _, _ = model.decode(x, xl, lm=lm, **DECODE_SETTINGS[2])
-            if not option.startswith("decode_coop"):
-                lib.set_option(option, 0)
-            assert lib.size_query("emoasr_decode_coop_status") == 0
-            assert hyps[0] == ref_h[0] and abs(scores[0] - ref_s[0]) < 2e-2 * abs(ref_s[0]) + 1e-3, (u, hyps[0], ref_h[0], scores[0], ref_s[0])
-    finally:
-        if not option.startswith("decode_coop"):
-            lib.set_option(option, 0)
-        lib.set_option("decode_coop", 1)
-        lib.set_option("decode_coop_merge", 1)
+        assert lib.size_query("emoasr_decode_coop_status") == 0
+        assert hyps[0] == ref_h[0] and abs(scores[0] - ref_s[0]) < 2e-2 * abs(ref_s[0]) + 1e-3, (u, hyps[0], ref_h[0], scores[0], ref_s[0])

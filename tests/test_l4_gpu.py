@@ -94,13 +94,10 @@ def test_greedy_on_the_device_equals_the_launch_chain(dev, dtype):
                           eng.r_nl) == 1
 
     def run(flag):
-        lib.set_option("rnnt_greedy_coop", flag)
-        try:
+        with lib.options(rnnt_greedy_coop=flag):
             with torch.no_grad():
                 eouts, elens, _ = model.encoder(g["xs"].to(dev), g["xlens"])
                 return model.decoder._greedy(eouts, elens)
-        finally:
-            lib.set_option("rnnt_greedy_coop", 1)
 
     hyps1, _, _, aligns1 = run(1)
     hyps0, _, _, aligns0 = run(0)
@@ -120,13 +117,10 @@ def test_greedy_window_sizes(dev, window):
     from emoasr_amd import lib
     model, g = _build(torch.float32, dev)
     model.eval()
-    lib.set_option("rnnt_greedy_coop", 0)   # (the windows belong to the launch chain; the device-resident search has none)
-    try:
+    with lib.options(rnnt_greedy_coop=0):   # (the windows belong to the launch chain; the device-resident search has none)
         with torch.no_grad():
             eouts, elens, _ = model.encoder(g["xs"].to(dev), g["xlens"])
             hyps, aligns = model.engine().rnnt_greedy(eouts, elens.tolist(), 0, 2, window=window)
-    finally:
-        lib.set_option("rnnt_greedy_coop", 1)
     assert hyps == split_ragged(g["eval/hyps"], g["eval/hyp_lens"])
     assert aligns == split_ragged(g["eval/aligns"], g["eval/align_lens"])
 
@@ -162,8 +156,7 @@ def test_beam_round_kernels(dev, dtype, nb, mfma):
     from emoasr_amd import lib, ops
     if dtype == torch.float32 and mfma:
         pytest.skip("the matrix-core form is bf16")
-    lib.set_option("rnnt_beam_mfma", mfma)
-    try:
+    with lib.options(rnnt_beam_mfma=mfma):
         torch.manual_seed(nb)
         E, H, J, V, POOL, Tm, k = 64, 96, 48, 200, 40, 7, 4
         r = lambda *s, sc=1.0: (torch.randn(*s, device=dev) * sc).to(dtype)
@@ -207,8 +200,6 @@ def test_beam_round_kernels(dev, dtype, nb, mfma):
             assert torch.equal(lp[:, 1:].gather(1, got), vals), Vp   # (bf16 logits tie: torch.topk's order among equals is unspecified)
             tie = vals[:, 1:] == vals[:, :-1]
             assert bool((got[:, 1:][tie] > got[:, :-1][tie]).all()), Vp   # ties -> lowest index first
-    finally:
-        lib.set_option("rnnt_beam_mfma", 1)
 
 
 def test_beam_search_bf16_fused_round_agrees_with_the_chain(dev, monkeypatch):

@@ -37,9 +37,8 @@ def _seed():
 @pytest.fixture(params=[1, 0], ids=["tr", "notr"])
 def tr_mode(request):
     from emoasr_amd import lib
-    lib.set_option("tr_read", request.param)
-    yield request.param
-    lib.set_option("tr_read", 1)
+    with lib.options(tr_read=request.param):
+        yield request.param
 
 
 # ---------------------------------------------------------------- GEMM NT
@@ -172,12 +171,9 @@ def test_conv1_two_rows_per_block_equals_one_row_per_block(dev, B, T, Fd):
     w1, b1 = _rnd(dev, C, 1, 3, 3, scale=0.3), _rnd(dev, C, scale=0.1)
     ref = F.relu(F.conv2d(x.unsqueeze(1), w1, b1, stride=2)).permute(0, 2, 3, 1)
     outs = []
-    try:
-        for pair in (1, 0):
-            lib.set_option("conv1_pair", pair)
+    for pair in (1, 0):
+        with lib.options(conv1_pair=pair):
             outs.append(ops.conv1_fwd(x, w1.reshape(C, 9).contiguous(), b1, torch.bfloat16))
-    finally:
-        lib.set_option("conv1_pair", 1)
     assert torch.equal(outs[0], outs[1])
     _close(outs[0], ref, 1e-2, "conv1")
 
@@ -236,16 +232,13 @@ def test_gemm_nt_big(dev, bm, M, N, K):
     a = _rnd(dev, M, K + 8, dtype=torch.bfloat16)[:, :K]  # lda != K
     b = _rnd(dev, N, K, dtype=torch.bfloat16, scale=K ** -0.5)
     bias = _rnd(dev, N, scale=0.5)
-    lib.set_option("big_bm", bm)
-    try:
+    with lib.options(big_bm=bm):
         for relu in (False, True):
             out = ops.gemm_nt_big(a, b, bias=bias, relu=relu)
             ref = a.float() @ b.float().t() + bias
             _close(out, F.relu(ref) if relu else ref, 1e-2, f"gemm_nt_big relu={relu}")
         out = ops.gemm_nt_big(a, b)
         _close(out, a.float() @ b.float().t(), 1e-2, "gemm_nt_big plain")
-    finally:
-        lib.set_option("big_bm", 0)
 
 
 @pytest.mark.parametrize("M,N,K", [(700, 512, 256), (7029, 1024, 256), (333, 768, 128), (2000, 1000, 512)])
@@ -257,16 +250,11 @@ def test_gemm_nt_dispatch_to_large_tile_kernel(dev, M, N, K):
     b = _rnd(dev, N, K, dtype=torch.bfloat16, scale=K ** -0.5)
     bias = _rnd(dev, N, scale=0.5)
     outs = []
-    try:
-        for big in (1, 0):
-            lib.set_option("conv_big", big)
-            lib.set_option("big_min_tiles", 1)
+    for big in (1, 0):
+        with lib.options(conv_big=big, big_min_tiles=1):
             pre = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
             y = ops.gemm_nt(a, b, bias=bias, alpha=0.5, act=ops.ACT_SWISH, pre_out=pre, drop_p=0.1, seed=77)
             outs.append((y, pre, ops.gemm_nt(a, b)))
-    finally:
-        lib.set_option("conv_big", 1)
-        lib.set_option("big_min_tiles", 2000)   # (the library's default)
     (y1, p1, r1), (y0, p0, r0) = outs
     assert torch.equal(y1 == 0, y0 == 0), "dropout masks differ"
     _close(p1, 0.5 * (a.float() @ b.float().t()) + bias, 1e-2, "pre-activation")
@@ -286,14 +274,11 @@ def test_gemm_nt_long_reductions_on_one_column_tile(dev, M, N, K):
     bias = _rnd(dev, N, scale=0.5)
     x0 = _rnd(dev, M, N, dtype=torch.bfloat16)
     outs = []
-    try:
-        for big in (2, 0):   # (2, the default: N = 256 from K = 512 on; 1 takes K >= 2048 only)
-            lib.set_option("big_n256", big)
+    for big in (2, 0):   # (2: N = 256 from K = 512 on; 1 takes K >= 2048 only)
+        with lib.options(big_n256=big):
             x = x0.clone()
             ops.gemm_nt(a, b, out=x, bias=bias, residual=x, res_scale=0.5, drop_p=0.1, seed=91)   # in place
             outs.append((x, ops.gemm_nt(a, b, bias=bias, residual=x0, res_scale=0.5), ops.gemm_nt(a, b, bias=bias)))
-    finally:
-        lib.set_option("big_n256", 2)   # (the library's default)
     (x1, r1, p1), (x0_, r0, p0) = outs
     assert torch.equal(x1 == x0, x0_ == x0), "dropout masks differ"
     ref = a.float() @ b.float().t() + bias
@@ -323,12 +308,10 @@ def test_conv2_large_tile_kernels(dev, bm, B, T, Fd):
     g = torch.randn_like(y2_ref)
     y2_ref.backward(g)
     w2p = _conv2_weight_repack(w2b)
-    lib.set_option("big_bm", bm)
-    try:
+    with lib.options(big_bm=bm):
         y2 = ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU)
-        lib.set_option("conv_big", 0)
-        y2_old = ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU)
-        lib.set_option("conv_big", 1)
+        with lib.options(conv_big=0):
+            y2_old = ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU)
         _close(y2, y2_ref.permute(0, 2, 3, 1), 1e-2, "conv2 big")
         _close(y2, y2_old, 1e-2, "conv2 big vs 128x64")
         dy2 = (g.permute(0, 2, 3, 1) * (y2_ref.permute(0, 2, 3, 1) > 0)).contiguous().to(dtype)
@@ -341,9 +324,6 @@ def test_conv2_large_tile_kernels(dev, bm, B, T, Fd):
         dy1_ref = (y1r.grad * (y1r > 0)).permute(0, 2, 3, 1)
         _close(dy1, dy1_ref, 1.5e-2, "conv2 big dgrad")
         _close(dy1, ops.conv2_dgrad(dy2, w2p, y1), 1.5e-2, "conv2 big dgrad vs parity-class launches")
-    finally:
-        lib.set_option("big_bm", 0)
-        lib.set_option("conv_big", 1)
 
 
 @pytest.mark.parametrize("B,T,C,K", [(3, 70, 256, 31), (2, 33, 256, 15), (2, 20, 144, 31), (1, 100, 512, 7), (4, 320, 256, 31)])
@@ -381,14 +361,11 @@ def test_fused_conv_module_kernels_are_bit_identical(dev, B, T, C, K):
         dg = ops.conv_bwd_fused(ds, c.view(B * T, C), mean, var, gamma, beta, 1e-5, dgam, dbet, g, w, dw, db, B, T)
         return dict(c=c, mean=mean, var=var, rm=rm, rv=rv, c_eval=c_eval, dgam=dgam, dbet=dbet, dw=dw, db=db, dg=dg)
 
-    try:
-        lib.set_option("dwconv_lds", 0)
+    with lib.options(dwconv_lds=0):
         ref = unfused()          # the round-1 kernels
-        lib.set_option("dwconv_lds", 1)
+    with lib.options(dwconv_lds=1):
         lds = unfused()          # same sequence, LDS-staged stencils
         got = fused()
-    finally:
-        lib.set_option("dwconv_lds", 1)
     for k, v in ref.items():
         assert torch.equal(lds[k], v), f"LDS-staged dwconv: {k} differs"
         if k in got:
@@ -500,12 +477,9 @@ def test_attention(dev, dtype, tr_mode, case, mat):
     dpos = torch.zeros(2 * Tq - 1, D, device=dev) if rel else None
     dbu = torch.zeros(D, device=dev) if rel else None
     dbv = torch.zeros(D, device=dev) if rel else None
-    lib.set_option("attn_bwd_split", 0 if single else 1)
-    try:
+    with lib.options(attn_bwd_split=0 if single else 1):
         ops.attn_bwd(dout, out, lse, q, k, v, H, scale, dq, dk_, dv, pos=pos, bias_u=bu, bias_v=bv, klens=klens,
                      causal=causal, dpos=dpos, dbias_u=dbu, dbias_v=dbv, materialise=mat if mat == "fused" else bool(mat), st=st)
-    finally:
-        lib.set_option("attn_bwd_split", 1)
     btol = _tol(dtype, 1e-4, 4e-2)
     _close(dq, leaves[0].grad, btol, f"attn dq {case}")
     _close(dk_, leaves[1].grad, btol, f"attn dk {case}")
@@ -590,15 +564,11 @@ def test_attention_fwd_block_staged_equals_per_wave_kernel(dev, shape, p):
     kw = dict(pos=pos, bias_u=bu, bias_v=bv, klens=klens, drop_p=p, seed=4)
     mask = ops.attn_dropmask(q, k, H, klens=klens, drop_p=p, seed=4) if p > 0 else None
     outs = {}
-    try:
-        lib.set_option("attn_fwd_split", 0)   # (small launches of the per-wave kernel split the KEYS over four waves: another summation order)
-        for flag in (0, 2):
-            lib.set_option("attn_fwd4", flag)
+    for flag in (0, 2):
+        # (attn_fwd_split: small launches of the per-wave kernel split the KEYS over four waves: another summation order)
+        with lib.options(attn_fwd_split=0, attn_fwd4=flag):
             outs[flag] = [ops.attn_fwd(q, k, v, H, 0.125, **kw), ops.attn_fwd(q, k, v, H, 0.125, keep_mask=mask, **kw)]
             torch.cuda.synchronize()
-    finally:
-        lib.set_option("attn_fwd4", 1)
-        lib.set_option("attn_fwd_split", 1)
     for (o0, l0), (o2, l2) in zip(outs[0], outs[2]):
         assert torch.equal(o0, o2) and torch.equal(l0, l2)
     assert torch.isfinite(outs[2][0][0].float()).all()
@@ -626,16 +596,15 @@ def test_attention_bwd_fused_vs_materialised(dev, case):
     res = {}
     from emoasr_amd import lib
     for mode in (True, "fused", "fused1"):
-        lib.set_option("attn_bwd_split", 0 if mode == "fused1" else 1)
-        dqkv = torch.full_like(qkv, float("nan"))  # every entry must be written
-        dq, dk_, dv = dqkv[..., :D], dqkv[..., D:2 * D], dqkv[..., 2 * D:]
-        dpos = torch.zeros(2 * T - 1, D, device=dev) if rel else None
-        dbu = torch.zeros(D, device=dev) if rel else None
-        dbv = torch.zeros(D, device=dev) if rel else None
-        ops.attn_bwd(dout, out, lse, q, k, v, H, scale, dq, dk_, dv, pos=pos, bias_u=bu, bias_v=bv, klens=klens,
-                     drop_p=0.1, seed=77, dpos=dpos, dbias_u=dbu, dbias_v=dbv, materialise="fused" if mode == "fused1" else mode)
-        res[mode] = (dqkv.float(), dpos, dbu, dbv)
-    lib.set_option("attn_bwd_split", 1)
+        with lib.options(attn_bwd_split=0 if mode == "fused1" else 1):
+            dqkv = torch.full_like(qkv, float("nan"))  # every entry must be written
+            dq, dk_, dv = dqkv[..., :D], dqkv[..., D:2 * D], dqkv[..., 2 * D:]
+            dpos = torch.zeros(2 * T - 1, D, device=dev) if rel else None
+            dbu = torch.zeros(D, device=dev) if rel else None
+            dbv = torch.zeros(D, device=dev) if rel else None
+            ops.attn_bwd(dout, out, lse, q, k, v, H, scale, dq, dk_, dv, pos=pos, bias_u=bu, bias_v=bv, klens=klens,
+                         drop_p=0.1, seed=77, dpos=dpos, dbias_u=dbu, dbias_v=dbv, materialise="fused" if mode == "fused1" else mode)
+            res[mode] = (dqkv.float(), dpos, dbu, dbv)
     a = res[True]
     for name in ("fused", "fused1"):   # the two-pass kernels (default) and the single-pass kernel
         f = res[name]
@@ -665,10 +634,8 @@ def test_attention_bwd_fused_run_to_run(dev):
     scale = 1 / math.sqrt(dk)
     out, lse = ops.attn_fwd(q, k, v, H, scale, pos=pos, bias_u=bu, bias_v=bv, klens=klens, drop_p=0.1, seed=5)
     dout = _rnd(dev, B, T, D, dtype=dt_)
-    try:
-        for fw in (0, 4, 2):   # 0: the two-pass backward (default); 4 / 2: the single-pass kernel at both workgroup sizes
-            lib.set_option("attn_bwd_split", 1 if fw == 0 else 0)
-            lib.set_option("attn_fw", fw)
+    for fw in (0, 4, 2):   # 0: the two-pass backward (default); 4 / 2: the single-pass kernel at both workgroup sizes
+        with lib.options(attn_bwd_split=1 if fw == 0 else 0, attn_fw=fw):
             first = None
             for it in range(8):
                 dqkv = torch.full_like(qkv, float("nan"))
@@ -688,9 +655,6 @@ def test_attention_bwd_fused_run_to_run(dev):
                 _close(cur[0][..., :D], first[0][..., :D], 1e-2, "dq run to run")
                 _close(cur[1], first[1], 1e-3, "dpos run to run")
                 _close(cur[2], first[2], 1e-3, "dbias_u run to run")
-    finally:
-        lib.set_option("attn_fw", 0)
-        lib.set_option("attn_bwd_split", 1)
 
 
 def test_gemm_nt_lse_is_the_product_plus_the_row_pass(dev):
@@ -995,11 +959,8 @@ def test_gemm_tn_grouped_layer_shapes(dev, place):
         alpha = 1.0 if i % 2 else 0.5
         refs.append((out + alpha * (a.float().t() @ b.float()), None if cs is None else cs + alpha * a.float().sum(0)))
         probs.append((a, b, out, alpha, cs, alpha))
-    lib.set_option("tn_place", place)
-    try:
+    with lib.options(tn_place=place):
         ops.gemm_tn_grouped(probs)
-    finally:
-        lib.set_option("tn_place", 0)
     for i, ((a, b, out, alpha, cs, _), (ref, ref_cs)) in enumerate(zip(probs, refs)):
         _close(out, ref, _tol(torch.bfloat16), f"layer product {i}")
         if cs is not None:

@@ -102,12 +102,9 @@ def test_cooperative_matches_the_chain(dev, B, H):
     xs, R = torch.randn(B, T, nin), torch.randn(B, T, H)
     y_coop, g_coop = _run_layer(model, xs, lens, R, dev)
     assert lib.size_query("emoasr_lstm_coop_status") == 0
-    lib.set_option("lstm_coop", 0)
-    try:
+    with lib.options(lstm_coop=0):
         assert not _coop_ok(dev, B, H)
         y_chain, g_chain = _run_layer(model, xs, lens, R, dev)
-    finally:
-        lib.set_option("lstm_coop", 1)
     for b, n in enumerate(lens.tolist()):
         assert torch.count_nonzero(y_coop[b, n:]) == 0 and torch.count_nonzero(y_chain[b, n:]) == 0
     assert _rel(y_coop, y_chain) < 2e-2, _rel(y_coop, y_chain)

@@ -272,8 +272,7 @@ def test_fused_head(dev, V, J, many_rows, bm):
         N = B * T * U
         hd, wd, bd = c["h"].to(dev), c["w"].to(dev), c["bias"].to(dev)
         L, E, Y = _i32(c["labels"], dev), _i32(c["elens"], dev), _i32(c["ylens"], dev)
-        lib.set_option("big_bm", bm)
-        try:
+        with lib.options(big_bm=bm):
             ctx, nll = ops.rnnt_head_forward(hd, wd, bd, B, T, U, L, E, Y, blank)
             coef, ycol = ops.rnnt_coef(ctx, nll, L, E, Y, gs)
             dz = torch.full((N, V), float("nan"), device=dev, dtype=torch.bfloat16)
@@ -283,8 +282,6 @@ def test_fused_head(dev, V, J, many_rows, bm):
                 if n:
                     ops.rnnt_head_grad(hd[r0:r0 + n], wd, bd, coef[r0:r0 + n], ycol[r0:r0 + n], blank, dz[r0:r0 + n])
                 r0 += n
-        finally:
-            lib.set_option("big_bm", 0)
         res = {}
         for k, t in zip(("lse", "lpb", "lpy"), ctx):
             res[k] = _close_2e3(t.cpu().numpy(), getattr(ref, k))
@@ -321,12 +318,9 @@ def test_fused_head_in_several_launches(dev, V, J, bm):
     B, T, U, blank = c["B"], c["T"], c["U"], c["blank"]
     hd, wd, bd = c["h"].to(dev), c["w"].to(dev), c["bias"].to(dev)
     L, E, Y = _i32(c["labels"], dev), _i32(c["elens"], dev), _i32(c["ylens"], dev)
-    lib.set_option("big_bm", bm)
-    try:
+    with lib.options(big_bm=bm):
         ctx1, nll1 = ops.rnnt_head_forward(hd, wd, bd, B, T, U, L, E, Y, blank)
         ctx6, nll6 = ops.rnnt_head_forward(hd, wd, bd, B, T, U, L, E, Y, blank, rows_per_launch=256)
-    finally:
-        lib.set_option("big_bm", 0)
     valid = torch.from_numpy(c["ref"].valid).to(dev)
     assert torch.equal(nll1, nll6)
     for k, a, b in zip(("lse", "lpb", "lpy", "alpha", "beta"), ctx1, ctx6):

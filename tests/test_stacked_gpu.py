@@ -158,17 +158,16 @@ def test_weight_gradients_on_the_side_stream_equal_the_inline_launches(dev, mode
             eng.arena.grad.zero_()
             if eng._layer_rt is not None:
                 eng._layer_rt.wgrad_side = side
-            lib.set_option("wgrad_side", int(side))
-            seen = []
-            eng.grad_hook = seen.append
-            losses = eng.ctc_train_stacked(batches, 0)
-            if eng._layer_rt.wgrad_side != side:   # (the runtime was created by this first pass: switch and repeat)
-                eng._layer_rt.wgrad_side = side
-            torch.cuda.synchronize()
-            res.setdefault(side, []).append((losses.tolist(), eng.arena.grad.clone(), seen))
+            with lib.options(wgrad_side=int(side)):
+                seen = []
+                eng.grad_hook = seen.append
+                losses = eng.ctc_train_stacked(batches, 0)
+                if eng._layer_rt.wgrad_side != side:   # (the runtime was created by this first pass: switch and repeat)
+                    eng._layer_rt.wgrad_side = side
+                torch.cuda.synchronize()
+                res.setdefault(side, []).append((losses.tolist(), eng.arena.grad.clone(), seen))
     finally:
         eng.grad_hook = None
-        lib.set_option("wgrad_side", 0)
         if eng._layer_rt is not None:
             eng._layer_rt.wgrad_side = False
     (l0, g0, h0), (l1, g1, h1) = res[False][0], res[True][0]
@@ -230,20 +229,15 @@ def test_one_launch_per_kernel_equals_one_launch_per_segment(dev):
     sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
 
     def run(flag):
-        lib.set_option("stack_launch", flag)
         # (a per-segment attention launch of this size would split its keys over four waves -- a different order of the soft-max
         # sums than the stacked launch's; the claim here is about the launch structure, so both run unsplit)
-        lib.set_option("attn_fwd_split", 0)
-        try:
+        with lib.options(stack_launch=flag, attn_fwd_split=0):
             model.load_state_dict(sd0)
             eng.step_count = 5
             eng.arena.grad.zero_()
             losses = eng.ctc_train_stacked(batches, 0)
             torch.cuda.synchronize()
             return losses.tolist(), eng.arena.grad.clone()
-        finally:
-            lib.set_option("stack_launch", 1)
-            lib.set_option("attn_fwd_split", 1)
 
     l1, g1 = run(1)
     l0, g0 = run(0)
@@ -265,16 +259,13 @@ def test_query_pass_from_the_image_equals_the_recomputing_query_pass(dev):
     sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
 
     def run(flag):
-        lib.set_option("attn_q2", flag)
-        try:
+        with lib.options(attn_q2=flag):
             model.load_state_dict(sd0)
             eng.step_count = 5
             eng.arena.grad.zero_()
             losses = eng.ctc_train_stacked(batches, 0)
             torch.cuda.synchronize()
             return losses.tolist(), eng.arena.grad.clone()
-        finally:
-            lib.set_option("attn_q2", 1)
 
     l1, g1 = run(1)
     l0, g0 = run(0)

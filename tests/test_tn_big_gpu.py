@@ -23,8 +23,8 @@ def _seed_and_options():
     from emoasr_amd import lib
     torch.manual_seed(4321)
     yield
-    lib.set_option("tn_big", 1)
-    lib.set_option("tn_big_blocks", 0)
+    for name in ("tn_big", "tn_big_blocks"):   # (whatever a test left behind)
+        lib.set_option(name, lib.option_default(name))
 
 
 def _err(got, ref):
@@ -49,8 +49,6 @@ def _make(dev, n1, n2, k, colsum, alpha, lda=None):
 
 def _run(problems, big, blocks=0, call="grouped"):
     from emoasr_amd import lib, ops
-    lib.set_option("tn_big", big)
-    lib.set_option("tn_big_blocks", blocks)
     outs, css, args = [], [], []
     for p in problems:
         out = p["out0"].clone()
@@ -58,16 +56,13 @@ def _run(problems, big, blocks=0, call="grouped"):
         outs.append(out)
         css.append(cs)
         args.append((p["a"], p["b"], out[:p["n1"]], p["alpha"], None if cs is None else cs[:p["n1"]], p["alpha"]))
-    try:
+    with lib.options(tn_big=big, tn_big_blocks=blocks):
         if call == "grouped":
             ops.gemm_tn_grouped(args)
         else:
             for a, b, out, alpha, cs, s in args:
                 ops.gemm_tn(a, b, out=out, alpha=alpha, accumulate=True, colsum=cs, colsum_scale=s)
         torch.cuda.synchronize()
-    finally:
-        lib.set_option("tn_big", 1)
-        lib.set_option("tn_big_blocks", 0)
     return outs, css
 
 
@@ -161,12 +156,9 @@ def _conv_check(dev, segs, what, run_old, run_new):
     res = {}
     for name, big, fn in (("old", 0, run_old), ("new", 1, run_new)):
         dw, db = dw0.clone(), db0.clone()
-        lib.set_option("tn_big", big)
-        try:
+        with lib.options(tn_big=big):
             fn([(s[0], s[1]) for s in segs], dw[:C], db[:C])
             torch.cuda.synchronize()
-        finally:
-            lib.set_option("tn_big", 1)
         res[name] = (_err(dw[:C], ref_w), _err(db[:C], ref_b))
         assert torch.equal(dw[C], dw0[C]) and torch.equal(db[C:], db0[C:]), f"{what} {name}: guard written"
     print(f"{what}: dw old {res['old'][0]:.3e} new {res['new'][0]:.3e}   dbias old {res['old'][1]:.3e} new {res['new'][1]:.3e}")

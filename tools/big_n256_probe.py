@@ -21,10 +21,9 @@ for name, N, K in (("ffn2/d_ffn1", 256, 1024), ("d_qkv", 256, 768), ("d_pw1", 25
     ref = out.clone()
     row = f"{name:12s} {M}x{N}x{K}: 64x64 {t0:7.1f} us"
     for bm in (128, 192, 256):
-        lib.set_option("big_bm", bm)
-        t = graph_time(lambda: ops.gemm_nt_big(a, b, out=out, bias=bias))
+        with lib.options(big_bm=bm):
+            t = graph_time(lambda: ops.gemm_nt_big(a, b, out=out, bias=bias))
         err = (out.float() - ref.float()).abs().max().item()
         row += f" | big bm={bm} {t:7.1f} us (diff {err:.1e})"
-    lib.set_option("big_bm", 0)
     tb = graph_time(lambda: torch.mm(a, b.t(), out=out))
     print(row + f" | blas {tb:7.1f} us   [{2.0 * M * N * K / 1e6:.0f} MFLOP]")

@@ -52,9 +52,6 @@ for name, fn in cases:
     row = f"{name:42s}"
     for waves in ((8, 4) if os.environ.get("WAVES4") else (8,)):
         for bm in (0, 128, 192, 256):
-            lib.set_option("big_waves", waves)
-            lib.set_option("big_bm", bm)
-            row += f" | w{waves} bm{bm:<3d} {graph_time(fn, n=5):7.1f}"
+            with lib.options(big_waves=waves, big_bm=bm):
+                row += f" | w{waves} bm{bm:<3d} {graph_time(fn, n=5):7.1f}"
     print(row, flush=True)
-lib.set_option("big_waves", 8)
-lib.set_option("big_bm", 0)

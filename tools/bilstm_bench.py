@@ -56,14 +56,11 @@ def bench(B, T, H, layers, iters, dev):
     from emoasr_amd import lib, ops
     rows = []
     for path in ("coop", "chain"):
-        lib.set_option("lstm_coop", 1 if path == "coop" else 0)
-        try:
+        with lib.options(lstm_coop=1 if path == "coop" else 0):
             if path == "coop" and not ops.bilstm_seq_supported(xs.to(torch.bfloat16), B, H):
                 continue
             f = timed(fwd)
             fb = timed(fwd_bwd)
-        finally:
-            lib.set_option("lstm_coop", 1)
         r = dict(B=B, T=T, H=H, layers=layers, path=path, iters=iters)
         r["fwd_ms_per_layer"] = [round(v / layers, 3) for v in f]              # median, min, max
         r["fwd_bwd_ms_per_layer"] = [round(v / layers, 3) for v in fb]

@@ -29,16 +29,14 @@ dy2 = torch.randn_like(y2)
 print(f"B {B} T {T}: y1 {tuple(y1.shape)} M = {M} rows, {flop / 1e9:.1f} GFLOP per product", flush=True)
 bms = [int(v) for v in os.environ.get("BMS", "0,256,192,128").split(",")]
 for bm in bms:
-    lib.set_option("big_bm", bm)
+    with lib.options(big_bm=bm):
+        us = graph_time(lambda: ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU), n=5)
+        print(f"conv2 fwd   big bm={bm:3d}: {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
+        us = graph_time(lambda: ops.conv2_dgrad_kc(dy2, wt, y1), n=5)
+        print(f"conv2 dgrad big bm={bm:3d}: {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
+with lib.options(conv_big=0):
     us = graph_time(lambda: ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU), n=5)
-    print(f"conv2 fwd   big bm={bm:3d}: {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
-    us = graph_time(lambda: ops.conv2_dgrad_kc(dy2, wt, y1), n=5)
-    print(f"conv2 dgrad big bm={bm:3d}: {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
-lib.set_option("big_bm", 0)
-lib.set_option("conv_big", 0)
-us = graph_time(lambda: ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU), n=5)
 print(f"conv2 fwd   128x64     : {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
-lib.set_option("conv_big", 1)
 us = graph_time(lambda: ops.conv2_dgrad(dy2, w2p, y1), n=5)
 print(f"conv2 dgrad 128x64 x4  : {us:7.1f} us  {flop / us / 1e6:6.0f} TF/s", flush=True)
 dw = torch.zeros(C, 9 * C, device=dev)
@@ -51,10 +49,9 @@ for (m, n, k) in [(136800, 256, 2304), (7029, 1024, 256), (7029, 768, 256), (702
     f = 2.0 * m * n * k
     out = torch.empty(m, n, device=dev, dtype=dt)
     for bm in bms:
-        lib.set_option("big_bm", bm)
-        us = graph_time(lambda: ops.gemm_nt_big(a, b, out=out), n=5)
+        with lib.options(big_bm=bm):
+            us = graph_time(lambda: ops.gemm_nt_big(a, b, out=out), n=5)
         print(f"gemm {m}x{n}x{k} big bm={bm:3d}: {us:7.1f} us {f / us / 1e6:6.0f} TF/s", flush=True)
-    lib.set_option("big_bm", 0)
     us = graph_time(lambda: ops.gemm_nt(a, b, out=out), n=5)
     print(f"gemm {m}x{n}x{k} 128x64      : {us:7.1f} us {f / us / 1e6:6.0f} TF/s", flush=True)
     bt = b.t().contiguous()

@@ -34,9 +34,8 @@ def timeit(fn):
     return e0.elapsed_time(e1) / REP * 1e3
 
 for name, opts in [("default", {}), ("tap-major k order", {"big_korder": 0})] + [(f"big_bm {b}", {"big_bm": b}) for b in (128, 192, 256)]:
-    for k, v in opts.items(): lib.set_option(k, v)
-    u1 = timeit(lambda: ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU))
-    u2 = timeit(lambda: ops.conv2_dgrad_kc(dy2, wt, y1))
-    u3 = timeit(lambda: ops.conv2_wgrad(dy2, y1, dw, db, accumulate=True))
+    with lib.options(**opts):
+        u1 = timeit(lambda: ops.conv2_fwd(y1, w2p, bias=b2, act=ops.ACT_RELU))
+        u2 = timeit(lambda: ops.conv2_dgrad_kc(dy2, wt, y1))
+        u3 = timeit(lambda: ops.conv2_wgrad(dy2, y1, dw, db, accumulate=True))
     print(f"{name:20s} fwd {u1:7.1f} us   dgrad {u2:7.1f} us   wgrad {u3:7.1f} us   ({REP + 1} launches each)")
-    for k in opts: lib.set_option(k, {"big_korder": 1}.get(k, 0))

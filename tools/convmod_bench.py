@@ -26,12 +26,11 @@ dc = ops.bn_swish_bwd(ds, c2, mean, var, gamma, beta, 1e-5, dgam, dbet)
 dgl = ops.dwconv_bwd_x(dc.view(B, T, C), w)
 rows = []
 for lds in (0, 1):
-    lib.set_option("dwconv_lds", lds)
     tag = "lds" if lds else "r1 "
-    rows.append((f"glu_fwd", graph_time(lambda: ops.glu_fwd(g), n=10)))
-    rows.append((f"dwconv+stats+finalize [{tag}]", graph_time(lambda: ops.dwconv_bn_stats_fwd(gl.view(B, T, C), w, bias, rm, rv, 0.1), n=10)))
-    rows.append((f"dwconv_bwd_x [{tag}]", graph_time(lambda: ops.dwconv_bwd_x(dc.view(B, T, C), w), n=10)))
-lib.set_option("dwconv_lds", 1)
+    with lib.options(dwconv_lds=lds):
+        rows.append((f"glu_fwd", graph_time(lambda: ops.glu_fwd(g), n=10)))
+        rows.append((f"dwconv+stats+finalize [{tag}]", graph_time(lambda: ops.dwconv_bn_stats_fwd(gl.view(B, T, C), w, bias, rm, rv, 0.1), n=10)))
+        rows.append((f"dwconv_bwd_x [{tag}]", graph_time(lambda: ops.dwconv_bwd_x(dc.view(B, T, C), w), n=10)))
 rows.append(("bn_swish_bwd (sums+fold+apply)", graph_time(lambda: ops.bn_swish_bwd(ds, c2, mean, var, gamma, beta, 1e-5, dgam, dbet), n=10)))
 rows.append(("dwconv_bwd_w (+reduce)", graph_time(lambda: ops.dwconv_bwd_w(dc.view(B, T, C), gl.view(B, T, C), dw, db, accumulate=True), n=10)))
 rows.append(("glu_bwd", graph_time(lambda: ops.glu_bwd(g, dgl.view(B * T, C)), n=10)))

@@ -23,11 +23,10 @@ out0, out1 = torch.empty(M, J, device=dev, dtype=dt), torch.empty(M, J, device=d
 t0 = graph_time(lambda: ops.gemm_nn(dzp[:, :V], w, out=out0, dact_pre=h, dact=ops.DACT_TANH_OUT))
 print(f"nn 64x64 (K = 1000): {t0:7.1f} us")
 for bm in (0, 128, 192, 256):
-    lib.set_option("big_bm", bm)
-    t1 = graph_time(lambda: ops.gemm_nt(dzp, w_t, out=out1, dact_pre=h, dact=ops.DACT_TANH_OUT))
+    with lib.options(big_bm=bm):
+        t1 = graph_time(lambda: ops.gemm_nt(dzp, w_t, out=out1, dact_pre=h, dact=ops.DACT_TANH_OUT))
     print(f"nt large tile bm={bm} (K = 1024): {t1:7.1f} us   max |diff| {(out0.float() - out1.float()).abs().max().item():.2e}")
-lib.set_option("big_bm", 0)
-lib.set_option("big_n256", 0)
-t2 = graph_time(lambda: ops.gemm_nt(dzp, w_t, out=out1, dact_pre=h, dact=ops.DACT_TANH_OUT))
+with lib.options(big_n256=0):
+    t2 = graph_time(lambda: ops.gemm_nt(dzp, w_t, out=out1, dact_pre=h, dact=ops.DACT_TANH_OUT))
 print(f"nt 64x64 (K = 1024): {t2:7.1f} us")
 print(f"blas: {graph_time(lambda: torch.mm(dzp, w_t.t(), out=out1)):7.1f} us")

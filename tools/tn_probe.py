@@ -33,7 +33,6 @@ def timeit(fn):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / REP * 1e3
 
-DEFAULTS = {"gemm_xcd": 1, "tn_big": 1}   # every other option the variants touch defaults to 0
 OLD = {"tn_big": 0}                        # the 128x128 tile of gemm_tn_grouped_kernel: what the older variants below tune
 variants = [("default (256 tile)", {}), ("256 tile, 160 blocks", {"tn_big_blocks": 160}), ("256 tile, 192 blocks", {"tn_big_blocks": 192}),
             ("256 tile, 256 blocks", {"tn_big_blocks": 256}), ("256 tile, 320 blocks", {"tn_big_blocks": 320}),
@@ -42,26 +41,23 @@ variants = [("default (256 tile)", {}), ("256 tile, 160 blocks", {"tn_big_blocks
             ("BK=32, 512 blocks", {**OLD, "tn_group_blocks": 512}), ("BK=32, 896 blocks", {**OLD, "tn_group_blocks": 896}),
             ("64x64 tiles", {**OLD, "gemm_tile": 3})]
 for name, opts in variants:
-    for k, v in opts.items(): lib.set_option(k, v)
-    us = timeit(lambda: ops.gemm_tn_grouped(probs))
+    with lib.options(**opts):
+        us = timeit(lambda: ops.gemm_tn_grouped(probs))
     print(f"group  {name:22s} {us:8.1f} us  {alg/us/1e3:7.1f} GB/s algorithmic   ({REP + 1} launches)")
-    for k in opts: lib.set_option(k, DEFAULTS.get(k, 0))
 # the vocabulary head alone in a grouped launch (N1 = 10 000 under lda = 10 048), as the training step issues it
 ha, hb = rnd(K, 10048)[:, :10000], rnd(K, 256)
 hout, hcs = torch.zeros(10000, 256, device=dev), torch.zeros(10000, device=dev)
 for name, opts in [("default (256 tile)", {}), ("256 tile, 192 blocks", {"tn_big_blocks": 192}), ("256 tile, 256 blocks", {"tn_big_blocks": 256}),
                    ("256 tile, 320 blocks", {"tn_big_blocks": 320}), ("128 tile", OLD)]:
-    for k, v in opts.items(): lib.set_option(k, v)
-    us = timeit(lambda: ops.gemm_tn_grouped([(ha, hb, hout, 1.0, hcs, 1.0)]))
+    with lib.options(**opts):
+        us = timeit(lambda: ops.gemm_tn_grouped([(ha, hb, hout, 1.0, hcs, 1.0)]))
     print(f"head   {name:22s} {us:8.1f} us   ({REP + 1} launches)")
-    for k in opts: lib.set_option(k, DEFAULTS.get(k, 0))
 for i in (0, 1, 2, 3):
     us = timeit(lambda: ops.gemm_tn_grouped(probs[i:i + 1]))
     n1, n2 = shapes[i][:2]
     print(f"single {n1}x{n2}        {us:8.1f} us  {K*(n1+n2)*2/us/1e3:7.1f} GB/s algorithmic   ({REP + 1} launches)")
 
 # plain launches, 128 tile (the Conv2d weight gradient is an implicit GEMM, K = B*T2*F2, and has no 256-tile form)
-lib.set_option("tn_big", 0)
 a, b = rnd(K, 10000), rnd(K, 256)
 out, cs = torch.zeros(10000, 256, device=dev), torch.zeros(10000, device=dev)
 B_, T1, F1, C = 16, 4 * (K // 5 // 16) // 2, 39, 256
@@ -70,18 +66,15 @@ dy2 = rnd(B_, T2, F2, C); dw = torch.zeros(C, 3, 3, C, device=dev); db = torch.z
 print(f"conv2 wgrad: K = {B_ * T2 * F2}")
 for name, opts in [("default", {}), ("BK=64, 512", {"gemm_kb": 2, "tn_group_blocks": 512}), ("288 blocks", {"tn_group_blocks": 288}),
                    ("576 blocks", {"tn_group_blocks": 576}), ("864 blocks", {"tn_group_blocks": 864})]:
-    for k, v in opts.items(): lib.set_option(k, v)
-    u1 = timeit(lambda: ops.gemm_tn(a, b, out=out, accumulate=True, colsum=cs))
-    u2 = timeit(lambda: ops.conv2_wgrad(dy2, y1, dw, db, accumulate=True))
+    with lib.options(tn_big=0, **opts):
+        u1 = timeit(lambda: ops.gemm_tn(a, b, out=out, accumulate=True, colsum=cs))
+        u2 = timeit(lambda: ops.conv2_wgrad(dy2, y1, dw, db, accumulate=True))
     print(f"plain  {name:16s} head wgrad {u1:8.1f} us   conv2 wgrad {u2:8.1f} us")
-    for k in opts: lib.set_option(k, 0)
-lib.set_option("tn_big", 1)
 # the Conv2d weight gradient of five micro-batches: five launches (gemm_tn_kernel) against ONE segmented launch of the 256 tile
 segs = [(rnd(B_ * T2 * F2, C), rnd(B_, T1, F1, C)) for _ in range(5)]
 def five():
     for d, y in segs: ops.conv2_wgrad(d, y, dw, db, accumulate=True)
 print(f"conv2 wgrad x 5: five launches {timeit(five):8.1f} us")
 for blocks in (0, 189, 252, 315):
-    lib.set_option("tn_big_blocks", blocks)
-    print(f"conv2 wgrad x 5: one segmented launch, {blocks or 'default'} blocks {timeit(lambda: ops.conv2_wgrad_seg(segs, dw, dbias=db)):8.1f} us")
-lib.set_option("tn_big_blocks", 0)
+    with lib.options(tn_big_blocks=blocks):
+        print(f"conv2 wgrad x 5: one segmented launch, {blocks or 'default'} blocks {timeit(lambda: ops.conv2_wgrad_seg(segs, dw, dbias=db)):8.1f} us")
