@@ -48,13 +48,14 @@ __global__ __launch_bounds__(256) void row_lse_kernel(int V, const T* __restrict
 #pragma unroll
     for (int j = 1; j < VEC; ++j) lm = fmaxf(lm, v.get(j));
     if (lm > m) { s *= __expf(m - lm); m = lm; }
+    if (m == -INFINITY) continue;   // nothing but -inf so far: exp(-inf - -inf) would be NaN
 #pragma unroll
     for (int j = 0; j < VEC; ++j) s += __expf(v.get(j) - m);
   }
   for (int i = nv * VEC + threadIdx.x; i < V; i += 256) {
     const float x = to_f32(row[i]);
     if (x > m) { s *= __expf(m - x); m = x; }
-    s += __expf(x - m);
+    if (m != -INFINITY) s += __expf(x - m);
   }
   const float gm = block_max(m, red);
   const float gs = block_sum(m == -INFINITY ? 0.f : s * __expf(m - gm), red);
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(int B, int Tn, int S,
   const bool fwd = blockIdx.x < B;
   const int b = fwd ? blockIdx.x : blockIdx.x - B;
   const int s = threadIdx.x;
-  const int len = elens[b], L = ylens[b], Sb = 2 * L + 1;
+  const int len = min(elens[b], Tn), L = ylens[b], Sb = 2 * L + 1;   // (a length past the tables is clamped, as in the decoders)
   const int* lab = labels + (long)b * Lmax;
   float* out = (fwd ? alpha : beta) + (long)b * Tn * S;
   const float* lpb = lp + (long)b * Tn * S;
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(int Tn, int V, int S, int
                                                        const float* __restrict__ beta,
                                                        const float* __restrict__ nll, float gscale,
                                                        const float* __restrict__ gscale_dev,
-                                                       T* __restrict__ grad, long ldg, const UttRows ur) {
+                                                       T* __restrict__ grad, long ldg, const UttRows ur, int aligned) {
   extern __shared__ float rowbuf[];  // [V]
   const int b = blockIdx.y, t = blockIdx.x;
   if (ur.tpad && t >= ur.tpad[b]) return;                   // (the grid follows the longest micro-batch)
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(int Tn, int V, int S, int
   const long lrow = ur.row0 ? ur.row0[b] + t : row;         // row of logits / lse / grad
   T* g = grad + lrow * ldg;
   const float nl = nll[b];
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0) && (ldg % 8 == 0);  // 16-byte row accesses
+  const bool vec = aligned && (V % 8 == 0) && (ld % 8 == 0) && (ldg % 8 == 0);  // 16-byte row accesses
   if (t >= elens[b] || !isfinite(nl)) {
     if (vec) {
       float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -353,13 +354,15 @@ extern "C" int emoasr_ctc_grad_rows(int dtype, int B, int Tn, int V, int Lmax, c
   EMO_CHECK((size_t)V * 4 <= 160 * 1024 - 256, "ctc_grad: V=%d too large for an LDS row", V);
   if (B == 0 || Tn == 0) return 0;
   dim3 grid(Tn, B);
+  // 16-byte row accesses need 16-byte aligned base pointers as well (a view that starts inside a larger buffer need not be)
+  const int aligned = (((uintptr_t)logits | (uintptr_t)grad) & 15) == 0;
   EMO_DISPATCH(dtype, {
     if ((size_t)V * 4 > 64 * 1024)
       hipFuncSetAttribute((const void*)ctc_grad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, V * 4);
     ctc_grad_kernel<T><<<grid, 256, sizeof(float) * V, (hipStream_t)stream>>>(
         Tn, V, S, Lmax, (const T*)logits, ld, lse, labels, elens, ylens, blank, lp, alpha, beta, nll, gscale,
         gscale_dev,
-        (T*)grad, ldg, ur);
+        (T*)grad, ldg, ur, aligned);
   });
   EMO_LAUNCH_CHECK();
   return 0;
