@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libemoasr_hip.so")
 SOURCES = ["api.hip", "gemm.hip", "layernorm.hip", "elementwise.hip", "convmodule.hip",
-           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_beam.hip", "ctc_beam_host.hip"]
+           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_beam.hip", "rnnlm.hip", "ctc_beam_host.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-Wno-unused-value", "-Wno-comment",
          "-ffp-contract=off"]
 
@@ -27,7 +27,7 @@ def build(force=False, verbose=True, variant=None, defines=()):
     objdir = os.path.join(HERE, "build") if not variant else os.path.join(HERE, "build", "variant_" + variant)
     LIB = globals()["LIB"] if not variant else os.path.join(HERE, "build", f"libemoasr_hip_{variant}.so")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h", "lstm_step.h")]
     headers.append(os.path.join(HERE, "..", "include", "emoasr_hip.h"))
     sources = SOURCES
     flags = FLAGS + ["-D" + d for d in defines]

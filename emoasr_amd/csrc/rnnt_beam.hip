@@ -19,6 +19,7 @@
 // product differs from the MFMA kernels', so near-ties of the top-k can differ (tests: the reference's golden hypotheses, both forms).
 #include <math.h>
 #include "common.h"
+#include "lstm_step.h"
 #include "../../include/emoasr_hip.h"
 
 namespace {
@@ -26,42 +27,6 @@ namespace {
 constexpr int BT = 256;        // threads per workgroup
 constexpr int NBMAX = 16;      // hypotheses per round
 constexpr int UN = 8;          // hidden units per workgroup (4 UN = 32 gate rows = the 32 eight-lane row groups of a workgroup)
-
-template <typename T> __device__ __forceinline__ float rnd(float x) { return to_f32(from_f32<T>(x)); }
-
-// acc[i] += sum_e w[k0 + e] * x_i[k0 + e] for this lane's 16-byte pieces of one weight row, every hypothesis i < nb.
-// xs: f32 [NBMAX][ldx] in LDS.  8 lanes share a row (sub = lane's piece index): pieces k0 = sub * VEC, + 8 * VEC, ...
-template <typename T>
-__device__ __forceinline__ void row_dots(const T* __restrict__ w, int K, const float* __restrict__ xs, int ldx, int nb, int sub,
-                                         float (&acc)[NBMAX]) {
-  constexpr int VEC = 16 / sizeof(T);
-  for (int k = sub * VEC; k < K; k += 8 * VEC) {
-    float wv[VEC];
-    if constexpr (sizeof(T) == 2) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(w + k);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) wv[e] = (float)v[e];
-    } else {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(w + k);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) wv[e] = v[e];
-    }
-#pragma unroll
-    for (int i = 0; i < NBMAX; ++i) {
-      if (i < nb) {
-        const float* x = xs + i * ldx + k;
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) s += wv[e] * x[e];
-        acc[i] += s;
-      }
-    }
-  }
-}
-__device__ __forceinline__ float group_sum8(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  return v;
-}
 
 struct BeamLstmArgs {
   int nb, nin, H;
@@ -277,22 +242,6 @@ __global__ __launch_bounds__(64) void rnnt_beam_pick16_kernel(int V, int k, int 
 // lane of the launch, all of a wave's loads are in flight together -- the B fragments (16 bytes of one hypothesis' input row) from an
 // LDS image [16][K + 8] (bf16; rows of hypotheses >= nb are zero).  The VALU form above spent its time re-reading the inputs from LDS
 // for every weight row (13 us per layer at H = 512; this form: weight-streaming latency).
-typedef __attribute__((ext_vector_type(4))) float f32x4_;
-__device__ __forceinline__ f32x4_ rows16_dot(const bf16* __restrict__ wrow0, long ldw, int K, const bf16* __restrict__ xs, int ldxs,
-                                             int lane) {
-  // wrow0: first of the wave's 16 rows; lane <-> (row lane & 15, k piece 8 * (lane >> 4)) of each 32-wide k step
-  const bf16* wp = wrow0 + (long)(lane & 15) * ldw + 8 * (lane >> 4);
-  const bf16* xp = xs + (lane & 15) * ldxs + 8 * (lane >> 4);
-  f32x4_ acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-  for (int k = 0; k < K; k += 32) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(wp + k);
-    const bf16x8 b = *reinterpret_cast<const bf16x8*>(xp + k);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-  return acc;   // acc[r] = D[row 4 * (lane >> 4) + r][hypothesis lane & 15]
-}
-
 // grid = H / 16 workgroups of 4 waves: wave q = gate q (i, f, g, o) of the workgroup's 16 hidden units
 __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

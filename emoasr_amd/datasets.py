@@ -236,12 +236,12 @@ def write_results_tsv(path, rows, comment=None):
 
 
 class LMDataset:
-    """lm/datasets.py:24-120 for the Transformer LM: a TSV with columns utt_id / token_id (space-separated ids).
+    """lm/datasets.py:24-120 for the Transformer and the RNN LM: a TSV with columns utt_id / token_id (space-separated ids).
     Items: (utt_id, y_in int64, ylen, label int64 | None).  phase "train": with params.add_sos_eos the ids are wrapped in <eos>,
     then y_in = y[:-1] and label = y[1:] (next-token targets); any other phase: y_in = y, no label."""
 
     def __init__(self, params, data_path, phase="train", size=-1):
-        if params.lm_type != "transformer":
+        if params.lm_type not in ("transformer", "rnn"):     # (next-token targets for both: lm/datasets.py:91)
             raise NotImplementedError(f"emoasr_amd: LMDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
         columns = ["utt_id", "token_id"] + (["ylen"] if getattr(params, "bucket_shuffle", False) else [])
         data = _read_table(data_path)[columns]

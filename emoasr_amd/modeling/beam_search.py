@@ -10,6 +10,10 @@ Device side per output step (all beams batched): decoder logits of the last posi
 log-probabilities, log-softmax + fusion, top-k candidate selection, CTC prefix scores for every
 (beam, candidate) with the scorer states kept on the device.  Host side: one small D2H per step
 (candidate ids/scores), then the reference's own list bookkeeping (sort, prune, finish).
+
+A stateful LM (the RNN LM, modeling/rnnlm.py) always takes the host-bookkeeping path: every beam carries the slot of its LM state
+(the LSTM run over hyp[:-1], as the reference's `lm_states`, decoders/transformer.py:190,223-253), an output step is ONE LM step
+for all beams from the parents' slots into the other half of a double-buffered slot pool.
 """
 import os
 
@@ -63,7 +67,20 @@ def joint_beam_search(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_w
             side = getattr(eng, "_lm_stream", None)
             if side is None:
                 side = eng._lm_stream = torch.cuda.Stream(device=dev)
-        beams = [dict(hyp=[eos], score=0.0, score_ctc=np.float32(0.0), parent=0, pcand=0)]
+        beams = [dict(hyp=[eos], score=0.0, score_ctc=np.float32(0.0), parent=0, pcand=0, lm_slot=-1)]     # (-1: the zero state)
+        stateful = use_lm and getattr(lm, "stateful", False)
+        if stateful:
+            pools = lm.new_pools(2 * beam_width, beam_width)
+
+        def lm_rows(ys_in, i, nb):
+            """f32 [nb, V]: the LM's next-token log-probabilities after every beam's hypothesis"""
+            if not stateful:
+                return lm.predict_device(ys_in, [i + 1] * nb)
+            base = (i % 2) * beam_width     # this step's half of the pool; the beams' slots are in the other one
+            ctl = h2d_i32([b["hyp"][-1] for b in beams] + [b["lm_slot"] for b in beams] + [base + m for m in range(nb)], dev)
+            lm.step(pools, nb, ctl[:nb], ctl[nb:2 * nb], ctl[2 * nb:])
+            return pools.logp[:nb]
+
         prev_states = None
         results = []
         for i in range(dec.max_decode_ylen):
@@ -84,13 +101,13 @@ def joint_beam_search(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_w
                 else:
                     with ops.stream_scope():
                         last = rt.step(ys_in)
-                        lm_lp = (lmrt.step(ys_in) if lmrt is not None else lm.predict_device(ys_in, [i + 1] * nb)) if use_lm else None
+                        lm_lp = (lmrt.step(ys_in) if lmrt is not None else lm_rows(ys_in, i, nb)) if use_lm else None
             else:
                 mem = eouts.expand(nb, T, eouts.shape[2]).contiguous()
                 el = h2d_i32([T] * nb, dev)
                 logits, _ = eng.dec_forward(mem, el, ys_in, [i] * nb, False, False)  # [nb, i+1, V]
                 last = logits[:, i]
-                lm_lp = lm.predict_device(ys_in, [i + 1] * nb) if use_lm else None
+                lm_lp = lm_rows(ys_in, i, nb) if use_lm else None
             scores_pre = ops.log_softmax(last, add=lm_lp, mu=mu)  # = scores_att (+ lm: the in-place alias quirk)
             if use_ctc:
                 vals, cands, lm_at = ops.topk(scores_pre, cw, aux=lm_lp)
@@ -115,11 +132,11 @@ def joint_beam_search(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_w
                     order = np.argsort(-sc, kind="stable")[:beam_width]
                     for j in order:
                         new_beams.append(dict(score=beam["score"] + float(sc[j]), hyp=beam["hyp"] + [int(cands_h[m, j])],
-                                              score_ctc=psi_h[m, j], parent=m, pcand=int(j)))
+                                              score_ctc=psi_h[m, j], parent=m, pcand=int(j), lm_slot=(i % 2) * beam_width + m))
                 else:
                     for j in range(beam_width):
                         new_beams.append(dict(score=beam["score"] + float(vals_h[m, j]), hyp=beam["hyp"] + [int(idx_h[m, j])],
-                                              score_ctc=np.float32(0.0), parent=m, pcand=0))
+                                              score_ctc=np.float32(0.0), parent=m, pcand=0, lm_slot=(i % 2) * beam_width + m))
             beams = sorted(new_beams, key=lambda b: b["score"], reverse=True)[:beam_width]
             alive = []
             for beam in beams:

@@ -11,6 +11,12 @@ is native host code in IEEE doubles, like the reference's python floats (csrc/ct
 emoasr_ctc_beam_step, 20 us per frame).  EMOASR_CTC_BEAM_NATIVE=0 runs the same bookkeeping as the Python
 loop below (bit-identical results; tests/test_ctc_beam_gpu.py compares the two).
 
+A stateful LM (the RNN LM, modeling/rnnlm.py: `lm.stateful`) is never re-run over a prefix: its state after a prefix is a function
+of the prefix alone (the reference's `lm_states` of a beam is the LSTM run over hyp[:-1], whichever path reached it), so the "score
+each distinct prefix once" scheme carries over with the state next to the row.  A live prefix's slot holds its log-probability row
+and the state after the whole prefix; a new prefix p + (v) is ONE step (token v, from p's slot, into a fresh slot), the root (<eos>,)
+a step from the zero state.  The slot of a prefix that died is freed only after the next frame's new prefixes were scored from it.
+
 Reference behaviour kept on purpose (it decides which prefixes survive):
   * the LM score of the k-th candidate extension of a prefix also contains the LM scores of the
     candidates tried before it (`score_lm +=` inside the candidate loop, ctc.py:309-310);
@@ -37,15 +43,49 @@ def _lse2(a, b):
 
 
 class _Prefix:
-    __slots__ = ("toks", "p_b", "p_nb", "asr", "lm", "len_bonus", "n_plain")
+    __slots__ = ("toks", "p_b", "p_nb", "asr", "lm", "len_bonus", "n_plain", "lm_states")
 
     def __init__(self, toks, p_b, p_nb, asr, lm, len_bonus, n_plain):
         self.toks, self.p_b, self.p_nb, self.asr, self.lm, self.len_bonus = toks, p_b, p_nb, asr, lm, len_bonus
         self.n_plain = n_plain  # tokens that are not <eos>
+        self.lm_states = None   # stateful LM without the prefix cache: (h, c) after toks[:-1], as the reference's beams carry it
 
     @property
     def total(self):
         return self.asr + self.lm + self.len_bonus
+
+
+class _LMSlots:
+    """slot bookkeeping of a stateful LM for the prefix searches: prefix -> slot of lm.new_pools (state after the prefix + its
+    log-probability row).  score(live) steps the prefixes that have no slot yet from their parents' slots; release(live) frees
+    what the PREVIOUS release found dead (its slots were still parents of this frame's new prefixes).  live <= beam_width prefixes,
+    as many dying ones: 2 * beam_width slots (+ 2 spare)."""
+
+    def __init__(self, lm, beam_width):
+        self.lm, self.n = lm, 2 * beam_width + 2
+        self.pools = lm.new_pools(self.n)
+        self.slot_of, self.free, self.dying = {}, list(range(self.n)), []
+        self.dev = self.pools.logp.device
+
+    def score(self, live):
+        """-> the prefixes that were new (now scored), in live order"""
+        need = [p for p in live if p not in self.slot_of]
+        if need:
+            from ..engine import h2d_i32
+            src = [self.slot_of[p[:-1]] if len(p) > 1 else -1 for p in need]     # (the root starts from the zero state)
+            dst = [self.free.pop() for _ in need]
+            ctl = h2d_i32([p[-1] for p in need] + src + dst, self.dev)
+            n = len(need)
+            self.lm.step(self.pools, n, ctl[:n], ctl[n:2 * n], ctl[2 * n:], ctl[2 * n:])
+            self.slot_of.update(zip(need, dst))
+        return need
+
+    def release(self, live):
+        keep = set(live)
+        for key in self.dying:
+            if key not in keep:     # (a prefix that died can be formed again one frame later: it keeps its slot)
+                self.free.append(self.slot_of.pop(key))
+        self.dying = [q for q in self.slot_of if q not in keep]
 
 
 def _search_native(logp_dev, top_dev, T, V, k, blank, eos, beam_width, len_weight, lm, lm_weight):
@@ -70,7 +110,12 @@ def _search_native(logp_dev, top_dev, T, V, k, blank, eos, beam_width, len_weigh
         tok = np.zeros(beam_width, dtype=np.int32)
         live = [(eos,)]
         dev = logp_dev.device
-        if use_lm:
+        stateful = use_lm and getattr(lm, "stateful", False)
+        if stateful:
+            slots = _LMSlots(lm, beam_width)
+            cache, slot_of = slots.pools.logp, slots.slot_of
+            top_long = top_dev.long()
+        elif use_lm:
             nslot = 2 * beam_width + 2
             cache = torch.empty(nslot, V, device=dev, dtype=torch.float32)   # LM rows of the live prefixes
             slot_of, free = {}, list(range(nslot))
@@ -78,6 +123,8 @@ def _search_native(logp_dev, top_dev, T, V, k, blank, eos, beam_width, len_weigh
         for t in range(T):
             lm_ptr = None
             if use_lm:
+                if stateful:
+                    slots.score(live)     # one step per new prefix, rows and states stay in the slot pools
                 need = [p for p in live if p not in slot_of]
                 if need:
                     n = max(len(p) for p in need)
@@ -98,7 +145,9 @@ def _search_native(logp_dev, top_dev, T, V, k, blank, eos, beam_width, len_weigh
             if n < 0:
                 raise lib.EmoasrHipError("emoasr_ctc_beam_step failed: " + L.emoasr_last_error().decode())
             live = [live[parent[i]] + ((int(tok[i]),) if tok[i] >= 0 else ()) for i in range(n)]
-            if use_lm:
+            if stateful:
+                slots.release(live)
+            elif use_lm:
                 keep = set(live)
                 for key in [q for q in slot_of if q not in keep]:
                     free.append(slot_of.pop(key))
@@ -107,6 +156,33 @@ def _search_native(logp_dev, top_dev, T, V, k, blank, eos, beam_width, len_weigh
         return [list(p) for p in live], [float(v) for v in scores]
     finally:
         L.emoasr_ctc_beam_free(h)
+
+
+def _stateless_rows(lm, live, lm_rows, lm_cache):
+    """LM rows (float64 numpy) of the live prefixes from a stateless LM, which re-runs a prefix to score it.
+    The reference scores EVERY live prefix with the LM at every frame (ctc.py:241-260) -- the same prefix again and again
+    while it survives.  The LM's next-token row is a function of the prefix alone, so each distinct prefix is scored
+    ONCE (the frame it first survives) and its row kept while it is live: a frame costs an LM call only for prefixes
+    that are new, in one batch (rows of a batched call do not depend on their neighbours).  EMOASR_CTC_LM_CACHE=0:
+    the reference's recomputation."""
+    need = [p for p in live if p.toks not in lm_rows] if lm_cache else list(live)
+    if need:
+        n = max(len(p.toks) for p in need)
+        batch = torch.zeros(len(need), n, dtype=torch.int64)  # 0-padded like pad_sequence (ctc.py:243-246)
+        for i, p in enumerate(need):
+            batch[i, : len(p.toks)] = torch.tensor(p.toks)
+        rows, _ = lm.predict(batch, [len(p.toks) for p in need])
+        rows = rows.cpu().numpy().astype(np.float64)
+        for i, p in enumerate(need):
+            lm_rows[p.toks] = rows[i]
+    lm_lp = [lm_rows[p.toks] for p in live]
+    if lm_cache:
+        keep = {p.toks for p in live}
+        for key in [k for k in lm_rows if k not in keep]:
+            del lm_rows[key]
+    else:
+        lm_rows.clear()
+    return lm_lp
 
 
 def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=None, lm_weight=0.0):
@@ -127,34 +203,37 @@ def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=Non
         top = top_dev.cpu().numpy()
     use_lm = lm is not None and lm_weight > 0
     lm_cache, lm_rows = os.environ.get("EMOASR_CTC_LM_CACHE", "1") != "0", {}
+    stateful, slots, new_states = use_lm and getattr(lm, "stateful", False), None, None
     live = [_Prefix((eos,), 0.0, NEG, 0.0, 0.0, 0.0, 0)]
+    if stateful and not lm_cache:
+        live[0].lm_states = lm.zero_states(1, logp_dev.device)     # (ctc.py:226)
     for t in range(T):
         row = logp[t]
         lp_blank = float(row[blank])
         cands = [(int(v), float(row[v])) for v in top[t] if int(v) != blank]
         if use_lm:
-            # The reference scores EVERY live prefix with the LM at every frame (ctc.py:241-260) -- the same prefix again and again
-            # while it survives.  The LM's next-token row is a function of the prefix alone, so each distinct prefix is scored
-            # ONCE (the frame it first survives) and its row kept while it is live: a frame costs an LM call only for prefixes
-            # that are new, in one batch (rows of a batched call do not depend on their neighbours).  EMOASR_CTC_LM_CACHE=0:
-            # the reference's recomputation.
-            need = [p for p in live if p.toks not in lm_rows] if lm_cache else list(live)
-            if need:
-                n = max(len(p.toks) for p in need)
-                batch = torch.zeros(len(need), n, dtype=torch.int64)  # 0-padded like pad_sequence (ctc.py:243-246)
-                for i, p in enumerate(need):
+            if stateful and not lm_cache:
+                # the reference literally (ctc.py:251-260, 312-331): every live beam carries (h, c) after hyp[:-1]; one batched step
+                # from the concatenated states, the extensions below take their slice of the new states
+                n = max(len(p.toks) for p in live)
+                batch = torch.zeros(len(live), n, dtype=torch.int64)
+                for i, p in enumerate(live):
                     batch[i, : len(p.toks)] = torch.tensor(p.toks)
-                rows, _ = lm.predict(batch, [len(p.toks) for p in need])
-                rows = rows.cpu().numpy().astype(np.float64)
-                for i, p in enumerate(need):
-                    lm_rows[p.toks] = rows[i]
-            lm_lp = [lm_rows[p.toks] for p in live]
-            if lm_cache:
-                keep = {p.toks for p in live}
-                for key in [k for k in lm_rows if k not in keep]:
-                    del lm_rows[key]
+                states = tuple(torch.cat([p.lm_states[j] for p in live], dim=1) for j in (0, 1))
+                rows, new_states = lm.predict(batch, [len(p.toks) for p in live], states=states)
+                lm_lp = list(rows.cpu().numpy().astype(np.float64))
+            elif stateful:
+                if slots is None:
+                    slots = _LMSlots(lm, beam_width)
+                toks = [p.toks for p in live]
+                fresh = slots.score(toks)
+                if fresh:
+                    sl = torch.tensor([slots.slot_of[q] for q in fresh], device=slots.dev)
+                    got = slots.pools.logp.index_select(0, sl).cpu().numpy().astype(np.float64)
+                    lm_rows.update(zip(fresh, got))
+                lm_lp = [lm_rows[q] for q in toks]
             else:
-                lm_rows.clear()
+                lm_lp = _stateless_rows(lm, live, lm_rows, lm_cache)
         table, order = {}, []  # prefix -> _Prefix, in first-seen order (dict merge of ctc.py:374-395)
 
         def put(q):
@@ -170,7 +249,9 @@ def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=Non
             # stay on the same prefix: blank, or a repeat of its last label
             stay_b = _lse2(p.p_b + lp_blank, p.p_nb + lp_blank)
             stay_nb = p.p_nb + float(row[last]) if last is not None else NEG
-            put(_Prefix(p.toks, stay_b, stay_nb, _lse2(stay_b, stay_nb), p.lm, p.len_bonus, p.n_plain))
+            stay = _Prefix(p.toks, stay_b, stay_nb, _lse2(stay_b, stay_nb), p.lm, p.len_bonus, p.n_plain)
+            stay.lm_states = p.lm_states     # (ctc.py:291: not updated)
+            put(stay)
             # extend by each of the frame's top-k labels
             lm_run = p.lm
             bonus = len_weight * (p.n_plain + 1)
@@ -178,8 +259,14 @@ def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=Non
                 ext_nb = p.p_b + lp_v if v == last else _lse2(p.p_b + lp_v, p.p_nb + lp_v)
                 if use_lm:
                     lm_run += lm_weight * float(lm_lp[i][v])
-                put(_Prefix(p.toks + (v,), NEG, ext_nb, _lse2(NEG, ext_nb), lm_run, bonus,
-                            p.n_plain + (0 if v == eos else 1)))
+                q = _Prefix(p.toks + (v,), NEG, ext_nb, _lse2(NEG, ext_nb), lm_run, bonus, p.n_plain + (0 if v == eos else 1))
+                if new_states is not None:
+                    q.lm_states = (new_states[0][:, i:i + 1], new_states[1][:, i:i + 1])
+                put(q)
         order.sort(key=lambda q: q.total, reverse=True)  # stable, like sorted() in ctc.py:338
         live = order[:beam_width]
+        if slots is not None:
+            slots.release([p.toks for p in live])
+            for key in [q for q in lm_rows if q not in slots.slot_of]:
+                del lm_rows[key]
     return [list(p.toks) for p in live], [p.total for p in live], logits

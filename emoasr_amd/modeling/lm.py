@@ -17,7 +17,8 @@ of the loss / score path never writes [rows, V] logits (ops.ce_head_fwd / ce_hea
 in forward() without labels, which returns them) the logits are materialised.  token_logprobs / score always run without dropout.
 
 State-dict keys match the reference (`lm.transformer.bert.*`, `lm.transformer.cls.predictions.*`,
-output embedding tied to the word embedding).  Only `lm_type == "transformer"` is on the path.
+output embedding tied to the word embedding).  `LM(params)` with `lm_type == "rnn"` returns the LSTM LM of modeling/rnnlm.py
+(same module API, `stateful = True`); every other type is outside the path.
 """
 import math
 from types import SimpleNamespace
@@ -124,6 +125,14 @@ class TransformerLM(nn.Module):
 
 
 class LM(nn.Module):
+    stateful = False     # predict() carries no state between calls: the searches re-run the prefix (RNN LM: modeling/rnnlm.py)
+
+    def __new__(cls, params=None, phase="test", compute_dtype=torch.bfloat16):     # (params=None: copy / pickle re-create the object bare)
+        if cls is LM and params is not None and params.lm_type == "rnn":
+            from .rnnlm import RNNLanguageModel
+            return RNNLanguageModel(params, phase, compute_dtype)     # (not an LM instance: __init__ below is not run on it)
+        return super().__new__(cls)
+
     def __init__(self, params, phase="test", compute_dtype=torch.bfloat16):
         super().__init__()
         self.lm_type = params.lm_type

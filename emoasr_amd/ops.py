@@ -1140,6 +1140,44 @@ def ce_head_bwd(x, w, bias, ctx, dw, dbias, gscale=1.0, gscale_dev=None, chunk=N
     return dx
 
 
+# ---- RNN LM: one shallow-fusion step for up to 32 hypotheses (csrc/rnnlm.hip) ------------------------------------------------------
+RNNLM_STEP_MAX = 32
+
+
+def rnnlm_step_supported(x, nb, L, E, H):
+    """does the step kernel's shape plan take nb rows of an L-layer LSTM LM (embedding E, hidden H) in x's dtype?"""
+    return lib.size_query("emoasr_rnnlm_step_supported", dt(x), nb, L, E, H) == 1
+
+
+class RnnlmStepWeights:
+    """the operands of emoasr_rnnlm_step that do not change between steps: per-layer pointer tables (host arrays of device
+    pointers) and the workspace.  Holds the tensors, so the addresses stay valid."""
+
+    def __init__(self, emb, w_ih, w_hh, bias, w_out, b_out):
+        self.tensors = (emb, list(w_ih), list(w_hh), list(bias), w_out, b_out)
+        self.L, self.E, self.H, self.V = len(w_ih), emb.shape[1], w_hh[0].shape[1], w_out.shape[0]
+        arr = c_void_p * self.L
+        self.p_ih = arr(*[t.data_ptr() for t in w_ih])
+        self.p_hh = arr(*[t.data_ptr() for t in w_hh])
+        self.p_b = arr(*[_chk(t, torch.float32).data_ptr() for t in bias])
+        self.ws_bytes = lib.size_query("emoasr_rnnlm_step_ws_bytes", _DT[emb.dtype], self.H, self.V)
+        self.ws = torch.empty(self.ws_bytes, device=emb.device, dtype=torch.uint8)
+
+
+def rnnlm_step(W, nb, ids, ph, pc, src, dst, logp, row_dst=None):
+    """ids / src / dst / row_dst int32 [>= nb] on the device; ph [L, slots, H] (compute dtype), pc f32 [L, slots, H]: the state pools,
+    read at src (< 0: zeros), written at dst; logp f32 [rows, >= V] (row stride allowed): row i -> logp[row_dst[i]] (None: i)"""
+    emb, _, _, _, w_out, b_out = W.tensors
+    L, slots, H = ph.shape
+    assert L == W.L and H == W.H and pc.shape == ph.shape and ph.is_contiguous() and pc.is_contiguous()
+    assert ph.dtype == emb.dtype and logp.stride(1) == 1 and logp.shape[1] >= W.V
+    for t in (ids, src, dst) + (() if row_dst is None else (row_dst,)):
+        assert t.dtype == torch.int32 and t.numel() >= nb and t.is_cuda
+    lib.call("emoasr_rnnlm_step", dt(emb), nb, L, W.E, H, W.V, slots, _p(ids), _p(emb), W.p_ih, W.p_hh, W.p_b, _p(ph),
+             _p(_chk(pc, torch.float32)), _p(src), _p(dst), _p(w_out), _p(b_out), _p(_chk(logp, torch.float32)), logp.stride(0),
+             logp.shape[0], _p(row_dst), _p(W.ws), W.ws_bytes, _stream())
+
+
 def argmax_rows(x):
     M, V, ld = _rows(_chk(x))
     out = torch.empty(M, device=x.device, dtype=torch.int32)

@@ -1,0 +1,57 @@
+"""One unidirectional LSTM layer over a whole sequence, TIME-MAJOR, forward and backward -- the recurrence shared by the transducer's
+prediction network (engine._RNNTMixin) and the RNN LM (modeling/rnnlm.py).
+
+The input projection is one product over all positions; the recurrence is one cooperative launch (csrc/lstm_coop.hip) where
+ops.lstm_seq_supported says so (bf16, H % 32 == 0, H <= 512, option "lstm_coop"), else the per-position chain: recurrent product
+with the stored pre-activation as its residual, then the cell kernel.  Hidden sizes above the cooperative kernel's 512 therefore
+run the chain (2 launches per position)."""
+import torch
+
+from . import ops
+
+
+def lstm_layer_fwd(x, w_ih, w_hh, bias, h0, c0):
+    """x [U,B,nin] (compute dtype), w_ih [4H,nin], w_hh [4H,H], bias f32 [4H] = bias_ih + bias_hh, h0 [B,H] | None, c0 f32 [B,H] | None
+    -> (hseq [U,B,H], cseq f32 [U,B,H], gact [U,B,4H] activated i | f | g | o)"""
+    U, B, nin = x.shape
+    H = w_hh.shape[1]
+    dev = x.device
+    pre = ops.gemm_nt(x.view(U * B, nin), w_ih, bias=bias).view(U, B, 4 * H)
+    hseq = torch.empty(U, B, H, device=dev, dtype=x.dtype)
+    cseq = torch.empty(U, B, H, device=dev, dtype=torch.float32)
+    gact = torch.empty(U, B, 4 * H, device=dev, dtype=x.dtype)
+    if U > 1 and ops.lstm_seq_supported(x, B, H):
+        # the whole recurrence in one cooperative launch (csrc/lstm_coop.hip) instead of 2 launches per position
+        ops.lstm_seq_fwd(pre, w_hh, h0, c0, hseq, cseq, gact)
+    else:
+        h_prev, c_prev = h0, c0
+        for u in range(U):
+            gates = pre[u] if h_prev is None else ops.gemm_nt(h_prev, w_hh, residual=pre[u], res_scale=1.0)
+            ops.lstm_cell_fwd(gates, c_prev, hseq[u], cseq[u], gact[u])
+            h_prev, c_prev = hseq[u], cseq[u]
+    return hseq, cseq, gact
+
+
+def lstm_layer_bwd(dh_seq, x_in, hseq, cseq, gact, h0, c0, w_ih, w_hh, g_w_ih, g_w_hh, g_b_ih, g_b_hh):
+    """dh_seq [U,B,H]: gradient w.r.t. the layer's outputs.  ACCUMULATES the four parameter gradients (f32; both biases receive the
+    same column sums; g_b_hh None: the caller copies g_b_ih's) -> dx [U,B,nin]"""
+    U, B, H = dh_seq.shape
+    dgp = torch.empty(U, B, 4 * H, device=dh_seq.device, dtype=dh_seq.dtype)
+    if U > 1 and ops.lstm_seq_supported(dh_seq, B, H):
+        # the whole backward recurrence in one cooperative launch (csrc/lstm_coop.hip)
+        ops.lstm_seq_bwd(dh_seq.contiguous(), gact, cseq, c0, w_hh, dgp)
+    else:
+        dc = torch.zeros(B, H, device=dh_seq.device, dtype=torch.float32)
+        dh_rec = None
+        for u in reversed(range(U)):
+            ops.lstm_cell_bwd(dh_seq[u], dh_rec, dc, gact[u], cseq[u - 1] if u > 0 else c0, cseq[u], dgp[u])
+            if u > 0 or h0 is not None:
+                dh_rec = ops.gemm_nn(dgp[u], w_hh)
+    nin = x_in.shape[-1]
+    dgp2 = dgp.view(U * B, 4 * H)
+    ops.gemm_tn(dgp2, x_in.reshape(U * B, nin), out=g_w_ih, accumulate=True, colsum=g_b_ih)
+    if g_b_hh is not None:
+        ops.colsum(dgp2, out=g_b_hh, accumulate=True)
+    if U > 1:
+        ops.gemm_tn(dgp[1:].reshape((U - 1) * B, 4 * H), hseq[:-1].reshape((U - 1) * B, H), out=g_w_hh, accumulate=True)
+    return ops.gemm_nn(dgp2, w_ih).view(U, B, nin)

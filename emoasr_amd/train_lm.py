@@ -1,4 +1,6 @@
-"""Transformer-LM training and evaluation drivers with the reference's semantics (lm/train_lm.py:40-130, lm/test_ppl.py:32-74):
+"""LM training and evaluation drivers with the reference's semantics (lm/train_lm.py:40-130, lm/test_ppl.py:32-74), for the
+Transformer LM (modeling/lm.py) and the RNN LM (lm_type="rnn", modeling/rnnlm.py) alike -- both are `LM(params)`, take
+`(ys_in, ylens, labels)` and expose `token_logprobs` for the perplexity:
 
     model = LM(params, compute_dtype=...).cuda().train()
     groups = get_optimizer_params_nodecay(list(model.named_parameters()), weight_decay=params.weight_decay)

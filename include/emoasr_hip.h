@@ -654,6 +654,23 @@ int emoasr_rnnt_beam_joint(int dtype, int nb, int H, int J, int Tmax, const void
 int emoasr_rnnt_beam_pick(int dtype, int nb, int V, int k, int blank, const void* logits, long ldl, float* out, long ldo,
                           void* stream);
 
+/* ---- one step of the RNN LM for the hypotheses of a beam search (csrc/rnnlm.hip; lm/modeling/rnn.py:62-81, RNNLM.predict): L + 2
+ * launches -- one per LSTM layer, emoasr_gemm_nt for the vocabulary head, a log-softmax.  1 <= nb <= 32 rows.  Row i reads the
+ * embedding of ids[i] (int32), the state (h, c) of every layer from the slot pools ph [L][slots][H] (compute dtype) / pc
+ * [L][slots][H] (f32) at src[i] (src[i] < 0: the zero state) and writes the new state at dst[i]; several rows may share one src, no
+ * dst may equal any src of the same call.  log_softmax(output(h_top)) of row i goes to logp[row_dst[i]] (f32, row stride ldlogp,
+ * logp_rows rows; row_dst NULL: row i).  ids / src / dst / row_dst are int32 DEVICE arrays (the call can be captured into a graph);
+ * w_ih / w_hh / bias are HOST arrays of L device pointers ([4H][E or H], [4H][H], f32 [4H] = bias_ih + bias_hh); ws:
+ * emoasr_rnnlm_step_ws_bytes(dtype, H, V) bytes.  Rounding as the sequence forward: f32 accumulation, h in the compute dtype, c in
+ * f32.  EMO_F32X3 runs the f32 kernels (the head's product is split).  emoasr_rnnlm_step_supported() -> 1 if the shape is inside
+ * the kernel's plan (bf16: E, H % 8 == 0; f32: % 4; H % 8 == 0; the LDS image of the rows fits). */
+int emoasr_rnnlm_step_supported(int dtype, int nb, int L, int E, int H);
+long emoasr_rnnlm_step_ws_bytes(int dtype, int H, int V);
+int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, int slots, const int* ids, const void* emb,
+                      const void* const* w_ih, const void* const* w_hh, const float* const* bias, void* ph, float* pc,
+                      const int* src, const int* dst, const void* w_out, const float* b_out, float* logp, long ldlogp,
+                      int logp_rows, const int* row_dst, void* ws, long ws_bytes, void* stream);
+
 /* ---- one Conformer encoder layer, forward, sequenced on the host in C++ ---------
  * ConformerEncoderLayer.forward (asr/modeling/conformer.py:146-225) with relative-position attention:
  *   x += 0.5 * drop(FFN_macaron(LN(x)));  x += drop(RelMHA(LN(x)));  x += drop(ConvModule(LN(x)));
