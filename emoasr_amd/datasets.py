@@ -235,13 +235,33 @@ def write_results_tsv(path, rows, comment=None):
             f.write("\t".join([str(r["utt_id"]), tok, str(r["text"]), str(r["reftext"])] + [str(r[k]) for k in extra]) + "\n")
 
 
+def create_masked_lm_label(y, mask_id, num_to_mask=-1, mask_proportion=-1, random_num_to_mask=False, eos_id=2):
+    """lm/datasets.py:319-341: mask `num_to_mask` (or max(int(candidates * mask_proportion), 1); with random_num_to_mask a uniform
+    draw from 1..that) of the positions whose token is not <eos>, always with mask_id -> (y_masked, labels int64, -100 where not
+    masked).  The `random` calls come in the reference's order (shuffle, randint, sample): the same seed gives the same masks."""
+    y_masked = y.clone()
+    label = torch.full(y.shape, -100, dtype=torch.int64)
+    cands = [j for j in range(y.size(0)) if y[j] != eos_id]
+    random.shuffle(cands)
+    if mask_proportion > 0:
+        num_to_mask = max(int(len(cands) * mask_proportion), 1)
+    if random_num_to_mask:
+        num_to_mask = random.randint(1, num_to_mask)
+    for j in sorted(random.sample(cands, num_to_mask)):
+        label[j] = y[j]
+        y_masked[j] = mask_id
+    return y_masked, label
+
+
 class LMDataset:
-    """lm/datasets.py:24-120 for the Transformer and the RNN LM: a TSV with columns utt_id / token_id (space-separated ids).
-    Items: (utt_id, y_in int64, ylen, label int64 | None).  phase "train": with params.add_sos_eos the ids are wrapped in <eos>,
-    then y_in = y[:-1] and label = y[1:] (next-token targets); any other phase: y_in = y, no label."""
+    """lm/datasets.py:24-120 for the Transformer, the RNN and the BERT masked LM: a TSV with columns utt_id / token_id
+    (space-separated ids).  Items: (utt_id, y_in int64, ylen, label int64 | None).  With params.add_sos_eos the ids are wrapped in
+    <eos>.  phase "train": y_in = y[:-1] and label = y[1:] (next-token targets) for lm_type "transformer" / "rnn"; for "bert"
+    y_in = y with mask_id at the masked positions and label = the hidden tokens there, -100 elsewhere (create_masked_lm_label;
+    exactly one of params.num_to_mask / params.mask_proportion is configured).  Any other phase: y_in = y, no label."""
 
     def __init__(self, params, data_path, phase="train", size=-1):
-        if params.lm_type not in ("transformer", "rnn"):     # (next-token targets for both: lm/datasets.py:91)
+        if params.lm_type not in ("transformer", "rnn", "bert"):     # (next-token targets for the first two: lm/datasets.py:91)
             raise NotImplementedError(f"emoasr_amd: LMDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
         columns = ["utt_id", "token_id"] + (["ylen"] if getattr(params, "bucket_shuffle", False) else [])
         data = _read_table(data_path)[columns]
@@ -249,10 +269,22 @@ class LMDataset:
         data = data.dropna().reset_index(drop=True)
         if len(data) != n:
             logging.warning(f"nan value in dataset is removed: {n:d} -> {len(data):d}")
+        self.lm_type = params.lm_type
         self.add_sos_eos = params.add_sos_eos
         self.eos_id = params.eos_id
         self.phase = phase
         self.data = data[:size] if size > 0 else data
+        if self.lm_type == "bert":
+            # a config written for another LM family (no mask token, no masking rule) is not one this dataset can be built from
+            missing = [f for f in ("mask_id", "random_num_to_mask") if not hasattr(params, f)]
+            if missing:
+                raise NotImplementedError(f"emoasr_amd: lm_type='bert' needs the masked LM's fields; {missing} are absent from the config")
+            self.mask_id = params.mask_id
+            # either `num_to_mask` or `mask_proportion` must be specified (lm/datasets.py:56)
+            assert hasattr(params, "num_to_mask") ^ hasattr(params, "mask_proportion")
+            self.num_to_mask = getattr(params, "num_to_mask", -1)
+            self.mask_proportion = getattr(params, "mask_proportion", -1)
+            self.random_num_to_mask = params.random_num_to_mask
 
     def __len__(self):
         return len(self.data)
@@ -263,7 +295,10 @@ class LMDataset:
         if self.add_sos_eos:
             ids = [self.eos_id] + ids + [self.eos_id]
         y = torch.tensor(ids, dtype=torch.long)
-        if self.phase == "train":
+        if self.phase == "train" and self.lm_type == "bert":
+            y_in, label = create_masked_lm_label(y, self.mask_id, self.num_to_mask, self.mask_proportion, self.random_num_to_mask,
+                                                 self.eos_id)
+        elif self.phase == "train":
             assert len(y) > 1
             y_in, label = y[:-1], y[1:]
         else:

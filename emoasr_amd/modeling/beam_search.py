@@ -23,11 +23,13 @@ import torch
 from .. import ops
 from ..engine import h2d_i32
 from .functions import _engine_of
+from .lm import require_next_token_lm
 
 CTC_BEAM_WIDTH_RATIO = 1.5
 
 
 def joint_beam_search(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
+    require_next_token_lm(lm, lm_weight)
     eng = _engine_of(dec)
     assert eouts.shape[0] == 1, "beam search decodes one utterance at a time (decoders/transformer.py:181)"
     V, eos, blank = dec.vocab_size, dec.eos_id, dec.blank_id

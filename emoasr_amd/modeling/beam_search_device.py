@@ -22,6 +22,7 @@ from .. import lib, ops
 from ..decode_rt import DecoderStepRuntime, LMStepRuntime, _lin, _ln
 from ..engine import h2d_i32
 from .functions import _engine_of
+from .lm import require_next_token_lm
 
 _STEP_DEADLINE_S = 30.0   # a search step takes ~0.5 ms; this only bounds the wait for a launch that will never report
 
@@ -58,6 +59,7 @@ _yield = os.sched_yield if os.environ.get("EMOASR_BEAM_YIELD", "1") != "0" else 
 
 
 def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
+    require_next_token_lm(lm, lm_weight)
     eng = _engine_of(dec)
     assert eouts.shape[0] == 1, "beam search decodes one utterance at a time (decoders/transformer.py:181)"
     V, eos, blank = dec.vocab_size, dec.eos_id, dec.blank_id

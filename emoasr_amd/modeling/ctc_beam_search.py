@@ -33,6 +33,7 @@ import torch
 
 from .. import ops
 from .functions import _engine_of
+from .lm import require_next_token_lm
 
 NEG = -1e10  # LOG_0 of decoders/ctc.py:23
 
@@ -187,6 +188,7 @@ def _stateless_rows(lm, live, lm_rows, lm_cache):
 
 def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=None, lm_weight=0.0):
     """-> (hyps, scores, logits) for ONE utterance (the reference asserts batch size 1, ctc.py:212)."""
+    require_next_token_lm(lm, lm_weight)
     assert eouts.shape[0] == 1, "CTC beam search decodes one utterance at a time (ctc.py:212)"
     eng = _engine_of(dec)
     blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size

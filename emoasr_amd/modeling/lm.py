@@ -18,7 +18,18 @@ in forward() without labels, which returns them) the logits are materialised.  t
 
 State-dict keys match the reference (`lm.transformer.bert.*`, `lm.transformer.cls.predictions.*`,
 output embedding tied to the word embedding).  `LM(params)` with `lm_type == "rnn"` returns the LSTM LM of modeling/rnnlm.py
-(same module API, `stateful = True`); every other type is outside the path.
+(same module API, `stateful = True`); every type but these and "bert" is outside the path.
+
+`lm_type == "bert"` is the masked LM of lm/modeling/bert.py:17-92 -- the same stack without the causal mask, keys `lm.bert.bert.*` /
+`lm.bert.cls.predictions.*`, `mask_id = params.mask_id` -- on the same code, parametrised by the key prefix and `causal`:
+
+    loss, loss_dict = lm(ys_masked, ylens, labels);  loss.backward()           # labels -100 except at the masked positions
+    lp = lm.masked_logprobs(ys, ylens)                                         # f64 [B, N] on the host: log p(ys[b,i] | the rest of ys[b])
+    scores = lm.score(ys, ylens)                                               # pseudo-log-likelihood: the row sums
+
+Its transform + vocabulary head run on the gathered labelled rows only (`head_at_labels`), its attention backward takes the
+single-pass kernel in bf16, `masked_logprobs` builds the masked copies on the device (ops.mlm_expand) and walks them in chunks of
+token rows, and `predict` / `zero_states` raise: a bidirectional LM has no next-token distribution.
 """
 import math
 from types import SimpleNamespace
@@ -124,6 +135,32 @@ class TransformerLM(nn.Module):
         return None  # stateless
 
 
+class BERTMaskedLM(nn.Module):
+    """parameter container of the masked LM (lm/modeling/bert.py:17-33): the same stack without the causal mask"""
+
+    def __init__(self, params):
+        super().__init__()
+        self.bert = _BertForMaskedLM(params.vocab_size, params.hidden_size, params.intermediate_size,
+                                     params.num_layers, params.max_seq_len)
+        self.mask_id = params.mask_id
+
+    def load_state_dict(self, state_dict, strict=True):
+        try:
+            return super().load_state_dict(state_dict, strict)
+        except RuntimeError:
+            return self.bert.load_state_dict(state_dict, strict)  # the bare BertForMaskedLM dict (bert.py:88-92)
+
+
+_NO_PREDICT = ("emoasr_amd: the BERT masked LM (lm_type='bert') has no next-token distribution: predict / zero_states and the "
+               "beam searches' shallow fusion need a causal LM (lm_type 'transformer' or 'rnn'); use LM.score for rescoring")
+
+
+def require_next_token_lm(lm, lm_weight):
+    """entry check of the beam searches: shallow fusion needs p(next token | prefix), which a bidirectional LM does not define"""
+    if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) == "bert":
+        raise NotImplementedError(_NO_PREDICT)
+
+
 class LM(nn.Module):
     stateful = False     # predict() carries no state between calls: the searches re-run the prefix (RNN LM: modeling/rnnlm.py)
 
@@ -136,13 +173,29 @@ class LM(nn.Module):
     def __init__(self, params, phase="test", compute_dtype=torch.bfloat16):
         super().__init__()
         self.lm_type = params.lm_type
-        if self.lm_type != "transformer":
+        if self.lm_type not in ("transformer", "bert"):
             raise NotImplementedError(f"emoasr_amd: lm_type={self.lm_type!r} is outside the HIP hot path")
         self.params = params
         # "f32x3" (f32 storage, split-bf16 products: modeling/asr.py) -> float32 + the library's split switch asserted per call
         self.f32_split = isinstance(compute_dtype, str) and compute_dtype == "f32x3"
         self.compute_dtype = torch.float32 if self.f32_split else compute_dtype
-        self.lm = TransformerLM(params)
+        # one stack, two LMs: the key prefix and the causal mask are all that differ (the reference's TransformerLM is its
+        # BertForMaskedLM run with causal=True)
+        self.causal = self.lm_type == "transformer"
+        root = "lm.transformer." if self.causal else "lm.bert."
+        self._PRE, self._CP = root + "bert.", root + "cls.predictions."
+        self._NO_GRAD = (self._PRE + "pooler.dense.weight", self._PRE + "pooler.dense.bias")
+        if self.causal:
+            self.lm = TransformerLM(params)
+        else:
+            if not hasattr(params, "mask_id"):
+                raise NotImplementedError("emoasr_amd: lm_type='bert' needs the masked LM's fields; ['mask_id'] is absent from the config")
+            self.lm = BERTMaskedLM(params)
+            self.mask_id = params.mask_id
+        # masked-LM labels cover a fraction of the positions: transform + vocabulary head run on the gathered labelled rows only
+        # (a causal LM labels nearly every row and keeps the all-rows head with row weights)
+        self.head_at_labels = not self.causal
+        self.attn_fused = True     # A/B switch of the single-pass attention backward (bf16, non-causal only)
         self._arena = None
         self._pe = None
         # the reference's TransformersConfig defaults (lm/modeling/transformer.py:22-29 passes neither): active in train() mode
@@ -160,13 +213,15 @@ class LM(nn.Module):
             return self.lm.load_state_dict(state_dict, strict)  # un-prefixed inner dict (lm.py:62-66)
 
     def zero_states(self, bs, device):
+        if not self.causal:
+            raise NotImplementedError(_NO_PREDICT)
         return self.lm.zero_states(bs, device)
 
     # ---------------------------------------------------------------- HIP forward
     def _bind(self):
         if self._arena is None or not self._arena.bound() or self._arena.compute_dtype != self.compute_dtype:
             self._arena = ParamArena(self, self.compute_dtype)
-            emb = "lm.transformer.bert.embeddings."
+            emb = self._PRE + "embeddings."
             A = self._arena
             # position + token-type(0) rows folded into one additive table (modeling_bert.py:196-201)
             self._pe = (A.p(emb + "position_embeddings.weight") + A.p(emb + "token_type_embeddings.weight")[0]).contiguous()
@@ -214,6 +269,8 @@ class LM(nn.Module):
         are replayed from a HIP graph over static buffers, one graph per (rows padded to 4 / 16, length padded to a multiple of
         8) -- the call was host-bound (1.5 ms of launch sequencing for ~0.4 ms of kernels).  Padding rows / positions are masked
         by their key lengths and never read back; the real rows' arithmetic is the eager call's.  EMOASR_LM_GRAPH=0: eager."""
+        if not self.causal:
+            raise NotImplementedError(_NO_PREDICT)
         arena_before = self._arena
         A = self._bind()
         if A is not arena_before:
@@ -279,15 +336,15 @@ class LM(nn.Module):
         return g.out[:B].clone()
 
     def predict(self, ys, ylens, states=None):
+        if not self.causal:
+            raise NotImplementedError(_NO_PREDICT)
         with torch.no_grad():
             ys_host = ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)
             yl = ylens.tolist() if torch.is_tensor(ylens) else list(ylens)
             return self.predict_device(ys_host, yl), states
 
     # ---------------------------------------------------------------- training, scoring
-    _PRE = "lm.transformer.bert."
-    _CP = "lm.transformer.cls.predictions."
-    _NO_GRAD = ("lm.transformer.bert.pooler.dense.weight", "lm.transformer.bert.pooler.dense.bias")
+    MAX_TOKEN_ROWS = 16384     # masked_logprobs: token rows (copies x padded length) per encoder run
 
     def _seed(self, site):
         return (self.seed * 1000003 + self.step_count * 4099 + site) & 0xFFFFFFFFFFFF
@@ -333,7 +390,7 @@ class LM(nn.Module):
             wqkv = A.w_span(lay + "attention.self.query.weight", lay + "attention.self.value.weight", (3 * d, d))
             bqkv = A.p_span(lay + "attention.self.query.bias", lay + "attention.self.value.bias", (3 * d,))
             qkv = ops.gemm_nt(x, wqkv, bias=bqkv).view(B, N, 3 * d)
-            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=True,
+            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=self.causal,
                                   drop_p=p_att, seed=s_att)
             y = ops.gemm_nt(o.view(B * N, d), A.w(lay + "attention.output.dense.weight"),
                             bias=A.p(lay + "attention.output.dense.bias"), residual=x, res_scale=1.0, drop_p=p_h, seed=s_o)
@@ -427,17 +484,27 @@ class LM(nn.Module):
         valid = labels != -100
         assert labels.shape == ys.shape and int(labels.max()) < self.params.vocab_size, "labels: [B, N] ids below vocab_size or -100"
         count = int(valid.sum())
-        w = valid.to(torch.float32) / max(count, 1)     # mean over the rows with a label (CrossEntropyLoss, ignore_index=-100)
+        sel = None
+        if self.head_at_labels:     # the M labelled rows only (no label at all: one row of weight 0)
+            rows_host = valid.view(-1).nonzero().view(-1) if count else torch.zeros(1, dtype=torch.int64)
+            lab_host = labels.view(-1)[rows_host].clamp(min=0)
+            w = torch.full((rows_host.numel(),), 1.0 / count if count else 0.0)
+        else:
+            lab_host = labels.clamp(min=0).view(-1)
+            w = valid.to(torch.float32) / max(count, 1)     # mean over the rows with a label (CrossEntropyLoss, ignore_index=-100)
         with ops.stream_scope(self._split()):
-            ids, klens, lab = h2d_i32(ys, dev), h2d_i32(yl, dev), h2d_i32(labels.clamp(min=0).view(-1), dev)
+            ids, klens, lab = h2d_i32(ys, dev), h2d_i32(yl, dev), h2d_i32(lab_host, dev)
             w_dev = w.view(-1).pin_memory().to(dev, non_blocking=True)
             x, st = self._encode(ids, klens, B, N, p_h, p_att, keep)
+            if self.head_at_labels:
+                sel = rows_host.pin_memory().to(dev, non_blocking=True)
+                x = x.index_select(0, sel)
             t2, tst = self._transform(x, keep)
             rows, head = self._head_rows(t2, lab, w_dev)
             loss = rows.sum()
         if keep:
             self._pe_stale = True     # (an update follows: predict() rebuilds the position table before its next use)
-            st.t2, st.tst, st.head, st.lab, st.w = t2, tst, head, lab, w_dev
+            st.t2, st.tst, st.head, st.lab, st.w, st.sel = t2, tst, head, lab, w_dev, sel
         return loss, st
 
     def _loss_backward(self, st, g):
@@ -472,6 +539,8 @@ class LM(nn.Module):
         x, tu, t, mt, rt = st.tst
         dpre = ops.act_bwd(ln_bwd(dt2, t, cp + "transform.LayerNorm", mt, rt), tu, ACT_GELU)
         dx = lin_bwd(dpre, x, cp + "transform.dense.weight", cp + "transform.dense.bias")
+        if st.sel is not None:     # the head ran on gathered rows: their gradient goes back to its rows, every other row has none
+            dx = torch.zeros(B * N, d, device=dx.device, dtype=dx.dtype).index_copy_(0, st.sel, dx)
         # ---- blocks, last to first.  Post-LN: LayerNorm backward first, then the branch and the residual together
         scale = 1.0 / math.sqrt(d // H)
         scratch = None
@@ -486,11 +555,16 @@ class LM(nn.Module):
             dqkv = torch.empty_like(qkv)
             q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
             dq, dk, dv = dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]
-            # (the single-pass attention backward has no causal mask: the materialised path, as the ASR decoder's self-attention)
-            if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
-                scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
-            ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=True, drop_p=p_att,
-                         seed=s_att, scratch=scratch)
+            # (the single-pass attention backward has no causal mask: the masked LM takes it in bf16, the causal LM the
+            # materialised path, as the ASR decoder's self-attention)
+            if self.attn_fused and ops.fused_attn_bwd_ok(q, None, None, None, self.causal):
+                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, drop_p=p_att, seed=s_att,
+                             materialise="fused")
+            else:
+                if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
+                    scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
+                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=self.causal,
+                             drop_p=p_att, seed=s_att, scratch=scratch)
             dqkv2 = dqkv.view(B * N, 3 * d)
             qn, vn = lay + "attention.self.query.", lay + "attention.self.value."
             ops.gemm_tn(dqkv2, xin, out=A.g_span(qn + "weight", vn + "weight", (3 * d, d)), accumulate=True,
@@ -522,9 +596,47 @@ class LM(nn.Module):
             rows, _ = self._head_rows(t2, lab, w_dev)
         return -rows.cpu().to(torch.float64).view(B, N) * valid.to(torch.float64)
 
+    def masked_logprobs(self, ys, ylens, max_token_rows=None):
+        """masked LM only.  Entry (b, i), i < ylens[b]: log p(ys[b,i] | ys[b] with position i replaced by mask_id); zeros elsewhere
+        -> float64 [B, N] on the HOST.  The R = sum(ylens) masked copies are built on the device (ops.mlm_expand) and walked in
+        chunks of at most max_token_rows token rows (copies x padded length; a chunk may begin and end inside a sequence); of every
+        copy only its masked row goes through transform + head, and the R row values come back in ONE device-to-host copy."""
+        assert not self.causal, "masked_logprobs is the masked LM's (lm_type='bert'); a causal LM has token_logprobs"
+        assert ylens is not None
+        ys, yl = self._inputs(ys, ylens)
+        A = self._prepare()
+        dev = A.flat.device
+        B, N = ys.shape
+        Np = min((N + 7) // 8 * 8, self.params.max_seq_len)     # (whole 32-byte id rows; the padding is masked by the key lengths)
+        row0 = [0]
+        for n in yl:
+            row0.append(row0[-1] + n)
+        R = row0[-1]
+        chunk = max(1, int(max_token_rows or self.MAX_TOKEN_ROWS) // Np)
+        with torch.no_grad(), ops.stream_scope(self._split()):
+            ys_dev, yl_dev, row0_dev = h2d_i32(ys, dev), h2d_i32(yl, dev), h2d_i32(row0, dev)
+            ones = torch.ones(min(chunk, R), device=dev, dtype=torch.float32)
+            out = torch.empty(R, device=dev, dtype=torch.float32)
+            for r0 in range(0, R, chunk):
+                rc = min(chunk, R - r0)
+                ids, klens, idx, lab = ops.mlm_expand(ys_dev, yl_dev, row0_dev, r0, rc, Np, int(self.mask_id), 0, total=R)
+                x, _ = self._encode(ids, klens, rc, Np, 0.0, 0.0, False)
+                t2, _ = self._transform(x.index_select(0, idx), False)
+                rows, _ = self._head_rows(t2, lab, ones[:rc])
+                out[r0:r0 + rc] = rows
+        flat = -out.cpu().to(torch.float64)
+        res = torch.zeros(B, N, dtype=torch.float64)
+        for b, n in enumerate(yl):
+            res[b, :n] = flat[row0[b]:row0[b + 1]]
+        return res
+
     def score(self, ys, ylens, batch_size=100):
-        """lm/modeling/transformer.py:79-99: per row sum_{i < ylens[b]-1} log p(ys[b,i+1] | ys[b,:i+1]) -> Python list of floats
+        """causal LM (lm/modeling/transformer.py:79-99): per row sum_{i < ylens[b]-1} log p(ys[b,i+1] | ys[b,:i+1]); masked LM
+        (lm/modeling/bert.py:54-86): the pseudo-log-likelihood, the row sums of masked_logprobs (all copies of a call are stacked and
+        chunked by token rows there, so `batch_size` -- copies per run in the reference -- changes nothing) -> Python list of floats
         (summed on the host in double precision, as the reference sums Python floats)"""
+        if not self.causal:
+            return self.masked_logprobs(ys, ylens).sum(dim=1).tolist()
         ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
         yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
         out = []

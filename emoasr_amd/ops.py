@@ -784,6 +784,29 @@ def lsm_loss(logits, labels, w, lsm_prob, want_grad=False, gscale=1.0, gscale_de
     return loss, grad
 
 
+# ---- masked LM -----------------------------------------------------------------------------
+def mlm_expand(ys, ylens, row0, r_begin, r_count, Np, mask_id, pad_id=0, total=None, out=None):
+    """the masked copies r_begin .. r_begin + r_count - 1 of ys int32 [B,N] (lengths ylens int32 [B], row0 int32 [B+1] their prefix
+    sums, all on the device; `total` = sum(ylens) where the caller knows it on the host)
+    -> (ids int32 [r_count,Np], klens [r_count], idx [r_count] = flat row of each copy's masked position, labels [r_count]).
+    out: that tuple of int32 buffers to write into (at least r_count rows each; the rest is left alone)"""
+    B, N = _chk(ys, torch.int32).shape
+    assert ys.is_contiguous() and ylens.numel() == B and row0.numel() == B + 1
+    _chk(ylens, torch.int32), _chk(row0, torch.int32)
+    assert r_begin >= 0 and r_count >= 1 and (total is None or r_begin + r_count <= total), (r_begin, r_count, total)
+    if out is None:
+        dev = ys.device
+        out = (torch.empty(r_count, Np, device=dev, dtype=torch.int32),) + tuple(
+            torch.empty(r_count, device=dev, dtype=torch.int32) for _ in range(3))
+    ids, klens, idx, labels = out
+    for t in out:
+        assert _chk(t, torch.int32).is_contiguous() and t.shape[0] >= r_count
+    assert ids.shape[1] == Np
+    lib.call("emoasr_mlm_expand", B, N, Np, _p(ys), _p(ylens), _p(row0), r_begin, r_count, mask_id, pad_id, _p(ids), _p(klens),
+             _p(idx), _p(labels), _stream())
+    return ids[:r_count], klens[:r_count], idx[:r_count], labels[:r_count]
+
+
 # ---- knowledge distillation ---------------------------------------------------------------
 def soft_ce(logits, soft=None, src=None, hard=None, w_soft=None, w_hard=None, lsm_prob=0.0, lrow=None, want_grad=False,
             gscale=1.0, gscale_dev=None, grad=None):

@@ -1,6 +1,7 @@
 """LM training and evaluation drivers with the reference's semantics (lm/train_lm.py:40-130, lm/test_ppl.py:32-74), for the
-Transformer LM (modeling/lm.py) and the RNN LM (lm_type="rnn", modeling/rnnlm.py) alike -- both are `LM(params)`, take
-`(ys_in, ylens, labels)` and expose `token_logprobs` for the perplexity:
+Transformer LM (modeling/lm.py), the RNN LM (lm_type="rnn", modeling/rnnlm.py) and the BERT masked LM (lm_type="bert",
+modeling/lm.py) alike -- all are `LM(params)` and take `(ys_in, ylens, labels)`; the causal ones expose `token_logprobs` for the
+perplexity (ppl_lm), the masked one `masked_logprobs` (ppl_masked_lm):
 
     model = LM(params, compute_dtype=...).cuda().train()
     groups = get_optimizer_params_nodecay(list(model.named_parameters()), weight_decay=params.weight_decay)
@@ -106,4 +107,25 @@ def ppl_lm(dataloader, model, device, add_sos_eos=False):
         lp = model.token_logprobs(ys_in, [int(data["ylens"][0]) - 1], labels)
         sum_logprob -= float(lp.sum())
         cnt += int((labels != -100).sum())
+    return cnt, math.exp(sum_logprob / cnt)
+
+
+def ppl_masked_lm(dataloader, model, device, mask_id=None, max_seq_len=None):
+    """lm/test_ppl.py:77-133: masked-LM perplexity over a loader of single utterances (LMDataset phase "test") -> (cnt, ppl): every
+    position of ys_in is masked in turn (the <eos> wrappers of add_sos_eos included) and predicted from the rest; an utterance
+    longer than max_seq_len is skipped with a warning.  Built on LM.masked_logprobs (the copies are made on the device, one
+    device-to-host copy per utterance), summed on the host in double precision.  mask_id / max_seq_len default to the model's."""
+    if mask_id is not None:
+        assert int(mask_id) == int(model.mask_id), "mask_id differs from the model's"
+    max_seq_len = model.params.max_seq_len if max_seq_len is None else max_seq_len
+    cnt, sum_logprob = 0, 0.0
+    for data in dataloader:
+        ys = data["ys_in"]
+        assert ys.size(0) == 1
+        if ys.size(1) > max_seq_len:
+            logging.warning(f"input length longer than {max_seq_len:d} skip")
+            continue
+        lp = model.masked_logprobs(ys, [int(data["ylens"][0])])
+        sum_logprob -= float(lp.sum())
+        cnt += ys.size(1)
     return cnt, math.exp(sum_logprob / cnt)

@@ -671,6 +671,15 @@ int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, int slots, 
                       const int* src, const int* dst, const void* w_out, const float* b_out, float* logp, long ldlogp,
                       int logp_rows, const int* row_dst, void* ws, long ws_bytes, void* stream);
 
+/* ---- masked LM: the masked copies of the pseudo-log-likelihood (lm/modeling/bert.py:54-86) ----
+ * ys int32 [B,N] with lengths ylens has R = sum(ylens) masked copies; copy r belongs to the sequence b with
+ * row0[b] <= r < row0[b+1] (row0 int32 [B+1]: prefix sums of ylens) and masks pos = r - row0[b].  For j < r_count, r = r_begin + j:
+ *   ids[j,:] = ys[b,:ylens[b]] with [pos] = mask_id, then pad_id up to Np;  klens[j] = ylens[b];
+ *   idx[j] = j*Np + pos (the flat row to gather);  labels[j] = ys[b,pos].
+ * One wave per output row, nothing is written outside the r_count rows; every pointer is device memory. */
+int emoasr_mlm_expand(int B, int N, int Np, const int* ys, const int* ylens, const int* row0, int r_begin, int r_count,
+                      int mask_id, int pad_id, int* ids, int* klens, int* idx, int* labels, void* stream);
+
 /* ---- one Conformer encoder layer, forward, sequenced on the host in C++ ---------
  * ConformerEncoderLayer.forward (asr/modeling/conformer.py:146-225) with relative-position attention:
  *   x += 0.5 * drop(FFN_macaron(LN(x)));  x += drop(RelMHA(LN(x)));  x += drop(ConvModule(LN(x)));

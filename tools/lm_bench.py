@@ -1,13 +1,21 @@
 """Transformer-LM training throughput and the vocabulary head A/B (fused = no [rows, V] logits, against materialised).
 
-    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100]
+    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert]
 
-Prints one JSON line:
+Prints one JSON line.  --leg transformer (the default):
   train_tokens_per_s   real (unpadded) tokens per second of a full training step (forward, backward, clip + AdamW) of the 12-layer
                        LM of bench.py (LM12: V = 10 000, d = 256) in bf16 at `--batch` sequences with Libri-like lengths, with the
                        head the gates select, and the same with the materialised head (EMOASR_CE_HEAD_FUSED=0's path);
   head_*_us            the head alone (loss rows forward + dX / dW / dbias backward) on that batch's rows, as same-box A/B pairs in
                        ONE process: fused, materialised, fused, ... -- the medians and every pair's ratio.
+
+--leg bert: the BERT masked LM (lm_type="bert") at the same size, bf16:
+  score                LM.masked_logprobs of a `--batch`-hypothesis Libri-like list for three values of max_token_rows: masked
+                       copies per second and token rows (copies x padded length) per second, host time from the call to the
+                       synchronised result (the upload, every chunk and the one copy back included), median of --pairs runs;
+  mlm_step             real tokens per second of a full masked-LM training step at mask_proportion 0.15 and 0.3 with transform +
+                       vocabulary head on the labelled rows only (LM.head_at_labels) against the head on all rows with row weights,
+                       as alternating legs in ONE process -- the medians and every pair's ratio.
 """
 import argparse
 import json
@@ -39,6 +47,75 @@ def libri_like_batch(batch, vocab, seed=0):
     return {"ys_in": ys, "ylens": torch.tensor(lens), "labels": labels}, sum(lens)
 
 
+def mlm_batch(batch, vocab, mask_id, proportion, seed=0):
+    """the lengths of libri_like_batch; max(int(n * proportion), 1) positions of every row masked and labelled"""
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.exp(torch.randn(batch, generator=g) * 0.55 + 3.65).clamp(4, 160).to(torch.int64).tolist()
+    N = max(lens)
+    ys = torch.full((batch, N), 2, dtype=torch.int64)
+    for b, n in enumerate(lens):
+        ys[b, :n] = torch.randint(3, mask_id, (n,), generator=g)
+    ys_in, labels = ys.clone(), torch.full((batch, N), -100, dtype=torch.int64)
+    for b, n in enumerate(lens):
+        for j in torch.randperm(n, generator=g)[: max(int(n * proportion), 1)].tolist():
+            labels[b, j], ys_in[b, j] = ys[b, j], mask_id
+    return {"ys": ys, "ys_in": ys_in, "ylens": torch.tensor(lens), "labels": labels}, sum(lens)
+
+
+def bert_leg(args):
+    import time
+    from emoasr_amd.modeling.lm import LM
+    from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
+    from emoasr_amd.train_lm import train_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    V = LM12["vocab_size"]
+    params = SimpleNamespace(**dict(LM12, lm_type="bert", mask_id=V - 1, learning_rate=1e-4, lr_schedule_type="lindecay",
+                                    num_warmup_steps=100, weight_decay=0.01, clip_grad_norm=1.0, accum_grad=1, log_step=10 ** 9))
+    lm = LM(params, compute_dtype=torch.bfloat16).to(dev)
+    out = {"leg": "bert", "batch": args.batch, "dtype": "bf16"}
+    # ---- (a) pseudo-log-likelihood of an N-best list
+    data, tokens = mlm_batch(args.batch, V, V - 1, 0.15)
+    N = int(data["ylens"].max())
+    Np = min((N + 7) // 8 * 8, LM12["max_seq_len"])
+    lm.eval()
+    out["score"] = {"hypotheses": args.batch, "copies": tokens, "padded_length": Np, "token_rows": tokens * Np, "runs": []}
+    for budget in args.token_rows:
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lm.masked_logprobs(data["ys"], data["ylens"], max_token_rows=budget)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        run()
+        sec = statistics.median(run() for _ in range(args.pairs))
+        out["score"]["runs"].append({"max_token_rows": budget, "chunks": -(-tokens // max(1, budget // Np)), "ms": round(sec * 1e3, 2),
+                                     "copies_per_s": round(tokens / sec), "token_rows_per_s": round(tokens * Np / sec),
+                                     "head_taken": lm.last_head})
+    # ---- (b) the masked-LM training step: head on the labelled rows against head on all rows
+    lm.train()
+    opt = ScheduledOptimizer(AdamW(get_optimizer_params_nodecay(list(lm.named_parameters()), params.weight_decay), lr=0,
+                                   weight_decay=params.weight_decay), params, num_total_steps=10 ** 6)
+    out["mlm_step"] = []
+    for proportion in (0.15, 0.3):
+        data, tokens = mlm_batch(args.batch, V, V - 1, proportion)
+        step = lambda: train_step(lm, opt, data, params, dev, sync=False)
+        rec = {"mask_proportion": proportion, "tokens": tokens, "rows_padded": data["ys_in"].numel(),
+               "rows_labelled": int((data["labels"] != -100).sum()), "labelled_us": [], "all_rows_us": []}
+        for _ in range(args.pairs):
+            for at_labels in (True, False):
+                lm.head_at_labels = at_labels
+                timed(step, args.warmup)
+                rec["labelled_us" if at_labels else "all_rows_us"].append(round(timed(step, args.steps), 1))
+                rec["head_taken_labelled" if at_labels else "head_taken_all_rows"] = lm.last_head
+        rec["pair_ratio_labelled_over_all_rows"] = [round(a / b, 3) for a, b in zip(rec["labelled_us"], rec["all_rows_us"])]
+        rec["tokens_per_s_labelled"] = round(tokens / statistics.median(rec["labelled_us"]) * 1e6)
+        rec["tokens_per_s_all_rows"] = round(tokens / statistics.median(rec["all_rows_us"]) * 1e6)
+        out["mlm_step"].append(rec)
+    lm.head_at_labels = True
+    print(json.dumps(out))
+
+
 def timed(fn, n):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -56,7 +133,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=100)
+    ap.add_argument("--leg", choices=["transformer", "bert"], default="transformer")
+    ap.add_argument("--token-rows", type=int, nargs="+", default=[16384, 65536, 262144], help="--leg bert: max_token_rows values")
     args = ap.parse_args()
+    if args.leg == "bert":
+        return bert_leg(args)
     from emoasr_amd import ops
     from emoasr_amd.modeling.lm import LM
     from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
