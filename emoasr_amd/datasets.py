@@ -254,16 +254,22 @@ def create_masked_lm_label(y, mask_id, num_to_mask=-1, mask_proportion=-1, rando
 
 
 class LMDataset:
-    """lm/datasets.py:24-120 for the Transformer, the RNN and the BERT masked LM: a TSV with columns utt_id / token_id
-    (space-separated ids).  Items: (utt_id, y_in int64, ylen, label int64 | None).  With params.add_sos_eos the ids are wrapped in
+    """lm/datasets.py:24-120 for the Transformer, the RNN, the BERT masked LM and ELECTRA: a TSV with columns utt_id / token_id
+    (space-separated ids).  Items: (utt_id, y_in int64, ylen, label int64 | None), for "electra-disc" with a fifth entry error_label float64.  With params.add_sos_eos the ids are wrapped in
     <eos>.  phase "train": y_in = y[:-1] and label = y[1:] (next-token targets) for lm_type "transformer" / "rnn"; for "bert"
     y_in = y with mask_id at the masked positions and label = the hidden tokens there, -100 elsewhere (create_masked_lm_label;
-    exactly one of params.num_to_mask / params.mask_proportion is configured).  Any other phase: y_in = y, no label."""
+    exactly one of params.num_to_mask / params.mask_proportion is configured); "electra" masks as "bert" does, with the same `random`
+    call order.  "electra-disc" reads a third column error_label -- space-separated tags, one per token; a token's target is 1 when
+    its tag is not "C" -- keeps y_in = y without labels, and its batches carry `error_labels` padded with -100.  Any other phase:
+    y_in = y, no label."""
 
     def __init__(self, params, data_path, phase="train", size=-1):
-        if params.lm_type not in ("transformer", "rnn", "bert"):     # (next-token targets for the first two: lm/datasets.py:91)
+        if params.lm_type not in ("transformer", "rnn", "bert", "electra", "electra-disc"):     # (next-token targets for the first two: lm/datasets.py:91)
             raise NotImplementedError(f"emoasr_amd: LMDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
-        columns = ["utt_id", "token_id"] + (["ylen"] if getattr(params, "bucket_shuffle", False) else [])
+        if params.lm_type == "electra-disc":
+            columns = ["utt_id", "token_id", "error_label"]
+        else:
+            columns = ["utt_id", "token_id"] + (["ylen"] if getattr(params, "bucket_shuffle", False) else [])
         data = _read_table(data_path)[columns]
         n = len(data)
         data = data.dropna().reset_index(drop=True)
@@ -274,11 +280,12 @@ class LMDataset:
         self.eos_id = params.eos_id
         self.phase = phase
         self.data = data[:size] if size > 0 else data
-        if self.lm_type == "bert":
+        self.masked = self.lm_type in ("bert", "electra")
+        if self.masked:
             # a config written for another LM family (no mask token, no masking rule) is not one this dataset can be built from
             missing = [f for f in ("mask_id", "random_num_to_mask") if not hasattr(params, f)]
             if missing:
-                raise NotImplementedError(f"emoasr_amd: lm_type='bert' needs the masked LM's fields; {missing} are absent from the config")
+                raise NotImplementedError(f"emoasr_amd: lm_type={self.lm_type!r} needs the masked LM's fields; {missing} are absent from the config")
             self.mask_id = params.mask_id
             # either `num_to_mask` or `mask_proportion` must be specified (lm/datasets.py:56)
             assert hasattr(params, "num_to_mask") ^ hasattr(params, "mask_proportion")
@@ -295,22 +302,30 @@ class LMDataset:
         if self.add_sos_eos:
             ids = [self.eos_id] + ids + [self.eos_id]
         y = torch.tensor(ids, dtype=torch.long)
-        if self.phase == "train" and self.lm_type == "bert":
+        err = None
+        if "error_label" in self.data:     # (lm/datasets.py:76-78)
+            err = torch.tensor([e != "C" for e in str(row["error_label"]).split()], dtype=torch.float64)
+        if self.phase == "train" and self.masked:
             y_in, label = create_masked_lm_label(y, self.mask_id, self.num_to_mask, self.mask_proportion, self.random_num_to_mask,
                                                  self.eos_id)
-        elif self.phase == "train":
+        elif self.phase == "train" and self.lm_type in ("transformer", "rnn"):
             assert len(y) > 1
             y_in, label = y[:-1], y[1:]
         else:
             y_in, label = y, None
-        return row["utt_id"], y_in, y_in.size(0), label
+        item = (row["utt_id"], y_in, y_in.size(0), label)
+        return item if err is None else item + (err,)
 
     def collate_fn(self, batch):
-        """dict with the reference's keys: ys_in padded with <eos>, ylens, labels padded with -100 (train phase only)"""
+        """dict with the reference's keys: ys_in padded with <eos>, ylens, labels padded with -100 (train phase only), error_labels
+        padded with -100 ("electra-disc")"""
         from torch.nn.utils.rnn import pad_sequence
-        utt_ids, ys_in, ylens, labels = zip(*batch)
+        utt_ids, ys_in, ylens, labels = list(zip(*batch))[:4]
+        errs = [it[4] for it in batch] if len(batch[0]) > 4 else None
         ret = {"utt_ids": list(utt_ids), "ys_in": pad_sequence(ys_in, batch_first=True, padding_value=self.eos_id),
                "ylens": torch.tensor(ylens)}
         if labels[0] is not None:
             ret["labels"] = pad_sequence(labels, batch_first=True, padding_value=-100)
+        if errs is not None:
+            ret["error_labels"] = pad_sequence(errs, batch_first=True, padding_value=-100)
         return ret

@@ -260,6 +260,11 @@ SIGNATURES = {
     "emoasr_rnnt_beam_pick": [I, I, I, I, I, P, L, P, L, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
     "emoasr_mlm_expand": [I, I, I, P, P, P, I, I, I, I, P, P, P, P, P],
+    "emoasr_sample_rows": [I, I, I, P, L, P, P, U64, L, P, P, P, P],
+    "emoasr_gumbel_noise": [I, I, U64, L, P, L, P],
+    "emoasr_electra_corrupt": [I, I, P, P, P, P, P, P, P, P],
+    "emoasr_bce_head_fwd": [I, I, I, P, L, P, P, P, P, P, P, P, P],
+    "emoasr_bce_head_bwd": [I, I, I, P, L, P, P, P, P, F, P, P, L, P, P, P],
     "emoasr_ctc_forward_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P],
     "emoasr_ctc_grad_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, F, P, P, P, P, P, L, P],
     "emoasr_ctc_greedy": [I, I, I, I, P, L, P, I, P, P, P, P],

@@ -18,7 +18,7 @@ in forward() without labels, which returns them) the logits are materialised.  t
 
 State-dict keys match the reference (`lm.transformer.bert.*`, `lm.transformer.cls.predictions.*`,
 output embedding tied to the word embedding).  `LM(params)` with `lm_type == "rnn"` returns the LSTM LM of modeling/rnnlm.py
-(same module API, `stateful = True`); every type but these and "bert" is outside the path.
+(same module API, `stateful = True`); every type but these, "bert", "electra" and "electra-disc" is outside the path.
 
 `lm_type == "bert"` is the masked LM of lm/modeling/bert.py:17-92 -- the same stack without the causal mask, keys `lm.bert.bert.*` /
 `lm.bert.cls.predictions.*`, `mask_id = params.mask_id` -- on the same code, parametrised by the key prefix and `causal`:
@@ -30,6 +30,18 @@ output embedding tied to the word embedding).  `LM(params)` with `lm_type == "rn
 Its transform + vocabulary head run on the gathered labelled rows only (`head_at_labels`), its attention backward takes the
 single-pass kernel in bf16, `masked_logprobs` builds the masked copies on the device (ops.mlm_expand) and walks them in chunks of
 token rows, and `predict` / `zero_states` raise: a bidirectional LM has no next-token distribution.
+
+`lm_type in ("electra", "electra-disc")` is ELECTRA (lm/modeling/electra.py:33-132): a generator (`lm.gmodel.*`, ElectraForMaskedLM)
+and a discriminator (`lm.dmodel.*`, ElectraForPreTraining), two stacks of the same blocks described by a `_Stack` each (key prefix,
+embedding / hidden / inner size, heads, layers, `embeddings_project` present), in one parameter arena:
+
+    loss, loss_dict = lm(ys_masked, ylens, labels);  loss.backward()           # loss_gen + electra_disc_weight * loss_disc
+    loss, loss_dict = lm.forward_disc(ys, ylens, error_labels)                 # the discriminator alone, BCE over n < ylens[b]
+    scores = lm.score(ys, ylens)                                               # one encoder pass: sums of sigmoid(logit), see score()
+
+The generator's replacement tokens are drawn on the device (ops.sample_rows: Gumbel-max, a function of `lm.seed`, `lm.step_count`,
+row and column), put in place by ops.electra_corrupt, and the discriminator's binary head runs on the rows n < ylens[b]
+(ops.bce_head_fwd / _bwd); `lm.forced_samples`, `lm.last_corruption` and `lm.sample_path` are the hooks.
 """
 import math
 from types import SimpleNamespace
@@ -151,14 +163,114 @@ class BERTMaskedLM(nn.Module):
             return self.bert.load_state_dict(state_dict, strict)  # the bare BertForMaskedLM dict (bert.py:88-92)
 
 
+class _ElectraEmbeddings(_Holder):
+    """modeling_electra.py:114-125: word, position, token-type tables and their LayerNorm at embedding_size"""
+
+    def __init__(self, vocab, e, max_len):
+        super().__init__()
+        self.word_embeddings = nn.Embedding(vocab, e, padding_idx=0)
+        self.position_embeddings = nn.Embedding(max_len, e)
+        self.token_type_embeddings = nn.Embedding(2, e)
+        self.LayerNorm = nn.LayerNorm(e, eps=1e-12)
+
+
+class _ElectraModel(_Holder):
+    """modeling_electra.py:240-253: no pooler; embeddings_project exists only when embedding_size != hidden_size"""
+
+    def __init__(self, vocab, e, d, inner, n, max_len):
+        super().__init__()
+        self.embeddings = _ElectraEmbeddings(vocab, e, max_len)
+        if e != d:
+            self.embeddings_project = nn.Linear(e, d)
+        self.encoder = _Encoder(d, inner, n)
+
+
+class _GeneratorPredictions(_Holder):
+    """modeling_electra.py:146-160: dense(hidden -> embedding), GELU, LayerNorm(embedding) built WITHOUT the config's eps (1e-5)"""
+
+    def __init__(self, e, d):
+        super().__init__()
+        self.LayerNorm = nn.LayerNorm(e)
+        self.dense = nn.Linear(d, e)
+
+
+class _DiscriminatorPredictions(_Holder):
+    def __init__(self, d):
+        super().__init__()
+        self.dense = nn.Linear(d, d)
+        self.dense_prediction = nn.Linear(d, 1)
+
+
+class _ElectraForMaskedLM(_Holder):
+    def __init__(self, vocab, e, d, inner, n, max_len):
+        super().__init__()
+        self.electra = _ElectraModel(vocab, e, d, inner, n, max_len)
+        self.generator_predictions = _GeneratorPredictions(e, d)
+        self.generator_lm_head = nn.Linear(e, vocab)
+        self.generator_lm_head.weight = self.electra.embeddings.word_embeddings.weight  # tied (init_weights -> tie_weights)
+
+
+class _ElectraForPreTraining(_Holder):
+    def __init__(self, vocab, e, d, inner, n, max_len):
+        super().__init__()
+        self.electra = _ElectraModel(vocab, e, d, inner, n, max_len)
+        self.discriminator_predictions = _DiscriminatorPredictions(d)
+
+
+_ELECTRA_FIELDS = ("mask_id", "electra_disc_weight") + tuple(
+    f"{s}_{f}" for s in ("gen", "disc") for f in ("embedding_size", "hidden_size", "num_layers", "num_attention_heads", "intermediate_size"))
+
+
+class ELECTRAModel(nn.Module):
+    """parameter container of lm/modeling/electra.py:33-69: generator (ElectraForMaskedLM) and discriminator (ElectraForPreTraining)"""
+
+    def __init__(self, params):
+        super().__init__()
+        P = params
+        self.gmodel = _ElectraForMaskedLM(P.vocab_size, P.gen_embedding_size, P.gen_hidden_size, P.gen_intermediate_size,
+                                          P.gen_num_layers, P.max_seq_len)
+        self.dmodel = _ElectraForPreTraining(P.vocab_size, P.disc_embedding_size, P.disc_hidden_size, P.disc_intermediate_size,
+                                             P.disc_num_layers, P.max_seq_len)
+        self.electra_disc_weight = P.electra_disc_weight
+        self.mask_id = P.mask_id
+
+    def load_state_dict(self, state_dict, strict=True):
+        try:
+            return super().load_state_dict(state_dict, strict)
+        except RuntimeError:
+            return self.dmodel.load_state_dict(state_dict, strict)  # a bare ElectraForPreTraining dict: the discriminator alone
+
+
+class _Stack:
+    """what _encode / _backward_stack need to know of one post-LN BERT stack: the key prefix of its model (`...bert.` /
+    `...electra.`), embedding / hidden / inner sizes, heads, layers, the causal mask, whether embeddings_project sits between the
+    embedding LayerNorm (+ dropout) and the blocks, the offset of its dropout seed sites and its position + token-type(0) table"""
+
+    def __init__(self, pre, emb, d, inner, heads, layers, causal, project=False, site=0):
+        assert d % heads == 0 and d // heads == 64, (
+            f"emoasr_amd: {pre!r} has hidden size {d} over {heads} heads = {d / heads:g} per head; the attention kernels need heads 64 wide")
+        assert project == (emb != d), "embeddings_project exists exactly when embedding_size != hidden_size"
+        self.pre, self.emb, self.d, self.inner, self.heads, self.layers = pre, emb, d, inner, heads, layers
+        self.causal, self.project, self.site = causal, project, site
+        self.pe = None
+
+
+_ELECTRA_TYPES = ("electra", "electra-disc")
 _NO_PREDICT = ("emoasr_amd: the BERT masked LM (lm_type='bert') has no next-token distribution: predict / zero_states and the "
                "beam searches' shallow fusion need a causal LM (lm_type 'transformer' or 'rnn'); use LM.score for rescoring")
+
+
+_NO_PREDICT_ELECTRA = ("emoasr_amd: ELECTRA (lm_type 'electra' / 'electra-disc') has no next-token distribution: predict / zero_states "
+                       "and the beam searches' shallow fusion need a causal LM (lm_type 'transformer' or 'rnn'); use LM.score for "
+                       "rescoring")
 
 
 def require_next_token_lm(lm, lm_weight):
     """entry check of the beam searches: shallow fusion needs p(next token | prefix), which a bidirectional LM does not define"""
     if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) == "bert":
         raise NotImplementedError(_NO_PREDICT)
+    if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) in _ELECTRA_TYPES:
+        raise NotImplementedError(_NO_PREDICT_ELECTRA)
 
 
 class LM(nn.Module):
@@ -173,7 +285,7 @@ class LM(nn.Module):
     def __init__(self, params, phase="test", compute_dtype=torch.bfloat16):
         super().__init__()
         self.lm_type = params.lm_type
-        if self.lm_type not in ("transformer", "bert"):
+        if self.lm_type not in ("transformer", "bert") + _ELECTRA_TYPES:
             raise NotImplementedError(f"emoasr_amd: lm_type={self.lm_type!r} is outside the HIP hot path")
         self.params = params
         # "f32x3" (f32 storage, split-bf16 products: modeling/asr.py) -> float32 + the library's split switch asserted per call
@@ -182,9 +294,16 @@ class LM(nn.Module):
         # one stack, two LMs: the key prefix and the causal mask are all that differ (the reference's TransformerLM is its
         # BertForMaskedLM run with causal=True)
         self.causal = self.lm_type == "transformer"
+        self.electra = self.lm_type in _ELECTRA_TYPES
+        if self.electra:
+            self._init_electra(params)
+            return
         root = "lm.transformer." if self.causal else "lm.bert."
         self._PRE, self._CP = root + "bert.", root + "cls.predictions."
         self._NO_GRAD = (self._PRE + "pooler.dense.weight", self._PRE + "pooler.dense.bias")
+        self._stack = _Stack(self._PRE, params.hidden_size, params.hidden_size, params.intermediate_size,
+                             params.num_attention_heads, params.num_layers, self.causal)
+        self._stacks = (self._stack,)
         if self.causal:
             self.lm = TransformerLM(params)
         else:
@@ -195,9 +314,11 @@ class LM(nn.Module):
         # masked-LM labels cover a fraction of the positions: transform + vocabulary head run on the gathered labelled rows only
         # (a causal LM labels nearly every row and keeps the all-rows head with row weights)
         self.head_at_labels = not self.causal
+        self._init_common()
+
+    def _init_common(self):
         self.attn_fused = True     # A/B switch of the single-pass attention backward (bf16, non-causal only)
         self._arena = None
-        self._pe = None
         # the reference's TransformersConfig defaults (lm/modeling/transformer.py:22-29 passes neither): active in train() mode
         self.hidden_dropout_prob = 0.1
         self.attention_probs_dropout_prob = 0.1
@@ -205,6 +326,30 @@ class LM(nn.Module):
         self.last_head = None     # "fused" / "materialised": the path the last loss / score call took
         self.seed = 0x5EED
         self.step_count = 0
+
+    def _init_electra(self, params):
+        missing = [f for f in _ELECTRA_FIELDS if not hasattr(params, f)]
+        if missing:
+            raise NotImplementedError(f"emoasr_amd: lm_type={self.lm_type!r} needs ELECTRA's fields; {missing} are absent from the config")
+        P = params
+        self.lm = ELECTRAModel(params)
+        self.mask_id = P.mask_id
+        self.electra_disc_weight = float(P.electra_disc_weight)
+        self._G, self._D = "lm.gmodel.", "lm.dmodel."
+        # dropout seed sites: the generator keeps the sites of the other LMs, the discriminator's are offset past any layer count
+        self._gen = _Stack(self._G + "electra.", P.gen_embedding_size, P.gen_hidden_size, P.gen_intermediate_size,
+                           P.gen_num_attention_heads, P.gen_num_layers, False, P.gen_embedding_size != P.gen_hidden_size, site=0)
+        self._disc = _Stack(self._D + "electra.", P.disc_embedding_size, P.disc_hidden_size, P.disc_intermediate_size,
+                            P.disc_num_attention_heads, P.disc_num_layers, False, P.disc_embedding_size != P.disc_hidden_size,
+                            site=1 << 20)
+        assert max(P.gen_num_layers, P.disc_num_layers) * 10 + 102 < 1 << 20, "dropout seed sites of the two stacks would collide"
+        self._stack, self._stacks = self._disc, (self._gen, self._disc)
+        self._NO_GRAD = ()
+        self.head_at_labels = True
+        self.sample_path = "hip"       # "torch": comparator of tools/lm_bench.py (softmax + multinomial + indexed assignment)
+        self.forced_samples = None     # int64 [B, N]: replaces the drawn samples at the masked positions (tests, replaying a run)
+        self.last_corruption = None    # (generated_ids int32 [B, N], labels_replaced f32 [B, N]) of the last forward, on the device
+        self._init_common()
 
     def load_state_dict(self, state_dict, strict=True):
         try:
@@ -214,18 +359,22 @@ class LM(nn.Module):
 
     def zero_states(self, bs, device):
         if not self.causal:
-            raise NotImplementedError(_NO_PREDICT)
+            raise NotImplementedError(_NO_PREDICT_ELECTRA if self.electra else _NO_PREDICT)
         return self.lm.zero_states(bs, device)
 
     # ---------------------------------------------------------------- HIP forward
     def _bind(self):
         if self._arena is None or not self._arena.bound() or self._arena.compute_dtype != self.compute_dtype:
             self._arena = ParamArena(self, self.compute_dtype)
-            emb = self._PRE + "embeddings."
             A = self._arena
-            # position + token-type(0) rows folded into one additive table (modeling_bert.py:196-201)
-            self._pe = (A.p(emb + "position_embeddings.weight") + A.p(emb + "token_type_embeddings.weight")[0]).contiguous()
+            for S in self._stacks:     # position + token-type(0) rows folded into one additive table per stack (modeling_bert.py:196-201)
+                emb = S.pre + "embeddings."
+                S.pe = (A.p(emb + "position_embeddings.weight") + A.p(emb + "token_type_embeddings.weight")[0]).contiguous()
         return self._arena
+
+    @property
+    def _pe(self):
+        return self._stack.pe
 
     def _forward_rows(self, ids, klens, idx, B, N):
         """ids int32 [B,N], klens int32 [B], idx [B] (flat position b * N + ylens[b] - 1 of every row's last token), all on the
@@ -270,7 +419,7 @@ class LM(nn.Module):
         8) -- the call was host-bound (1.5 ms of launch sequencing for ~0.4 ms of kernels).  Padding rows / positions are masked
         by their key lengths and never read back; the real rows' arithmetic is the eager call's.  EMOASR_LM_GRAPH=0: eager."""
         if not self.causal:
-            raise NotImplementedError(_NO_PREDICT)
+            raise NotImplementedError(_NO_PREDICT_ELECTRA if self.electra else _NO_PREDICT)
         arena_before = self._arena
         A = self._bind()
         if A is not arena_before:
@@ -337,7 +486,7 @@ class LM(nn.Module):
 
     def predict(self, ys, ylens, states=None):
         if not self.causal:
-            raise NotImplementedError(_NO_PREDICT)
+            raise NotImplementedError(_NO_PREDICT_ELECTRA if self.electra else _NO_PREDICT)
         with torch.no_grad():
             ys_host = ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)
             yl = ylens.tolist() if torch.is_tensor(ylens) else list(ylens)
@@ -346,7 +495,8 @@ class LM(nn.Module):
     # ---------------------------------------------------------------- training, scoring
     MAX_TOKEN_ROWS = 16384     # masked_logprobs: token rows (copies x padded length) per encoder run
 
-    def _seed(self, site):
+    def _seed(self, site, S=None):
+        site += S.site if S is not None else 0
         return (self.seed * 1000003 + self.step_count * 4099 + site) & 0xFFFFFFFFFFFF
 
     def _prepare(self):
@@ -361,42 +511,47 @@ class LM(nn.Module):
         return A
 
     def _refresh_pe(self):
-        A, emb = self._arena, self._PRE + "embeddings."
-        pos, typ = A.p(emb + "position_embeddings.weight"), A.p(emb + "token_type_embeddings.weight")
-        ops.strided_copy(pos, out=self._pe)
-        ops.strided_copy(typ[0].expand(pos.shape[0], pos.shape[1]), out=self._pe, accumulate=True)
+        A = self._arena
+        for S in self._stacks:
+            emb = S.pre + "embeddings."
+            pos, typ = A.p(emb + "position_embeddings.weight"), A.p(emb + "token_type_embeddings.weight")
+            ops.strided_copy(pos, out=S.pe)
+            ops.strided_copy(typ[0].expand(pos.shape[0], pos.shape[1]), out=S.pe, accumulate=True)
         self._pe_stale = False
 
     def _split(self):
         return self.f32_split if self.compute_dtype == torch.float32 else None
 
-    def _encode(self, ids, klens, B, N, p_h, p_att, keep):
-        """ids int32 [B,N], klens int32 [B] on the device -> (hidden [B*N, d], stash | None): embeddings + the post-LN blocks
-        (modeling_bert.py:159-436), dropout by the seeded sites"""
-        A, P = self._arena, self.params
-        d, H, nl = P.hidden_size, P.num_attention_heads, P.num_layers
-        pre = self._PRE
-        e = ops.embed_fwd(ids, A.w(pre + "embeddings.word_embeddings.weight"), self._pe, 1.0).view(B * N, d)
+    def _encode(self, ids, klens, B, N, p_h, p_att, keep, S=None):
+        """ids int32 [B,N], klens int32 [B] on the device -> (hidden [B*N, d], stash | None): embeddings (+ embeddings_project) + the
+        post-LN blocks of stack S (modeling_bert.py:159-436, modeling_electra.py:324-337), dropout by the seeded sites"""
+        A, S = self._arena, S or self._stack
+        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
+        pre = S.pre
+        e = ops.embed_fwd(ids, A.w(pre + "embeddings.word_embeddings.weight"), S.pe, 1.0).view(B * N, S.emb)
         x, m0, r0 = ops.layernorm_fwd(e, A.p(pre + "embeddings.LayerNorm.weight"), A.p(pre + "embeddings.LayerNorm.bias"),
                                       1e-12, keep)
-        s_emb = self._seed(1)
+        s_emb = self._seed(1, S)
         if p_h > 0:
             x = ops.scale_dropout(x, 1.0, p_h, s_emb)
+        xe = x
+        if S.project:
+            x = ops.gemm_nt(xe, A.w(pre + "embeddings_project.weight"), bias=A.p(pre + "embeddings_project.bias"))
         scale = 1.0 / math.sqrt(d // H)
         layers = []
         for i in range(nl):
             lay = f"{pre}encoder.layer.{i}."
-            s_att, s_o, s_f = self._seed(100 + 10 * i), self._seed(101 + 10 * i), self._seed(102 + 10 * i)
+            s_att, s_o, s_f = self._seed(100 + 10 * i, S), self._seed(101 + 10 * i, S), self._seed(102 + 10 * i, S)
             wqkv = A.w_span(lay + "attention.self.query.weight", lay + "attention.self.value.weight", (3 * d, d))
             bqkv = A.p_span(lay + "attention.self.query.bias", lay + "attention.self.value.bias", (3 * d,))
             qkv = ops.gemm_nt(x, wqkv, bias=bqkv).view(B, N, 3 * d)
-            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=self.causal,
+            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=causal,
                                   drop_p=p_att, seed=s_att)
             y = ops.gemm_nt(o.view(B * N, d), A.w(lay + "attention.output.dense.weight"),
                             bias=A.p(lay + "attention.output.dense.bias"), residual=x, res_scale=1.0, drop_p=p_h, seed=s_o)
             x1, m1, r1 = ops.layernorm_fwd(y, A.p(lay + "attention.output.LayerNorm.weight"),
                                            A.p(lay + "attention.output.LayerNorm.bias"), 1e-12, keep)
-            u = torch.empty(B * N, P.intermediate_size, device=x.device, dtype=x.dtype) if keep else None
+            u = torch.empty(B * N, S.inner, device=x.device, dtype=x.dtype) if keep else None
             a = ops.gemm_nt(x1, A.w(lay + "intermediate.dense.weight"), bias=A.p(lay + "intermediate.dense.bias"),
                             act=ACT_GELU, pre_out=u)
             y2 = ops.gemm_nt(a, A.w(lay + "output.dense.weight"), bias=A.p(lay + "output.dense.bias"), residual=x1,
@@ -410,7 +565,7 @@ class LM(nn.Module):
             return x, None
         st = _Stash()
         st.B, st.N, st.ids, st.klens, st.p_h, st.p_att = B, N, ids, klens, p_h, p_att
-        st.e, st.m0, st.r0, st.s_emb, st.layers = e, m0, r0, s_emb, layers
+        st.e, st.m0, st.r0, st.s_emb, st.layers, st.xe = e, m0, r0, s_emb, layers, xe
         return x, st
 
     def _transform(self, x, keep):
@@ -450,7 +605,10 @@ class LM(nn.Module):
         return ys.contiguous(), yl
 
     def forward(self, ys, ylens=None, labels=None, ps=None, plens=None):
-        """lm/modeling/lm.py:45-46, transformer.py:35-56: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss})"""
+        """lm/modeling/lm.py:45-46, transformer.py:35-56: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss});
+        ELECTRA (electra.py:71-100): (loss, {loss_gen, loss_disc, num_replaced, num_masked}), labels required"""
+        if self.electra:
+            return self._electra_forward(ys, ylens, labels)
         ys, yl = self._inputs(ys, ylens)
         A = self._prepare()
         if labels is None:
@@ -512,23 +670,25 @@ class LM(nn.Module):
         with ops.stream_scope(self._split()):
             self._backward(st, g.to(torch.float32).reshape(1))
 
+    def _lin_bwd(self, dy, x_in, wname, bname, **epi):   # gradients of y = x_in W^T + b; -> dy W with the epilogue
+        A = self._arena
+        w = A.w(wname)
+        ops.gemm_tn(dy, x_in, out=A.g(wname), accumulate=True, colsum=A.g(bname))
+        return ops.gemm_nn(dy, w, **epi)
+
+    def _ln_bwd(self, dy, x_in, name, mean, rstd):
+        A = self._arena
+        return ops.layernorm_bwd(dy, x_in, A.p(name + ".weight"), mean, rstd, None, A.g(name + ".weight"), A.g(name + ".bias"))
+
     def _backward(self, st, g1):
-        A, P = self._arena, self.params
+        A = self._arena
         A.attach_grads()
-        d, H, nl = P.hidden_size, P.num_attention_heads, P.num_layers
-        B, N, p_h, p_att = st.B, st.N, st.p_h, st.p_att
+        S = self._stack
+        d = S.d
+        B, N = st.B, st.N
         pre, cp = self._PRE, self._CP
         word = pre + "embeddings.word_embeddings.weight"
-
-        def lin_bwd(dy, x_in, wname, bname, **epi):   # gradients of y = x_in W^T + b; -> dy W with the epilogue
-            w = A.w(wname)
-            ops.gemm_tn(dy, x_in, out=A.g(wname), accumulate=True, colsum=A.g(bname))
-            return ops.gemm_nn(dy, w, **epi)
-
-        def ln_bwd(dy, x_in, name, mean, rstd):
-            return ops.layernorm_bwd(dy, x_in, A.p(name + ".weight"), mean, rstd, None, A.g(name + ".weight"), A.g(name + ".bias"))
-
-        drop = lambda t, seed: ops.scale_dropout(t, 1.0, p_h, seed) if p_h > 0 else t
+        lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
         # ---- vocabulary head (tied to the word embedding: its weight gradient lands in the embedding's slot)
         kind, hctx = st.head
         if kind == "fused":
@@ -541,6 +701,19 @@ class LM(nn.Module):
         dx = lin_bwd(dpre, x, cp + "transform.dense.weight", cp + "transform.dense.bias")
         if st.sel is not None:     # the head ran on gathered rows: their gradient goes back to its rows, every other row has none
             dx = torch.zeros(B * N, d, device=dx.device, dtype=dx.dtype).index_copy_(0, st.sel, dx)
+        self._backward_stack(st, dx, S)
+        for n in self._NO_GRAD:      # never read by the LM: .grad stays None as in the reference (AdamW then leaves them alone)
+            A.params[A.names.index(n)].grad = None
+
+    def _backward_stack(self, st, dx, S):
+        """dx [B*N, d]: the gradient of stack S's last hidden state -> every gradient of its blocks and embeddings, accumulated"""
+        A = self._arena
+        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
+        B, N, p_h, p_att = st.B, st.N, st.p_h, st.p_att
+        pre = S.pre
+        word = pre + "embeddings.word_embeddings.weight"
+        lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
+        drop = lambda t, seed: ops.scale_dropout(t, 1.0, p_h, seed) if p_h > 0 else t
         # ---- blocks, last to first.  Post-LN: LayerNorm backward first, then the branch and the residual together
         scale = 1.0 / math.sqrt(d // H)
         scratch = None
@@ -557,13 +730,13 @@ class LM(nn.Module):
             dq, dk, dv = dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]
             # (the single-pass attention backward has no causal mask: the masked LM takes it in bf16, the causal LM the
             # materialised path, as the ASR decoder's self-attention)
-            if self.attn_fused and ops.fused_attn_bwd_ok(q, None, None, None, self.causal):
+            if self.attn_fused and ops.fused_attn_bwd_ok(q, None, None, None, causal):
                 ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, drop_p=p_att, seed=s_att,
                              materialise="fused")
             else:
                 if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
                     scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
-                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=self.causal,
+                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=causal,
                              drop_p=p_att, seed=s_att, scratch=scratch)
             dqkv2 = dqkv.view(B * N, 3 * d)
             qn, vn = lay + "attention.self.query.", lay + "attention.self.value."
@@ -571,17 +744,18 @@ class LM(nn.Module):
                         colsum=A.g_span(qn + "bias", vn + "bias", (3 * d,)))
             dx = ops.gemm_nn(dqkv2, A.w_span(qn + "weight", vn + "weight", (3 * d, d)), residual=dy, res_scale=1.0)
         # ---- embeddings (modeling_bert.py:159-201): word rows scattered, positions summed over the batch, token type 0 over all rows
-        emb = pre + "embeddings."
+        emb, E = pre + "embeddings.", S.emb
+        if S.project:     # (modeling_electra.py:328-329: after the embedding dropout)
+            dx = lin_bwd(dx, st.xe, pre + "embeddings_project.weight", pre + "embeddings_project.bias")
         de = ln_bwd(drop(dx, st.s_emb), st.e, emb + "LayerNorm", st.m0, st.r0)
-        ops.embed_bwd(st.ids, de.view(B, N, d), 1.0, A.g(word))
-        ops.colsum(de.view(B, N * d), out=A.g(emb + "position_embeddings.weight").view(-1)[: N * d], accumulate=True)
+        ops.embed_bwd(st.ids, de.view(B, N, E), 1.0, A.g(word))
+        ops.colsum(de.view(B, N * E), out=A.g(emb + "position_embeddings.weight").view(-1)[: N * E], accumulate=True)
         ops.colsum(de, out=A.g(emb + "token_type_embeddings.weight")[0], accumulate=True)
-        for n in self._NO_GRAD:      # never read by the LM: .grad stays None as in the reference (AdamW then leaves them alone)
-            A.params[A.names.index(n)].grad = None
 
     def token_logprobs(self, ys, ylens, labels):
         """log p(labels[b,i] | ys[b,:i+1]) for every position with labels != -100 (zeros elsewhere) -> float64 [B, N] on the HOST:
         the logit-free head forward (label logit minus log-sum-exp), ONE device-to-host copy of the row values"""
+        assert not self.electra, "token_logprobs is a next-token or masked LM's; ELECTRA scores with replaced_probs"
         ys, yl = self._inputs(ys, ylens)
         labels = (labels.cpu() if torch.is_tensor(labels) else torch.as_tensor(labels)).to(torch.int64)[:, : ys.shape[1]]
         A = self._prepare()
@@ -601,7 +775,7 @@ class LM(nn.Module):
         -> float64 [B, N] on the HOST.  The R = sum(ylens) masked copies are built on the device (ops.mlm_expand) and walked in
         chunks of at most max_token_rows token rows (copies x padded length; a chunk may begin and end inside a sequence); of every
         copy only its masked row goes through transform + head, and the R row values come back in ONE device-to-host copy."""
-        assert not self.causal, "masked_logprobs is the masked LM's (lm_type='bert'); a causal LM has token_logprobs"
+        assert not self.causal and not self.electra, "masked_logprobs is the masked LM's (lm_type='bert'); a causal LM has token_logprobs"
         assert ylens is not None
         ys, yl = self._inputs(ys, ylens)
         A = self._prepare()
@@ -634,7 +808,13 @@ class LM(nn.Module):
         """causal LM (lm/modeling/transformer.py:79-99): per row sum_{i < ylens[b]-1} log p(ys[b,i+1] | ys[b,:i+1]); masked LM
         (lm/modeling/bert.py:54-86): the pseudo-log-likelihood, the row sums of masked_logprobs (all copies of a call are stacked and
         chunked by token rows there, so `batch_size` -- copies per run in the reference -- changes nothing) -> Python list of floats
-        (summed on the host in double precision, as the reference sums Python floats)"""
+        (summed on the host in double precision, as the reference sums Python floats).
+        ELECTRA (lm/modeling/electra.py:116-132): one discriminator pass, p = sigmoid(logit) = the probability that a token was
+        replaced, one device-to-host copy of the [B, N] probabilities, `batch_size` unused as in the reference.  The reference's
+        SIGN QUIRK is kept: a call with B > 1 rows returns -sum(p[b, :ylens[b]]) per row (higher = fewer suspected errors), a call
+        with ONE row returns +sum(p[0, :]) over ALL N positions of `ys` as given, padding included -- the two are not comparable."""
+        if self.electra:
+            return self._electra_score(ys, ylens)
         if not self.causal:
             return self.masked_logprobs(ys, ylens).sum(dim=1).tolist()
         ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
@@ -648,6 +828,227 @@ class LM(nn.Module):
                 labels[b, : n - 1] = y[b, 1:n]
             out += self.token_logprobs(y, l, labels).sum(dim=1).tolist()
         return out
+
+    # ---------------------------------------------------------------- ELECTRA (lm/modeling/electra.py:33-132)
+    SITE_SAMPLE = 7      # seed site of the generator's samples (the dropout sites are 1 and 100 + 10 * layer + {0, 1, 2})
+
+    def _electra_inputs(self, ys, ylens, target, name):
+        ys, yl = self._inputs(ys, ylens)
+        if target is None:
+            raise ValueError(f"emoasr_amd: lm_type={self.lm_type!r} needs `{name}` (the reference dereferences them unconditionally)")
+        target = (target.cpu() if torch.is_tensor(target) else torch.as_tensor(target)).to(torch.int64)[:, : ys.shape[1]].contiguous()
+        assert target.shape == ys.shape, f"{name}: [B, N] like ys"
+        return ys, yl, target
+
+    def _electra_forward(self, ys, ylens, labels):
+        """electra.py:71-100 -> (loss_gen + electra_disc_weight * loss_disc, {loss_gen, loss_disc, num_replaced, num_masked}): one
+        autograd node; the sample is discrete, so no gradient flows from the discriminator into the generator"""
+        ys, yl, labels = self._electra_inputs(ys, ylens, labels, "labels")
+        A = self._prepare()
+        loss = _ElectraLossFn.apply(self, "both", ys, yl, labels, *A.params)
+        aux = self._aux
+        B = ys.shape[0]
+        return loss, {"loss_gen": aux["loss_gen"], "loss_disc": aux["loss_disc"], "num_replaced": aux["counters"][0] / B,
+                      "num_masked": aux["counters"][1] / B}
+
+    def forward_disc(self, ys, ylens=None, error_labels=None):
+        """electra.py:102-114: the discriminator alone on `ys`, BCE against error_labels (0 / 1, -100 where n >= ylens[b]) over the
+        positions n < ylens[b] -> (loss, {"loss_total": loss}).  The generator is not run and its parameters' .grad is None after the
+        backward (do not mix forward and forward_disc inside one gradient-accumulation window)."""
+        if not self.electra:
+            raise NotImplementedError(f"emoasr_amd: forward_disc is ELECTRA's; lm_type={self.lm_type!r} has no discriminator")
+        ys, yl, err = self._electra_inputs(ys, ylens, error_labels, "error_labels")
+        A = self._prepare()
+        loss = _ElectraLossFn.apply(self, "disc", ys, yl, err, *A.params)
+        return loss, {"loss_total": loss}
+
+    def _active_rows(self, yl, B, N, dev):
+        """flat rows b * N + n with n < ylens[b] -> (int64 device tensor | None when every row is active, their number)"""
+        if min(yl) >= N:
+            return None, B * N
+        rows = torch.cat([torch.arange(b * N, b * N + n, dtype=torch.int32) for b, n in enumerate(yl)])
+        return h2d_i32(rows, dev).long(), rows.numel()
+
+    def _electra_loss_forward(self, mode, ys, yl, target, keep):
+        A = self._arena
+        dev = A.flat.device
+        B, N = ys.shape
+        training = self.training
+        if training:
+            self.step_count += 1
+        p_h = float(self.hidden_dropout_prob) if training else 0.0
+        p_att = float(self.attention_probs_dropout_prob) if training else 0.0
+        G, D = self._G, self._D
+        st = _Stash()
+        st.mode = mode
+        with ops.stream_scope(self._split()):
+            ids, klens = h2d_i32(ys, dev), h2d_i32(yl, dev)
+            if mode == "both":
+                labels = target
+                valid = labels != -100
+                assert int(labels.max()) < self.params.vocab_size, "labels: [B, N] ids below vocab_size or -100"
+                count = int(valid.sum())
+                rows_host = valid.view(-1).nonzero().view(-1) if count else torch.zeros(1, dtype=torch.int64)     # (no label: one row of weight 0)
+                lab = h2d_i32(labels.view(-1)[rows_host].clamp(min=0), dev)
+                sel = h2d_i32(rows_host, dev)
+                w = torch.full((rows_host.numel(),), 1.0 / count if count else 0.0).pin_memory().to(dev, non_blocking=True)
+                # ---- generator: encoder, transform + vocabulary head on the labelled rows, loss rows and one sample per row
+                x, gst = self._encode(ids, klens, B, N, p_h, p_att, keep, self._gen)
+                sel64 = sel.long()
+                xs = x.index_select(0, sel64)
+                tu = torch.empty(xs.shape[0], self._gen.emb, device=dev, dtype=xs.dtype) if keep else None
+                gp = G + "generator_predictions."
+                t = ops.gemm_nt(xs, A.w(gp + "dense.weight"), bias=A.p(gp + "dense.bias"), act=ACT_GELU, pre_out=tu)
+                t2, mt, rt = ops.layernorm_fwd(t, A.p(gp + "LayerNorm.weight"), A.p(gp + "LayerNorm.bias"), 1e-5, keep)
+                # [M, V] logits in rows padded to a multiple of 8 columns: the shipped V = 9 798 is none, and the gradient
+                # products read dz with that row stride
+                W = A.w(G + "electra.embeddings.word_embeddings.weight")
+                V = W.shape[0]
+                logits = torch.empty(xs.shape[0], (V + 7) // 8 * 8, device=dev, dtype=t2.dtype)[:, :V]
+                ops.gemm_nt(t2, W, out=logits, bias=A.p(G + "generator_lm_head.bias"))
+                if self.sample_path == "torch":     # comparator: what the reference does, on the gathered rows
+                    rows, _ = ops.lsm_loss(logits, lab, w, 0.0)
+                    samples = torch.softmax(logits.float(), dim=1).multinomial(1).view(-1).to(torch.int32)
+                else:
+                    rows, samples, _ = ops.sample_rows(logits, lab, w, self._seed(self.SITE_SAMPLE))
+                if self.forced_samples is not None:
+                    forced = torch.as_tensor(self.forced_samples).to(torch.int64)[:, :N].contiguous()
+                    assert forced.shape == ys.shape, "forced_samples: int64 [B, N]"
+                    forced = forced.view(-1)[rows_host]
+                    assert 0 <= int(forced.min()) and int(forced.max()) < V, "forced_samples: token id outside the vocabulary"
+                    samples = h2d_i32(forced, dev)
+                loss_gen = rows.sum()
+                m = slice(0, rows_host.numel() if count else 0)
+                if self.sample_path == "torch":
+                    generated = ids.clone()
+                    original = ids.clone()
+                    generated.view(-1)[sel64[m]] = samples[m]
+                    original.view(-1)[sel64[m]] = lab[m]
+                    replaced = (generated != original).to(torch.float32)
+                    counters = torch.stack([replaced.sum(), torch.full((), float(count), device=dev)]).to(torch.int32)
+                else:
+                    generated, replaced, counters = ops.electra_corrupt(ids, sel[m], lab[m], samples[m])
+                self.last_corruption = (generated, replaced)
+                st.gst, st.xs, st.tu, st.t, st.mt, st.rt, st.t2 = gst, xs, tu, t, mt, rt, t2
+                st.logits, st.lab, st.w, st.sel = logits, lab, w, sel64
+                d_ids, y_all = generated, replaced.view(-1)
+            else:
+                err = target
+                mask = torch.arange(N)[None, :] < torch.tensor(yl)[:, None]
+                assert bool(((err == 0) | (err == 1))[mask].all()), "error_labels: 0 / 1 at every position n < ylens[b]"
+                d_ids = ids
+                y_all = err.clamp(min=0).to(torch.float32).view(-1).pin_memory().to(dev, non_blocking=True)
+                loss_gen = counters = None
+            # ---- discriminator: encoder, dense + GELU, binary head on the rows n < ylens[b]
+            x, dst = self._encode(d_ids, klens, B, N, p_h, p_att, keep, self._disc)
+            act, n_act = self._active_rows(yl, B, N, dev)
+            xa, ya = (x, y_all) if act is None else (x.index_select(0, act), y_all.index_select(0, act))
+            wa = torch.full((n_act,), 1.0 / n_act, device=dev, dtype=torch.float32)
+            dp = D + "discriminator_predictions."
+            hu = torch.empty_like(xa) if keep else None
+            hh = ops.gemm_nt(xa, A.w(dp + "dense.weight"), bias=A.p(dp + "dense.bias"), act=ACT_GELU, pre_out=hu)
+            z, lrows, _ = ops.bce_head_fwd(hh, A.w(dp + "dense_prediction.weight").view(-1), A.p(dp + "dense_prediction.bias"), ya, wa)
+            loss_disc = lrows.sum()
+            loss = loss_disc if mode == "disc" else loss_gen + self.electra_disc_weight * loss_disc
+        self._aux = {"loss_gen": loss_gen, "loss_disc": loss_disc, "counters": counters}
+        if not keep:
+            return loss, None
+        self._pe_stale = True
+        st.dst, st.xa, st.ya, st.wa, st.hu, st.hh, st.z, st.act = dst, xa, ya, wa, hu, hh, z, act
+        return loss, st
+
+    def _padded_word(self, W):
+        """the generator's word embedding [V, E] with zero rows up to a multiple of 8 (the inner dimension of dz . W): W itself
+        where V already is one, else a copy refreshed here, once per backward"""
+        V, E = W.shape
+        Vp = (V + 7) // 8 * 8
+        if Vp == V:
+            return W
+        buf = self.__dict__.get("_wpad")
+        if buf is None or buf.shape != (Vp, E) or buf.dtype != W.dtype or buf.device != W.device:
+            buf = self.__dict__["_wpad"] = torch.zeros(Vp, E, device=W.device, dtype=W.dtype)
+        ops.strided_copy(W, out=buf[:V])
+        return buf
+
+    def _electra_loss_backward(self, st, g):
+        A = self._arena
+        G, D = self._G, self._D
+        lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
+        with ops.stream_scope(self._split()):
+            g1 = g.to(torch.float32).reshape(1)
+            A.attach_grads()
+            B, N = st.dst.B, st.dst.N
+            dev = g1.device
+            # ---- discriminator
+            dp = D + "discriminator_predictions."
+            wd = 1.0 if st.mode == "disc" else self.electra_disc_weight
+            dhh = ops.bce_head_bwd(st.hh, A.w(dp + "dense_prediction.weight").view(-1), st.z, st.ya, st.wa,
+                                   A.g(dp + "dense_prediction.weight").view(-1), A.g(dp + "dense_prediction.bias"), wd, g1)
+            dxa = lin_bwd(ops.act_bwd(dhh, st.hu, ACT_GELU), st.xa, dp + "dense.weight", dp + "dense.bias")
+            if st.act is not None:
+                dxa = torch.zeros(B * N, self._disc.d, device=dev, dtype=dxa.dtype).index_copy_(0, st.act, dxa)
+            self._backward_stack(st.dst, dxa, self._disc)
+            if st.mode == "disc":
+                # the generator was not run: its .grad is None, as in the reference (AdamW then leaves it bit-identical).  A
+                # discriminator-only step therefore does not share an accumulation window with a generator step.
+                for n, p in zip(A.names, A.params):
+                    if n.startswith(G):
+                        p.grad = None
+                return
+            # ---- generator: vocabulary head (tied to its word embedding), transform, the labelled rows scattered back
+            gp, word = G + "generator_predictions.", G + "electra.embeddings.word_embeddings.weight"
+            M, V = st.logits.shape
+            Wp = self._padded_word(A.w(word))
+            dzp = torch.zeros(M, Wp.shape[0], device=dev, dtype=st.logits.dtype)     # (the padding columns stay 0)
+            dz = dzp[:, :V]
+            ops.lsm_loss(st.logits, st.lab, st.w, 0.0, True, 1.0, g1, grad=dz)
+            ops.gemm_tn(dz, st.t2, out=A.g(word), accumulate=True, colsum=A.g(G + "generator_lm_head.bias"))
+            dt2 = ops.gemm_nn(dzp, Wp)
+            dpre = ops.act_bwd(ln_bwd(dt2, st.t, gp + "LayerNorm", st.mt, st.rt), st.tu, ACT_GELU)
+            dxs = lin_bwd(dpre, st.xs, gp + "dense.weight", gp + "dense.bias")
+            dx = torch.zeros(B * N, self._gen.d, device=dev, dtype=dxs.dtype).index_copy_(0, st.sel, dxs)
+            self._backward_stack(st.gst, dx, self._gen)
+
+    def replaced_probs(self, ys, ylens):
+        """ELECTRA only.  sigmoid of the discriminator's logit at every position of `ys` as given (padding included; keys at
+        n >= ylens[b] are masked) -> float64 [B, N] on the HOST: one encoder pass, ONE device-to-host copy"""
+        assert self.electra, "replaced_probs is ELECTRA's discriminator (lm_type 'electra' / 'electra-disc')"
+        ys, _ = self._inputs(ys, None)
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        B, N = ys.shape
+        assert len(yl) == B and 1 <= min(yl) and max(yl) <= N, "ylens: one length in 1..N per row"
+        A = self._prepare()
+        dev = A.flat.device
+        D = self._D + "discriminator_predictions."
+        with torch.no_grad(), ops.stream_scope(self._split()):
+            x, _ = self._encode(h2d_i32(ys, dev), h2d_i32(yl, dev), B, N, 0.0, 0.0, False, self._disc)
+            hh = ops.gemm_nt(x, A.w(D + "dense.weight"), bias=A.p(D + "dense.bias"), act=ACT_GELU)
+            _, _, sig = ops.bce_head_fwd(hh, A.w(D + "dense_prediction.weight").view(-1), A.p(D + "dense_prediction.bias"),
+                                         want_sigmoid=True)
+        return sig.cpu().to(torch.float64).view(B, N)
+
+    def _electra_score(self, ys, ylens):
+        probs = self.replaced_probs(ys, ylens)
+        if probs.shape[0] == 1:
+            return [float(probs[0].sum())]
+        return [-float(probs[b, : int(n)].sum()) for b, n in enumerate(ylens)]
+
+
+class _ElectraLossFn(torch.autograd.Function):
+    """ELECTRA's training loss (mode "both": generator + weighted discriminator; "disc": the discriminator alone) as ONE autograd node"""
+
+    @staticmethod
+    def forward(ctx, lm, mode, ys, yl, target, *params):
+        keep = any(ctx.needs_input_grad)
+        loss, st = lm._electra_loss_forward(mode, ys, yl, target, keep)
+        ctx.lm, ctx.st = lm, st
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.lm._electra_loss_backward(ctx.st, g)
+        ctx.st = None
+        return (None, None, None, None, None) + (None,) * len(ctx.lm._arena.params)
 
 
 class _LMLossFn(torch.autograd.Function):

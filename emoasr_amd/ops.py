@@ -774,11 +774,15 @@ def embed_bwd(ids, dout, scale, dtable, drop_p=0.0, seed=0):
              _p(_chk(dtable, torch.float32)), _stream())
 
 
-def lsm_loss(logits, labels, w, lsm_prob, want_grad=False, gscale=1.0, gscale_dev=None):
-    """logits [M,V]; labels int32 [M]; w f32 [M] row weights (0 = padded) -> (loss_rows f32 [M], grad | None)"""
+def lsm_loss(logits, labels, w, lsm_prob, want_grad=False, gscale=1.0, gscale_dev=None, grad=None):
+    """logits [M,V]; labels int32 [M]; w f32 [M] row weights (0 = padded) -> (loss_rows f32 [M], grad | None).
+    grad: a [M,V] buffer of the logits' dtype to write the gradient into (rows may be padded: last dim contiguous)"""
     M, V, ld = _rows(_chk(logits))
     loss = torch.empty(M, device=logits.device, dtype=torch.float32)
-    grad = torch.empty_like(logits) if want_grad else None
+    if grad is not None:
+        assert want_grad and _chk(grad, logits.dtype).shape == logits.shape and grad.stride(1) == 1
+    else:
+        grad = torch.empty_like(logits) if want_grad else None
     lib.call("emoasr_lsm_loss", dt(logits), M, V, _p(logits), ld, _p(labels), _p(w), lsm_prob, _p(loss), gscale,
              _p(gscale_dev), _p(grad), 0 if grad is None else grad.stride(0), _stream())
     return loss, grad
@@ -805,6 +809,78 @@ def mlm_expand(ys, ylens, row0, r_begin, r_count, Np, mask_id, pad_id=0, total=N
     lib.call("emoasr_mlm_expand", B, N, Np, _p(ys), _p(ylens), _p(row0), r_begin, r_count, mask_id, pad_id, _p(ids), _p(klens),
              _p(idx), _p(labels), _stream())
     return ids[:r_count], klens[:r_count], idx[:r_count], labels[:r_count]
+
+
+# ---- ELECTRA ---------------------------------------------------------------------------------
+def sample_rows(logits, labels, w, seed, row0=0, want_lse=False):
+    """logits [M,V] (f32 / bf16, last dim contiguous); labels int32 [M]; w f32 [M] -> (loss rows f32 [M] = -w * log p(label),
+    samples int32 [M] ~ softmax(logits[m]), lse f32 [M] | None).  sample[m] = argmax_v (logits[m,v].float() + gumbel_noise(...)[m,v])
+    with ties to the lowest column: a function of (seed, row0 + m, v) only, so chunks of rows (row0) draw what one call draws."""
+    M, V, ld = _rows(_chk(logits))
+    assert logits.dim() == 2 and V >= 2 and labels.numel() == M and w.numel() == M and row0 >= 0
+    _chk(labels, torch.int32), _chk(w, torch.float32)
+    loss = torch.empty(M, device=logits.device, dtype=torch.float32)
+    sample = torch.empty(M, device=logits.device, dtype=torch.int32)
+    lse = torch.empty(M, device=logits.device, dtype=torch.float32) if want_lse else None
+    lib.call("emoasr_sample_rows", _DT[logits.dtype], M, V, _p(logits), ld, _p(labels), _p(w), int(seed) & (2 ** 64 - 1), int(row0),
+             _p(loss), _p(lse), _p(sample), _stream())
+    return loss, sample, lse
+
+
+def gumbel_noise(M, V, seed, row0=0, device="cuda"):
+    """the Gumbel(0, 1) variates sample_rows adds to an [M, V] block of logits -> f32 [M, V]"""
+    out = torch.empty(M, V, device=device, dtype=torch.float32)
+    lib.call("emoasr_gumbel_noise", M, V, int(seed) & (2 ** 64 - 1), int(row0), _p(out), V, _stream())
+    return out
+
+
+def electra_corrupt(ids, sel, labels, samples, out=None):
+    """ids int32 [B*N] (any shape, contiguous); sel / labels / samples int32 [M]: the flat masked rows, the tokens the masks hide and
+    the generator's samples -> (generated int32 like ids, replaced f32 0/1 like ids, counters int32 [2] = (replaced, masked)).
+    out: that tuple of buffers to write into (only their first B*N / 2 entries are written)"""
+    BN, M = ids.numel(), sel.numel()
+    assert _chk(ids, torch.int32).is_contiguous() and labels.numel() == M and samples.numel() == M and M <= BN
+    for t in (sel, labels, samples):
+        assert _chk(t, torch.int32).is_contiguous()
+    if out is None:
+        out = (torch.empty_like(ids), torch.empty(ids.shape, device=ids.device, dtype=torch.float32),
+               torch.empty(2, device=ids.device, dtype=torch.int32))
+    generated, replaced, counters = out
+    assert _chk(generated, torch.int32).is_contiguous() and _chk(replaced, torch.float32).is_contiguous()
+    assert generated.numel() >= BN and replaced.numel() >= BN and _chk(counters, torch.int32).numel() >= 2
+    lib.call("emoasr_electra_corrupt", BN, M, _p(ids), _p(sel), _p(labels), _p(samples), _p(generated), _p(replaced), _p(counters),
+             _stream())
+    return generated, replaced, counters
+
+
+def bce_head_fwd(h, wp, bp, y=None, w=None, want_sigmoid=False):
+    """h [M,H]; wp [H] or [1,H] (h's dtype); bp f32 [1]; y, w f32 [M] (both or neither)
+    -> (z f32 [M] = h . wp + bp, loss rows f32 [M] = w * BCEWithLogits(z, y) | None, sigmoid(z) f32 [M] | None)"""
+    M, H, ldh = _rows(_chk(h))
+    assert h.dim() == 2 and _chk(wp, h.dtype).numel() == H and wp.is_contiguous() and _chk(bp, torch.float32).numel() == 1
+    assert (y is None) == (w is None)
+    z = torch.empty(M, device=h.device, dtype=torch.float32)
+    loss = sig = None
+    if y is not None:
+        assert _chk(y, torch.float32).numel() == M and _chk(w, torch.float32).numel() == M and y.is_contiguous() and w.is_contiguous()
+        loss = torch.empty(M, device=h.device, dtype=torch.float32)
+    if want_sigmoid:
+        sig = torch.empty(M, device=h.device, dtype=torch.float32)
+    lib.call("emoasr_bce_head_fwd", _DT[h.dtype], M, H, _p(h), ldh, _p(wp), _p(bp), _p(y), _p(w), _p(z), _p(loss), _p(sig), _stream())
+    return z, loss, sig
+
+
+def bce_head_bwd(h, wp, z, y, w, dwp, dbp, gscale=1.0, gscale_dev=None):
+    """-> dh [M,H] = dz wp with dz = w * (sigmoid(z) - y) * gscale * [gscale_dev]; dwp f32 [H] += sum_m dz h, dbp f32 [1] += sum_m dz"""
+    M, H, ldh = _rows(_chk(h))
+    assert _chk(wp, h.dtype).numel() == H and _chk(dwp, torch.float32).numel() == H and _chk(dbp, torch.float32).numel() == 1
+    assert dwp.is_contiguous() and wp.is_contiguous()
+    for t in (z, y, w):
+        assert _chk(t, torch.float32).numel() == M and t.is_contiguous()
+    dh = torch.empty(M, H, device=h.device, dtype=h.dtype)
+    lib.call("emoasr_bce_head_bwd", _DT[h.dtype], M, H, _p(h), ldh, _p(wp), _p(z), _p(y), _p(w), gscale, _p(gscale_dev), _p(dh), H,
+             _p(dwp), _p(dbp), _stream())
+    return dh
 
 
 # ---- knowledge distillation ---------------------------------------------------------------

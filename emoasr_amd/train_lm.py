@@ -1,6 +1,6 @@
 """LM training and evaluation drivers with the reference's semantics (lm/train_lm.py:40-130, lm/test_ppl.py:32-74), for the
-Transformer LM (modeling/lm.py), the RNN LM (lm_type="rnn", modeling/rnnlm.py) and the BERT masked LM (lm_type="bert",
-modeling/lm.py) alike -- all are `LM(params)` and take `(ys_in, ylens, labels)`; the causal ones expose `token_logprobs` for the
+Transformer LM (modeling/lm.py), the RNN LM (lm_type="rnn", modeling/rnnlm.py), the BERT masked LM (lm_type="bert",
+modeling/lm.py) and ELECTRA (lm_type="electra" / "electra-disc", modeling/lm.py) alike -- all are `LM(params)` and take `(ys_in, ylens, labels)`; the causal ones expose `token_logprobs` for the
 perplexity (ppl_lm), the masked one `masked_logprobs` (ppl_masked_lm):
 
     model = LM(params, compute_dtype=...).cuda().train()
@@ -26,9 +26,15 @@ from . import checkpoint
 
 def train_step(model, optimizer, data, params, device, no_grad=False, empty_cache=False, sync=True):
     """One micro-batch (lm/train_lm.py:40-84): forward, loss / accum_grad, backward; unless `no_grad` (still accumulating): clip,
-    skip on a NaN gradient norm, step, zero_grad.  -> loss_dict of floats / accum_grad (sync=False: 0-dim device tensors)"""
+    skip on a NaN gradient norm, step, zero_grad.  -> loss_dict of floats / accum_grad (sync=False: 0-dim device tensors); ELECTRA's
+    per-utterance counts `num_replaced` / `num_masked` go through the same division, so logging stays one code path.
+    A batch that carries `error_labels` (LMDataset for lm_type="electra-disc") goes to model.forward_disc, the discriminator-only
+    step; the reference's driver never calls forward_disc (its electra-disc batches have no `labels` and fail there)."""
     from .optimizers import Adam as HipAdam
-    loss, loss_dict = model(data["ys_in"], data["ylens"], data["labels"], data.get("ps"), data.get("plens"))
+    if "error_labels" in data:
+        loss, loss_dict = model.forward_disc(data["ys_in"], data["ylens"], data["error_labels"])
+    else:
+        loss, loss_dict = model(data["ys_in"], data["ylens"], data["labels"], data.get("ps"), data.get("plens"))
     accum = params.accum_grad
     loss_dict = {k: (v.item() / accum if sync else v.detach() / accum) for k, v in loss_dict.items()}
     (loss / accum).backward()

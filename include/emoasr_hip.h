@@ -680,6 +680,31 @@ int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, int slots, 
 int emoasr_mlm_expand(int B, int N, int Np, const int* ys, const int* ylens, const int* row0, int r_begin, int r_count,
                       int mask_id, int pad_id, int* ids, int* klens, int* idx, int* labels, void* stream);
 
+/* ---- ELECTRA (lm/modeling/electra.py:20-132): generator sampling, corruption, the discriminator's binary head ----
+ * emoasr_sample_rows: logits [M,V] (row stride ld >= V, any V >= 2), one 256-thread block per row, ONE pass over the row:
+ *   lse[m] (may be NULL) = log sum_v exp z[m,v];  loss[m] = -w[m] * (z[m,labels[m]] - lse[m]) (0 for w[m] == 0);
+ *   sample[m] = argmax_v (f32(z[m,v]) + g(seed, row0 + m, v)), ties to the lowest column: a draw from softmax(z[m]).
+ *   g = -log(-log(u)), u = (k + 0.5) * 2^-24, k = the 24-bit counter hash of (seed, (row0 + m) * V + v) -- a function of the seed
+ *   and the element alone, so a caller that walks M in chunks (row0) draws the same samples.
+ * emoasr_gumbel_noise: out[m,v] (f32, row stride ldo) = that g, from the same device function (tests; not on the training path). */
+int emoasr_sample_rows(int dtype, int M, int V, const void* logits, long ld, const int* labels, const float* w, uint64_t seed,
+                       long row0, float* loss, float* lse, int* sample, void* stream);
+int emoasr_gumbel_noise(int M, int V, uint64_t seed, long row0, float* out, long ldo, void* stream);
+/* generated[BN] = ids with samples[m] at the flat rows sel[m] (m < M, each row named once); replaced[BN] (f32 0 / 1) =
+ * generated != (ids with labels[m] at sel[m]);  counters[0] = number replaced, counters[1] = number masked (= M).  M == 0 copies the
+ * ids and zeroes the rest.  Nothing is written outside [0, BN). */
+int emoasr_electra_corrupt(int BN, int M, const int* ids, const int* sel, const int* labels, const int* samples, int* generated,
+                           float* replaced, int* counters, void* stream);
+/* discriminator_predictions.dense_prediction + BCEWithLogits rows over h [M,H] (the GELU output of .dense):
+ *   z[m] = h[m,:] . wp + bp[0];  loss[m] (may be NULL) = w[m] * (max(z,0) - z*y[m] + log1p(exp(-|z|)));  sig[m] (may be NULL) = sigmoid(z)
+ * backward: dz = w * (sigmoid(z) - y) * gscale * [gscale_dev];  dh[m,:] = dz[m] * wp;  dwp += sum_m dz[m] h[m,:];  dbp += sum_m dz[m]
+ * (f32 atomics into the gradient slots, one per column and block of 64 rows). */
+int emoasr_bce_head_fwd(int dtype, int M, int H, const void* h, long ldh, const void* wp, const float* bp, const float* y,
+                        const float* w, float* z, float* loss, float* sig, void* stream);
+int emoasr_bce_head_bwd(int dtype, int M, int H, const void* h, long ldh, const void* wp, const float* z, const float* y,
+                        const float* w, float gscale, const float* gscale_dev, void* dh, long lddh, float* dwp, float* dbp,
+                        void* stream);
+
 /* ---- one Conformer encoder layer, forward, sequenced on the host in C++ ---------
  * ConformerEncoderLayer.forward (asr/modeling/conformer.py:146-225) with relative-position attention:
  *   x += 0.5 * drop(FFN_macaron(LN(x)));  x += drop(RelMHA(LN(x)));  x += drop(ConvModule(LN(x)));

@@ -1,6 +1,6 @@
 """Transformer-LM training throughput and the vocabulary head A/B (fused = no [rows, V] logits, against materialised).
 
-    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert]
+    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert|electra]
 
 Prints one JSON line.  --leg transformer (the default):
   train_tokens_per_s   real (unpadded) tokens per second of a full training step (forward, backward, clip + AdamW) of the 12-layer
@@ -16,6 +16,15 @@ Prints one JSON line.  --leg transformer (the default):
   mlm_step             real tokens per second of a full masked-LM training step at mask_proportion 0.15 and 0.3 with transform +
                        vocabulary head on the labelled rows only (LM.head_at_labels) against the head on all rows with row weights,
                        as alternating legs in ONE process -- the medians and every pair's ratio.
+
+--leg electra: ELECTRA (lm_type="electra") at the size of the reference's recipe (12 + 12 layers, d = 256, V = 9 798, batch 90,
+num_to_mask 35, electra_disc_weight 50), bf16:
+  step                 a full training step (train_lm.train_step: generator, sampling, corruption, discriminator, both backwards,
+                       clip + AdamW) with the sampling kernels (LM.sample_path = "hip": sample_rows + electra_corrupt) against the
+                       comparator (LM.sample_path = "torch": softmax + torch.multinomial + indexed assignment, all on the device),
+                       as alternating legs of --steps steps after --warmup in ONE process, --pairs pairs: median, min, max and every
+                       pair's ratio;
+  score                LM.score of a 100-hypothesis list: host time from the call to the synchronised result, median and min-max.
 """
 import argparse
 import json
@@ -116,6 +125,70 @@ def bert_leg(args):
     print(json.dumps(out))
 
 
+def electra_batch(batch, vocab, mask_id, num_to_mask, max_len, seed=0):
+    """sequences of concatenated utterances (median ~120 tokens, 40 .. max_len), exactly num_to_mask positions of every row masked"""
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.exp(torch.randn(batch, generator=g) * 0.4 + 4.8).clamp(max(40, num_to_mask), max_len).to(torch.int64).tolist()
+    N = max(lens)
+    ys = torch.full((batch, N), 2, dtype=torch.int64)
+    for b, n in enumerate(lens):
+        ys[b, :n] = torch.randint(3, mask_id, (n,), generator=g)
+    ys_in, labels = ys.clone(), torch.full((batch, N), -100, dtype=torch.int64)
+    for b, n in enumerate(lens):
+        for j in torch.randperm(n, generator=g)[:num_to_mask].tolist():
+            labels[b, j], ys_in[b, j] = ys[b, j], mask_id
+    return {"ys": ys, "ys_in": ys_in, "ylens": torch.tensor(lens), "labels": labels}, sum(lens)
+
+
+def electra_leg(args):
+    import time
+    from emoasr_amd.modeling.lm import LM
+    from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
+    from emoasr_amd.train_lm import train_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    V, batch, num_to_mask = 9798, 90, 35
+    size = dict(embedding_size=256, hidden_size=256, intermediate_size=1024, num_attention_heads=4, num_layers=12)
+    cfg = dict(lm_type="electra", vocab_size=V, max_seq_len=256, mask_id=V - 1, electra_disc_weight=50,
+               **{f"{s}_{k}": v for s in ("gen", "disc") for k, v in size.items()})
+    params = SimpleNamespace(**dict(cfg, learning_rate=1e-4, lr_schedule_type="lindecay", num_warmup_steps=100, weight_decay=0.01,
+                                    clip_grad_norm=5.0, accum_grad=1, log_step=10 ** 9))
+    lm = LM(params, compute_dtype=torch.bfloat16).to(dev).train()
+    opt = ScheduledOptimizer(AdamW(get_optimizer_params_nodecay(list(lm.named_parameters()), params.weight_decay), lr=0,
+                                   weight_decay=params.weight_decay), params, num_total_steps=10 ** 6)
+    data, tokens = electra_batch(batch, V, V - 1, num_to_mask, 256)
+    step = lambda: train_step(lm, opt, data, params, dev, sync=False)
+    rec = {"tokens": tokens, "rows_padded": data["ys_in"].numel(), "rows_labelled": int((data["labels"] != -100).sum()),
+           "hip_us": [], "torch_us": []}
+    for _ in range(args.pairs):
+        for path in ("hip", "torch"):
+            lm.sample_path = path
+            timed(step, args.warmup)
+            rec[path + "_us"].append(round(timed(step, args.steps), 1))
+    lm.sample_path = "hip"
+    for path in ("hip", "torch"):
+        us = rec[path + "_us"]
+        rec[path + "_median_us"], rec[path + "_min_max_us"] = statistics.median(us), [min(us), max(us)]
+        rec["tokens_per_s_" + path] = round(tokens / statistics.median(us) * 1e6)
+    rec["pair_ratio_hip_over_torch"] = [round(a / b, 4) for a, b in zip(rec["hip_us"], rec["torch_us"])]
+    out = {"leg": "electra", "batch": batch, "dtype": "bf16", "step": rec}
+    # ---- N-best scoring: one discriminator pass per list
+    hyps, _ = mlm_batch(100, V, V - 1, 0.15, seed=1)
+    lm.eval()
+
+    def run():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lm.score(hyps["ys"], hyps["ylens"])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    run()
+    ms = [run() for _ in range(max(args.pairs, 5))]
+    out["score"] = {"hypotheses": 100, "tokens": int(hyps["ylens"].sum()), "padded_length": int(hyps["ys"].shape[1]),
+                    "median_ms": round(statistics.median(ms), 3), "min_max_ms": [round(min(ms), 3), round(max(ms), 3)]}
+    print(json.dumps(out))
+
+
 def timed(fn, n):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -133,11 +206,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=100)
-    ap.add_argument("--leg", choices=["transformer", "bert"], default="transformer")
+    ap.add_argument("--leg", choices=["transformer", "bert", "electra"], default="transformer")
     ap.add_argument("--token-rows", type=int, nargs="+", default=[16384, 65536, 262144], help="--leg bert: max_token_rows values")
     args = ap.parse_args()
     if args.leg == "bert":
         return bert_leg(args)
+    if args.leg == "electra":
+        return electra_leg(args)
     from emoasr_amd import ops
     from emoasr_amd.modeling.lm import LM
     from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
