@@ -329,3 +329,157 @@ class LMDataset:
         if errs is not None:
             ret["error_labels"] = pad_sequence(errs, batch_first=True, padding_value=-100)
         return ret
+
+
+# ---- phone-to-word data (lm/datasets.py:123-369, lm/text_augment.py) --------------------------------------------------------------
+def create_masked_lm_label_insert(y, mask_id, num_to_mask=-1, mask_proportion=-1, random_num_to_mask=False, insert_poisson_lam=-1,
+                                  pad_id=0, eos_id=2):
+    """lm/datasets.py:344-369: create_masked_lm_label, then a Poisson(insert_poisson_lam) number of extra <mask> tokens after every
+    position (numpy's global generator, one draw of len(y) values after the `random` calls of the masking); an inserted mask's
+    label is pad_id.  -> (y_masked_insert, labels int64)"""
+    y_masked, label = create_masked_lm_label(y, mask_id, num_to_mask, mask_proportion, random_num_to_mask, eos_id)
+    if not insert_poisson_lam > 0:     # (the reference returns unbound names here; its dataset never calls it so)
+        return y_masked, label
+    num_inserts = np.random.poisson(insert_poisson_lam, len(y_masked))
+    n = len(y_masked) + int(sum(num_inserts))
+    y_ins = torch.full([n], mask_id, dtype=torch.int64)
+    label_ins = torch.full([n], pad_id, dtype=torch.int64)
+    index = 0
+    for tok, lab, k in zip(y_masked, label, num_inserts):
+        y_ins[index], label_ins[index] = tok, lab
+        index += 1 + int(k)
+    return y_ins, label_ins
+
+
+class TextAugment:
+    """lm/text_augment.py:12-55 on a phone sequence: up to int(len * textaug_max_mask_prob) positions become phone_mask_id, then up
+    to int(len * textaug_max_replace_prob) positions get a random phone; <eos> positions are never touched.  The `random` calls
+    come in the reference's order (randint, sample; randint, sample, choices)."""
+
+    def __init__(self, params):
+        self.max_mask_prob = params.textaug_max_mask_prob
+        self.max_replace_prob = params.textaug_max_replace_prob
+        self.phone_vocab_size = params.src_vocab_size
+        self.eos_id = params.phone_eos_id
+        self.mask_id = params.phone_mask_id
+
+    def __call__(self, x):
+        return self._text_replace(self._text_mask(x))
+
+    def _text_mask(self, x):
+        x_masked = x.clone()
+        if self.max_mask_prob <= 0:
+            return x_masked
+        num_to_mask = random.randint(0, int(len(x) * self.max_mask_prob))
+        cands = [j for j in range(len(x)) if x[j] != self.eos_id]
+        x_masked[random.sample(cands, min(len(cands), num_to_mask))] = self.mask_id
+        return x_masked
+
+    def _text_replace(self, x):
+        x_replaced = x.clone()
+        if self.max_replace_prob <= 0:
+            return x_replaced
+        num_to_replace = random.randint(0, int(len(x) * self.max_replace_prob))
+        cands = [j for j in range(len(x)) if x[j] != self.eos_id]
+        indices = random.sample(cands, min(len(cands), num_to_replace))
+        vocab = [j for j in range(self.phone_vocab_size) if j != self.eos_id]
+        # (more replacements asked for than candidates: the shapes differ and the assignment fails, as in the reference)
+        x_replaced[indices] = torch.tensor(random.choices(vocab, k=num_to_replace), dtype=torch.long)
+        return x_replaced
+
+
+class P2WDataset:
+    """lm/datasets.py:123-243: a TSV with columns utt_id / token_id / phone_token_id (and ylen / plen with params.bucket_shuffle).
+    Items: (utt_id, p int64, plen, y_in int64, ylen, label | None).  phase "train": the phones go through TextAugment when
+    params.text_augment; "pbert" masks the words (create_masked_lm_label, or create_masked_lm_label_insert with
+    params.mask_insert_poisson_lam > 0); "pctc" has y_in = y and label = p, as the reference does.  Any other phase: no label."""
+
+    def __init__(self, params, data_path, phase="train", size=-1):
+        if params.lm_type not in ("pbert", "pctc"):
+            raise NotImplementedError(f"emoasr_amd: P2WDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
+        columns = ["utt_id", "token_id", "phone_token_id"] + (["ylen", "plen"] if getattr(params, "bucket_shuffle", False) else [])
+        data = _read_table(data_path)[columns]
+        n = len(data)
+        data = data.dropna().reset_index(drop=True)
+        if len(data) != n:
+            logging.warning(f"nan value in dataset is removed: {n:d} -> {len(data):d}")
+        self.lm_type = params.lm_type
+        self.add_sos_eos = params.add_sos_eos
+        self.eos_id, self.phone_eos_id = params.eos_id, params.phone_eos_id
+        self.phase = phase
+        self.data = data[:size] if size > 0 else data
+        self.textaug = TextAugment(params) if phase == "train" and params.text_augment else None
+        if self.lm_type == "pbert":
+            self.mask_id = params.mask_id
+            assert hasattr(params, "num_to_mask") ^ hasattr(params, "mask_proportion")     # (lm/datasets.py:162)
+            self.num_to_mask = getattr(params, "num_to_mask", -1)
+            self.mask_proportion = getattr(params, "mask_proportion", -1)
+            self.random_num_to_mask = params.random_num_to_mask
+            self.mask_insert_poisson_lam = getattr(params, "mask_insert_poisson_lam", -1)
+            self.pad_id = getattr(params, "pad_id", 0)
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, idx):
+        row = self.data.loc[idx]
+        ids = [int(t) for t in str(row["token_id"]).split()]
+        if self.add_sos_eos:
+            ids = [self.eos_id] + ids + [self.eos_id]
+        y = torch.tensor(ids, dtype=torch.long)
+        p = torch.tensor([int(t) for t in str(row["phone_token_id"]).split()], dtype=torch.long)
+        if self.textaug is not None:
+            p = self.textaug(p)
+        if self.phase == "train" and self.lm_type == "pbert":
+            if self.mask_insert_poisson_lam > 0:
+                y_in, label = create_masked_lm_label_insert(y, self.mask_id, self.num_to_mask, self.mask_proportion,
+                                                            self.random_num_to_mask, self.mask_insert_poisson_lam, self.pad_id,
+                                                            self.eos_id)
+            else:
+                y_in, label = create_masked_lm_label(y, self.mask_id, self.num_to_mask, self.mask_proportion,
+                                                     self.random_num_to_mask, self.eos_id)
+        elif self.phase == "train":
+            y_in, label = y, p
+        else:
+            y_in, label = y, None
+        return row["utt_id"], p, p.size(0), y_in, y_in.size(0), label
+
+    def collate_fn(self, batch):
+        """dict with the reference's keys: ps padded with the phone <eos>, plens, ys_in padded with <eos>, ylens, labels (-100)"""
+        from torch.nn.utils.rnn import pad_sequence
+        utt_ids, ps, plens, ys_in, ylens, labels = zip(*batch)
+        ret = {"utt_ids": list(utt_ids), "ps": pad_sequence(ps, batch_first=True, padding_value=self.phone_eos_id),
+               "plens": torch.tensor(plens), "ys_in": pad_sequence(ys_in, batch_first=True, padding_value=self.eos_id),
+               "ylens": torch.tensor(ylens)}
+        if labels[0] is not None:
+            ret["labels"] = pad_sequence(labels, batch_first=True, padding_value=-100)
+        return ret
+
+
+class LMBatchSampler:
+    """lm/datasets.py:247-316: consecutive utterances until sum(plen) > max_plens_batch (P2W data; absent: no phone limit),
+    sum(ylen) > max_ylens_batch or batch_size utterances; the batches are shuffled each epoch with the `random` module"""
+
+    def __init__(self, dataset, params, min_batch_size=1):
+        ylens = dataset.data["ylen"].values
+        plens = dataset.data["plen"].values if "plen" in dataset.data else np.zeros(len(ylens), dtype=np.int64)
+        max_plens = getattr(params, "max_plens_batch", 1)     # (without phones every plen counts 0)
+        assert plens.max(initial=0) <= max_plens and ylens.max(initial=0) <= params.max_ylens_batch
+        self.indices_batches, i, n = [], 0, len(ylens)
+        while i < n:
+            cur, sp, sy = [], 0, 0
+            while i < n and not (sp + plens[i] > max_plens or sy + ylens[i] > params.max_ylens_batch
+                                 or len(cur) + 1 > params.batch_size):
+                cur.append(i)
+                sp, sy, i = sp + plens[i], sy + ylens[i], i + 1
+            if len(cur) < min_batch_size:
+                logging.warning(f"{len(cur)} utterances are skipped because of they are smaller than min_batch_size")
+            else:
+                self.indices_batches.append(cur)
+
+    def __iter__(self):
+        random.shuffle(self.indices_batches)
+        yield from self.indices_batches
+
+    def __len__(self):
+        return len(self.indices_batches)

@@ -257,6 +257,8 @@ class CTCEngine(_DecoderMixinPlaceholder):
         # bidirectional LSTM stack (encoders/rnn.py; _RNNEncMixin below) in place of the Transformer / Conformer layers
         self.rnn_enc = cfg.encoder_type == "rnn"
         self.rel = _cfg(cfg, "pos_encode_type", "abs") == "rel"
+        # nn.Embedding front-end over token ids (encoders/transformer.py:35-36,87-89: the phone encoder of lm/modeling/p2w.py)
+        self.embed_in = _cfg(cfg, "input_layer", "conv2d") == "embed"
         # intermediate branch after layer `inter_layer` (encoders/transformer.py:75-82); 0 = none
         inter_on = (_cfg(cfg, "mtl_inter_ctc_weight", 0) or 0) > 0 or (_cfg(cfg, "mtl_phone_ctc_weight", 0) or 0) > 0
         self.inter_layer = int(cfg.inter_ctc_layer_id) if inter_on else 0
@@ -370,9 +372,11 @@ class CTCEngine(_DecoderMixinPlaceholder):
         st = _Stash() if stash else None
         p_enc = self.p_enc if training else 0.0
         p_att = self.p_att if training else 0.0
-        B, T, Fd = xs.shape
+        B, T = xs.shape[:2]
         dev = xs.device
         xlens_host = [int(v) for v in xlens_host]
+        if self.embed_in:
+            return self._forward_embed(xs, xlens_host, training, stash, st)
         elens_host = [((v - 1) // 2 - 1) // 2 for v in xlens_host]
         elens = h2d_i32(elens_host, dev)
         x, y1, y2, w2r, wlr = self._frontend_fwd(xs)
@@ -426,6 +430,30 @@ class CTCEngine(_DecoderMixinPlaceholder):
         if st is not None:
             st.x_final, st.fin_mean, st.fin_rstd = x, mean, rstd
         return eouts.view(B, T2, d), elens_host, elens, st
+
+    def _forward_embed(self, ids, xlens_host, training, stash, st):
+        """the absolute-position Transformer stack over token ids int32 [B,P] (input_layer "embed": x = embed(ids) * sqrt(d) + pe,
+        dropout -- the reference's PositionalEncoder -- and elens = xlens)"""
+        A, d = self.arena, self.d
+        B, T = ids.shape
+        dev = ids.device
+        M = B * T
+        p_enc = self.p_enc if training else 0.0
+        p_att = self.p_att if training else 0.0
+        elens = h2d_i32(xlens_host, dev)
+        s_pe = self._seed(1)
+        x = ops.embed_fwd(ids, A.w("encoder.embed.weight"), self._pos_table(T, dev), math.sqrt(d), p_enc, s_pe).view(M, d)
+        if st is not None:
+            st.ids, st.B, st.T2, st.M, st.elens, st.s_pe, st.p_enc, st.layers = ids, B, T, M, elens, s_pe, p_enc, []
+        for li in range(self.nl):
+            x, ls = self._layer_fwd(li, x, B, T, elens, None, p_enc, p_att, training)
+            if st is not None:
+                st.layers.append(ls)
+        self.eouts_inter = None
+        eouts, mean, rstd = ops.layernorm_fwd(x, A.p("encoder.norm.weight"), A.p("encoder.norm.bias"), 1e-12, stash)
+        if st is not None:
+            st.x_final, st.fin_mean, st.fin_rstd = x, mean, rstd
+        return eouts.view(B, T, d), xlens_host, elens, st
 
     def _frontend_fwd(self, xs):
         """Conv2d subsampling (encoders/conv.py:20-28, channels-last) of xs f32 [B,T,F] -> (x [B*T',d] compute dtype, and the
@@ -1122,6 +1150,9 @@ class CTCEngine(_DecoderMixinPlaceholder):
                 self.grad_hook(self._layer_offset(0))
         ops.layernorm_bwd_finalize(self._ln_deferred)
         # ---- positional scaling, Linear, Conv2d x2 -----------------------------------
+        if self.embed_in:
+            ops.embed_bwd(st.ids, dx, math.sqrt(d), A.g("encoder.embed.weight"), st.p_enc, st.s_pe)
+            return
         dlin = ops.scale_dropout(dx, math.sqrt(d), self.p_enc, st.s_pe)
         self._frontend_bwd(dlin, st)
 
@@ -1191,6 +1222,9 @@ class _DecoderMixin:
         self.norm_len = bool(_cfg(cfg, "loss_normalize_length", False))
         self.norm_batch = bool(_cfg(cfg, "loss_normalize_batch", True))
         self.mtl_ctc = float(_cfg(cfg, "mtl_ctc_weight", 0.0))
+        # the conditional masked LM's head (cmlm_head): the logit-free kernels where their row rule applies (False: always the
+        # materialised logits, the tests' comparator); cmlm_last_head names the branch the last loss took
+        self.cmlm_fused_head, self.cmlm_last_head = True, None
 
     def _abs_table(self, L, device, d):
         key = ("abs", d, str(device))
@@ -1198,12 +1232,14 @@ class _DecoderMixin:
             self._tables[key] = sinusoid(torch.arange(max(L, 512)), d, device)
         return self._tables[key]
 
-    def dec_forward(self, eouts, elens_dev, ys_in, ylens_host, training, keep):
-        """teacher-forced decoder: -> logits [B, L, V] (compute dtype), stash"""
+    def dec_forward(self, eouts, elens_dev, ys_in, ylens_host, training, keep, causal=True, head=True):
+        """teacher-forced decoder: -> logits [B, L, V] (compute dtype), stash.  causal=False is the conditional masked LM
+        (decoders/transformer.py:102-105): every position attends to the keys below ylens (not ylens + 1).  head=False stops before
+        the final LayerNorm: -> hidden rows [B*L, dd], stash (cmlm_head runs the LayerNorm and the vocabulary head on chosen rows)"""
         with self._scope():
-            return self._dec_forward(eouts, elens_dev, ys_in, ylens_host, training, keep)
+            return self._dec_forward(eouts, elens_dev, ys_in, ylens_host, training, keep, causal, head)
 
-    def _dec_forward(self, eouts, elens_dev, ys_in, ylens_host, training, keep):
+    def _dec_forward(self, eouts, elens_dev, ys_in, ylens_host, training, keep, causal=True, head=True):
         A, dd, dh = self.arena, self.dd, self.dh
         self._keep = keep
         B, T, d = eouts.shape
@@ -1212,7 +1248,7 @@ class _DecoderMixin:
         p = self.p_dec if training else 0.0
         p_att = self.p_att if training else 0.0
         ids = h2d_i32(torch.as_tensor(ys_in).contiguous(), dev)
-        kself = h2d_i32([int(y) + 1 for y in ylens_host], dev)
+        kself = h2d_i32([int(y) + (1 if causal else 0) for y in ylens_host], dev)
         s_emb = self._seed(5000)
         x = ops.embed_fwd(ids, A.w("decoder.embed.weight"), self._abs_table(L, dev, dd), math.sqrt(dd), p, s_emb)
         x = x.view(B * L, dd)
@@ -1223,7 +1259,7 @@ class _DecoderMixin:
             name = f"decoder.transformers.{li}"
             site = 5100 + li * 20
             x, s_self = self._attn_fwd(name + ".self_attn", x, B, L, kself, None, name + ".norm1", 1e-12, p, p_att, site,
-                                       training, dims=(dd, dh), causal=True)
+                                       training, dims=(dd, dh), causal=causal)
             # ---- source attention: queries from the decoder, keys/values from the encoder memory
             sa = name + ".src_attn"
             h2, m2, r2 = ops.layernorm_fwd(x, A.p(name + ".norm2.weight"), A.p(name + ".norm2.bias"), 1e-12, keep)
@@ -1238,15 +1274,59 @@ class _DecoderMixin:
             s_src = (x, m2, r2, h2, q2, kv, o2, lse2, s_att, s_out)
             x, s_ff = self._ffn_fwd(name + ".feed_forward", x1, 1.0, ACT_RELU, name + ".norm3", 1e-12, p, site + 8, training)
             layers.append((s_self, s_src, s_ff))
-        y, mean, rstd = ops.layernorm_fwd(x, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, keep)
-        logits = ops.gemm_nt(y, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
         st = None
         if keep:
             st = _Stash()
             st.B, st.L, st.T, st.ids, st.kself, st.elens, st.s_emb = B, L, T, ids, kself, elens_dev, s_emb
-            st.layers, st.x_final, st.mean, st.rstd, st.y, st.mem2 = layers, x, mean, rstd, y, mem2
-            st.p, st.p_att = p, p_att
+            st.layers, st.x_final, st.mem2 = layers, x, mem2
+            st.p, st.p_att, st.causal = p, p_att, causal
+        if not head:
+            return x, st
+        y, mean, rstd = ops.layernorm_fwd(x, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, keep)
+        logits = ops.gemm_nt(y, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+        if keep:
+            st.mean, st.rstd, st.y = mean, rstd, y
         return logits.view(B, L, -1), st
+
+    def cmlm_head(self, x, sel, labels, w, keep, want_logits=False):
+        """MaskedLMLoss (cross-entropy, mean over the labelled positions) of the conditional masked LM on the labelled rows alone:
+        x [B*L, dd] the decoder's last hidden rows, sel int64 [R] the labelled flat rows, labels int32 [R], w f32 [R] (1 / R; one
+        row of weight 0 when nothing is labelled) -> (loss 0-dim f32, head stash, logits of ALL rows [B*L, V] | None)"""
+        with self._scope():
+            A = self.arena
+            xr = x.index_select(0, sel)
+            y, mean, rstd = ops.layernorm_fwd(xr, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, keep)
+            W, bias = A.w("decoder.output.weight"), A.p("decoder.output.bias")
+            if self.cmlm_fused_head and ops.ce_head_ok(y, W):
+                rows, _, ctx = ops.ce_head_fwd(y, W, bias, labels, w)
+                head = ("fused", ctx)
+            else:
+                z = self.head_logits(y.view(1, -1, y.shape[1]), "decoder.output")[0]
+                rows, _ = ops.lsm_loss(z, labels, w, 0.0)
+                head = ("materialised", z)
+            self.cmlm_last_head = head[0]
+            logits = None
+            if want_logits:
+                ya, _, _ = ops.layernorm_fwd(x, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, False)
+                logits = self.head_logits(ya.view(1, -1, ya.shape[1]), "decoder.output")[0]
+            return rows.sum(), (xr, y, mean, rstd, head, sel, labels, w), logits
+
+    def cmlm_head_backward(self, hst, n_rows, gscale_dev):
+        """-> the gradient of the decoder's last hidden rows [n_rows, dd] (zero off the labelled rows); accumulates decoder.norm
+        and decoder.output gradients"""
+        with self._scope():
+            A = self.arena
+            A.attach_grads()
+            xr, y, mean, rstd, (kind, hctx), sel, labels, w = hst
+            wn, bn = "decoder.output.weight", "decoder.output.bias"
+            if kind == "fused":
+                dy = ops.ce_head_bwd(y, A.w(wn), A.p(bn), hctx, A.g(wn), A.g(bn), 1.0, gscale_dev)
+            else:
+                _, dz = ops.lsm_loss(hctx, labels, w, 0.0, True, 1.0, gscale_dev)
+                dy = self.head_backward(y.view(1, -1, y.shape[1]), dz.view(1, -1, dz.shape[1]), "decoder.output")[0]
+            dxr = ops.layernorm_bwd(dy, xr, A.p("decoder.norm.weight"), mean, rstd, None, A.g("decoder.norm.weight"),
+                                    A.g("decoder.norm.bias"))
+            return torch.zeros(n_rows, xr.shape[1], device=dxr.device, dtype=dxr.dtype).index_copy_(0, sel, dxr)
 
     def att_loss(self, logits, ys_out, ylens_host, want_grad=False, gscale_dev=None):
         """LabelSmoothingLoss over t < ylens+1 -> (loss 0-dim f32, dlogits | None)"""
@@ -1282,20 +1362,22 @@ class _DecoderMixin:
         _, grad = ops.soft_ce(z, q, src, labels, w * scale_soft, w * scale_hard, self.lsm, want_grad=True)
         return None, None, grad.view(B, L, V)
 
-    def dec_backward(self, st, dlogits):
-        """-> d_eouts [B,T,d]; accumulates decoder parameter gradients"""
+    def dec_backward(self, st, dlogits, dx=None):
+        """-> d_eouts [B,T,d]; accumulates decoder parameter gradients.  dx: the gradient of the last hidden rows instead of
+        dlogits (the head's own backward has run: cmlm_head_backward)"""
         with self._scope():
-            return self._dec_backward(st, dlogits)
+            return self._dec_backward(st, dlogits, dx)
 
-    def _dec_backward(self, st, dlogits):
+    def _dec_backward(self, st, dlogits, dx=None):
         A, dd, dh = self.arena, self.dd, self.dh
         A.attach_grads()
         B, L, T = st.B, st.L, st.T
         p, p_att = st.p, st.p_att
         d = st.mem2.shape[1]
-        dy = self._lin_bwd(dlogits.reshape(B * L, -1), st.y, "decoder.output.weight", "decoder.output.bias")
-        dx = ops.layernorm_bwd(dy, st.x_final, A.p("decoder.norm.weight"), st.mean, st.rstd, None,
-                               A.g("decoder.norm.weight"), A.g("decoder.norm.bias"))
+        if dx is None:
+            dy = self._lin_bwd(dlogits.reshape(B * L, -1), st.y, "decoder.output.weight", "decoder.output.bias")
+            dx = ops.layernorm_bwd(dy, st.x_final, A.p("decoder.norm.weight"), st.mean, st.rstd, None,
+                                   A.g("decoder.norm.weight"), A.g("decoder.norm.bias"))
         scale = 1.0 / math.sqrt(dd // dh)
         dmem = None
         for li in reversed(range(self.dnl)):
@@ -1328,7 +1410,7 @@ class _DecoderMixin:
             dx = ops.layernorm_bwd(dh2, x, A.p(name + ".norm2.weight"), m2, r2, dx, A.g(name + ".norm2.weight"),
                                    A.g(name + ".norm2.bias"))
             dx = self._attn_bwd(name + ".self_attn", name + ".norm1", s_self, dx, B, L, st.kself, None, dims=(dd, dh),
-                                causal=True, p_res=p, p_att=p_att)
+                                causal=st.causal, p_res=p, p_att=p_att)
         ops.embed_bwd(st.ids, dx, math.sqrt(dd), A.g("decoder.embed.weight"), p, st.s_emb)
         return dmem.view(B, T, d)
 

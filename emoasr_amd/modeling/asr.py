@@ -109,3 +109,12 @@ class ASR(nn.Module):
             eouts, elens, eouts_inter = self.encoder(xs, xlens)
             return self.decoder.decode(eouts, elens, eouts_inter, beam_width, len_weight, lm, lm_weight,
                                        decode_ctc_weight, decode_phone)
+
+    def decode_word_and_phone(self, xs, xlens):
+        """greedy word and phone hypotheses from ONE encoder pass: -> (decode(xs, xlens), decode(xs, xlens, decode_phone=True)).
+        In eval mode the two results equal the two separate calls exactly (the reference runs the encoder twice)."""
+        with torch.no_grad():
+            eouts, elens, eouts_inter = self.encoder(xs, xlens)
+            word = self.decoder.decode(eouts, elens, eouts_inter, 1)
+            phone = self.decoder.decode(eouts, elens, eouts_inter, 1, decode_phone=True)
+        return word, phone

@@ -2,6 +2,7 @@
 
     decoder(eouts, elens, eouts_inter=None, ys=None, ylens=None, ...) -> logits | (loss, loss_dict, logits)
     decoder.decode(eouts, elens, eouts_inter, beam_width, ...) -> (hyps, scores, logits, aligns)
+    decoder.decode(..., decode_phone=True) -> the same through the phone head (greedy only)
     (beam_width <= 1: greedy; > 1: CTC prefix beam search with optional LM fusion, ctc.py:203-344)
 
 With every auxiliary weight at 0 (the L-series configs) the head GEMM, CTC lattice and gradient run as one
@@ -103,8 +104,15 @@ class CTCDecoder(nn.Module):
 
     def decode(self, eouts, elens, eouts_inter=None, beam_width=1, len_weight=0, lm=None, lm_weight=0,
                decode_ctc_weight=0, decode_phone=False):
-        if decode_phone:
-            raise NotImplementedError("emoasr_amd: decode_phone (broken in the reference, test_asr.py:222) is not provided")
+        if decode_phone:      # greedy through the phone head (ctc.py:133-137: on the intermediate layer when hierarchical)
+            if beam_width > 1:
+                raise NotImplementedError("emoasr_amd: decode_phone is greedy only (no phone beam search)")
+            if not self.mtl_phone_ctc_weight > 0:
+                raise ValueError("emoasr_amd: decode_phone needs a phone head (mtl_phone_ctc_weight > 0)")
+            src = eouts_inter if self.hie_mtl_phone else eouts
+            if src is None:
+                raise ValueError("emoasr_amd: decode_phone with hie_mtl_phone needs the encoder's intermediate output")
+            return ctc_greedy_apply(self, src, elens, head="phone_output")
         if beam_width <= 1:
             if lm_weight > 0:
                 logging.warning("greedy decoding: LM is not used")

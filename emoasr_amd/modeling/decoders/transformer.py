@@ -7,15 +7,14 @@
 import torch.nn as nn
 
 from ..blocks import TransformerDecoderLayer
-from ..functions import attn_decoder_apply, attn_decoder_logits
+from ..functions import attn_decoder_apply, attn_decoder_logits, cmlm_decoder_apply
 from .ctc import CTCDecoder
 
 
 class TransformerDecoder(nn.Module):
     def __init__(self, params, cmlm=False):
         super().__init__()
-        if cmlm:
-            raise NotImplementedError("emoasr_amd: conditional masked LM decoding is outside the HIP hot path")
+        self.cmlm = cmlm      # conditional masked LM: bidirectional self-attention, MaskedLMLoss on the labelled positions
         self.vocab_size = params.vocab_size
         self.embed = nn.Embedding(self.vocab_size, params.dec_hidden_size)
         self.dec_num_layers = params.dec_num_layers
@@ -37,6 +36,10 @@ class TransformerDecoder(nn.Module):
                 soft_labels=None, ps=None, plens=None):
         if ys_out is None:
             return attn_decoder_logits(self, eouts, elens, ys_in, ylens)
+        if self.cmlm:
+            want = bool(getattr(self._owner[0], "return_logits", False)) if self._owner else False
+            loss, logits = cmlm_decoder_apply(self, eouts, elens, ylens, ys_in, ys_out, want)
+            return loss, {"loss_att": loss, "loss_total": loss}, logits
         kd = self.kd_weight > 0 and soft_labels is not None  # DistillLoss replaces the label-smoothing loss (:71-79)
         loss, loss_att, loss_ctc, logits, loss_kd = attn_decoder_apply(self, eouts, elens, ys, ylens, ys_in, ys_out,
                                                                        soft_labels if kd else None, self.kd_weight)

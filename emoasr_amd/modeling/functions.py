@@ -45,8 +45,15 @@ class _EncoderFn(torch.autograd.Function):
 
 def encoder_apply(enc, xs, xlens):
     eng = _engine_of(enc)
-    xs = xs.to(torch.float32).contiguous()
     host = _host_list(xlens)
+    embed = getattr(enc, "input_layer", "conv2d") == "embed"
+    if embed:      # token ids [B, P]: they go up as int32 from pinned memory
+        ids = (xs.cpu() if torch.is_tensor(xs) else torch.as_tensor(xs)).to(torch.int64)
+        assert ids.dim() == 2 and 0 <= int(ids.min()) and int(ids.max()) < enc.embed.num_embeddings, "phone id outside the vocabulary"
+        assert len(host) == ids.shape[0] and 1 <= min(host) and max(host) <= ids.shape[1], "plens: one length in [1, P] per row"
+        xs = h2d_i32(ids.contiguous(), enc.embed.weight.device)
+    else:
+        xs = xs.to(torch.float32).contiguous()
     if torch.is_grad_enabled():
         eng.step_count += 1
         eouts, elens_dev, inter = _EncoderFn.apply(eng, enc.training, xs, host, *eng.arena.params)
@@ -54,7 +61,7 @@ def encoder_apply(enc, xs, xlens):
     else:
         eouts, _, elens_dev, _ = eng.forward(xs, host, enc.training, stash=False)
         inter = eng.eouts_inter
-    elens = torch.tensor([((v - 1) // 2 - 1) // 2 for v in host], dtype=torch.int64)
+    elens = torch.tensor(host if embed else [((v - 1) // 2 - 1) // 2 for v in host], dtype=torch.int64)
     if torch.is_tensor(xlens):
         elens = elens.to(xlens.device)
     eouts._emo_elens_dev = elens_dev
@@ -242,9 +249,10 @@ def ctc_loss_apply(dec, eouts, elens, ys, ylens, head="decoder.output"):
                             *eng.arena.params)
 
 
-def ctc_greedy_apply(dec, eouts, elens):
+def ctc_greedy_apply(dec, eouts, elens, head="output"):
+    """greedy CTC decoding through the head `head` of the decoder ("output": words, "phone_output": phones)"""
     eng = _engine_of(dec)
-    logits = eng.head_logits(eouts, getattr(dec, "_prefix", "decoder") + ".output", out_f32=eng.f32_head)
+    logits = eng.head_logits(eouts, getattr(dec, "_prefix", "decoder") + "." + head, out_f32=eng.f32_head)
     best, hyp, hyplen = eng.greedy(logits, _elens_dev(eouts, elens), dec.blank_id)
     B, T = best.shape
     packed = best._base.cpu() if best._base is not None and best._base.numel() == 2 * B * T + B else None   # one D2H per batch
@@ -321,10 +329,55 @@ def attn_decoder_apply(dec, eouts, elens, ys, ylens, ys_in, ys_out, soft_labels=
 def attn_decoder_logits(dec, eouts, elens, ys_in, ylens):
     eng = _engine_of(dec)
     ys_in = ys_in.cpu() if torch.is_tensor(ys_in) else torch.as_tensor(ys_in)
-    ylens_host = _host_list(ylens) if ylens is not None else [ys_in.shape[1] - 1] * ys_in.shape[0]
+    cmlm = getattr(dec, "cmlm", False)
+    ylens_host = _host_list(ylens) if ylens is not None else [ys_in.shape[1] - (0 if cmlm else 1)] * ys_in.shape[0]
     with torch.no_grad():
-        logits, _ = eng.dec_forward(eouts, _elens_dev(eouts, elens), ys_in, ylens_host, dec.training, False)
+        logits, _ = eng.dec_forward(eouts, _elens_dev(eouts, elens), ys_in, ylens_host, dec.training, False, causal=not cmlm)
     return logits
+
+
+class _CMLMDecoderFn(torch.autograd.Function):
+    """the conditional masked LM decoder (decoders/transformer.py:102-105,127-128): bidirectional self-attention over ylens keys,
+    MaskedLMLoss on the labelled rows"""
+
+    @staticmethod
+    def forward(ctx, eng, training, eouts, elens_dev, ys_in, ylens_host, labels, want_logits, *params):
+        x, st = eng.dec_forward(eouts, elens_dev, ys_in, ylens_host, training, True, causal=False, head=False)
+        B, L = ys_in.shape
+        dev = eouts.device
+        valid = labels != -100
+        count = int(valid.sum())
+        # the labelled rows only (no label at all: one row of weight 0, as the BERT LM does)
+        rows_host = valid.reshape(-1).nonzero().view(-1) if count else torch.zeros(1, dtype=torch.int64)
+        lab = h2d_i32(labels.reshape(-1)[rows_host].clamp(min=0), dev)
+        w = torch.full((rows_host.numel(),), 1.0 / count if count else 0.0).pin_memory().to(dev, non_blocking=True)
+        sel = rows_host.pin_memory().to(dev, non_blocking=True)
+        loss, hst, logits = eng.cmlm_head(x, sel, lab, w, True, want_logits)
+        ctx.eng, ctx.st, ctx.hst, ctx.rows = eng, st, hst, B * L
+        logits = logits.view(B, L, -1) if logits is not None else eouts.new_empty(0)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, g, _):
+        eng = ctx.eng
+        dx = eng.cmlm_head_backward(ctx.hst, ctx.rows, g.to(torch.float32).reshape(1))
+        deouts = eng.dec_backward(ctx.st, None, dx=dx)
+        ctx.st = ctx.hst = None
+        return (None, None, deouts, None, None, None, None, None) + (None,) * len(eng.arena.params)
+
+
+def cmlm_decoder_apply(dec, eouts, elens, ylens, ys_in, labels, want_logits=False):
+    """-> (loss, logits [B, L, V] | an empty tensor)"""
+    eng = _engine_of(dec)
+    ylens_host = _host_list(ylens)
+    L = max(ylens_host)
+    ys_in = (ys_in.cpu() if torch.is_tensor(ys_in) else torch.as_tensor(ys_in))[:, :L].to(torch.int64).contiguous()
+    labels = (labels.cpu() if torch.is_tensor(labels) else torch.as_tensor(labels))[:, :L].to(torch.int64).contiguous()
+    assert labels.shape == ys_in.shape and int(labels.max()) < dec.vocab_size, "labels: [B, L] ids below vocab_size or -100"
+    assert 0 <= int(ys_in.min()) and int(ys_in.max()) < dec.vocab_size, "token id outside the vocabulary"
+    return _CMLMDecoderFn.apply(eng, dec.training, eouts, _elens_dev(eouts, elens), ys_in, ylens_host, labels, want_logits,
+                                *eng.arena.params)
 
 
 # ---------------------------------------------------------------------------------------

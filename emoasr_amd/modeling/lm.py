@@ -265,12 +265,20 @@ _NO_PREDICT_ELECTRA = ("emoasr_amd: ELECTRA (lm_type 'electra' / 'electra-disc')
                        "rescoring")
 
 
+_P2W_TYPES = ("pbert", "pctc", "ptransformer")
+_NO_PREDICT_P2W = ("emoasr_amd: the phone-to-word models (modeling/p2w.py: lm_type 'pbert' / 'pctc') have no next-token "
+                   "distribution: predict / zero_states and the beam searches' shallow fusion need a causal LM (lm_type "
+                   "'transformer' or 'rnn'); they correct a CTC hypothesis through emoasr_amd.correct")
+
+
 def require_next_token_lm(lm, lm_weight):
     """entry check of the beam searches: shallow fusion needs p(next token | prefix), which a bidirectional LM does not define"""
     if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) == "bert":
         raise NotImplementedError(_NO_PREDICT)
     if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) in _ELECTRA_TYPES:
         raise NotImplementedError(_NO_PREDICT_ELECTRA)
+    if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) in _P2W_TYPES:
+        raise NotImplementedError(_NO_PREDICT_P2W)
 
 
 class LM(nn.Module):

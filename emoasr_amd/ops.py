@@ -883,6 +883,43 @@ def bce_head_bwd(h, wp, z, y, w, dwp, dbp, gscale=1.0, gscale_dev=None):
     return dh
 
 
+# ---- CTC error correction ----------------------------------------------------------------------
+def ctc_token_conf(logits, lse, best, elens, blank):
+    """logits [B,T,V] (f32 / bf16, last dim contiguous, utterance stride T * row stride); lse f32 [B*T]; best int32 [B,T] the greedy
+    frame ids; elens int32 [B] -> (frame int32 [B,T], conf f32 [B,T], ntok int32 [B]): for token j of the collapsed path, the frame
+    of its run where softmax(logits)[id] is largest (earliest on ties) and that probability.  Entries from ntok[b] on are unset."""
+    B, T, V = _chk(logits).shape
+    assert logits.dtype in _DT and logits.stride(2) == 1 and (B == 1 or logits.stride(0) == T * logits.stride(1))
+    assert _chk(lse, torch.float32).numel() == B * T and lse.is_contiguous()
+    assert _chk(best, torch.int32).shape == (B, T) and best.is_contiguous() and _chk(elens, torch.int32).numel() == B
+    dev = logits.device
+    frame = torch.empty(B, T, device=dev, dtype=torch.int32)
+    conf = torch.empty(B, T, device=dev, dtype=torch.float32)
+    ntok = torch.empty(B, device=dev, dtype=torch.int32)
+    lib.call("emoasr_ctc_token_conf", _DT[logits.dtype], B, T, V, _p(logits), logits.stride(1), _p(lse), _p(best), _p(elens),
+             int(blank), _p(frame), _p(conf), _p(ntok), _stream())
+    return frame, conf, ntok
+
+
+def correct_fuse(asr_logits, asr_lse, lm_logits, w, n_cols, asr_rows=None):
+    """asr_logits [R,V_asr] with asr_lse f32 [R]; lm_logits [n,V_lm] (f32 / bf16 each, last dim contiguous); asr_rows int32 [n]: the
+    recogniser row of each LM row (None: row i) -> (ids int32 [n], values f32 [n]) = arg-max and maximum over v < n_cols of
+    (1 - w) softmax(asr row)[v] + w softmax(lm row)[v], the lowest column on ties.  The LM's log-sum-exp is formed in the kernel."""
+    R, Va, lda = _rows(_chk(asr_logits))
+    n, Vl, ldl = _rows(_chk(lm_logits))
+    assert asr_logits.dim() == 2 and lm_logits.dim() == 2 and asr_logits.dtype in _DT and lm_logits.dtype in _DT
+    assert _chk(asr_lse, torch.float32).numel() == R and asr_lse.is_contiguous()
+    if asr_rows is not None:
+        assert _chk(asr_rows, torch.int32).numel() == n and asr_rows.is_contiguous()
+    else:
+        assert R >= n
+    ids = torch.empty(n, device=lm_logits.device, dtype=torch.int32)
+    val = torch.empty(n, device=lm_logits.device, dtype=torch.float32)
+    lib.call("emoasr_correct_fuse", _DT[asr_logits.dtype], _DT[lm_logits.dtype], n, Va, Vl, int(n_cols), _p(asr_logits), lda,
+             _p(asr_lse), _p(asr_rows), R, _p(lm_logits), ldl, float(w), _p(ids), _p(val), _stream())
+    return ids, val
+
+
 # ---- knowledge distillation ---------------------------------------------------------------
 def soft_ce(logits, soft=None, src=None, hard=None, w_soft=None, w_hard=None, lsm_prob=0.0, lrow=None, want_grad=False,
             gscale=1.0, gscale_dev=None, grad=None):

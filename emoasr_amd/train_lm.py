@@ -120,9 +120,10 @@ def ppl_masked_lm(dataloader, model, device, mask_id=None, max_seq_len=None):
     """lm/test_ppl.py:77-133: masked-LM perplexity over a loader of single utterances (LMDataset phase "test") -> (cnt, ppl): every
     position of ys_in is masked in turn (the <eos> wrappers of add_sos_eos included) and predicted from the rest; an utterance
     longer than max_seq_len is skipped with a warning.  Built on LM.masked_logprobs (the copies are made on the device, one
-    device-to-host copy per utterance), summed on the host in double precision.  mask_id / max_seq_len default to the model's."""
+    device-to-host copy per utterance), summed on the host in double precision.  mask_id / max_seq_len default to the model's.
+    A P2W (lm_type "pbert", batches of P2WDataset) is scored the same way with the utterance's phones passed through."""
     if mask_id is not None:
-        assert int(mask_id) == int(model.mask_id), "mask_id differs from the model's"
+        assert int(mask_id) == int(getattr(model, "mask_id", model.params.mask_id)), "mask_id differs from the model's"
     max_seq_len = model.params.max_seq_len if max_seq_len is None else max_seq_len
     cnt, sum_logprob = 0, 0.0
     for data in dataloader:
@@ -131,7 +132,15 @@ def ppl_masked_lm(dataloader, model, device, mask_id=None, max_seq_len=None):
         if ys.size(1) > max_seq_len:
             logging.warning(f"input length longer than {max_seq_len:d} skip")
             continue
-        lp = model.masked_logprobs(ys, [int(data["ylens"][0])])
+        if hasattr(model, "masked_logprobs"):
+            lp = model.masked_logprobs(ys, [int(data["ylens"][0])])
+        else:      # a P2W "pbert": the N masked copies as one batch, every copy conditioned on the utterance's phones
+            n = ys.size(1)
+            copies = ys.repeat(n, 1)
+            copies[torch.arange(n), torch.arange(n)] = int(model.params.mask_id)
+            ps = data["ps"][:, : int(data["plens"][0])].repeat(n, 1)
+            logp = torch.log_softmax(model(copies, ps=ps).float(), dim=-1).cpu()
+            lp = logp[torch.arange(n), torch.arange(n), ys[0]]
         sum_logprob -= float(lp.sum())
         cnt += ys.size(1)
     return cnt, math.exp(sum_logprob / cnt)

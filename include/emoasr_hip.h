@@ -705,6 +705,24 @@ int emoasr_bce_head_bwd(int dtype, int M, int H, const void* h, long ldh, const 
                         const float* w, float gscale, const float* gscale_dev, void* dh, long lddh, float* dwp, float* dbp,
                         void* stream);
 
+/* ---- CTC error correction (asr/test_asr_correct.py:39-172): token confidences and the recogniser / LM fusion ----
+ * emoasr_ctc_token_conf: logits [B,T,V] (row stride ld >= V, utterance stride T * ld), lse f32 [B*T] their row log-sum-exps, best
+ *   int32 [B,T] the greedy frame ids.  A token of utterance b is a maximal run of equal non-blank frames below min(elens[b], T)
+ *   (the CTC collapse: token j is hyp[b,j] of emoasr_ctc_greedy).  For token j:
+ *     frame[b,j] = the frame t of the run with the largest exp(logits[b,t,id] - lse[b,t]) (f32), the earliest on ties;
+ *     conf[b,j]  = that value;   ntok[b] = number of tokens.   frame / conf are [B,T]; entries from ntok[b] on are left alone.
+ *   One wave per utterance; frames at or past elens[b] are never read; an id outside [0, V) counts as blank.
+ * emoasr_correct_fuse: for row i < n: a = asr[asr_rows[i]] (asr_rows int32 [n], NULL: row i; clamped to [0, asr_nrows)), with its
+ *   log-sum-exp asr_lse[that row]; l = lm[i] (its log-sum-exp over all V_lm columns is formed in the kernel);
+ *     out_id[i] = argmax_{v < n_cols} (1 - w) exp(a[v] - lse_a) + w exp(l[v] - lse_l), lowest v on ties;  out_val[i] = that maximum.
+ *   n_cols <= min(V_asr, V_lm); 0 <= w <= 1; the two dtypes are independent (EMO_F32 / EMO_BF16).  One 256-thread block per row,
+ *   f32 accumulation, 16-byte loads on 16-byte aligned rows (element loads for the ragged end and for unaligned rows). */
+int emoasr_ctc_token_conf(int dtype, int B, int T, int V, const void* logits, long ld, const float* lse, const int* best,
+                          const int* elens, int blank, int* frame, float* conf, int* ntok, void* stream);
+int emoasr_correct_fuse(int dtype_asr, int dtype_lm, int n, int V_asr, int V_lm, int n_cols, const void* asr, long ld_asr,
+                        const float* asr_lse, const int* asr_rows, long asr_nrows, const void* lm, long ld_lm, float w,
+                        int* out_id, float* out_val, void* stream);
+
 /* ---- one Conformer encoder layer, forward, sequenced on the host in C++ ---------
  * ConformerEncoderLayer.forward (asr/modeling/conformer.py:146-225) with relative-position attention:
  *   x += 0.5 * drop(FFN_macaron(LN(x)));  x += drop(RelMHA(LN(x)));  x += drop(ConvModule(LN(x)));

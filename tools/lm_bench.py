@@ -1,6 +1,6 @@
 """Transformer-LM training throughput and the vocabulary head A/B (fused = no [rows, V] logits, against materialised).
 
-    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert|electra]
+    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert|electra|pbert]
 
 Prints one JSON line.  --leg transformer (the default):
   train_tokens_per_s   real (unpadded) tokens per second of a full training step (forward, backward, clip + AdamW) of the 12-layer
@@ -25,6 +25,13 @@ num_to_mask 35, electra_disc_weight 50), bf16:
                        as alternating legs of --steps steps after --warmup in ONE process, --pairs pairs: median, min, max and every
                        pair's ratio;
   score                LM.score of a 100-hypothesis list: host time from the call to the synchronised result, median and min-max.
+
+--leg pbert: the phone-to-word masked LM (modeling/p2w.py, lm_type="pbert") at the size of the reference's del_pc_mlm.yaml (d = 256,
+4 + 4 layers, V = 10 872, 45 phones), bf16:
+  step                 a full training step (30 % of the words masked, about three phones per word): us per step, tokens/s;
+  correct_kernels      the correction step's kernels at T' = 300 frames, 40 tokens (row_lse + ctc_token_conf + correct_fuse) against
+                       the same step composed from torch ops (softmax, gather, argmax) as alternating legs in ONE process;
+  correct_step         host milliseconds per corrected utterance end to end (correct_step_timing below): T' = 300, 40 tokens.
 """
 import argparse
 import json
@@ -189,6 +196,120 @@ def electra_leg(args):
     print(json.dumps(out))
 
 
+def pbert_leg(args):
+    """the phone-to-word masked LM at the size of the reference's asr/correct/exps/csj/del_pc_mlm.yaml, and the correction kernels"""
+    from emoasr_amd import ops
+    from emoasr_amd.modeling.p2w import P2W
+    from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
+    from emoasr_amd.train_lm import train_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    V, PV = 10872, 45
+    cfg = dict(lm_type="pbert", input_layer="embed", enc_hidden_size=256, enc_num_attention_heads=4, enc_num_layers=4,
+               enc_intermediate_size=1024, dec_hidden_size=256, dec_num_attention_heads=4, dec_num_layers=4,
+               dec_intermediate_size=1024, dropout_enc_rate=0.1, dropout_dec_rate=0.1, dropout_attn_rate=0.1, mtl_ctc_weight=0,
+               lsm_prob=0, kd_weight=0, max_decode_ylen=256, vocab_size=V, src_vocab_size=PV, max_seq_len=256, eos_id=2,
+               mask_id=V - 1, phone_eos_id=2, phone_mask_id=PV - 2, blank_id=0, add_sos_eos=False)
+    params = SimpleNamespace(**dict(cfg, learning_rate=1e-4, lr_schedule_type="lindecay", num_warmup_steps=100, weight_decay=0.01,
+                                    clip_grad_norm=5.0, accum_grad=1, log_step=10 ** 9))
+    lm = P2W(params, compute_dtype=torch.bfloat16).to(dev).train()
+    opt = ScheduledOptimizer(AdamW(get_optimizer_params_nodecay(list(lm.named_parameters()), params.weight_decay), lr=0,
+                                   weight_decay=params.weight_decay), params, num_total_steps=10 ** 6)
+    data, tokens = mlm_batch(args.batch, V, V - 1, 0.3)
+    g = torch.Generator().manual_seed(1)
+    plens = (data["ylens"] * 3).clamp(max=256)      # about three phones per word
+    data["plens"] = plens
+    data["ps"] = torch.randint(3, PV - 2, (args.batch, int(plens.max())), generator=g)
+    step = lambda: train_step(lm, opt, data, params, dev, sync=False)
+    timed(step, args.warmup)
+    us = [round(timed(step, args.steps), 1) for _ in range(args.pairs)]
+    out = {"leg": "pbert", "batch": args.batch, "dtype": "bf16",
+           "step": {"tokens": tokens, "phones": int(plens.sum()), "rows_labelled": int((data["labels"] != -100).sum()), "us": us,
+                    "median_us": statistics.median(us), "tokens_per_s": round(tokens / statistics.median(us) * 1e6)}}
+    # ---- the correction kernels at T' = 300 frames, 40 tokens, against the same step composed from torch ops
+    T, n, Va = 300, 40, V
+    best = torch.zeros(1, T, dtype=torch.int32)
+    best[0, 2:T:7] = torch.randint(1, Va, (len(range(2, T, 7)),), generator=g, dtype=torch.int32)[: len(range(2, T, 7))]
+    best[0, 3:T:7] = best[0, 2:T:7][: len(range(3, T, 7))]
+    ntok = len(range(2, T, 7))
+    n = min(n, ntok)
+    logits = torch.randn(1, T, Va, generator=g).to(dev)
+    lm_logits = torch.randn(n, V, generator=g).to(dev).to(torch.bfloat16)
+    best_d, el = best.to(dev), torch.tensor([T], dtype=torch.int32, device=dev)
+
+    def hip():
+        lse = ops.row_lse(logits.view(T, Va))
+        frame, conf, _ = ops.ctc_token_conf(logits, lse, best_d, el, 0)
+        return ops.correct_fuse(logits.view(T, Va), lse, lm_logits, 0.5, Va, asr_rows=frame.view(-1)[:n])
+
+    tok_frames = torch.tensor(list(range(2, T, 7))[:n], device=dev)
+    tok_ids = best_d[0, tok_frames].long()
+
+    def composed():     # soft-max of every frame, gather, the two frames of a run compared, gather, soft-max, mix, arg-max
+        p = torch.softmax(logits[0], dim=-1)
+        two = torch.stack([p[tok_frames, tok_ids], p[tok_frames + 1, tok_ids]])
+        fr = tok_frames + two.argmax(dim=0)
+        mix = 0.5 * p[fr] + 0.5 * torch.softmax(lm_logits.float(), dim=-1)[:, :Va]
+        return mix.argmax(dim=-1), mix.max(dim=-1).values
+
+    a, b = hip(), composed()
+    assert torch.equal(a[0].long(), b[0]), "the kernels and the composed step disagree"
+    rec = {"frames": T, "tokens": n, "V": Va, "hip_us": [], "torch_us": []}
+    for _ in range(args.pairs):
+        for name, fn in (("hip", hip), ("torch", composed)):
+            timed(fn, args.warmup)
+            rec[name + "_us"].append(round(timed(fn, args.steps), 1))
+    rec["hip_median_us"], rec["torch_median_us"] = statistics.median(rec["hip_us"]), statistics.median(rec["torch_us"])
+    rec["pair_ratio_hip_over_torch"] = [round(x / y, 3) for x, y in zip(rec["hip_us"], rec["torch_us"])]
+    out["correct_kernels"] = rec
+    out["correct_step"] = correct_step_timing(args, lm.eval(), V, PV, dev)
+    print(json.dumps(out))
+
+
+def correct_step_timing(args, lm, V, PV, dev):
+    """host milliseconds per corrected utterance (correct.correct_step: encoder pass, both heads, greedy paths, confidences, one copy,
+    the LM forward, the fusion, one copy) with the 23 M Conformer-CTC of bench.py plus a hierarchical phone head, bf16, on 1 203
+    input frames = T' = 300.  The weights are random: the word head is sharpened and the blank's bias is bisected until the greedy
+    hypothesis has 40 tokens (or as near as the bisection gets: the count is reported)."""
+    import time
+    from emoasr_amd.correct import correct_step
+    from emoasr_amd.modeling.asr import ASR
+    cfg = dict(input_layer="conv2d", feat_dim=80, num_framestacks=1, encoder_type="conformer", decoder_type="ctc",
+               pos_encode_type="rel", enc_hidden_size=256, enc_num_attention_heads=4, enc_num_layers=12, enc_intermediate_size=1024,
+               dropout_enc_rate=0.1, dropout_attn_rate=0.1, vocab_size=V, blank_id=0, eos_id=2, kd_weight=0,
+               mtl_phone_ctc_weight=0.3, hie_mtl_phone=True, phone_vocab_size=PV, inter_ctc_layer_id=6)
+    torch.manual_seed(2)
+    asr = ASR(SimpleNamespace(**cfg), phase="test", compute_dtype=torch.bfloat16).to(dev).eval()
+    xs = torch.randn(1, 1203, 80)
+    data = {"utt_ids": ["utt"], "xs": xs, "xlens": torch.tensor([1203]), "texts": [""]}
+    with torch.no_grad():
+        asr.decoder.output.weight.mul_(20.0)
+        asr.decoder.phone_output.weight.mul_(20.0)
+        lo, hi = -2000.0, 2000.0
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            asr.decoder.output.bias[0] = mid
+            n = len(asr.decode(xs.to(dev), data["xlens"])[0][0])
+            if n == 40:
+                break
+            lo, hi = (mid, hi) if n > 40 else (lo, mid)
+    det = {}
+    step = lambda: correct_step(asr, lm, data, 0, V - 1, 0.9, 0.5, dev, V, details=det)
+    _, hyp, _, _, num_masked, num_tokens = step()
+
+    def run():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    for _ in range(args.warmup):
+        run()
+    ms = [run() for _ in range(max(args.steps, 5))]
+    return {"frames": 300, "tokens": num_tokens, "phones": int(len(det["hyp_phone"])), "masked": num_masked, "lm": "pbert",
+            "median_ms": round(statistics.median(ms), 3), "min_max_ms": [round(min(ms), 3), round(max(ms), 3)]}
+
+
 def timed(fn, n):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -206,13 +327,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=100)
-    ap.add_argument("--leg", choices=["transformer", "bert", "electra"], default="transformer")
+    ap.add_argument("--leg", choices=["transformer", "bert", "electra", "pbert"], default="transformer")
     ap.add_argument("--token-rows", type=int, nargs="+", default=[16384, 65536, 262144], help="--leg bert: max_token_rows values")
     args = ap.parse_args()
     if args.leg == "bert":
         return bert_leg(args)
     if args.leg == "electra":
         return electra_leg(args)
+    if args.leg == "pbert":
+        return pbert_leg(args)
     from emoasr_amd import ops
     from emoasr_amd.modeling.lm import LM
     from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
