@@ -185,6 +185,18 @@ class ConformerBwd(Structure):
                 ("ln_part", c_void_p), ("ln_part_stride", c_long), ("attn_img", c_void_p), ("attn_img_bytes", ctypes.c_size_t)]
 
 
+class LasAttend(Structure):
+    _fields_ = [("B", c_int), ("T", c_int), ("A", c_int), ("D", c_int),
+                ("pk", c_void_p), ("pk_bstride", c_long), ("pq", c_void_p), ("aw_prev", c_void_p),
+                ("filt", c_void_p), ("w_conv", c_void_p), ("b_conv", c_void_p), ("w_score", c_void_p),
+                ("eouts", c_void_p), ("eo_bstride", c_long), ("elens", c_void_p),
+                ("drop_p", c_float), ("seed", c_uint64), ("step", c_int),
+                ("scores", c_void_p), ("aw", c_void_p), ("lse", c_void_p), ("ctx", c_void_p), ("ctx_ld", c_long),
+                ("dctx", c_void_p), ("dctx_ld", c_long), ("daw", c_void_p),
+                ("dpq", c_void_p), ("daw_prev", c_void_p), ("dpk", c_void_p), ("deouts", c_void_p),
+                ("dw_score", c_void_p), ("dw_conv", c_void_p), ("db_conv", c_void_p), ("dfilt", c_void_p)]
+
+
 P, I, L, F, U64 = c_void_p, c_int, c_long, c_float, c_uint64
 
 # name -> argtypes (every function returns int status); mirrors include/emoasr_hip.h
@@ -259,6 +271,9 @@ SIGNATURES = {
     "emoasr_rnnt_beam_joint": [I, I, I, I, I, P, P, P, P, P, P, P, P],
     "emoasr_rnnt_beam_pick": [I, I, I, I, I, P, L, P, L, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
+    "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],
+    "emoasr_las_attend_bwd": [I, POINTER(LasAttend), P],
+    "emoasr_las_dropmask": [POINTER(LasAttend), P, P],
     "emoasr_mlm_expand": [I, I, I, P, P, P, I, I, I, I, P, P, P, P, P],
     "emoasr_sample_rows": [I, I, I, P, L, P, P, U64, L, P, P, P, P],
     "emoasr_gumbel_noise": [I, I, U64, L, P, L, P],

@@ -336,6 +336,76 @@ def attn_decoder_logits(dec, eouts, elens, ys_in, ylens):
     return logits
 
 
+# ---------------------------------------------------------------------------------------
+# LAS decoder: attention loss (+ auxiliary CTC) as one autograd node over the encoder output (engine._LASMixin)
+# ---------------------------------------------------------------------------------------
+class _LASDecoderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eng, training, p_attn, eouts, elens_dev, ys_host, ylens_host, ys_in, ys_out, blank, soft, kd, *params):
+        logits, st = eng.las_forward(eouts, elens_dev, ys_in, ylens_host, training, p_attn, True)
+        if soft is None:
+            loss_att, _ = eng.att_loss(logits, ys_out, ylens_host)
+            loss_kd, loss = torch.zeros_like(loss_att), loss_att
+        else:  # DistillLoss (las.py:109-116, criteria.py:66-100)
+            loss_kd, loss_att, _ = eng.att_kd_loss(logits, ys_out, ylens_host, soft)
+            loss = kd * loss_kd + (1 - kd) * loss_att
+        loss_ctc, cctx = None, None
+        ctx.soft, ctx.kd = soft, kd
+        if eng.mtl_ctc > 0:
+            ctc_logits = eng.head_logits(eouts, "decoder.ctc.output")
+            loss_ctc, cctx = eng.ctc_loss(ctc_logits, elens_dev, ys_host, ylens_host, blank, True)
+            loss = loss + eng.mtl_ctc * loss_ctc
+        else:
+            loss_ctc = torch.zeros_like(loss_att)
+        ctx.eng, ctx.st, ctx.cctx, ctx.eouts, ctx.logits = eng, st, cctx, eouts, logits
+        ctx.ys_out, ctx.ylens_host = ys_out, ylens_host
+        ctx.mark_non_differentiable(logits)
+        return loss, loss_att, loss_ctc, logits, loss_kd
+
+    @staticmethod
+    def backward(ctx, g_total, g_att, g_ctc, _, g_kd):
+        eng = ctx.eng
+        if ctx.soft is None:
+            g_att_eff = (g_total + g_att).to(torch.float32).reshape(1)
+            _, dlogits = eng.att_loss(ctx.logits, ctx.ys_out, ctx.ylens_host, True, g_att_eff)
+        else:
+            _, _, dlogits = eng.att_kd_loss(ctx.logits, ctx.ys_out, ctx.ylens_host, ctx.soft,
+                                            (g_total * ctx.kd + g_kd).to(torch.float32),
+                                            (g_total * (1 - ctx.kd) + g_att).to(torch.float32))
+        deouts = eng.las_backward(ctx.st, dlogits)
+        if ctx.cctx is not None:
+            g_ctc_eff = (g_total * eng.mtl_ctc + g_ctc).to(torch.float32).reshape(1)
+            dcl = eng.ctc_grad(ctx.cctx, 1.0, g_ctc_eff)
+            from .. import ops
+            deouts = ops.add(deouts, eng.head_backward(ctx.eouts, dcl, "decoder.ctc.output"))
+        ctx.st = ctx.cctx = ctx.soft = None
+        return (None, None, None, deouts, None, None, None, None, None, None, None, None) + (None,) * len(eng.arena.params)
+
+
+def las_decoder_apply(dec, eouts, elens, ys, ylens, ys_in, ys_out, soft_labels=None, kd_weight=0.0):
+    """LASDecoder.forward -> (loss, loss_att, loss_ctc, logits [B, L, V], loss_kd); the logits are specified on the positions
+    below ylens + 1 of every row (the rest is never read by the loss)"""
+    eng = _engine_of(dec)
+    ylens_host = _host_list(ylens)
+    L = max(ylens_host) + 1
+    ys_host = ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)
+    ys_in = (ys_in.cpu() if torch.is_tensor(ys_in) else torch.as_tensor(ys_in))[:, :L]
+    ys_out = (ys_out.cpu() if torch.is_tensor(ys_out) else torch.as_tensor(ys_out))[:, :L]
+    assert 0 <= int(ys_in.min()) and int(ys_in.max()) < dec.vocab_size, "token id outside the vocabulary"
+    T = int(max(_host_list(elens)))
+    eouts = eouts[:, :T].to(eng.dtype).contiguous()    # frames past the longest utterance carry no weight
+    soft = None
+    if soft_labels is not None:
+        soft = torch.as_tensor(soft_labels)[:, :L].to(device=eouts.device, dtype=torch.float32).contiguous()
+    return _LASDecoderFn.apply(eng, dec.training, float(dec.score.dropout_attn_rate), eouts, _elens_dev(eouts, elens), ys_host,
+                               ylens_host, ys_in, ys_out, dec.blank_id, soft, float(kd_weight), *eng.arena.params)
+
+
+def las_beam_apply(dec, eouts, beam_width, len_weight):
+    """LASDecoder.decode's beam search for one utterance -> (hyps, scores)"""
+    return _engine_of(dec).las_beam_search(eouts, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+
+
 class _CMLMDecoderFn(torch.autograd.Function):
     """the conditional masked LM decoder (decoders/transformer.py:102-105,127-128): bidirectional self-attention over ylens keys,
     MaskedLMLoss on the labelled rows"""

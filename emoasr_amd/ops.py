@@ -634,8 +634,10 @@ def transpose_cast_batched(pairs):
         lib.call("emoasr_transpose_cast_batched", dt(chunk[0][1]), len(chunk), arr, _stream())
 
 
-def scale_dropout(x, scale=1.0, drop_p=0.0, seed=0):
-    y = torch.empty_like(x)
+def scale_dropout(x, scale=1.0, drop_p=0.0, seed=0, out=None):
+    """out: where to write (contiguous, x's shape and dtype; x itself: in place)"""
+    assert out is None or (out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype)
+    y = torch.empty_like(x) if out is None else out
     lib.call("emoasr_scale_dropout", dt(x), x.numel(), _p(_chk(x)), _p(y), scale, drop_p, seed, _stream())
     return y
 
@@ -1312,6 +1314,99 @@ def rnnlm_step(W, nb, ids, ph, pc, src, dst, logp, row_dst=None):
     lib.call("emoasr_rnnlm_step", dt(emb), nb, L, W.E, H, W.V, slots, _p(ids), _p(emb), W.p_ih, W.p_hh, W.p_b, _p(ph),
              _p(_chk(pc, torch.float32)), _p(src), _p(dst), _p(w_out), _p(b_out), _p(_chk(logp, torch.float32)), logp.stride(0),
              logp.shape[0], _p(row_dst), _p(W.ws), W.ws_bytes, _stream())
+
+
+# ---- LAS decoder: location-aware attention, one position (csrc/las.hip) -------------------------------------------
+LAS_MAX_ATTN_DIM = 512
+
+
+class LasWeights:
+    """the f32 operands of the attention step that do not change between positions: score.conv.weight [10,1,201], score.w_conv
+    weight [A,10] + bias [A], score.w_score.weight [1,A]"""
+
+    def __init__(self, filt, w_conv, b_conv, w_score):
+        for t in (filt, w_conv, b_conv, w_score):
+            assert _chk(t, torch.float32).is_contiguous()
+        A = w_conv.shape[0]
+        assert tuple(filt.shape[-1:]) == (201,) and filt.numel() == 2010 and tuple(w_conv.shape) == (A, 10)
+        assert b_conv.numel() == A and w_score.numel() == A
+        self.filt, self.w_conv, self.b_conv, self.w_score, self.A = filt, w_conv, b_conv, w_score, A
+
+
+def _las_args(W, pk, pq, aw_prev, eouts, elens, drop_p, seed, step):
+    B, A = pq.shape
+    T, D = eouts.shape[-2], eouts.shape[-1]
+    assert A == W.A and pk.shape[-2:] == (T, A) and pk.dtype == pq.dtype == eouts.dtype
+    assert pq.is_contiguous() and pk.stride(-1) == 1 and pk.stride(-2) == A and eouts.stride(-1) == 1 and eouts.stride(-2) == D
+    a = lib.LasAttend()
+    a.B, a.T, a.A, a.D = B, T, A, D
+    a.pk, a.pq, a.eouts = _chk(pk).data_ptr(), _chk(pq).data_ptr(), _chk(eouts).data_ptr()
+    # a [T,A] / [T,D] operand is one utterance read by every row (the beam's hypotheses); [B,T,*] gives each row its own
+    a.pk_bstride = pk.stride(0) if pk.dim() == 3 else 0
+    a.eo_bstride = eouts.stride(0) if eouts.dim() == 3 else 0
+    assert (pk.dim() == 2 or pk.shape[0] == B) and (eouts.dim() == 2 or eouts.shape[0] == B)
+    if aw_prev is not None:
+        assert _chk(aw_prev, torch.float32).shape == (B, T) and aw_prev.is_contiguous()
+        a.aw_prev = aw_prev.data_ptr()
+    a.filt, a.w_conv, a.b_conv, a.w_score = W.filt.data_ptr(), W.w_conv.data_ptr(), W.b_conv.data_ptr(), W.w_score.data_ptr()
+    if elens is not None:
+        assert _chk(elens, torch.int32).numel() >= B
+        a.elens = elens.data_ptr()
+    a.drop_p, a.seed, a.step = float(drop_p), int(seed), int(step)
+    return a
+
+
+def las_attend_fwd(W, pk, pq, aw_prev, eouts, elens=None, drop_p=0.0, seed=0, step=0, aw=None, ctx=None, lse=None, scores=None):
+    """one position of the location-aware attention for all rows (include/emoasr_hip.h: emoasr_las_attend_t).
+    pk [B,T,A] | [T,A] key projection (+ bias), pq [B,A] query projection (+ bias), aw_prev f32 [B,T] | None (position 0),
+    eouts [B,T,D] | [T,D], elens int32 [B] | None -> (aw f32 [B,T] the DROPPED weights, ctx [B,D] (a view with a row stride is
+    written in place), lse f32 [B])"""
+    a = _las_args(W, pk, pq, aw_prev, eouts, elens, drop_p, seed, step)
+    dev = pq.device
+    aw = torch.empty(a.B, a.T, device=dev, dtype=torch.float32) if aw is None else aw
+    ctx = torch.empty(a.B, a.D, device=dev, dtype=pq.dtype) if ctx is None else ctx
+    lse = torch.empty(a.B, device=dev, dtype=torch.float32) if lse is None else lse
+    scores = torch.empty(a.B, a.T, device=dev, dtype=torch.float32) if scores is None else scores
+    assert aw.is_contiguous() and aw.shape == (a.B, a.T) and ctx.shape == (a.B, a.D) and ctx.stride(1) == 1 and ctx.dtype == pq.dtype
+    assert scores.numel() >= a.B * a.T and lse.numel() >= a.B
+    a.aw, a.ctx, a.ctx_ld, a.lse, a.scores = aw.data_ptr(), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), scores.data_ptr()
+    lib.call("emoasr_las_attend_fwd", dt(pq), byref(a), _stream())
+    return aw, ctx, lse
+
+
+def las_attend_bwd(W, pk, pq, aw_prev, eouts, elens, drop_p, seed, step, aw, ctx, lse, dctx, daw, dpq, daw_prev, dpk, deouts,
+                   dw_score, dw_conv, db_conv, dfilt):
+    """the reverse of las_attend_fwd at one position: aw / ctx / lse as the forward left them, dctx [B,D] (row stride allowed), daw
+    f32 [B,T] | None the gradient arriving at aw from the next position's convolution.  ACCUMULATES (all f32) into dpq [B,A],
+    daw_prev [B,T] | None, dpk [B,T,A], deouts [B,T,D] | None and the parameter gradients dw_score [A], dw_conv [A,10], db_conv [A],
+    dfilt [10,201]"""
+    a = _las_args(W, pk, pq, aw_prev, eouts, elens, drop_p, seed, step)
+    B, T, A, D = a.B, a.T, a.A, a.D
+    assert pk.dim() == 3 and eouts.dim() == 3
+    assert _chk(aw, torch.float32).shape == (B, T) and aw.is_contiguous() and ctx.stride(1) == 1 and dctx.stride(1) == 1
+    assert ctx.dtype == pq.dtype and dctx.dtype == pq.dtype and ctx.shape == (B, D) and dctx.shape == (B, D)
+    a.aw, a.ctx, a.ctx_ld, a.lse = aw.data_ptr(), ctx.data_ptr(), ctx.stride(0), _chk(lse, torch.float32).data_ptr()
+    a.dctx, a.dctx_ld = dctx.data_ptr(), dctx.stride(0)
+    for t, shape in ((daw, (B, T)), (daw_prev, (B, T)), (dpq, (B, A)), (dpk, (B, T, A)), (deouts, (B, T, D)), (dw_score, None),
+                     (dw_conv, (A, 10)), (db_conv, (A,)), (dfilt, None)):
+        if t is not None:
+            assert _chk(t, torch.float32).is_contiguous() and (shape is None or tuple(t.shape) == shape), (t.shape, shape)
+    assert dw_score.numel() == A and dfilt.numel() == 2010
+    a.daw = None if daw is None else daw.data_ptr()
+    a.daw_prev = None if daw_prev is None else daw_prev.data_ptr()
+    a.deouts = None if deouts is None else deouts.data_ptr()
+    a.dpq, a.dpk = dpq.data_ptr(), dpk.data_ptr()
+    a.dw_score, a.dw_conv, a.db_conv, a.dfilt = dw_score.data_ptr(), dw_conv.data_ptr(), db_conv.data_ptr(), dfilt.data_ptr()
+    lib.call("emoasr_las_attend_bwd", dt(pq), byref(a), _stream())
+
+
+def las_dropmask(B, T, drop_p, seed, step, device="cuda"):
+    """the keep mask las_attend_fwd / _bwd derive at (seed, step): uint8 [B,T], 1 = kept (for tests)"""
+    a = lib.LasAttend()
+    a.B, a.T, a.drop_p, a.seed, a.step = B, T, float(drop_p), int(seed), int(step)
+    mask = torch.empty(B, T, device=device, dtype=torch.uint8)
+    lib.call("emoasr_las_dropmask", byref(a), _p(mask), _stream())
+    return mask
 
 
 def argmax_rows(x):

@@ -671,6 +671,42 @@ int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, int slots, 
                       const int* src, const int* dst, const void* w_out, const float* b_out, float* logp, long ldlogp,
                       int logp_rows, const int* row_dst, void* ws, long ws_bytes, void* stream);
 
+/* ---- LAS decoder: location-aware additive attention, one decoder position (decoders/las.py:289-342; csrc/las.hip) ----
+ *   f[t][c] = Conv1d(1, 10, 201, padding 100, no bias)(aw_prev)[c][t]
+ *   e[t]    = w_score . tanh(pk[t] + pq + W_conv f[t] + b_conv)      t >= elens[b]: -FLT_MAX (elens NULL: no mask)
+ *   aw      = softmax_t(e);  awd[t] = aw[t] * keep(seed, step, b, t) / (1 - drop_p);  ctx = sum_t awd[t] eouts[t]
+ * pk = W_key eouts + b_key [B,T,A] and pq = W_query q + b_query [B,A] arrive from the GEMMs (compute dtype T); score.w_score.bias
+ * shifts every e[t] alike and never enters.  The weights stay f32; keep() is the counter-based mask of common.h at element
+ * (step * B + b) * T + t, derived alike by the forward, the backward and emoasr_las_dropmask (uint8 [B,T], 1 = kept) -- never stored.
+ * A % 8 == 0, A <= 512, D % 8 == 0; B, T free.  pk_bstride / eo_bstride: elements between rows' [T,A] / [T,D] blocks (0: every
+ * row reads the same utterance -- the beam search's hypotheses).
+ * forward (2 launches): reads pk, pq, aw_prev (NULL: zeros, position 0), filt, w_conv, b_conv, w_score, eouts, elens; writes
+ *   scores (scratch f32 [B,T]), aw (the DROPPED weights f32 [B,T]), lse (f32 [B], NULL: not wanted), ctx (T, rows of stride ctx_ld).
+ * backward (1 launch): reads the above with aw / ctx / lse as the forward left them, dctx (T, row stride dctx_ld) and daw (f32 [B,T]
+ *   the gradient arriving at aw from the next position's convolution, NULL: none); ACCUMULATES into dpq f32 [B,A], daw_prev f32
+ *   [B,T] (NULL at position 0), dpk f32 [B,T,A], deouts f32 [B,T,D] (NULL: skipped), dw_score [A], dw_conv [A,10], db_conv [A],
+ *   dfilt [10,201] (all f32; f32 atomics where tiles or rows meet, so the caller zero-fills what it has not accumulated into). */
+#define EMOASR_LAS_CONV_CHANNELS 10
+#define EMOASR_LAS_CONV_WIDTH 201
+typedef struct {
+  int B, T, A, D;
+  const void* pk; long pk_bstride;
+  const void* pq;
+  const float* aw_prev;
+  const float *filt, *w_conv, *b_conv, *w_score;
+  const void* eouts; long eo_bstride;
+  const int* elens;
+  float drop_p; uint64_t seed; int step;
+  float *scores, *aw, *lse;
+  void* ctx; long ctx_ld;
+  const void* dctx; long dctx_ld;
+  const float* daw;
+  float *dpq, *daw_prev, *dpk, *deouts, *dw_score, *dw_conv, *db_conv, *dfilt;
+} emoasr_las_attend_t;
+int emoasr_las_attend_fwd(int dtype, const emoasr_las_attend_t* a, void* stream);
+int emoasr_las_attend_bwd(int dtype, const emoasr_las_attend_t* a, void* stream);
+int emoasr_las_dropmask(const emoasr_las_attend_t* a, unsigned char* mask, void* stream);
+
 /* ---- masked LM: the masked copies of the pseudo-log-likelihood (lm/modeling/bert.py:54-86) ----
  * ys int32 [B,N] with lengths ylens has R = sum(ylens) masked copies; copy r belongs to the sequence b with
  * row0[b] <= r < row0[b+1] (row0 int32 [B+1]: prefix sums of ylens) and masks pos = r - row0[b].  For j < r_count, r = r_begin + j:
