@@ -1,0 +1,599 @@
+"""RNN-Transducer decoder: LSTM prediction network, joint network, transducer loss, greedy and beam search.
+  reference: asr/modeling/decoders/rnn_transducer.py:81-240"""
+import os
+from ctypes import c_void_p
+
+import torch
+
+from .. import ops
+from ..recurrence import lstm_stack_bwd, lstm_stack_fwd
+from .arena import _Stash, _cfg, h2d_i32
+
+
+class RNNTDecoder:
+    def _rnnt_init(self):
+        cfg = self.cfg
+        self.r_emb = cfg.embedding_size
+        self.r_H = cfg.dec_hidden_size
+        self.r_nl = cfg.dec_num_layers
+        self.r_J = cfg.joint_hidden_size
+        self.p_emb = float(_cfg(cfg, "dropout_emb_rate", 0.0))
+        self.p_dec = float(_cfg(cfg, "dropout_dec_rate", 0.0))
+        self.mtl_ctc = float(_cfg(cfg, "mtl_ctc_weight", 0.0))
+        # the output layer + transducer loss without the [B,T,U,V] logits (csrc/gemm_big.hip epilogues); EMOASR_RNNT_FUSED=0: the
+        # materialised path.  rnnt_chunk: lattice cells per gradient chunk of the backward
+        self.rnnt_fused = os.environ.get("EMOASR_RNNT_FUSED", "1") != "0"
+        self.rnnt_chunk = int(os.environ.get("EMOASR_RNNT_CHUNK", 65536))
+
+    def _lstm_bias(self, name):
+        A = self.arena
+        return A.p(name + ".bias_ih_l0") + A.p(name + ".bias_hh_l0")  # tiny f32 add (glue)
+
+    def rnnt_recurrency(self, ids_tm, state, training, keep):
+        """prediction network, TIME-MAJOR: ids_tm int32 [U,B] -> douts [U,B,H]; state = (hs, cs) lists of
+        per-layer [B,H] tensors (h in compute dtype, c f32) or None."""
+        self._apply_mode()
+        A = self.arena
+        p_emb = self.p_emb if training else 0.0
+        p = self.p_dec if training else 0.0
+        s_emb = self._seed(7000)
+        x = ops.embed_fwd(ids_tm, A.w("decoder.embed.weight"), None, 1.0, p_emb, s_emb)  # [U,B,E]
+        # per layer the input projection + the recurrence (one cooperative launch or the per-position chain), then dropout; a
+        # generator: each bias sum is launched when the stack reaches its layer
+        spec = ((A.w(f"decoder.rnns.{l}.weight_ih_l0"), A.w(f"decoder.rnns.{l}.weight_hh_l0"), self._lstm_bias(f"decoder.rnns.{l}"),
+                 self._seed(7010 + l), state[0][l] if state is not None else None, state[1][l] if state is not None else None)
+                for l in range(self.r_nl))
+        x, new_state, layers = lstm_stack_fwd(x, spec, p, keep)
+        st = None
+        if keep:
+            st = _Stash()
+            st.ids, st.layers, st.s_emb, st.p, st.p_emb = ids_tm, layers, s_emb, p, p_emb
+        return x, new_state, st
+
+    def rnnt_recurrency_bwd(self, st, dy):
+        """dy [U,B,H] gradient w.r.t. the prediction-network output; accumulates parameter gradients"""
+        self._apply_mode()
+        A = self.arena
+        grads = [tuple(A.g(f"decoder.rnns.{l}.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                 for l in range(self.r_nl)]
+        dy = lstm_stack_bwd(dy, st.layers, grads, st.p)
+        ops.embed_bwd(st.ids, dy, 1.0, A.g("decoder.embed.weight"), st.p_emb, st.s_emb)
+
+    def rnnt_prediction_stacked(self, ys_in_list, training):
+        """the prediction network of SEVERAL micro-batches in one pass (it reads the labels only): their <sos>-prefixed label
+        matrices [B_k, U_k] are padded to the longest and stacked along the batch; the cooperative recurrence takes up to eight
+        groups of 64 sequences in one launch (csrc/lstm_coop.hip), so the 2 x layers launches of ~0.3 / 0.5 ms that every
+        micro-batch paid are paid once.  Padded positions sit behind every real one of their sequence: they change neither the
+        real outputs nor (with a zero output gradient) any parameter gradient.
+        -> (douts [U_max, B_tot, H] time-major, stash for rnnt_recurrency_bwd, [(b0, b1, U_k)] per micro-batch)"""
+        with self._scope():
+            mats = [torch.as_tensor(y).to(torch.int32) for y in ys_in_list]
+            Umax, Btot = max(m.shape[1] for m in mats), sum(m.shape[0] for m in mats)
+            ids = torch.zeros(Btot, Umax, dtype=torch.int32)
+            spans, b0 = [], 0
+            for m in mats:
+                ids[b0:b0 + m.shape[0], : m.shape[1]] = m
+                spans.append((b0, b0 + m.shape[0], m.shape[1]))
+                b0 += m.shape[0]
+            dev = self.arena.flat.device
+            ids_tm = h2d_i32(ids.t().contiguous(), dev)
+            douts, _, rst = self.rnnt_recurrency(ids_tm, None, training, True)
+            return douts, rst, spans
+
+    def rnnt_prediction_stacked_ok(self, n_seqs):
+        """does the stacked prediction network pay?  (only with the cooperative recurrence: bf16, <= 512 sequences)"""
+        if os.environ.get("EMOASR_RNNT_PRED_STACKED", "1") == "0":   # (A/B switch)
+            return False
+        probe = torch.empty(0, device=self.arena.flat.device, dtype=self.dtype)
+        return self.dtype == torch.bfloat16 and ops.lstm_seq_supported(probe, n_seqs, self.r_H)
+
+    def rnnt_fused_ok(self, h, w_out):
+        """can the output layer run without materialising the logits?  (bf16, V % 8 == 0, J % 64 == 0; EMOASR_RNNT_FUSED=0 or
+        engine.rnnt_fused = False select the materialised path)"""
+        return (self.rnnt_fused and h.dtype == torch.bfloat16 and w_out.shape[0] % 8 == 0 and w_out.shape[0] >= 64
+                and w_out.shape[1] % 64 == 0)
+
+    def rnnt_forward(self, eouts, elens_dev, ys_in, ys_host, ylens_host, blank, training, want_logits=True, pred=None,
+                     defer_lattice=False):
+        """-> (loss_rnnt 0-dim, logits [B,T,U,V] (None on the fused path: want_logits=False), stash)
+        pred: the prediction network's output for this micro-batch, [U, B, H] time-major, when it was computed for several
+        micro-batches at once (rnnt_prediction_stacked); rnnt_backward then leaves its gradient in st.ddouts
+        defer_lattice (fused output layer only): the lattice runs on a side stream and the first value returned is None; the
+        caller does other work of the micro-batch (the auxiliary CTC branch), then calls rnnt_lattice_join(st) -> loss"""
+        with self._scope():
+            A, J = self.arena, self.r_J
+            B, T, d = eouts.shape
+            dev = eouts.device
+            U = ys_in.shape[1]
+            lat_pending = None
+            if pred is not None:
+                assert tuple(pred.shape) == (U, B, self.r_H) and pred.is_contiguous(), (pred.shape, (U, B, self.r_H))
+                douts, rst = pred, None
+            else:
+                ids_tm = h2d_i32(torch.as_tensor(ys_in).t().contiguous(), dev)  # [U,B]
+                douts, _, rst = self.rnnt_recurrency(ids_tm, None, training, True)
+            e = ops.gemm_nt(eouts.reshape(B * T, d), A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias")).view(B, T, J)
+            g_tm = ops.gemm_nt(douts.view(U * B, self.r_H), A.w("decoder.w_dec.weight"), bias=A.p("decoder.w_dec.bias"))
+            g = ops.strided_copy(g_tm.view(U, B, J).permute(1, 0, 2))  # [B,U,J]
+            h = ops.joint_tanh(e, g)
+            labels = torch.as_tensor(ys_host)[:, : max(U - 1, 1)].to(torch.int32)
+            if labels.shape[1] < max(U - 1, 1):
+                labels = torch.nn.functional.pad(labels, (0, max(U - 1, 1) - labels.shape[1]))
+            labels = h2d_i32(labels.contiguous(), dev)
+            ylens = h2d_i32([int(v) for v in ylens_host], dev)
+            w_out = A.w("decoder.output.weight")
+            if want_logits or not self.rnnt_fused_ok(h, w_out):
+                logits = ops.gemm_nt(h.view(B * T * U, J), w_out, bias=A.p("decoder.output.bias"))
+                logits = logits.view(B, T, U, -1)
+                ctx, nll = ops.rnnt_forward(logits, labels, elens_dev, ylens, blank)
+            else:
+                # the output layer reduced in the GEMM's epilogue (csrc/gemm_big.hip): soft-max partials + the blank / label logits of
+                # every lattice cell; the [B,T,U,V] logits (0.9 GB per micro-batch at the L4 sizes) are never formed
+                logits = None
+                if defer_lattice and os.environ.get("EMOASR_RNNT_LATTICE_SIDE", "1") != "0":
+                    if getattr(self, "_lat_stream", None) is None:
+                        self._lat_stream = torch.cuda.Stream(device=dev)
+                    ctx, nll, ev, keep = ops.rnnt_head_forward(h.view(B * T * U, J), w_out, A.p("decoder.output.bias"), B, T, U,
+                                                               labels, elens_dev, ylens, blank, lattice_stream=self._lat_stream)
+                    lat_pending = (ev, keep)
+                else:
+                    ctx, nll = ops.rnnt_head_forward(h.view(B * T * U, J), w_out, A.p("decoder.output.bias"), B, T, U, labels,
+                                                     elens_dev, ylens, blank)
+            st = _Stash()
+            st.rst, st.douts, st.h, st.logits, st.ctx, st.nll = rst, douts, h, logits, ctx, nll
+            st.labels, st.elens, st.ylens, st.blank, st.eouts = labels, elens_dev, ylens, blank, eouts
+            st.B, st.T, st.U = B, T, U
+            if lat_pending is not None:
+                st.lat_pending = lat_pending
+                return None, logits, st
+            return nll.mean(), logits, st
+
+    def rnnt_lattice_join(self, st):
+        """the loss of a rnnt_forward(..., defer_lattice=True) call: the calling stream waits for the side stream's lattice"""
+        pend = getattr(st, "lat_pending", None)
+        if pend is not None:
+            torch.cuda.current_stream().wait_event(pend[0])
+            st.lat_pending = None
+        return st.nll.mean()
+
+    def rnnt_backward(self, st, gscale_dev, extra_dlogits=None):
+        """-> d_eouts [B,T,d]; accumulates decoder gradients (the logits buffer is overwritten by its gradient).
+        extra_dlogits [B*T*U,V] (or (rows int64 [R], [R,V])): gradient of another loss on the same logits
+        (distillation), added in."""
+        with self._scope():
+            A, J, H = self.arena, self.r_J, self.r_H
+            A.attach_grads()
+            B, T, U = st.B, st.T, st.U
+            if st.logits is None:
+                return self._rnnt_backward_fused(st, gscale_dev)
+            dz = ops.rnnt_grad(st.logits, st.ctx, st.nll, st.labels, st.elens, st.ylens, st.blank, 1.0 / B, gscale_dev,
+                               out=st.logits)
+            if isinstance(extra_dlogits, tuple):  # (row indices, a few gradient rows)
+                dz.view(-1, dz.shape[-1]).index_add_(0, extra_dlogits[0], extra_dlogits[1])
+            elif extra_dlogits is not None:
+                ops.strided_copy(extra_dlogits.view(dz.shape), out=dz, accumulate=True)
+            V = dz.shape[-1]
+            dz2 = dz.view(B * T * U, V)
+            h2 = st.h.view(B * T * U, J)
+            ops.gemm_tn(dz2, h2, out=A.g("decoder.output.weight"), accumulate=True, colsum=A.g("decoder.output.bias"))
+            dpre = ops.gemm_nn(dz2, A.w("decoder.output.weight"), dact_pre=h2, dact=ops.DACT_TANH_OUT)
+            return self._rnnt_joint_bwd(st, dpre)
+
+    def _rnnt_joint_bwd(self, st, dpre):
+        """dpre [B*T*U, J]: gradient of the joint network's pre-activation -> d_eouts [B,T,d]; w_enc, w_dec, then the prediction network"""
+        J, H, (B, T, U) = self.r_J, self.r_H, (st.B, st.T, st.U)
+        de, dg = ops.joint_reduce(dpre.view(B, T, U, J))
+        d = st.eouts.shape[2]
+        deouts = self._lin_bwd(de.view(B * T, J), st.eouts.reshape(B * T, d), "decoder.w_enc.weight",
+                               "decoder.w_enc.bias").view(B, T, d)
+        dg_tm = ops.strided_copy(dg.permute(1, 0, 2)).view(U * B, J)
+        ddouts = self._lin_bwd(dg_tm, st.douts.view(U * B, H), "decoder.w_dec.weight", "decoder.w_dec.bias")
+        self._rnnt_pred_bwd(st, ddouts.view(U, B, H))
+        return deouts
+
+    def _rnnt_pred_bwd(self, st, ddouts):
+        """the prediction network's backward -- or, when its forward ran stacked over several micro-batches, the gradient handed
+        back to that pass (st.ddouts)"""
+        if st.rst is None:
+            st.ddouts = ddouts
+        else:
+            self.rnnt_recurrency_bwd(st.rst, ddouts)
+
+    def _rnnt_backward_fused(self, st, gscale_dev):
+        """backward of the fused output layer: the cells are walked in row chunks; per chunk the logits are recomputed and turned
+        into their gradient inside the GEMM's epilogue (emoasr_rnnt_head_grad), then consumed by the weight-gradient and the
+        data-gradient products.  The chunk buffer (RNNT_CHUNK rows x V, 128 MB at the L4 sizes) is the only [cells, V] storage."""
+        A, J, H = self.arena, self.r_J, self.r_H
+        B, T, U = st.B, st.T, st.U
+        N = B * T * U
+        w_out, b_out = A.w("decoder.output.weight"), A.p("decoder.output.bias")
+        V = w_out.shape[0]
+        coef, ycol = ops.rnnt_coef(st.ctx, st.nll, st.labels, st.elens, st.ylens, 1.0 / B, gscale_dev)
+        h2 = st.h.view(N, J)
+        dpre = torch.empty(N, J, device=h2.device, dtype=h2.dtype)
+        CH = min(N, self.rnnt_chunk)
+        # (rows padded to a multiple of 64 columns: with V = 1000 a row is 2000 bytes and every 128-byte store of the gradient tile
+        # straddles two lines written by different workgroups)
+        Vp = (V + 63) // 64 * 64
+        dzp = torch.zeros(CH, Vp, device=h2.device, dtype=h2.dtype)   # (the pad columns stay zero: the kernels write V of them)
+        dzc = dzp[:, :V]
+        # the data gradient dz . W_out as an NT product over the PADDED columns against W_out^T [J, Vp] (zero pad): a long reduction
+        # onto two 256-column tiles, which the large-tile kernel takes (csrc/gemm_big.hip: emo_gemm_nt_big_wants) -- 143 -> ~80 us
+        # per 65 536-cell chunk on the 64 x 64 NN kernel
+        nt_form = os.environ.get("EMOASR_RNNT_DJOINT_NT", "1") != "0" and J % 256 == 0
+        if nt_form:
+            w_t = torch.zeros(J, Vp, device=h2.device, dtype=h2.dtype)
+            w_t[:, :V].copy_(w_out.t())
+        for r0 in range(0, N, CH):
+            n = min(CH, N - r0)
+            dz = ops.rnnt_head_grad(h2[r0:r0 + n], w_out, b_out, coef[r0:r0 + n], ycol[r0:r0 + n], st.blank, dzc[:n])
+            ops.gemm_tn(dz, h2[r0:r0 + n], out=A.g("decoder.output.weight"), accumulate=True, colsum=A.g("decoder.output.bias"))
+            if nt_form:
+                ops.gemm_nt(dzp[:n], w_t, out=dpre[r0:r0 + n], dact_pre=h2[r0:r0 + n], dact=ops.DACT_TANH_OUT)
+            else:
+                ops.gemm_nn(dz, w_out, out=dpre[r0:r0 + n], dact_pre=h2[r0:r0 + n], dact=ops.DACT_TANH_OUT)
+        return self._rnnt_joint_bwd(st, dpre)
+
+    def rnnt_greedy(self, eouts, elens_host, blank, eos, max_seq_len=256, window=64):
+        """time-synchronous greedy search (rnn_transducer.py:194-240).  While the arg-max is blank the
+        prediction network does not move, so the frames t, t+1, ... can be scored against the SAME decoder
+        state in one batched joint + output GEMM: each round scores up to `window` frames, finds the first
+        non-blank one on the device and brings (index, token) back with one 8-byte copy -- one host round
+        trip per emitted label (plus one per all-blank window) instead of one per frame.  The sequence of
+        (frame, token) decisions is exactly the reference's."""
+        with self._scope(), torch.no_grad():
+            A, J = self.arena, self.r_J
+            A.refresh_shadow()
+            dev = eouts.device
+            hyps, aligns = [], []
+            V = A.w("decoder.output.weight").shape[0]
+            # the one-launch search per utterance that fits it (model shape, LDS image, step-tag range); the launch chain otherwise
+            fits = [bool(ops.lib.size_query("emoasr_rnnt_greedy_fits", ops.dt(eouts), self.r_emb, self.r_H, J, V, self.r_nl,
+                                            int(elens_host[b]), max_seq_len)) for b in range(eouts.shape[0])]
+            if all(fits):
+                return self._rnnt_greedy_device(eouts, elens_host, blank, eos, max_seq_len)
+            for b in range(eouts.shape[0]):
+                if fits[b]:
+                    h1, a1 = self._rnnt_greedy_device(eouts[b:b + 1], [int(elens_host[b])], blank, eos, max_seq_len)
+                    hyps += h1
+                    aligns += a1
+                    continue
+                hyp, align = self._rnnt_greedy_chain(eouts[b], int(elens_host[b]), blank, eos, max_seq_len, window)
+                hyps.append(hyp)
+                aligns.append(align)
+            return hyps, aligns
+
+    def _rnnt_greedy_chain(self, eouts_b, T, blank, eos, max_seq_len, window):
+        """one utterance through the launch chain: windows of frames scored against the same decoder state, the first non-blank
+        frame found on the device, one host round trip per emitted label"""
+        A, J = self.arena, self.r_J
+        dev = eouts_b.device
+        e_all = ops.gemm_nt(eouts_b[:max(T, 1)], A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias"))
+        dout, state, _ = self.rnnt_recurrency(h2d_i32([[eos]], dev), None, False, False)
+        g = ops.gemm_nt(dout.view(1, self.r_H), A.w("decoder.w_dec.weight"), bias=A.p("decoder.w_dec.bias"))
+        hyp, align, t = [], [], 0
+        while t < T:
+            n = min(window, T - t)
+            h = ops.joint_tanh(e_all[t:t + n].view(1, n, J), g.view(1, 1, J))
+            logits = ops.gemm_nt(h.view(n, J), A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+            k, tok = ops.first_not_equal(ops.argmax_rows(logits), blank).tolist()
+            if k < 0:  # every frame of the window is blank
+                align += [blank] * n
+                t += n
+                continue
+            align += [blank] * k + [tok]
+            t += k  # the label is emitted AT frame t+k: the search stays on that frame
+            hyp.append(tok)
+            dout, state, _ = self.rnnt_recurrency(h2d_i32([[tok]], dev), state, False, False)
+            g = ops.gemm_nt(dout.view(1, self.r_H), A.w("decoder.w_dec.weight"), bias=A.p("decoder.w_dec.bias"))
+            if len(hyp) > max_seq_len:
+                break
+        return hyp, align
+
+    def _rnnt_greedy_device(self, eouts, elens_host, blank, eos, max_seq_len):
+        """the whole search of an utterance as ONE cooperative launch (csrc/rnnt_greedy.hip): no host round trip per label; the
+        utterances of a batch are enqueued one after the other and read back with a single synchronisation"""
+        from .. import lib
+        A, J, H, E = self.arena, self.r_J, self.r_H, self.r_emb
+        dev = eouts.device
+        w_out = A.w("decoder.output.weight")
+        V = w_out.shape[0]
+        nbytes = lib.size_query("emoasr_rnnt_greedy_ws_bytes", H, J)
+        b_l = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(2)]
+        outs = []
+        for b in range(eouts.shape[0]):
+            T = int(elens_host[b])
+            e_all = ops.gemm_nt(eouts[b, :max(T, 1)], A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias"))
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            hyp = torch.empty(max_seq_len + 1, device=dev, dtype=torch.int32)
+            align = torch.empty(T + max_seq_len + 1, device=dev, dtype=torch.int32)
+            lens = torch.zeros(2, device=dev, dtype=torch.int32)
+            lib.call("emoasr_rnnt_greedy", ops.dt(eouts), T, E, H, J, V, blank, eos, max_seq_len, ops._p(e_all),
+                     ops._p(A.w("decoder.embed.weight")), ops._p(A.w("decoder.rnns.0.weight_ih_l0")),
+                     ops._p(A.w("decoder.rnns.0.weight_hh_l0")), ops._p(b_l[0]), ops._p(A.w("decoder.rnns.1.weight_ih_l0")),
+                     ops._p(A.w("decoder.rnns.1.weight_hh_l0")), ops._p(b_l[1]), ops._p(A.w("decoder.w_dec.weight")),
+                     ops._p(A.p("decoder.w_dec.bias")), ops._p(w_out), ops._p(A.p("decoder.output.bias")), ops._p(ws), nbytes,
+                     ops._p(hyp), ops._p(align), ops._p(lens), ops._stream())
+            outs.append((e_all, ws, hyp, align, lens))
+        hyps, aligns = [], []
+        for e_all, ws, hyp, align, lens in outs:
+            nh, na = lens.tolist()    # (the first read synchronises)
+            err = int(ws[64:68].view(torch.int32).item())
+            if err:
+                raise RuntimeError("rnnt_greedy: a grid barrier gave up waiting (csrc/rnnt_greedy.hip); "
+                                   "emoasr_set_option('rnnt_greedy_coop', 0) selects the launch chain")
+            hyps.append(hyp[:nh].tolist())
+            aligns.append(align[:na].tolist())
+        return hyps, aligns
+
+    def rnnt_beam_search(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
+        """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359): the expansion round as a
+        replayed HIP graph (_rnnt_beam_search_graph) unless EMOASR_RNNT_BEAM_GRAPH=0 or the utterance does not fit its static
+        buffers; then the launch chain below.  return_scores: (hyps, float64 scores) instead of hyps (tests compare the two forms)."""
+        T = eouts.shape[1]
+        if (os.environ.get("EMOASR_RNNT_BEAM_GRAPH", "1") != "0" and beam_width <= 16
+                and (T * num_expands + 2) * beam_width + 1 <= self._BEAM_POOL - 16 and T <= self._BEAM_TMAX):
+            return self._rnnt_beam_search_graph(eouts, beam_width, blank, eos, num_expands, return_scores)
+        return self._rnnt_beam_search_chain(eouts, beam_width, blank, eos, num_expands, return_scores)
+
+    _BEAM_POOL, _BEAM_TMAX = 32768, 4096   # (the pool's last 16 slots are the warm-up's scratch, never a hypothesis's)
+
+    def _rnnt_beam_round_graph(self, beam_width, nb, blank):
+        """the device work of ONE expansion round over nb live hypotheses, captured once as a HIP graph over static buffers:
+        control words (last labels, source / destination slots of the LSTM states in the pool, frame index) come in through
+        `ctl`, (blank log-prob, top-k log-probs, top-k ids) per hypothesis go out through `out`.  The host loop pays one replay
+        per round instead of ~12 C-ABI calls, ~16 allocations and the torch glue (246 us per round, host-bound:
+        tools/l4_beam_prof.py).  Round 5: the captured body is five launches (csrc/rnnt_beam.hip) that read the control words from
+        the PINNED host record and write the result record into pinned host memory -- no upload / download launches: 124 -> 66 us
+        per round; EMOASR_RNNT_BEAM_FUSED=0 captures the launch chain with explicit copies as before."""
+        st = self.__dict__.setdefault("_beam_static", None)
+        A, J, H, nl = self.arena, self.r_J, self.r_H, self.r_nl
+        dev = A.flat.device
+        if st is None:
+            st = self._beam_static = _Stash()
+            st.ph = [torch.zeros(self._BEAM_POOL, H, device=dev, dtype=self.dtype) for _ in range(nl)]
+            st.pc = [torch.zeros(self._BEAM_POOL, H, device=dev, dtype=torch.float32) for _ in range(nl)]
+            st.e = torch.zeros(self._BEAM_TMAX, J, device=dev, dtype=self.dtype)
+            st.ctl = torch.zeros(3 * 16 + 1, device=dev, dtype=torch.int64)
+            st.ctl_host = torch.zeros(3 * 16 + 1, dtype=torch.int64).pin_memory()
+            st.out = torch.zeros(16, 1 + 2 * 16, device=dev, dtype=torch.float32)
+            st.out_host = torch.zeros(16, 1 + 2 * 16, dtype=torch.float32).pin_memory()
+            st.hj = torch.zeros(16, J, device=dev, dtype=self.dtype)
+            st.bias = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(nl)]   # (refreshed per search, below)
+            st.graphs = {}
+        key = (beam_width, nb, blank)
+        if key in st.graphs:
+            return st, st.graphs[key]
+
+        # the fused round's kernels have LDS plans of their own (csrc/rnnt_beam.hip: a vocabulary row of <= 60 KB in the pick
+        # kernel, 16 rows of H floats in the joint kernel, nin + H columns in the f32 LSTM step); a model outside them decodes
+        # through the launch chain as before round 5 -- decided here from the same limits, and once more by the warm-up below
+        # (an entry point that still refuses turns the round into the chain body instead of failing the search)
+        V_ = A.w("decoder.output.weight").shape[0]
+        nin_max = max(A.w(f"decoder.rnns.{l}.weight_ih_l0").shape[1] for l in range(nl)) if nl else 0
+        fits = V_ * 4 <= 60 * 1024 and 16 * H * 4 <= 64 * 1024 and (self.dtype == torch.bfloat16 or nin_max + H <= 2368)
+        mode = {"fused": os.environ.get("EMOASR_RNNT_BEAM_FUSED", "1") != "0" and nl >= 1 and fits}
+        st.zero_copy = mode["fused"]
+
+        def body_fused():
+            # csrc/rnnt_beam.hip: five launches -- one per LSTM layer (gather, both products, cell, scatter), the joint input, the
+            # output layer, the pick (log-softmax + blank + top-k into the result record)
+            from .. import lib
+            with self._scope():
+                # zero-copy hand-off: the kernels read the control words straight from the PINNED host record (each word once,
+                # through LDS) and the pick kernel writes the result record into pinned host memory -- no upload / download
+                # launches (two ~5 us copy kernels + their enqueue per round)
+                dtc = ops.dt(st.ph[0])
+                words = lambda base: tuple(c_void_p(base.data_ptr() + 8 * o) for o in (0, 16, 32, 48))
+                h_ids, h_src, h_dst, _ = words(st.ctl_host)       # the first launch reads the host record (and copies it over) ...
+                p_ids, p_src, p_dst, p_t = words(st.ctl)          # ... the later ones its device twin
+                emb = A.w("decoder.embed.weight")
+                xtab, ldx, xidx = emb, emb.shape[1], h_ids
+                for l in range(nl):
+                    name = f"decoder.rnns.{l}"
+                    w_ih, w_hh = A.w(name + ".weight_ih_l0"), A.w(name + ".weight_hh_l0")
+                    first = l == 0
+                    lib.call("emoasr_rnnt_beam_lstm", dtc, nb, w_ih.shape[1], H, ops._p(xtab), ldx, xidx, ops._p(w_ih), ops._p(w_hh),
+                             ops._p(st.bias[l]), ops._p(st.ph[l]), ops._p(st.pc[l]), h_src if first else p_src,
+                             h_dst if first else p_dst, ops._p(st.ctl_host) if first else None, ops._p(st.ctl) if first else None,
+                             st.ctl.numel() if first else 0, ops._stream())
+                    xtab, ldx, xidx = st.ph[l], H, p_dst
+                hj = st.hj[:nb]
+                lib.call("emoasr_rnnt_beam_joint", dtc, nb, H, J, self._BEAM_TMAX, ops._p(st.ph[nl - 1]), p_dst,
+                         ops._p(A.w("decoder.w_dec.weight")), ops._p(A.p("decoder.w_dec.bias")), ops._p(st.e), p_t, ops._p(hj),
+                         ops._stream())
+                logits = ops.gemm_nt(hj, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+                lib.call("emoasr_rnnt_beam_pick", dtc, nb, logits.shape[1], beam_width, blank, ops._p(logits), logits.stride(0),
+                         ops._p(st.out_host), st.out_host.stride(0), ops._stream())
+
+        def body():
+            if mode["fused"]:
+                return body_fused()
+            with self._scope():
+                ids = st.ctl[:nb].to(torch.int32).view(1, nb)
+                src, dst, t = st.ctl[16:16 + nb], st.ctl[32:32 + nb], st.ctl[48:49]
+                prev = ([p.index_select(0, src) for p in st.ph], [p.index_select(0, src) for p in st.pc])
+                dout, (nh, nc), _ = self.rnnt_recurrency(ids, prev, False, False)
+                for l in range(nl):
+                    st.ph[l].index_copy_(0, dst, nh[l])
+                    st.pc[l].index_copy_(0, dst, nc[l])
+                g = ops.gemm_nt(dout.view(nb, H), A.w("decoder.w_dec.weight"), bias=A.p("decoder.w_dec.bias"))
+                h = ops.joint_tanh(st.e.index_select(0, t).view(1, 1, J), g.view(1, nb, J))
+                logits = ops.gemm_nt(h.view(nb, J), A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+                lp = ops.log_softmax(logits)
+                vals, idx, _ = ops.topk(lp[:, 1:], beam_width)
+                st.out[:nb, 0:1].copy_(lp[:, blank:blank + 1])
+                st.out[:nb, 1:1 + beam_width].copy_(vals)
+                st.out[:nb, 1 + beam_width:1 + 2 * beam_width].copy_(idx)
+
+        # the warm-up runs the body for real: give it control words of its own -- label 0, the zero state of slot 0 as source and
+        # the pool's reserved scratch slots as destination -- so that it never writes a slot a live hypothesis reads (the
+        # caller uploads the round's words after this call, before the replay)
+        st.ctl_host.zero_()
+        st.ctl_host[32:32 + 16] = torch.arange(self._BEAM_POOL - 16, self._BEAM_POOL)
+        st.ctl.copy_(st.ctl_host)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        from .. import lib
+        with torch.cuda.stream(side):
+            try:
+                body()   # warm-up outside the capture (allocator, lazy initialisation)
+            except lib.EmoasrHipError:
+                if not mode["fused"]:
+                    raise
+                mode["fused"] = st.zero_copy = False   # outside a fused kernel's limits: the launch chain's body
+                st.ctl.copy_(st.ctl_host)
+                body()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g_ = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_):
+            body()
+        st.graphs[key] = g_
+        return st, g_
+
+    def _rnnt_beam_search_graph(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
+        """the search of rnnt_beam_search with every expansion round's device work replayed from a HIP graph; the bookkeeping
+        (stable sort by float64 score, merge of equal label sequences by log-add, cut to the beam) stays on the host, as in the
+        reference and in _rnnt_beam_search_chain, whose arithmetic and launch order the captured body repeats."""
+        import numpy as np
+        with self._scope(), torch.no_grad():
+            A, J = self.arena, self.r_J
+            A.refresh_shadow()
+            T = eouts.shape[1]
+            e_all = ops.gemm_nt(eouts[0], A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias"))  # [T,J]
+            st, _ = self._rnnt_beam_round_graph(beam_width, 1, blank)
+            st.e[:T].copy_(e_all)
+            for l in range(self.r_nl):   # bias_ih + bias_hh of the current weights, into the buffers the captured launches read
+                st.bias[l].copy_(self._lstm_bias(f"decoder.rnns.{l}"))
+            for l in range(self.r_nl):   # slot 0: the zero state every search starts from
+                st.ph[l][0].zero_()
+                st.pc[l][0].zero_()
+            ctl, out = st.ctl_host.numpy(), st.out_host.numpy()
+            stream = torch.cuda.current_stream()
+            nslot = 1
+            beams = [([eos], 0.0, 0)]   # (hyp, score, slot of the LSTM state from BEFORE its last label)
+
+            def merge(cands):
+                seen = {}
+                for hyp, score, slot in cands:
+                    key = tuple(hyp)
+                    if key in seen:
+                        seen[key][1] = float(np.logaddexp(seen[key][1], score))
+                    else:
+                        seen[key] = [hyp, score, slot]
+                return [tuple(c) for c in seen.values()]
+
+            for t in range(T):
+                frame_out, live = [], beams
+                for v in range(num_expands):
+                    nb = len(live)
+                    if nb == 0:
+                        break
+                    _, graph = self._rnnt_beam_round_graph(beam_width, nb, blank)
+                    for i, (hyp, _, slot) in enumerate(live):
+                        ctl[i], ctl[16 + i], ctl[32 + i] = hyp[-1], slot, nslot + i
+                    ctl[48] = t
+                    if not st.zero_copy:
+                        st.ctl.copy_(st.ctl_host, non_blocking=True)
+                    graph.replay()
+                    if not st.zero_copy:
+                        st.out_host.copy_(st.out, non_blocking=True)
+                    stream.synchronize()
+                    host = out[:nb].astype(np.float64)
+                    last = v == num_expands - 1
+                    for i, (hyp, score, slot) in enumerate(live):
+                        frame_out.append((hyp, score + float(host[i, 0]), slot))
+                    grown = []
+                    if not last:
+                        for i, (hyp, score, slot) in enumerate(live):
+                            for k in range(beam_width):
+                                grown.append((hyp + [int(host[i, 1 + beam_width + k]) + 1], score + float(host[i, 1 + k]), nslot + i))
+                    nslot += nb
+                    grown.sort(key=lambda c: -c[1])
+                    live = merge(grown)[:beam_width]
+                frame_out.sort(key=lambda c: -c[1])
+                beams = merge(frame_out)[:beam_width]
+            if return_scores:
+                return [hyp for hyp, _, _ in beams], [score for _, score, _ in beams]
+            return [hyp for hyp, _, _ in beams]
+
+    def _rnnt_beam_search_chain(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
+        """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359).
+
+        eouts [1,T,d].  Per frame up to `num_expands` rounds; each round is one batched prediction-network
+        step over the live hypotheses (every hypothesis keeps the LSTM state from before its last label, as
+        the reference does), one joint + output GEMM, log-softmax and top-k on the device, and ONE D2H of
+        (blank score, k scores, k ids) per live hypothesis; bookkeeping (stable sort by float64 score, merge
+        of equal label sequences by log-add, cut to the beam) stays on the host like the reference.
+        Returns the surviving label sequences best-first, including the leading <sos>."""
+        import numpy as np
+        with self._scope(), torch.no_grad():
+            A, J, H, nl = self.arena, self.r_J, self.r_H, self.r_nl
+            A.refresh_shadow()
+            dev = eouts.device
+            T = eouts.shape[1]
+            e_all = ops.gemm_nt(eouts[0], A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias"))  # [T,J]
+            cdt = e_all.dtype
+            zero = ([torch.zeros(1, H, device=dev, dtype=cdt) for _ in range(nl)],
+                    [torch.zeros(1, H, device=dev, dtype=torch.float32) for _ in range(nl)])
+            beams = [([eos], 0.0, (zero, 0))]  # (hyp, score, (state tensors, row))
+
+            def merge(cands):
+                seen = {}
+                for hyp, score, st in cands:
+                    key = tuple(hyp)
+                    if key in seen:
+                        seen[key][1] = float(np.logaddexp(seen[key][1], score))
+                    else:
+                        seen[key] = [hyp, score, st]
+                return [tuple(c) for c in seen.values()]
+
+            def gather(live):
+                srcs = {id(st[0]): st[0] for _, _, st in live}
+                if len(srcs) == 1:
+                    (hs, cs), = srcs.values()
+                    rows = [st[1] for _, _, st in live]
+                    if rows == list(range(hs[0].shape[0])):
+                        return hs, cs
+                    ix = torch.tensor(rows, device=dev)
+                    return [h.index_select(0, ix) for h in hs], [c.index_select(0, ix) for c in cs]
+                hs = [torch.cat([st[0][0][l][st[1]:st[1] + 1] for _, _, st in live]) for l in range(nl)]
+                cs = [torch.cat([st[0][1][l][st[1]:st[1] + 1] for _, _, st in live]) for l in range(nl)]
+                return hs, cs
+
+            for t in range(T):
+                frame_out, live = [], beams
+                for v in range(num_expands):
+                    nb = len(live)
+                    if nb == 0:
+                        break
+                    prev = gather(live)
+                    ids = h2d_i32([[hyp[-1] for hyp, _, _ in live]], dev)  # [1,nb]
+                    dout, (nh, nc), _ = self.rnnt_recurrency(ids, prev, False, False)
+                    g = ops.gemm_nt(dout.view(nb, H), A.w("decoder.w_dec.weight"), bias=A.p("decoder.w_dec.bias"))
+                    h = ops.joint_tanh(e_all[t].view(1, 1, J), g.view(1, nb, J))
+                    logits = ops.gemm_nt(h.view(nb, J), A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+                    lp = ops.log_softmax(logits)
+                    last = v == num_expands - 1
+                    if last:
+                        host = lp[:, blank].cpu().double().numpy().reshape(nb, 1)
+                    else:
+                        vals, idx, _ = ops.topk(lp[:, 1:], beam_width)
+                        host = torch.cat([lp[:, blank:blank + 1], vals, idx.to(torch.float32)], 1).cpu().double().numpy()
+                    for i, (hyp, score, st) in enumerate(live):
+                        frame_out.append((hyp, score + float(host[i, 0]), st))
+                    grown = []
+                    if not last:
+                        after = (nh, nc)
+                        for i, (hyp, score, st) in enumerate(live):
+                            for k in range(beam_width):
+                                grown.append((hyp + [int(host[i, 1 + beam_width + k]) + 1],
+                                              score + float(host[i, 1 + k]), (after, i)))
+                    grown.sort(key=lambda c: -c[1])
+                    live = merge(grown)[:beam_width]
+                frame_out.sort(key=lambda c: -c[1])
+                beams = merge(frame_out)[:beam_width]
+            if return_scores:
+                return [hyp for hyp, _, _ in beams], [score for _, score, _ in beams]
+            return [hyp for hyp, _, _ in beams]

@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import lib, ops
+from .engine.arena import AttnStash, ConvStash, FFNStash, LayerRecord
 
 _ALIGN_T, _ALIGN_F = 64, 16  # elements: 128-byte (bf16) / 64-byte (f32) aligned slots
 
@@ -64,8 +65,8 @@ class _Layout:
 
 
 class LayerStash:
-    """What one layer's forward left behind; iterating yields the (s_ffm, s_att, s_conv, s_ff, s_fin) tuples
-    engine._backward expects, with tensor views built on first use."""
+    """What one layer's forward left behind; iterating yields the fields of the engine.arena.LayerRecord that
+    CTCEngine._backward expects, with tensor views built on first use."""
     __slots__ = ("wt", "wf", "lay", "x_in", "seeds", "_tup", "io", "B", "T", "sweep")
 
     def __init__(self, wt, wf, lay, x_in, seeds):
@@ -94,12 +95,13 @@ class LayerStash:
             tv, fv, s = self.tv, self.fv, self.seeds
             x0 = self.input()
             x1, x2, x3, x4 = tv("ffm_y"), tv("at_y"), tv("cv_y"), tv("ff_y")
-            s_ffm = (x0, fv("ffm_mean"), fv("ffm_rstd"), tv("ffm_h"), tv("ffm_u"), tv("ffm_a"), s[0], s[1])
-            s_att = (x1, fv("at_mean"), fv("at_rstd"), tv("at_h"), tv("qkv"), tv("pp"), tv("o"), fv("lse"), s[2], s[3], None)
-            s_conv = (x2, fv("cv_mean"), fv("cv_rstd"), tv("cv_h"), tv("g"), tv("gl"), tv("c"), fv("bmean"), fv("bvar"),
-                      tv("z"), s[4])
-            s_ff = (x3, fv("ff_mean"), fv("ff_rstd"), tv("ff_h"), tv("ff_u"), tv("ff_a"), s[5], s[6])
-            self._tup = (s_ffm, s_att, s_conv, s_ff, (x4, fv("fin_mean"), fv("fin_rstd")))
+            s_ffm = FFNStash(x0, fv("ffm_mean"), fv("ffm_rstd"), tv("ffm_h"), tv("ffm_u"), tv("ffm_a"), s[0], s[1])
+            s_att = AttnStash(x1, fv("at_mean"), fv("at_rstd"), tv("at_h"), tv("qkv"), tv("pp"), tv("o"), fv("lse"), s[2], s[3],
+                              None)
+            s_conv = ConvStash(x2, fv("cv_mean"), fv("cv_rstd"), tv("cv_h"), tv("g"), tv("gl"), tv("c"), fv("bmean"), fv("bvar"),
+                               tv("z"), s[4])
+            s_ff = FFNStash(x3, fv("ff_mean"), fv("ff_rstd"), tv("ff_h"), tv("ff_u"), tv("ff_a"), s[5], s[6])
+            self._tup = LayerRecord(s_ffm, s_att, s_conv, s_ff, (x4, fv("fin_mean"), fv("fin_rstd")))
         return iter(self._tup)
 
     def __getitem__(self, i):

@@ -2,7 +2,7 @@
 
 These classes exist so that `state_dict()` keys, shapes and default initialisation match
 the reference checkpoints.  They carry no compute: the HIP engine
-(emoasr_amd/engine.py) reads their parameters through the flat arena.  Calling them like
+(emoasr_amd/engine/) reads their parameters through the flat arena.  Calling them like
 an nn.Module is an error on purpose -- there is no eager/CPU fallback path.
 
 State-dict layout mirrored (reference file:line):

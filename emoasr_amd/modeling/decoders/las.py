@@ -5,7 +5,7 @@ attention) on the HIP engine.
     decoder.decode(eouts, elens, eouts_inter, beam_width, len_weight, ...)    -> (hyps, scores, None, None)
 
 The sub-modules carry the reference's names (nn.LSTMCell `rnns`, `score.w_key / w_query / w_conv / w_score / conv`, `intermed`,
-`output`, `ctc.output`), so its checkpoints load; they hold parameters only, the arithmetic runs in engine._LASMixin and
+`output`, `ctc.output`), so its checkpoints load; they hold parameters only, the arithmetic runs in engine/las.py and
 csrc/las.hip.  As in the reference, the attention weights are dropped with p = 0.1 in train mode -- AttentionLoc's constructor
 default, which LASDecoder never overrides and no config field reaches (`decoder.score.dropout_attn_rate` is the attribute).
 

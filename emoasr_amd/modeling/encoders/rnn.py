@@ -3,7 +3,7 @@
     encoder(xs, xlens) -> (eouts [B, max elens, enc_hidden_size], elens [B] int64, None)
 
 `rnns` holds one nn.LSTM(bidirectional=True, batch_first=True) per layer as a parameter container (state_dict keys
-encoder.rnns.{l}.{weight,bias}_{ih,hh}_l0[_reverse]); the compute is engine._RNNEncMixin over csrc/bilstm.hip.
+encoder.rnns.{l}.{weight,bias}_{ih,hh}_l0[_reverse]); the compute is engine/rnn_encoder.py over csrc/bilstm.hip.
 """
 import torch.nn as nn
 

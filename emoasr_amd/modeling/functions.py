@@ -71,7 +71,7 @@ def encoder_apply(enc, xs, xlens):
 
 
 def rnn_encoder_apply(enc, xs, xlens):
-    """RNNEncoder.forward on the engine (engine._RNNEncMixin) -> (eouts [B, max elens, H], elens, None); the output length and the
+    """RNNEncoder.forward on the engine (engine/rnn_encoder.py) -> (eouts [B, max elens, H], elens, None); the output length and the
     lengths are pad_packed_sequence's (input_layer "none": elens = xlens)"""
     eng = _engine_of(enc)
     xs = xs.to(torch.float32).contiguous()
@@ -337,7 +337,7 @@ def attn_decoder_logits(dec, eouts, elens, ys_in, ylens):
 
 
 # ---------------------------------------------------------------------------------------
-# LAS decoder: attention loss (+ auxiliary CTC) as one autograd node over the encoder output (engine._LASMixin)
+# LAS decoder: attention loss (+ auxiliary CTC) as one autograd node over the encoder output (engine/las.py)
 # ---------------------------------------------------------------------------------------
 class _LASDecoderFn(torch.autograd.Function):
     @staticmethod

@@ -51,9 +51,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ParamArena, h2d_i32
+from ..engine import ParamArena, _Stash, h2d_i32
 from ..ops import ACT_GELU
-from ..engine import _Stash
 from .blocks import _Holder
 
 
@@ -239,6 +238,19 @@ class ELECTRAModel(nn.Module):
             return super().load_state_dict(state_dict, strict)
         except RuntimeError:
             return self.dmodel.load_state_dict(state_dict, strict)  # a bare ElectraForPreTraining dict: the discriminator alone
+
+
+def lm_inputs(ys, ylens, vocab_size):
+    """token rows and their lengths as every LM takes them -> (ys int64 [B, max(ylens)] on the host, [length per row])"""
+    ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
+    if ylens is None:
+        yl = [ys.shape[1]] * ys.shape[0]      # (no mask: every position is a key)
+    else:
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        ys = ys[:, : max(yl)]      # (lm/modeling/rnn.py:37-39)
+    assert len(yl) == ys.shape[0] and min(yl) >= 1, "ylens: one length >= 1 per row"
+    assert 0 <= int(ys.min()) and int(ys.max()) < vocab_size, "token id outside the vocabulary"
+    return ys.contiguous(), yl
 
 
 class _Stack:
@@ -589,28 +601,16 @@ class LM(nn.Module):
         """the tied output projection + soft-max, reduced per row: labels int32 [M] (clamped), w f32 [M]
         -> (rows f32 [M] = -w[m] * log p(labels[m] | row m), head stash)"""
         A = self._arena
-        W, bias = A.w(self._PRE + "embeddings.word_embeddings.weight"), A.p(self._CP + "bias")
-        if self.fused_head and ops.ce_head_ok(t2, W):
-            rows, _, ctx = ops.ce_head_fwd(t2, W, bias, labels, w)
-            self.last_head = "fused"
-            return rows, ("fused", ctx)
-        logits = ops.gemm_nt(t2, W, bias=bias)
-        rows, _ = ops.lsm_loss(logits, labels, w, 0.0)
-        self.last_head = "materialised"
-        return rows, ("materialised", logits)
+        rows, head = ops.lm_head_fwd(self.fused_head, t2, A.w(self._PRE + "embeddings.word_embeddings.weight"),
+                                     A.p(self._CP + "bias"), labels, w)
+        self.last_head = head[0]
+        return rows, head
 
     def _inputs(self, ys, ylens):
-        ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
-        if ylens is None:
-            yl = [ys.shape[1]] * ys.shape[0]      # (no mask: every position is a key)
-        else:
-            yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
-            ys = ys[:, : max(yl)]
         P = self.params
+        ys, yl = lm_inputs(ys, ylens, P.vocab_size)
         assert ys.shape[1] <= P.max_seq_len, f"sequence length {ys.shape[1]} exceeds max_seq_len {P.max_seq_len}"
-        assert len(yl) == ys.shape[0] and min(yl) >= 1, "ylens: one length >= 1 per row"
-        assert 0 <= int(ys.min()) and int(ys.max()) < P.vocab_size, "token id outside the vocabulary"
-        return ys.contiguous(), yl
+        return ys, yl
 
     def forward(self, ys, ylens=None, labels=None, ps=None, plens=None):
         """lm/modeling/lm.py:45-46, transformer.py:35-56: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss});
@@ -698,12 +698,7 @@ class LM(nn.Module):
         word = pre + "embeddings.word_embeddings.weight"
         lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
         # ---- vocabulary head (tied to the word embedding: its weight gradient lands in the embedding's slot)
-        kind, hctx = st.head
-        if kind == "fused":
-            dt2 = ops.ce_head_bwd(st.t2, A.w(word), A.p(cp + "bias"), hctx, A.g(word), A.g(cp + "bias"), 1.0, g1)
-        else:
-            _, dz = ops.lsm_loss(hctx, st.lab, st.w, 0.0, True, 1.0, g1)
-            dt2 = lin_bwd(dz, st.t2, word, cp + "bias")
+        dt2 = ops.lm_head_bwd(st.head, st.t2, A.w(word), A.p(cp + "bias"), st.lab, st.w, A.g(word), A.g(cp + "bias"), g1)
         x, tu, t, mt, rt = st.tst
         dpre = ops.act_bwd(ln_bwd(dt2, t, cp + "transform.LayerNorm", mt, rt), tu, ACT_GELU)
         dx = lin_bwd(dpre, x, cp + "transform.dense.weight", cp + "transform.dense.bias")

@@ -30,9 +30,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..engine import ParamArena, _Stash, h2d_i32
-from ..recurrence import lstm_layer_bwd, lstm_layer_fwd
+from ..recurrence import lstm_stack_bwd, lstm_stack_fwd
 from .blocks import _Holder
-from .lm import _LMLossFn
+from .lm import _LMLossFn, lm_inputs
 
 
 class RNNLM(_Holder):
@@ -109,17 +109,6 @@ class RNNLanguageModel(nn.Module):
         A = self._arena
         return A.w(f"lm.rnns.weight_ih_l{l}"), A.w(f"lm.rnns.weight_hh_l{l}")
 
-    def _inputs(self, ys, ylens):
-        ys = (ys.cpu() if torch.is_tensor(ys) else torch.as_tensor(ys)).to(torch.int64)
-        if ylens is None:
-            yl = [ys.shape[1]] * ys.shape[0]
-        else:
-            yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
-            ys = ys[:, : max(yl)]      # (lm/modeling/rnn.py:37-39)
-        assert len(yl) == ys.shape[0] and min(yl) >= 1, "ylens: one length >= 1 per row"
-        assert 0 <= int(ys.min()) and int(ys.max()) < self.V, "token id outside the vocabulary"
-        return ys.contiguous(), yl
-
     # ---------------------------------------------------------------- sequence forward / backward, time-major
     def _encode(self, ids_tm, p, keep):
         """ids_tm int32 [N,B] on the device -> (dropout(top layer's h) [N*B, H], stash | None)"""
@@ -127,15 +116,9 @@ class RNNLanguageModel(nn.Module):
         N, B = ids_tm.shape
         s_emb = self._seed(1)
         x = ops.embed_fwd(ids_tm, A.w("lm.embed.weight"), None, 1.0, p, s_emb)     # [N,B,E], dropout fused
-        layers = []
-        for l in range(self.L):
-            w_ih, w_hh = self._w(l)
-            hseq, cseq, gact = lstm_layer_fwd(x, w_ih, w_hh, self._bias[l], None, None)
-            s_do = self._seed(10 + l)      # after layer l: between layers (nn.LSTM(dropout=)), and before `output` after the last
-            y = ops.scale_dropout(hseq, 1.0, p, s_do) if p > 0 else hseq
-            if keep:
-                layers.append((x, hseq, cseq, gact, s_do))
-            x = y
+        # dropout after layer l: between layers (nn.LSTM(dropout=)), and before `output` after the last
+        spec = [(*self._w(l), self._bias[l], self._seed(10 + l), None, None) for l in range(self.L)]
+        x, _, layers = lstm_stack_fwd(x, spec, p, keep)
         st = None
         if keep:
             st = _Stash()
@@ -146,19 +129,13 @@ class RNNLanguageModel(nn.Module):
         """output layer + soft-max, reduced per row: labels int32 [M] (clamped), w f32 [M] -> (rows f32 [M] = -w[m] log p(labels[m] | row m),
         head stash)"""
         A = self._arena
-        W, bias = A.w("lm.output.weight"), A.p("lm.output.bias")
-        if self.fused_head and ops.ce_head_ok(x, W):
-            rows, _, ctx = ops.ce_head_fwd(x, W, bias, labels, w)
-            self.last_head = "fused"
-            return rows, ("fused", ctx)
-        logits = ops.gemm_nt(x, W, bias=bias)
-        rows, _ = ops.lsm_loss(logits, labels, w, 0.0)
-        self.last_head = "materialised"
-        return rows, ("materialised", logits)
+        rows, head = ops.lm_head_fwd(self.fused_head, x, A.w("lm.output.weight"), A.p("lm.output.bias"), labels, w)
+        self.last_head = head[0]
+        return rows, head
 
     def forward(self, ys, ylens=None, labels=None, ps=None, plens=None):
         """lm/modeling/rnn.py:36-53: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss})"""
-        ys, yl = self._inputs(ys, ylens)
+        ys, yl = lm_inputs(ys, ylens, self.V)
         A = self._prepare()
         if labels is None:
             B, N = ys.shape
@@ -203,32 +180,22 @@ class RNNLanguageModel(nn.Module):
             A.attach_grads()
             g1 = g.to(torch.float32).reshape(1)
             N, B = st.ids.shape
-            W, wname, bname = A.w("lm.output.weight"), "lm.output.weight", "lm.output.bias"
-            kind, hctx = st.head
-            if kind == "fused":
-                dy = ops.ce_head_bwd(st.x, W, A.p(bname), hctx, A.g(wname), A.g(bname), 1.0, g1)
-            else:
-                _, dz = ops.lsm_loss(hctx, st.lab, st.w, 0.0, True, 1.0, g1)
-                ops.gemm_tn(dz, st.x, out=A.g(wname), accumulate=True, colsum=A.g(bname))
-                dy = ops.gemm_nn(dz, W)
-            dy = dy.view(N, B, self.H)
-            for l in reversed(range(self.L)):
-                x_in, hseq, cseq, gact, s_do = st.layers[l]
-                w_ih, w_hh = self._w(l)
-                dh = ops.scale_dropout(dy, 1.0, st.p, s_do) if st.p > 0 else dy
-                # one set of column sums for both biases: they enter the gates as a sum, their gradients are the same numbers
-                db = torch.zeros(4 * self.H, device=dy.device, dtype=torch.float32)
-                dy = lstm_layer_bwd(dh, x_in, hseq, cseq, gact, None, None, w_ih, w_hh, A.g(f"lm.rnns.weight_ih_l{l}"),
-                                    A.g(f"lm.rnns.weight_hh_l{l}"), db, None)
-                A.g(f"lm.rnns.bias_ih_l{l}").add_(db)
-                A.g(f"lm.rnns.bias_hh_l{l}").add_(db)
+            wname, bname = "lm.output.weight", "lm.output.bias"
+            dy = ops.lm_head_bwd(st.head, st.x, A.w(wname), A.p(bname), st.lab, st.w, A.g(wname), A.g(bname), g1)
+            # one set of column sums for both biases: they enter the gates as a sum, their gradients are the same numbers
+            db = [torch.zeros(4 * self.H, device=dy.device, dtype=torch.float32) for _ in range(self.L)]
+            grads = [(A.g(f"lm.rnns.weight_ih_l{l}"), A.g(f"lm.rnns.weight_hh_l{l}"), db[l], None) for l in range(self.L)]
+            dy = lstm_stack_bwd(dy.view(N, B, self.H), st.layers, grads, st.p)
+            for l in range(self.L):
+                A.g(f"lm.rnns.bias_ih_l{l}").add_(db[l])
+                A.g(f"lm.rnns.bias_hh_l{l}").add_(db[l])
             ops.embed_bwd(st.ids, dy, 1.0, A.g("lm.embed.weight"), st.p, st.s_emb)
 
     # ---------------------------------------------------------------- scoring
     def token_logprobs(self, ys, ylens, labels):
         """log p(labels[b,i] | ys[b,:i+1]) for every position with labels != -100 (zeros elsewhere) -> float64 [B, N] on the HOST
         (the Transformer LM's definition; one device-to-host copy of the row values)"""
-        ys, yl = self._inputs(ys, ylens)
+        ys, yl = lm_inputs(ys, ylens, self.V)
         labels = (labels.cpu() if torch.is_tensor(labels) else torch.as_tensor(labels)).to(torch.int64)[:, : ys.shape[1]]
         A = self._prepare()
         dev = A.flat.device

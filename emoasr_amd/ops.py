@@ -3,7 +3,7 @@
 torch is used only as the owner of device memory and of the current HIP stream; every
 function here enqueues hand-written HIP kernels from libemoasr_hip.so.  Nothing in this
 module has autograd: forward and backward ops are separate entry points and the model
-code (emoasr_amd/engine.py) sequences them explicitly.
+code (emoasr_amd/engine/) sequences them explicitly.
 """
 import ctypes
 from ctypes import byref, c_void_p
@@ -1276,6 +1276,26 @@ def ce_head_bwd(x, w, bias, ctx, dw, dbias, gscale=1.0, gscale_dev=None, chunk=N
             gemm_nn(dz[:n], w, out=dx[r0:r0 + n])
         gemm_tn(dz[:n], x[r0:r0 + n], out=dw, accumulate=True, colsum=dbias)
     return dx
+
+
+def lm_head_fwd(fused_wanted, x, w, bias, labels, wrow):
+    """the LMs' output projection + soft-max reduced per row (logit-free where wanted and ce_head_ok); labels int32 [M] (clamped), wrow
+    f32 [M] -> (rows f32 [M] = -wrow[m] * log p(labels[m] | row m), head stash for lm_head_bwd: ("fused" | "materialised", ...))"""
+    if fused_wanted and ce_head_ok(x, w):
+        rows, _, ctx = ce_head_fwd(x, w, bias, labels, wrow)
+        return rows, ("fused", ctx)
+    logits = gemm_nt(x, w, bias=bias)
+    rows, _ = lsm_loss(logits, labels, wrow, 0.0)
+    return rows, ("materialised", logits)
+
+
+def lm_head_bwd(head, x, w, bias, labels, wrow, dw, dbias, gscale_dev):
+    """gradients of sum(rows) * gscale_dev of lm_head_fwd: dw f32 [V, K] and dbias f32 [V] are ACCUMULATED into, -> dx [M, K]"""
+    if head[0] == "fused":
+        return ce_head_bwd(x, w, bias, head[1], dw, dbias, 1.0, gscale_dev)
+    _, dz = lsm_loss(head[1], labels, wrow, 0.0, True, 1.0, gscale_dev)
+    gemm_tn(dz, x, out=dw, accumulate=True, colsum=dbias)
+    return gemm_nn(dz, w)
 
 
 # ---- RNN LM: one shallow-fusion step for up to 32 hypotheses (csrc/rnnlm.hip) ------------------------------------------------------

@@ -1,13 +1,20 @@
-"""One unidirectional LSTM layer over a whole sequence, TIME-MAJOR, forward and backward -- the recurrence shared by the transducer's
-prediction network (engine._RNNTMixin) and the RNN LM (modeling/rnnlm.py).
+"""Unidirectional LSTM layers over a whole sequence, TIME-MAJOR, forward and backward: one layer (lstm_layer_fwd / lstm_layer_bwd) and
+the teacher-forced stack of them with dropout after every layer (lstm_stack_fwd / lstm_stack_bwd) -- shared by the transducer's
+prediction network (engine/rnnt.py), the RNN LM (modeling/rnnlm.py) and the LAS decoder's layers 1 and up (engine/las.py).  The
+embedding in front of the stack, and its gradient, stay with the callers.
 
 The input projection is one product over all positions; the recurrence is one cooperative launch (csrc/lstm_coop.hip) where
 ops.lstm_seq_supported says so (bf16, H % 32 == 0, H <= 512, option "lstm_coop"), else the per-position chain: recurrent product
 with the stored pre-activation as its residual, then the cell kernel.  Hidden sizes above the cooperative kernel's 512 therefore
 run the chain (2 launches per position)."""
+from typing import NamedTuple
+
 import torch
 
 from . import ops
+
+# one layer of lstm_stack_fwd for lstm_stack_bwd: input, lstm_layer_fwd's outputs, the output dropout's seed, initial state | None, weights
+LSTMRecord = NamedTuple("LSTMRecord", [(f, object) for f in "x hseq cseq gact s_do h0 c0 w_ih w_hh".split()])
 
 
 def lstm_layer_fwd(x, w_ih, w_hh, bias, h0, c0):
@@ -55,3 +62,27 @@ def lstm_layer_bwd(dh_seq, x_in, hseq, cseq, gact, h0, c0, w_ih, w_hh, g_w_ih, g
     if U > 1:
         ops.gemm_tn(dgp[1:].reshape((U - 1) * B, 4 * H), hseq[:-1].reshape((U - 1) * B, H), out=g_w_hh, accumulate=True)
     return ops.gemm_nn(dgp2, w_ih).view(U, B, nin)
+
+
+def lstm_stack_fwd(x, layers, p, keep):
+    """x [U,B,nin]; layers: per layer (w_ih, w_hh, bias, seed, h0 | None, c0 | None), taken one at a time as the stack reaches the
+    layer (a caller whose bias sum is a launch of its own hands in a generator); p: dropout rate on every layer's output
+    -> (dropped output of the top layer [U,B,H], ([h_final per layer], [c_final per layer]), [LSTMRecord per layer] if keep else None)"""
+    hs, cs, records = [], [], []
+    for w_ih, w_hh, bias, seed, h0, c0 in layers:
+        hseq, cseq, gact = lstm_layer_fwd(x, w_ih, w_hh, bias, h0, c0)
+        hs.append(hseq[-1])
+        cs.append(cseq[-1])
+        if keep:
+            records.append(LSTMRecord(x, hseq, cseq, gact, seed, h0, c0, w_ih, w_hh))
+        x = ops.scale_dropout(hseq, 1.0, p, seed) if p > 0 else hseq
+    return x, (hs, cs), (records if keep else None)
+
+
+def lstm_stack_bwd(dy, records, grads, p):
+    """dy [U,B,H]: gradient w.r.t. lstm_stack_fwd's output; grads: per layer (g_w_ih, g_w_hh, g_b_ih, g_b_hh | None), accumulated
+    into (lstm_layer_bwd) -> gradient w.r.t. the stack's input [U,B,nin]"""
+    for r, g in zip(reversed(records), reversed(grads)):
+        dh_seq = ops.scale_dropout(dy, 1.0, p, r.s_do) if p > 0 else dy
+        dy = lstm_layer_bwd(dh_seq, r.x, r.hseq, r.cseq, r.gact, r.h0, r.c0, r.w_ih, r.w_hh, *g)
+    return dy

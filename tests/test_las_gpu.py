@@ -1,4 +1,4 @@
-"""The LAS decoder (decoder_type "las": emoasr_amd/modeling/decoders/las.py, engine._LASMixin, csrc/las.hip) on the device against
+"""The LAS decoder (decoder_type "las": emoasr_amd/modeling/decoders/las.py, engine/las.py, csrc/las.hip) on the device against
 the reference's values (tests/golden/las_tiny*.npz, written by tests/golden/make_golden_las.py) and against tests/las_ref.py.
 
 Model bars are those of tests/test_p2w_gpu.py: loss 1e-3 (f32) / 2e-2 (bf16) relative, f32 gradients 5e-3 in the max-error form with

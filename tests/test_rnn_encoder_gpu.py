@@ -1,4 +1,4 @@
-"""The RNN encoder (encoder_type "rnn": bidirectional LSTMs over packed sequences, csrc/bilstm.hip + engine._RNNEncMixin) on the GPU.
+"""The RNN encoder (encoder_type "rnn": bidirectional LSTMs over packed sequences, csrc/bilstm.hip + engine/rnn_encoder.py) on the GPU.
 
 Bars: f32 / f32x3 as tests/test_model_gpu.py (1e-3 on loss / logits, greedy ids bit-exact, gradients to rtol 1e-3; the layer alone
 to 1e-5); bf16 loss 2e-2, outputs 6e-2 of their range, gradients by cosine."""

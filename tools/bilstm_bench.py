@@ -1,4 +1,4 @@
-"""Device time of the RNN encoder's bidirectional LSTM stack (engine._RNNEncMixin) per micro-batch, forward and forward + backward,
+"""Device time of the RNN encoder's bidirectional LSTM stack (engine/rnn_encoder.py) per micro-batch, forward and forward + backward,
 for the cooperative recurrence (csrc/lstm_coop.hip) and the per-step chain (csrc/bilstm.hip, option lstm_coop = 0), at a
 LibriSpeech-like shape (bf16, B 36, T' 350 frames after subsampling, ragged lengths).  Events around each call; median, min and
 max over the runs.  The Conv2d
