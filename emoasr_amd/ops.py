@@ -1032,6 +1032,11 @@ def lstm_seq_supported(x, B, H):
 def lstm_seq_fwd(pre, w_hh, h0, c0, hseq, cseq, gact):
     """pre [U,B,4H] (input projection + biases) -> hseq [U,B,H], cseq f32 [U,B,H], gact [U,B,4H] in one launch"""
     U, B, H4 = pre.shape
+    for t in (pre, w_hh, hseq, cseq, gact) + tuple(t for t in (h0, c0) if t is not None):
+        assert t.is_contiguous()
+    for t in (w_hh, hseq, gact) + ((h0,) if h0 is not None else ()):
+        assert t.dtype == pre.dtype, (t.dtype, pre.dtype)
+    assert cseq.dtype == torch.float32 and (c0 is None or c0.dtype == torch.float32)
     lib.call("emoasr_lstm_seq_fwd", dt(pre), U, B, H4 // 4, _p(pre), _p(w_hh), _p(h0), _p(c0), _p(hseq), _p(cseq), _p(gact), _stream())
 
 
@@ -1041,6 +1046,11 @@ _lstm_ws = {}
 def lstm_seq_bwd(dh_seq, gact, cseq, c0, w_hh, dgp):
     """dh_seq [U,B,H] (gradient w.r.t. the layer outputs) -> dgp [U,B,4H] (w.r.t. the gate pre-activations) in one launch"""
     U, B, H = dh_seq.shape
+    for t in (dh_seq, gact, cseq, w_hh, dgp) + ((c0,) if c0 is not None else ()):
+        assert t.is_contiguous()
+    for t in (gact, w_hh, dgp):
+        assert t.dtype == dh_seq.dtype, (t.dtype, dh_seq.dtype)
+    assert cseq.dtype == torch.float32 and (c0 is None or c0.dtype == torch.float32)
     need = lib.size_query("emoasr_lstm_seq_bwd_ws_bytes", B, H)
     key = (dh_seq.device, need)
     ws = _lstm_ws.get(key)

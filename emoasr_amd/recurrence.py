@@ -52,7 +52,7 @@ def lstm_layer_bwd(dh_seq, x_in, hseq, cseq, gact, h0, c0, w_ih, w_hh, g_w_ih, g
         dh_rec = None
         for u in reversed(range(U)):
             ops.lstm_cell_bwd(dh_seq[u], dh_rec, dc, gact[u], cseq[u - 1] if u > 0 else c0, cseq[u], dgp[u])
-            if u > 0 or h0 is not None:
+            if u > 0:
                 dh_rec = ops.gemm_nn(dgp[u], w_hh)
     nin = x_in.shape[-1]
     dgp2 = dgp.view(U * B, 4 * H)
@@ -61,6 +61,9 @@ def lstm_layer_bwd(dh_seq, x_in, hseq, cseq, gact, h0, c0, w_ih, w_hh, g_w_ih, g
         ops.colsum(dgp2, out=g_b_hh, accumulate=True)
     if U > 1:
         ops.gemm_tn(dgp[1:].reshape((U - 1) * B, 4 * H), hseq[:-1].reshape((U - 1) * B, H), out=g_w_hh, accumulate=True)
+    if h0 is not None:
+        # position 0's gates contain h0 . W_hh^T
+        ops.gemm_tn(dgp[0], h0, out=g_w_hh, accumulate=True)
     return ops.gemm_nn(dgp2, w_ih).view(U, B, nin)
 
 
