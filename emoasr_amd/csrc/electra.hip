@@ -8,23 +8,10 @@
 //   emoasr_bce_head_fwd     z = h . w_p + b_p per row, BCE-with-logits rows, optionally sigmoid(z)
 //   emoasr_bce_head_bwd     dz = w (sigmoid(z) - y) g;  dh = dz w_p;  dw_p += sum_m dz h;  db_p += sum_m dz
 #include "common.h"
+#include "gumbel.h"
 #include "../../include/emoasr_hip.h"
 
 namespace {
-
-// Gumbel(0, 1) variate of element idx: k = 24-bit counter hash, u = (k + 0.5) * 2^-24 in (0, 1), g = -log(-log(u)).
-// k + 0.5 has 25 significant bits: for u >= 0.5 the complement 1 - u = (2^24 - 1 - k + 0.5) * 2^-24 is formed instead (exact in
-// f32) and -log(u) = -log1p(-(1 - u)), so no u rounds to 1 and every g is finite: -2.86 < g < 17.4.
-__device__ __forceinline__ float gumbel_of(uint64_t seed, uint64_t idx) {
-  const uint32_t k = dropout_hash(seed, idx) & 0xFFFFFFu;
-  float e;
-  if (k < 0x800000u) {
-    e = -logf(((float)k + 0.5f) * 5.9604644775390625e-8f);
-  } else {
-    e = -log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 5.9604644775390625e-8f));
-  }
-  return -logf(e);
-}
 
 // One block per row.  Every thread walks its columns once with a running maximum and a running sum of exp(x - maximum) (rescaled
 // when the maximum moves: rare, so the precise expf there costs nothing), its best perturbed logit and the label's logit; the block

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include "mma.h"
 #include "lds_dma.h"
+#include "gumbel.h"
 #include "../../include/emoasr_hip.h"
 
 namespace {
@@ -55,6 +56,9 @@ struct BigDgrad {  // data gradient, one entry per output-parity class (pt, pf)
 //                     row constants (already scaled) in coef[n, 4], the label column in ycol[n];
 //   mode 3 (CTC head): the product is stored AND the partials of mode 1 are produced (of the values as rounded to bf16): the
 //                     vocabulary projection and the soft-max denominators in one pass over the logits.
+//   mode 7 (cross-entropy head that also samples): mode 1 without zb, and per row and chunk the best PERTURBED logit
+//                     p[v] = z32[n, v] + gumbel_of(seed, (row0 + n) * V + v) (z32 = f32 accumulator + bias, never rounded) and its
+//                     column, ties to the lower column -> part[chunk, n, 4] = (max, sum, best p, column as an int bit pattern).
 struct BigRnnt {
   int mode, Tn, U, Lmax, blank, nchunk;
   long row0;               // cell index of row 0 of this launch
@@ -62,6 +66,7 @@ struct BigRnnt {
   const int* labels; const int* ylens;
   float* part; float* zb; float* zy;
   const float* coef; const int* ycol;
+  unsigned long long seed;   // mode 7: the sampler's seed (row0 = the noise row of row 0)
 };
 struct BigArgs {
   int M, N, K;
@@ -91,12 +96,22 @@ __device__ __forceinline__ float max8(float x) {
 __device__ __forceinline__ float sum8(float x) {
   x += dpp8<0xB1>(x); x += dpp8<0x4E>(x); return x + dpp8<0x141>(x);
 }
+// (value, column) arg-max over the same eight lanes, the steps of max8; equal values keep the lower column, so every lane of the
+// group ends with the same pair
+template <int CTRL> __device__ __forceinline__ void argmax_step(float& v, int& c) {
+  const float ov = dpp8<CTRL>(v);
+  const int oc = __builtin_amdgcn_update_dpp(0, c, CTRL, 0xF, 0xF, true);
+  if (ov > v || (ov == v && oc < c)) { v = ov; c = oc; }
+}
+__device__ __forceinline__ void argmax8(float& v, int& c) {
+  argmax_step<0xB1>(v, c); argmax_step<0x4E>(v, c); argmax_step<0x141>(v, c);
+}
 
 // AMODE 0: plain row-major A.  1: Conv2d forward gather.  2: Conv2d data gradient (parity classes).
 // NW = waves per workgroup: 8 (2 x 4 waves of (BM/2) x 64) or, round 4, 4 (2 x 2 waves of (BM/2) x 128 -- one wave per SIMD with
 // 256 accumulator registers at BM = 256: per k-tile and wave (BM/2 + 128) * 128 B of LDS reads for TWICE the flops of the 8-wave
 // layout, whose fragment reads alone need 85 % of the LDS bandwidth at the MFMA peak).
-// MODE (AMODE 0 only): the epilogue variant -- 0 general, 1 / 2 / 3 the transducer / CTC head modes of BigRnnt -- as a TEMPLATE
+// MODE (AMODE 0 only): the epilogue variant -- 0 general, 1 / 2 / 3 / 7 the transducer / CTC / sampling head modes of BigRnnt -- as a TEMPLATE
 // parameter: with the mode a run-time field every instantiation carried all four fully unrolled epilogues (20 k instructions
 // for TMW = 4; a wave runs the epilogue once per tile, straight through: SQ_WAIT_INST_ANY was 43 % of the wave cycles of the
 // head-gradient launch, i.e. instruction fetch).
@@ -479,6 +494,78 @@ __global__ __launch_bounds__(NW * 64) void big_nt_kernel(const BigArgs g) {
     const emoasr_epilogue_t& ep = g.ep;
     bf16* Cp = static_cast<bf16*>(g.C);
     bf16* pre_out = static_cast<bf16*>(ep.pre_out);
+    if constexpr (MODE == 7) {
+      // The cross-entropy head that also samples: mode 1's partials (max, sum exp(z - max)) and z[n, ycol[n]], and per row and chunk
+      // the best perturbed logit z32 + gumbel_of(...) with its column.  The pass loop and the noise loop are ROLLED: unrolled like
+      // mode 1's they put 16 * TMW copies of the hash and its three logarithms into the kernel (165 KB of code at TMW = 8 against
+      // mode 1's 25 KB -- the instruction-fetch cost described above).  z32 therefore goes back into the lane's own eight slab
+      // entries (no other lane reads them) and the noise loop takes one entry at a time.
+      const BigRnnt& rn = g.rn;
+      const int chunk0 = ncol0 >> 6;
+      int* ycs = reinterpret_cast<int*>(smem + 40960 + BM * 16);    // [BM], behind the wave-private slabs as in mode 1
+      if (tid < BM) ycs[tid] = (m0 + tid < M) ? rn.ycol[m0 + tid] : -1;
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < TMW; ++i) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) *reinterpret_cast<f32x4*>(fslab + frow * FLD + j * 16 + 4 * (lane >> 4)) = acc[i][j];
+#pragma unroll 1
+        for (int hh = 0; hh < HH; ++hh) {
+          const int id = lane + 64 * hh, row = id / LPR, cc = id % LPR;
+          const int chunk = chunk0 + (cc >> 3);   // (eight lanes = one 64-column chunk of the row)
+          float* seg = fslab + row * FLD + cc * 8;
+          const f32x4 v0 = *reinterpret_cast<const f32x4*>(seg);
+          const f32x4 v1 = *reinterpret_cast<const f32x4*>(seg + 4);
+          const int grow = m0 + wr * (BM / 2) + i * 16 + row;
+          const int col = ncol0 + cc * 8;
+          const bool rok = grow < M, cok = col < g.N;   // (N % 8 == 0: a lane's eight columns are all inside or all outside)
+          float v[8];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { v[e] = v0[e]; v[4 + e] = v1[e]; }
+          if (ep.bias && cok) {
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(ep.bias + col);
+            const f32x4 b1 = *reinterpret_cast<const f32x4*>(ep.bias + col + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] += b0[e]; v[4 + e] += b1[e]; }
+          }
+          float m = -INFINITY, sm = 0.f;
+          if (cok) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) m = fmaxf(m, v[e]);
+          }
+          m = max8(m);
+          if (cok) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm += __expf(v[e] - m);
+          }
+          sm = sum8(sm);
+          *reinterpret_cast<f32x4*>(seg) = f32x4{v[0], v[1], v[2], v[3]};
+          *reinterpret_cast<f32x4*>(seg + 4) = f32x4{v[4], v[5], v[6], v[7]};
+          // a lane's columns ascend, so its first maximum stays; lanes outside the matrix carry (-inf, INT_MAX) into the exchange
+          // and never win
+          float best = -INFINITY;
+          int bcol = 0x7fffffff;
+          if (rok && cok) {
+            const uint64_t base = (uint64_t)(rn.row0 + grow) * (uint64_t)g.N + (uint64_t)col;
+#pragma unroll 1
+            for (int e = 0; e < 8; ++e) {
+              const float pv = seg[e] + gumbel_of(rn.seed, base + (uint64_t)e);
+              if (pv > best) { best = pv; bcol = col + e; }
+            }
+          }
+          argmax8(best, bcol);
+          if (rok) {
+            // chunk-major table, as mode 1's (the last column tile may reach past ceil(N / 64) chunks)
+            if ((cc & 7) == 0 && chunk < rn.nchunk)
+              *reinterpret_cast<f32x4*>(rn.part + ((long)chunk * rn.part_rows + rn.part_row0 + grow) * 4) =
+                  f32x4{m, sm, best, __builtin_bit_cast(float, bcol)};
+            const int ky = ycs[grow - m0] - col;
+            if (cok && ky >= 0 && ky < 8) rn.zy[grow] = seg[ky];
+          }
+        }
+      }
+      return;
+    }
     if constexpr (MODE >= 1 && MODE <= 3) {
       const BigRnnt& rn = g.rn;
       const int chunk0 = ncol0 >> 6;
@@ -786,6 +873,7 @@ int launch_big_bm(const BigArgs& a, int bm, int tiles, hipStream_t s) {
       case 1: return launch_big_bm_<0, 8, 1>(a, bm, tiles, s);
       case 2: return launch_big_bm_<0, 8, 2>(a, bm, tiles, s);
       case 3: return launch_big_bm_<0, 8, 3>(a, bm, tiles, s);
+      case 7: return launch_big_bm_<0, 8, 7>(a, bm, tiles, s);
       default: break;
     }
     const emoasr_epilogue_t& ep = a.ep;
@@ -973,6 +1061,33 @@ __global__ __launch_bounds__(64) void ce_fold_kernel(int rows, int nchunk, const
   if (loss) loss[row] = wrow ? -wrow[row] * lp : -lp;
 }
 
+// ce_fold_kernel over the four-float entries of the sampling head: also sample[row] = the column of the best perturbed logit over the
+// chunks; chunks ascend, so a strict comparison keeps the lowest column among equal values
+__global__ __launch_bounds__(64) void ce_sample_fold_kernel(int rows, int nchunk, int V, const float* __restrict__ part,
+                                                            const float* __restrict__ zy, const float* __restrict__ wrow,
+                                                            float* __restrict__ lse, float* __restrict__ logp,
+                                                            float* __restrict__ loss, int* __restrict__ sample) {
+  const int row = blockIdx.x * 64 + threadIdx.x;
+  if (row >= rows) return;
+  const f32x4* pp = reinterpret_cast<const f32x4*>(part) + row;
+  float m = -INFINITY, s = 0.f, best = -INFINITY;
+  int col = 0;
+  for (int c = 0; c < nchunk; ++c) {
+    const f32x4 v = pp[(long)c * rows];
+    const float mn = fmaxf(m, v[0]);
+    s = s * expf(m - mn) + v[1] * expf(v[0] - mn);
+    m = mn;
+    const float colbits = v[3];   // (a copy: __builtin_bit_cast of the vector ELEMENT itself read element 0)
+    if (v[2] > best) { best = v[2]; col = __float_as_int(colbits); }
+  }
+  const float l = m + logf(s);
+  const float lp = zy[row] - l;
+  lse[row] = l;
+  if (logp) logp[row] = lp;
+  if (loss) loss[row] = wrow ? -wrow[row] * lp : -lp;
+  sample[row] = min(max(col, 0), V - 1);
+}
+
 __global__ __launch_bounds__(256) void ce_coef_kernel(int n, const float* __restrict__ lse, const float* __restrict__ wrow,
                                                       float gscale, const float* __restrict__ gscale_dev,
                                                       float* __restrict__ coef) {
@@ -997,6 +1112,28 @@ extern "C" int emoasr_ce_head_fwd(int dtype, int nrows, int V, int K, const void
   rn.part = part; rn.part_rows = nrows; rn.part_row0 = 0; rn.zb = zscr; rn.zy = zscr + nrows; rn.ycol = ycol;
   if (rnnt_head_launch(nrows, V, K, x, w, bias, nullptr, V, rn, s)) return 1;
   ce_fold_kernel<<<cdiv(nrows, 64), 64, 0, s>>>(nrows, rn.nchunk, part, zscr + nrows, wrow, lse, logp, loss);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+// emoasr_ce_head_fwd that also draws one Gumbel-max sample per row in the product's epilogue (mode 7): sample[n] = argmax_v (z32[n, v] +
+// g(seed, row0 + n, v)) with the g of emoasr_gumbel_noise, ties to the lowest column.  part: scratch [ceil(V / 64), nrows, 4] f32;
+// zscr: scratch [nrows] f32.  (lse, ycol, wrow) are emoasr_ce_head_grad's context as after emoasr_ce_head_fwd.
+extern "C" int emoasr_ce_head_sample_fwd(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias,
+                                         const int* labels, const float* wrow, float* part, float* zscr, int* ycol, float* lse,
+                                         float* logp, float* loss, uint64_t seed, long row0, int* sample, void* stream) {
+  EMO_CHECK(dtype == EMO_BF16, "ce_head_sample_fwd: bf16 only");
+  if (nrows == 0) return 0;
+  EMO_CHECK(labels && part && zscr && ycol && lse && sample, "ce_head_sample_fwd: labels / part / zscr / ycol / lse / sample required");
+  EMO_CHECK(row0 >= 0, "ce_head_sample_fwd: row0=%ld", row0);
+  hipStream_t s = (hipStream_t)stream;
+  ce_ycol_kernel<<<cdiv(nrows, 256), 256, 0, s>>>(nrows, V, labels, ycol);
+  EMO_LAUNCH_CHECK();
+  BigRnnt rn{};
+  rn.mode = 7; rn.blank = 0; rn.nchunk = cdiv(V, 64); rn.row0 = row0; rn.seed = seed;
+  rn.part = part; rn.part_rows = nrows; rn.part_row0 = 0; rn.zy = zscr; rn.ycol = ycol;
+  if (rnnt_head_launch(nrows, V, K, x, w, bias, nullptr, V, rn, s)) return 1;
+  ce_sample_fold_kernel<<<cdiv(nrows, 64), 64, 0, s>>>(nrows, rn.nchunk, V, part, zscr, wrow, lse, logp, loss, sample);
   EMO_LAUNCH_CHECK();
   return 0;
 }

@@ -392,10 +392,11 @@ class P2WDataset:
     """lm/datasets.py:123-243: a TSV with columns utt_id / token_id / phone_token_id (and ylen / plen with params.bucket_shuffle).
     Items: (utt_id, p int64, plen, y_in int64, ylen, label | None).  phase "train": the phones go through TextAugment when
     params.text_augment; "pbert" masks the words (create_masked_lm_label, or create_masked_lm_label_insert with
-    params.mask_insert_poisson_lam > 0); "pctc" has y_in = y and label = p, as the reference does.  Any other phase: no label."""
+    params.mask_insert_poisson_lam > 0), and so does "pelectra" (modeling/pelectra.py: lm/datasets.py:159,195); "pctc" has y_in = y and
+    label = p, as the reference does.  Any other phase: no label."""
 
     def __init__(self, params, data_path, phase="train", size=-1):
-        if params.lm_type not in ("pbert", "pctc"):
+        if params.lm_type not in ("pbert", "pctc", "pelectra"):
             raise NotImplementedError(f"emoasr_amd: P2WDataset for lm_type={params.lm_type!r} is outside the HIP hot path")
         columns = ["utt_id", "token_id", "phone_token_id"] + (["ylen", "plen"] if getattr(params, "bucket_shuffle", False) else [])
         data = _read_table(data_path)[columns]
@@ -409,7 +410,8 @@ class P2WDataset:
         self.phase = phase
         self.data = data[:size] if size > 0 else data
         self.textaug = TextAugment(params) if phase == "train" and params.text_augment else None
-        if self.lm_type == "pbert":
+        self.masked = self.lm_type in ("pbert", "pelectra")
+        if self.masked:
             self.mask_id = params.mask_id
             assert hasattr(params, "num_to_mask") ^ hasattr(params, "mask_proportion")     # (lm/datasets.py:162)
             self.num_to_mask = getattr(params, "num_to_mask", -1)
@@ -430,7 +432,7 @@ class P2WDataset:
         p = torch.tensor([int(t) for t in str(row["phone_token_id"]).split()], dtype=torch.long)
         if self.textaug is not None:
             p = self.textaug(p)
-        if self.phase == "train" and self.lm_type == "pbert":
+        if self.phase == "train" and self.masked:
             if self.mask_insert_poisson_lam > 0:
                 y_in, label = create_masked_lm_label_insert(y, self.mask_id, self.num_to_mask, self.mask_proportion,
                                                             self.random_num_to_mask, self.mask_insert_poisson_lam, self.pad_id,

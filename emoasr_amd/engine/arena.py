@@ -187,6 +187,62 @@ class ParamArena:
         return self._cached(("gs", first, last, shape), lambda: self._span(self.grad, first, last, shape))
 
 
+class ArenaView:
+    """A ParamArena seen through a key prefix: the names an engine uses for its module (`encoder.*`, `decoder.*`) address the
+    parameters of that module inside a larger model's arena (`lm.gmodel.encoder.*`), so that the whole model keeps ONE arena -- one
+    fused optimizer update, one gradient norm.  names / params / offsets cover the prefixed parameters only; the buffers are the
+    whole arena's."""
+
+    def __init__(self, arena, prefix):
+        self.arena, self.prefix = arena, prefix
+        n = len(prefix)
+        keep = [i for i, name in enumerate(arena.names) if name.startswith(prefix)]
+        self.names = [arena.names[i][n:] for i in keep]
+        self.params = [arena.params[i] for i in keep]
+        self.offsets = {name[n:]: o for name, o in arena.offsets.items() if name.startswith(prefix)}
+        self.pviews = {name[n:]: v for name, v in arena.pviews.items() if name.startswith(prefix)}
+        self.gviews = {name[n:]: v for name, v in arena.gviews.items() if name.startswith(prefix)}
+
+    flat = property(lambda self: self.arena.flat)
+    grad = property(lambda self: self.arena.grad)
+    shadow = property(lambda self: self.arena.shadow)
+    size = property(lambda self: self.arena.size)
+    compute_dtype = property(lambda self: self.arena.compute_dtype)
+
+    def bound(self):
+        return self.arena.bound()
+
+    def refresh_shadow(self):
+        self.arena.refresh_shadow()
+
+    def hold_shadow(self, on):
+        self.arena.hold_shadow(on)
+
+    def attach_grads(self):
+        self.arena.attach_grads()
+
+    def transposed(self, first, last=None, shape=None):
+        return self.arena.transposed(self.prefix + first, None if last is None else self.prefix + last, shape)
+
+    def w(self, name, shape=None):
+        return self.arena.w(self.prefix + name, shape)
+
+    def w_span(self, first, last, shape):
+        return self.arena.w_span(self.prefix + first, self.prefix + last, shape)
+
+    def p(self, name):
+        return self.arena.pviews[self.prefix + name]
+
+    def p_span(self, first, last, shape):
+        return self.arena.p_span(self.prefix + first, self.prefix + last, shape)
+
+    def g(self, name, shape=None):
+        return self.arena.g(self.prefix + name, shape)
+
+    def g_span(self, first, last, shape):
+        return self.arena.g_span(self.prefix + first, self.prefix + last, shape)
+
+
 def sinusoid(positions, d, device):
     positions = positions.to(torch.float32).view(-1, 1)
     div = torch.exp(torch.arange(0, d, 2, dtype=torch.float32) * -(math.log(10000.0) / d))

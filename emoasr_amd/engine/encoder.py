@@ -29,7 +29,9 @@ from .transformer_decoder import TransformerDecoder
 class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
     """Forward / backward of encoder + CTC head on HIP kernels."""
 
-    def __init__(self, cfg, module, compute_dtype=torch.bfloat16, bn_buffers=None, f32_split=False):
+    def __init__(self, cfg, module, compute_dtype=torch.bfloat16, bn_buffers=None, f32_split=False, arena=None):
+        """arena: an ArenaView over a larger model's arena, under whose key prefix `module` sits (P-ELECTRA's generator); the owner
+        of that arena re-homes the parameters and rebuilds this engine.  Default: the engine's own ParamArena over `module`."""
         self.cfg = cfg
         # f32 storage with every product as three bf16 MFMAs over (hi, lo) operand pairs (csrc/gemm.hip SplitCfg): the
         # throughput mode that meets the 1e-3 bar; compute_dtype stays torch.float32
@@ -61,7 +63,8 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
         self.p_att = float(_cfg(cfg, "dropout_attn_rate", 0.0))
         self.dtype = compute_dtype
         self.module = module
-        self.arena = ParamArena(module, compute_dtype)
+        self._own_arena = arena is None
+        self.arena = ParamArena(module, compute_dtype) if arena is None else arena
         self._tables = {}
         self._scratch_cache = {}
         # weight gradients of one encoder layer as one grouped launch (EMOASR_WGRAD_GROUP=0: one by one)
@@ -98,6 +101,7 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
     # ------------------------------------------------------------------ helpers
     def ensure_bound(self):
         if not self.arena.bound():
+            assert self._own_arena, "emoasr_amd: the parameters left the shared arena; its owner re-binds them and rebuilds this engine"
             # the parameters were moved / re-created (model.cpu().cuda(), .to(dtype), load_state_dict on another
             # device): re-home them and drop everything derived from the old arena's addresses
             self.arena = ParamArena(self.module, self.dtype)

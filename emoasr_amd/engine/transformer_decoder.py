@@ -86,28 +86,45 @@ class TransformerDecoder:
             st.mean, st.rstd, st.y = mean, rstd, y
         return logits.view(B, L, -1), st
 
-    def cmlm_head(self, x, sel, labels, w, keep, want_logits=False):
+    def cmlm_head(self, x, sel, labels, w, keep, want_logits=False, sample_seed=None, sample_fused=True, sample_min_rows=None):
         """MaskedLMLoss (cross-entropy, mean over the labelled positions) of the conditional masked LM on the labelled rows alone:
         x [B*L, dd] the decoder's last hidden rows, sel int64 [R] the labelled flat rows, labels int32 [R], w f32 [R] (1 / R; one
-        row of weight 0 when nothing is labelled) -> (loss 0-dim f32, head stash, logits of ALL rows [B*L, V] | None)"""
+        row of weight 0 when nothing is labelled) -> (loss 0-dim f32, head stash, logits of ALL rows [B*L, V] | None).
+        sample_seed (P-ELECTRA's generator): one Gumbel-max sample per labelled row as well, noise row = the index among the labelled
+        rows -> (loss, head stash, logits | None, samples int32 [R]).  The samples leave the head product's epilogue
+        (ops.ce_head_sample_fwd: no [R, V] logits; cmlm_last_head "fused-sample") where sample_fused and ops.ce_head_sample_ok with
+        sample_min_rows hold, else ops.sample_rows reads the materialised logits of the labelled rows."""
         with self._scope():
             A = self.arena
             xr = x.index_select(0, sel)
             y, mean, rstd = ops.layernorm_fwd(xr, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, keep)
             W, bias = A.w("decoder.output.weight"), A.p("decoder.output.bias")
-            if self.cmlm_fused_head and ops.ce_head_ok(y, W):
+            samples = None
+            if sample_seed is not None:
+                if sample_fused and ops.ce_head_sample_ok(y, W, sample_min_rows):
+                    rows, _, samples, ctx = ops.ce_head_sample_fwd(y, W, bias, labels, w, sample_seed, 0, sample_min_rows)
+                    head = ("fused", ctx)
+                else:
+                    z = self.head_logits(y.view(1, -1, y.shape[1]), "decoder.output")[0]
+                    rows, _ = ops.lsm_loss(z, labels, w, 0.0)
+                    _, samples, _ = ops.sample_rows(z, labels, w, sample_seed)
+                    head = ("materialised", z)
+                self.cmlm_last_head = "fused-sample" if head[0] == "fused" else head[0]
+            elif self.cmlm_fused_head and ops.ce_head_ok(y, W):
                 rows, _, ctx = ops.ce_head_fwd(y, W, bias, labels, w)
                 head = ("fused", ctx)
             else:
                 z = self.head_logits(y.view(1, -1, y.shape[1]), "decoder.output")[0]
                 rows, _ = ops.lsm_loss(z, labels, w, 0.0)
                 head = ("materialised", z)
-            self.cmlm_last_head = head[0]
+            if sample_seed is None:
+                self.cmlm_last_head = head[0]
             logits = None
             if want_logits:
                 ya, _, _ = ops.layernorm_fwd(x, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, False)
                 logits = self.head_logits(ya.view(1, -1, ya.shape[1]), "decoder.output")[0]
-            return rows.sum(), (xr, y, mean, rstd, head, sel, labels, w), logits
+            out = (rows.sum(), (xr, y, mean, rstd, head, sel, labels, w), logits)
+            return out if sample_seed is None else out + (samples,)
 
     def cmlm_head_backward(self, hst, n_rows, gscale_dev):
         """-> the gradient of the decoder's last hidden rows [n_rows, dd] (zero off the labelled rows); accumulates decoder.norm

@@ -315,6 +315,7 @@ SIGNATURES = {
     "emoasr_rnnt_coef": [I, I, I, I, P, P, P, P, P, P, P, P, P, F, P, P, P, P],
     "emoasr_rnnt_head_grad": [I, I, I, I, P, P, P, P, P, I, P, L, P],
     "emoasr_ce_head_fwd": [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
+    "emoasr_ce_head_sample_fwd": [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, U64, L, P, P],
     "emoasr_ce_head_grad": [I, I, I, I, P, P, P, P, P, P, F, P, P, P, L, P],
     "emoasr_act_bwd": [I, L, I, P, P, P, P],
     "emoasr_argmax_rows": [I, I, I, P, L, P, P],

@@ -283,6 +283,12 @@ _NO_PREDICT_P2W = ("emoasr_amd: the phone-to-word models (modeling/p2w.py: lm_ty
                    "'transformer' or 'rnn'); they correct a CTC hypothesis through emoasr_amd.correct")
 
 
+_PELECTRA_TYPES = ("pelectra", "pelectra-disc")
+_NO_PREDICT_PELECTRA = ("emoasr_amd: P-ELECTRA (modeling/pelectra.py: lm_type 'pelectra' / 'pelectra-disc') has no next-token "
+                        "distribution: predict / zero_states and the beam searches' shallow fusion need a causal LM (lm_type "
+                        "'transformer' or 'rnn'); use PELECTRA.score for rescoring")
+
+
 def require_next_token_lm(lm, lm_weight):
     """entry check of the beam searches: shallow fusion needs p(next token | prefix), which a bidirectional LM does not define"""
     if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) == "bert":
@@ -291,9 +297,212 @@ def require_next_token_lm(lm, lm_weight):
         raise NotImplementedError(_NO_PREDICT_ELECTRA)
     if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) in _P2W_TYPES:
         raise NotImplementedError(_NO_PREDICT_P2W)
+    if lm is not None and lm_weight > 0 and getattr(lm, "lm_type", None) in _PELECTRA_TYPES:
+        raise NotImplementedError(_NO_PREDICT_PELECTRA)
 
 
-class LM(nn.Module):
+class _StackOps:
+    """What LM and PELECTRA (modeling/pelectra.py) share: the post-LN BERT stacks (_encode / _backward_stack over a `_Stack` each) and
+    ELECTRA's discriminator on top of one (_disc_forward / _disc_backward, replaced_probs, _electra_score).  The host class provides
+    `_arena` (a bound ParamArena), `_stack` / `_stacks`, `seed`, `step_count`, `attn_fused`, `params`, `compute_dtype` / `f32_split`
+    and, for the discriminator, `_D` (its key prefix), `_disc`, `electra`, `lm_type` and `_prepare()`."""
+
+    def _seed(self, site, S=None):
+        site += S.site if S is not None else 0
+        return (self.seed * 1000003 + self.step_count * 4099 + site) & 0xFFFFFFFFFFFF
+
+    def _split(self):
+        return self.f32_split if self.compute_dtype == torch.float32 else None
+
+    def _inputs(self, ys, ylens):
+        P = self.params
+        ys, yl = lm_inputs(ys, ylens, P.vocab_size)
+        assert ys.shape[1] <= P.max_seq_len, f"sequence length {ys.shape[1]} exceeds max_seq_len {P.max_seq_len}"
+        return ys, yl
+
+    def _electra_inputs(self, ys, ylens, target, name):
+        ys, yl = self._inputs(ys, ylens)
+        if target is None:
+            raise ValueError(f"emoasr_amd: lm_type={self.lm_type!r} needs `{name}` (the reference dereferences them unconditionally)")
+        target = (target.cpu() if torch.is_tensor(target) else torch.as_tensor(target)).to(torch.int64)[:, : ys.shape[1]].contiguous()
+        assert target.shape == ys.shape, f"{name}: [B, N] like ys"
+        return ys, yl, target
+
+    def _refresh_pe(self):
+        A = self._arena
+        for S in self._stacks:
+            emb = S.pre + "embeddings."
+            pos, typ = A.p(emb + "position_embeddings.weight"), A.p(emb + "token_type_embeddings.weight")
+            ops.strided_copy(pos, out=S.pe)
+            ops.strided_copy(typ[0].expand(pos.shape[0], pos.shape[1]), out=S.pe, accumulate=True)
+        self._pe_stale = False
+
+    def _encode(self, ids, klens, B, N, p_h, p_att, keep, S=None):
+        """ids int32 [B,N], klens int32 [B] on the device -> (hidden [B*N, d], stash | None): embeddings (+ embeddings_project) + the
+        post-LN blocks of stack S (modeling_bert.py:159-436, modeling_electra.py:324-337), dropout by the seeded sites"""
+        A, S = self._arena, S or self._stack
+        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
+        pre = S.pre
+        e = ops.embed_fwd(ids, A.w(pre + "embeddings.word_embeddings.weight"), S.pe, 1.0).view(B * N, S.emb)
+        x, m0, r0 = ops.layernorm_fwd(e, A.p(pre + "embeddings.LayerNorm.weight"), A.p(pre + "embeddings.LayerNorm.bias"),
+                                      1e-12, keep)
+        s_emb = self._seed(1, S)
+        if p_h > 0:
+            x = ops.scale_dropout(x, 1.0, p_h, s_emb)
+        xe = x
+        if S.project:
+            x = ops.gemm_nt(xe, A.w(pre + "embeddings_project.weight"), bias=A.p(pre + "embeddings_project.bias"))
+        scale = 1.0 / math.sqrt(d // H)
+        layers = []
+        for i in range(nl):
+            lay = f"{pre}encoder.layer.{i}."
+            s_att, s_o, s_f = self._seed(100 + 10 * i, S), self._seed(101 + 10 * i, S), self._seed(102 + 10 * i, S)
+            wqkv = A.w_span(lay + "attention.self.query.weight", lay + "attention.self.value.weight", (3 * d, d))
+            bqkv = A.p_span(lay + "attention.self.query.bias", lay + "attention.self.value.bias", (3 * d,))
+            qkv = ops.gemm_nt(x, wqkv, bias=bqkv).view(B, N, 3 * d)
+            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=causal,
+                                  drop_p=p_att, seed=s_att)
+            y = ops.gemm_nt(o.view(B * N, d), A.w(lay + "attention.output.dense.weight"),
+                            bias=A.p(lay + "attention.output.dense.bias"), residual=x, res_scale=1.0, drop_p=p_h, seed=s_o)
+            x1, m1, r1 = ops.layernorm_fwd(y, A.p(lay + "attention.output.LayerNorm.weight"),
+                                           A.p(lay + "attention.output.LayerNorm.bias"), 1e-12, keep)
+            u = torch.empty(B * N, S.inner, device=x.device, dtype=x.dtype) if keep else None
+            a = ops.gemm_nt(x1, A.w(lay + "intermediate.dense.weight"), bias=A.p(lay + "intermediate.dense.bias"),
+                            act=ACT_GELU, pre_out=u)
+            y2 = ops.gemm_nt(a, A.w(lay + "output.dense.weight"), bias=A.p(lay + "output.dense.bias"), residual=x1,
+                             res_scale=1.0, drop_p=p_h, seed=s_f)
+            x2, m2, r2 = ops.layernorm_fwd(y2, A.p(lay + "output.LayerNorm.weight"), A.p(lay + "output.LayerNorm.bias"),
+                                           1e-12, keep)
+            if keep:
+                layers.append((x, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f))
+            x = x2
+        if not keep:
+            return x, None
+        st = _Stash()
+        st.B, st.N, st.ids, st.klens, st.p_h, st.p_att = B, N, ids, klens, p_h, p_att
+        st.e, st.m0, st.r0, st.s_emb, st.layers, st.xe = e, m0, r0, s_emb, layers, xe
+        return x, st
+
+    def _lin_bwd(self, dy, x_in, wname, bname, **epi):   # gradients of y = x_in W^T + b; -> dy W with the epilogue
+        A = self._arena
+        w = A.w(wname)
+        ops.gemm_tn(dy, x_in, out=A.g(wname), accumulate=True, colsum=A.g(bname))
+        return ops.gemm_nn(dy, w, **epi)
+
+    def _ln_bwd(self, dy, x_in, name, mean, rstd):
+        A = self._arena
+        return ops.layernorm_bwd(dy, x_in, A.p(name + ".weight"), mean, rstd, None, A.g(name + ".weight"), A.g(name + ".bias"))
+
+    def _backward_stack(self, st, dx, S):
+        """dx [B*N, d]: the gradient of stack S's last hidden state -> every gradient of its blocks and embeddings, accumulated"""
+        A = self._arena
+        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
+        B, N, p_h, p_att = st.B, st.N, st.p_h, st.p_att
+        pre = S.pre
+        word = pre + "embeddings.word_embeddings.weight"
+        lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
+        drop = lambda t, seed: ops.scale_dropout(t, 1.0, p_h, seed) if p_h > 0 else t
+        # ---- blocks, last to first.  Post-LN: LayerNorm backward first, then the branch and the residual together
+        scale = 1.0 / math.sqrt(d // H)
+        scratch = None
+        for i in reversed(range(nl)):
+            lay = f"{pre}encoder.layer.{i}."
+            xin, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f = st.layers[i]
+            dy2 = ln_bwd(dx, y2, lay + "output.LayerNorm", m2, r2)
+            du = lin_bwd(drop(dy2, s_f), a, lay + "output.dense.weight", lay + "output.dense.bias", dact_pre=u, dact=ACT_GELU)
+            dx1 = lin_bwd(du, x1, lay + "intermediate.dense.weight", lay + "intermediate.dense.bias", residual=dy2, res_scale=1.0)
+            dy = ln_bwd(dx1, y, lay + "attention.output.LayerNorm", m1, r1)
+            do = lin_bwd(drop(dy, s_o), o.view(B * N, d), lay + "attention.output.dense.weight", lay + "attention.output.dense.bias")
+            dqkv = torch.empty_like(qkv)
+            q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+            dq, dk, dv = dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]
+            # (the single-pass attention backward has no causal mask: the masked LM takes it in bf16, the causal LM the
+            # materialised path, as the ASR decoder's self-attention)
+            if self.attn_fused and ops.fused_attn_bwd_ok(q, None, None, None, causal):
+                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, drop_p=p_att, seed=s_att,
+                             materialise="fused")
+            else:
+                if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
+                    scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
+                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=causal,
+                             drop_p=p_att, seed=s_att, scratch=scratch)
+            dqkv2 = dqkv.view(B * N, 3 * d)
+            qn, vn = lay + "attention.self.query.", lay + "attention.self.value."
+            ops.gemm_tn(dqkv2, xin, out=A.g_span(qn + "weight", vn + "weight", (3 * d, d)), accumulate=True,
+                        colsum=A.g_span(qn + "bias", vn + "bias", (3 * d,)))
+            dx = ops.gemm_nn(dqkv2, A.w_span(qn + "weight", vn + "weight", (3 * d, d)), residual=dy, res_scale=1.0)
+        # ---- embeddings (modeling_bert.py:159-201): word rows scattered, positions summed over the batch, token type 0 over all rows
+        emb, E = pre + "embeddings.", S.emb
+        if S.project:     # (modeling_electra.py:328-329: after the embedding dropout)
+            dx = lin_bwd(dx, st.xe, pre + "embeddings_project.weight", pre + "embeddings_project.bias")
+        de = ln_bwd(drop(dx, st.s_emb), st.e, emb + "LayerNorm", st.m0, st.r0)
+        ops.embed_bwd(st.ids, de.view(B, N, E), 1.0, A.g(word))
+        ops.colsum(de.view(B, N * E), out=A.g(emb + "position_embeddings.weight").view(-1)[: N * E], accumulate=True)
+        ops.colsum(de, out=A.g(emb + "token_type_embeddings.weight")[0], accumulate=True)
+
+    def _active_rows(self, yl, B, N, dev):
+        """flat rows b * N + n with n < ylens[b] -> (int64 device tensor | None when every row is active, their number)"""
+        if min(yl) >= N:
+            return None, B * N
+        rows = torch.cat([torch.arange(b * N, b * N + n, dtype=torch.int32) for b, n in enumerate(yl)])
+        return h2d_i32(rows, dev).long(), rows.numel()
+
+    def _disc_forward(self, d_ids, klens, yl, y_all, B, N, p_h, p_att, keep):
+        """the discriminator on ids d_ids: encoder, dense + GELU, binary head on the rows n < ylens[b] against y_all f32 [B*N]
+        -> (loss_disc 0-dim, stash | None)"""
+        A, dev = self._arena, d_ids.device
+        x, dst = self._encode(d_ids, klens, B, N, p_h, p_att, keep, self._disc)
+        act, n_act = self._active_rows(yl, B, N, dev)
+        xa, ya = (x, y_all) if act is None else (x.index_select(0, act), y_all.index_select(0, act))
+        wa = torch.full((n_act,), 1.0 / n_act, device=dev, dtype=torch.float32)
+        dp = self._D + "discriminator_predictions."
+        hu = torch.empty_like(xa) if keep else None
+        hh = ops.gemm_nt(xa, A.w(dp + "dense.weight"), bias=A.p(dp + "dense.bias"), act=ACT_GELU, pre_out=hu)
+        z, lrows, _ = ops.bce_head_fwd(hh, A.w(dp + "dense_prediction.weight").view(-1), A.p(dp + "dense_prediction.bias"), ya, wa)
+        if not keep:
+            return lrows.sum(), None
+        st = _Stash()
+        st.dst, st.xa, st.ya, st.wa, st.hu, st.hh, st.z, st.act = dst, xa, ya, wa, hu, hh, z, act
+        return lrows.sum(), st
+
+    def _disc_backward(self, st, wd, g1):
+        """gradients of wd * g1 * loss_disc of _disc_forward's stash, accumulated into the arena"""
+        A = self._arena
+        B, N = st.dst.B, st.dst.N
+        dp = self._D + "discriminator_predictions."
+        dhh = ops.bce_head_bwd(st.hh, A.w(dp + "dense_prediction.weight").view(-1), st.z, st.ya, st.wa,
+                               A.g(dp + "dense_prediction.weight").view(-1), A.g(dp + "dense_prediction.bias"), wd, g1)
+        dxa = self._lin_bwd(ops.act_bwd(dhh, st.hu, ACT_GELU), st.xa, dp + "dense.weight", dp + "dense.bias")
+        if st.act is not None:
+            dxa = torch.zeros(B * N, self._disc.d, device=g1.device, dtype=dxa.dtype).index_copy_(0, st.act, dxa)
+        self._backward_stack(st.dst, dxa, self._disc)
+
+    def replaced_probs(self, ys, ylens):
+        """ELECTRA only.  sigmoid of the discriminator's logit at every position of `ys` as given (padding included; keys at
+        n >= ylens[b] are masked) -> float64 [B, N] on the HOST: one encoder pass, ONE device-to-host copy"""
+        assert self.electra, "replaced_probs is ELECTRA's discriminator (lm_type 'electra' / 'electra-disc')"
+        ys, _ = self._inputs(ys, None)
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        B, N = ys.shape
+        assert len(yl) == B and 1 <= min(yl) and max(yl) <= N, "ylens: one length in 1..N per row"
+        A = self._prepare()
+        dev = A.flat.device
+        D = self._D + "discriminator_predictions."
+        with torch.no_grad(), ops.stream_scope(self._split()):
+            x, _ = self._encode(h2d_i32(ys, dev), h2d_i32(yl, dev), B, N, 0.0, 0.0, False, self._disc)
+            hh = ops.gemm_nt(x, A.w(D + "dense.weight"), bias=A.p(D + "dense.bias"), act=ACT_GELU)
+            _, _, sig = ops.bce_head_fwd(hh, A.w(D + "dense_prediction.weight").view(-1), A.p(D + "dense_prediction.bias"),
+                                         want_sigmoid=True)
+        return sig.cpu().to(torch.float64).view(B, N)
+
+    def _electra_score(self, ys, ylens):
+        probs = self.replaced_probs(ys, ylens)
+        if probs.shape[0] == 1:
+            return [float(probs[0].sum())]
+        return [-float(probs[b, : int(n)].sum()) for b, n in enumerate(ylens)]
+
+
+class LM(_StackOps, nn.Module):
     stateful = False     # predict() carries no state between calls: the searches re-run the prefix (RNN LM: modeling/rnnlm.py)
 
     def __new__(cls, params=None, phase="test", compute_dtype=torch.bfloat16):     # (params=None: copy / pickle re-create the object bare)
@@ -515,10 +724,6 @@ class LM(nn.Module):
     # ---------------------------------------------------------------- training, scoring
     MAX_TOKEN_ROWS = 16384     # masked_logprobs: token rows (copies x padded length) per encoder run
 
-    def _seed(self, site, S=None):
-        site += S.site if S is not None else 0
-        return (self.seed * 1000003 + self.step_count * 4099 + site) & 0xFFFFFFFFFFFF
-
     def _prepare(self):
         """arena bound, compute-dtype weights and the additive position + token-type(0) table current (the parameters move
         between training steps; the table is rebuilt IN PLACE, so captured predict graphs keep reading the right address)"""
@@ -529,64 +734,6 @@ class LM(nn.Module):
         A.refresh_shadow()
         self._refresh_pe()
         return A
-
-    def _refresh_pe(self):
-        A = self._arena
-        for S in self._stacks:
-            emb = S.pre + "embeddings."
-            pos, typ = A.p(emb + "position_embeddings.weight"), A.p(emb + "token_type_embeddings.weight")
-            ops.strided_copy(pos, out=S.pe)
-            ops.strided_copy(typ[0].expand(pos.shape[0], pos.shape[1]), out=S.pe, accumulate=True)
-        self._pe_stale = False
-
-    def _split(self):
-        return self.f32_split if self.compute_dtype == torch.float32 else None
-
-    def _encode(self, ids, klens, B, N, p_h, p_att, keep, S=None):
-        """ids int32 [B,N], klens int32 [B] on the device -> (hidden [B*N, d], stash | None): embeddings (+ embeddings_project) + the
-        post-LN blocks of stack S (modeling_bert.py:159-436, modeling_electra.py:324-337), dropout by the seeded sites"""
-        A, S = self._arena, S or self._stack
-        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
-        pre = S.pre
-        e = ops.embed_fwd(ids, A.w(pre + "embeddings.word_embeddings.weight"), S.pe, 1.0).view(B * N, S.emb)
-        x, m0, r0 = ops.layernorm_fwd(e, A.p(pre + "embeddings.LayerNorm.weight"), A.p(pre + "embeddings.LayerNorm.bias"),
-                                      1e-12, keep)
-        s_emb = self._seed(1, S)
-        if p_h > 0:
-            x = ops.scale_dropout(x, 1.0, p_h, s_emb)
-        xe = x
-        if S.project:
-            x = ops.gemm_nt(xe, A.w(pre + "embeddings_project.weight"), bias=A.p(pre + "embeddings_project.bias"))
-        scale = 1.0 / math.sqrt(d // H)
-        layers = []
-        for i in range(nl):
-            lay = f"{pre}encoder.layer.{i}."
-            s_att, s_o, s_f = self._seed(100 + 10 * i, S), self._seed(101 + 10 * i, S), self._seed(102 + 10 * i, S)
-            wqkv = A.w_span(lay + "attention.self.query.weight", lay + "attention.self.value.weight", (3 * d, d))
-            bqkv = A.p_span(lay + "attention.self.query.bias", lay + "attention.self.value.bias", (3 * d,))
-            qkv = ops.gemm_nt(x, wqkv, bias=bqkv).view(B, N, 3 * d)
-            o, lse = ops.attn_fwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, klens=klens, causal=causal,
-                                  drop_p=p_att, seed=s_att)
-            y = ops.gemm_nt(o.view(B * N, d), A.w(lay + "attention.output.dense.weight"),
-                            bias=A.p(lay + "attention.output.dense.bias"), residual=x, res_scale=1.0, drop_p=p_h, seed=s_o)
-            x1, m1, r1 = ops.layernorm_fwd(y, A.p(lay + "attention.output.LayerNorm.weight"),
-                                           A.p(lay + "attention.output.LayerNorm.bias"), 1e-12, keep)
-            u = torch.empty(B * N, S.inner, device=x.device, dtype=x.dtype) if keep else None
-            a = ops.gemm_nt(x1, A.w(lay + "intermediate.dense.weight"), bias=A.p(lay + "intermediate.dense.bias"),
-                            act=ACT_GELU, pre_out=u)
-            y2 = ops.gemm_nt(a, A.w(lay + "output.dense.weight"), bias=A.p(lay + "output.dense.bias"), residual=x1,
-                             res_scale=1.0, drop_p=p_h, seed=s_f)
-            x2, m2, r2 = ops.layernorm_fwd(y2, A.p(lay + "output.LayerNorm.weight"), A.p(lay + "output.LayerNorm.bias"),
-                                           1e-12, keep)
-            if keep:
-                layers.append((x, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f))
-            x = x2
-        if not keep:
-            return x, None
-        st = _Stash()
-        st.B, st.N, st.ids, st.klens, st.p_h, st.p_att = B, N, ids, klens, p_h, p_att
-        st.e, st.m0, st.r0, st.s_emb, st.layers, st.xe = e, m0, r0, s_emb, layers, xe
-        return x, st
 
     def _transform(self, x, keep):
         """cls.predictions.transform (modeling_bert.py:537-554): dense + GELU + LayerNorm -> (t2, stash)"""
@@ -605,12 +752,6 @@ class LM(nn.Module):
                                      A.p(self._CP + "bias"), labels, w)
         self.last_head = head[0]
         return rows, head
-
-    def _inputs(self, ys, ylens):
-        P = self.params
-        ys, yl = lm_inputs(ys, ylens, P.vocab_size)
-        assert ys.shape[1] <= P.max_seq_len, f"sequence length {ys.shape[1]} exceeds max_seq_len {P.max_seq_len}"
-        return ys, yl
 
     def forward(self, ys, ylens=None, labels=None, ps=None, plens=None):
         """lm/modeling/lm.py:45-46, transformer.py:35-56: logits [B, N, V] (f32) without labels, else (loss, {"loss_total": loss});
@@ -678,16 +819,6 @@ class LM(nn.Module):
         with ops.stream_scope(self._split()):
             self._backward(st, g.to(torch.float32).reshape(1))
 
-    def _lin_bwd(self, dy, x_in, wname, bname, **epi):   # gradients of y = x_in W^T + b; -> dy W with the epilogue
-        A = self._arena
-        w = A.w(wname)
-        ops.gemm_tn(dy, x_in, out=A.g(wname), accumulate=True, colsum=A.g(bname))
-        return ops.gemm_nn(dy, w, **epi)
-
-    def _ln_bwd(self, dy, x_in, name, mean, rstd):
-        A = self._arena
-        return ops.layernorm_bwd(dy, x_in, A.p(name + ".weight"), mean, rstd, None, A.g(name + ".weight"), A.g(name + ".bias"))
-
     def _backward(self, st, g1):
         A = self._arena
         A.attach_grads()
@@ -707,53 +838,6 @@ class LM(nn.Module):
         self._backward_stack(st, dx, S)
         for n in self._NO_GRAD:      # never read by the LM: .grad stays None as in the reference (AdamW then leaves them alone)
             A.params[A.names.index(n)].grad = None
-
-    def _backward_stack(self, st, dx, S):
-        """dx [B*N, d]: the gradient of stack S's last hidden state -> every gradient of its blocks and embeddings, accumulated"""
-        A = self._arena
-        d, H, nl, causal = S.d, S.heads, S.layers, S.causal
-        B, N, p_h, p_att = st.B, st.N, st.p_h, st.p_att
-        pre = S.pre
-        word = pre + "embeddings.word_embeddings.weight"
-        lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
-        drop = lambda t, seed: ops.scale_dropout(t, 1.0, p_h, seed) if p_h > 0 else t
-        # ---- blocks, last to first.  Post-LN: LayerNorm backward first, then the branch and the residual together
-        scale = 1.0 / math.sqrt(d // H)
-        scratch = None
-        for i in reversed(range(nl)):
-            lay = f"{pre}encoder.layer.{i}."
-            xin, qkv, o, lse, y, m1, r1, x1, u, a, y2, m2, r2, s_att, s_o, s_f = st.layers[i]
-            dy2 = ln_bwd(dx, y2, lay + "output.LayerNorm", m2, r2)
-            du = lin_bwd(drop(dy2, s_f), a, lay + "output.dense.weight", lay + "output.dense.bias", dact_pre=u, dact=ACT_GELU)
-            dx1 = lin_bwd(du, x1, lay + "intermediate.dense.weight", lay + "intermediate.dense.bias", residual=dy2, res_scale=1.0)
-            dy = ln_bwd(dx1, y, lay + "attention.output.LayerNorm", m1, r1)
-            do = lin_bwd(drop(dy, s_o), o.view(B * N, d), lay + "attention.output.dense.weight", lay + "attention.output.dense.bias")
-            dqkv = torch.empty_like(qkv)
-            q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
-            dq, dk, dv = dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]
-            # (the single-pass attention backward has no causal mask: the masked LM takes it in bf16, the causal LM the
-            # materialised path, as the ASR decoder's self-attention)
-            if self.attn_fused and ops.fused_attn_bwd_ok(q, None, None, None, causal):
-                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, drop_p=p_att, seed=s_att,
-                             materialise="fused")
-            else:
-                if scratch is None:   # (zeroed once: every layer of the step masks the same entries)
-                    scratch = ops.AttnScratch(B, H, N, N, qkv.dtype, qkv.device, False)
-                ops.attn_bwd(do.view(B, N, d), o, lse, q, k, v, H, scale, dq, dk, dv, klens=st.klens, causal=causal,
-                             drop_p=p_att, seed=s_att, scratch=scratch)
-            dqkv2 = dqkv.view(B * N, 3 * d)
-            qn, vn = lay + "attention.self.query.", lay + "attention.self.value."
-            ops.gemm_tn(dqkv2, xin, out=A.g_span(qn + "weight", vn + "weight", (3 * d, d)), accumulate=True,
-                        colsum=A.g_span(qn + "bias", vn + "bias", (3 * d,)))
-            dx = ops.gemm_nn(dqkv2, A.w_span(qn + "weight", vn + "weight", (3 * d, d)), residual=dy, res_scale=1.0)
-        # ---- embeddings (modeling_bert.py:159-201): word rows scattered, positions summed over the batch, token type 0 over all rows
-        emb, E = pre + "embeddings.", S.emb
-        if S.project:     # (modeling_electra.py:328-329: after the embedding dropout)
-            dx = lin_bwd(dx, st.xe, pre + "embeddings_project.weight", pre + "embeddings_project.bias")
-        de = ln_bwd(drop(dx, st.s_emb), st.e, emb + "LayerNorm", st.m0, st.r0)
-        ops.embed_bwd(st.ids, de.view(B, N, E), 1.0, A.g(word))
-        ops.colsum(de.view(B, N * E), out=A.g(emb + "position_embeddings.weight").view(-1)[: N * E], accumulate=True)
-        ops.colsum(de, out=A.g(emb + "token_type_embeddings.weight")[0], accumulate=True)
 
     def token_logprobs(self, ys, ylens, labels):
         """log p(labels[b,i] | ys[b,:i+1]) for every position with labels != -100 (zeros elsewhere) -> float64 [B, N] on the HOST:
@@ -835,14 +919,6 @@ class LM(nn.Module):
     # ---------------------------------------------------------------- ELECTRA (lm/modeling/electra.py:33-132)
     SITE_SAMPLE = 7      # seed site of the generator's samples (the dropout sites are 1 and 100 + 10 * layer + {0, 1, 2})
 
-    def _electra_inputs(self, ys, ylens, target, name):
-        ys, yl = self._inputs(ys, ylens)
-        if target is None:
-            raise ValueError(f"emoasr_amd: lm_type={self.lm_type!r} needs `{name}` (the reference dereferences them unconditionally)")
-        target = (target.cpu() if torch.is_tensor(target) else torch.as_tensor(target)).to(torch.int64)[:, : ys.shape[1]].contiguous()
-        assert target.shape == ys.shape, f"{name}: [B, N] like ys"
-        return ys, yl, target
-
     def _electra_forward(self, ys, ylens, labels):
         """electra.py:71-100 -> (loss_gen + electra_disc_weight * loss_disc, {loss_gen, loss_disc, num_replaced, num_masked}): one
         autograd node; the sample is discrete, so no gradient flows from the discriminator into the generator"""
@@ -865,13 +941,6 @@ class LM(nn.Module):
         loss = _ElectraLossFn.apply(self, "disc", ys, yl, err, *A.params)
         return loss, {"loss_total": loss}
 
-    def _active_rows(self, yl, B, N, dev):
-        """flat rows b * N + n with n < ylens[b] -> (int64 device tensor | None when every row is active, their number)"""
-        if min(yl) >= N:
-            return None, B * N
-        rows = torch.cat([torch.arange(b * N, b * N + n, dtype=torch.int32) for b, n in enumerate(yl)])
-        return h2d_i32(rows, dev).long(), rows.numel()
-
     def _electra_loss_forward(self, mode, ys, yl, target, keep):
         A = self._arena
         dev = A.flat.device
@@ -881,7 +950,7 @@ class LM(nn.Module):
             self.step_count += 1
         p_h = float(self.hidden_dropout_prob) if training else 0.0
         p_att = float(self.attention_probs_dropout_prob) if training else 0.0
-        G, D = self._G, self._D
+        G = self._G
         st = _Stash()
         st.mode = mode
         with ops.stream_scope(self._split()):
@@ -943,21 +1012,13 @@ class LM(nn.Module):
                 y_all = err.clamp(min=0).to(torch.float32).view(-1).pin_memory().to(dev, non_blocking=True)
                 loss_gen = counters = None
             # ---- discriminator: encoder, dense + GELU, binary head on the rows n < ylens[b]
-            x, dst = self._encode(d_ids, klens, B, N, p_h, p_att, keep, self._disc)
-            act, n_act = self._active_rows(yl, B, N, dev)
-            xa, ya = (x, y_all) if act is None else (x.index_select(0, act), y_all.index_select(0, act))
-            wa = torch.full((n_act,), 1.0 / n_act, device=dev, dtype=torch.float32)
-            dp = D + "discriminator_predictions."
-            hu = torch.empty_like(xa) if keep else None
-            hh = ops.gemm_nt(xa, A.w(dp + "dense.weight"), bias=A.p(dp + "dense.bias"), act=ACT_GELU, pre_out=hu)
-            z, lrows, _ = ops.bce_head_fwd(hh, A.w(dp + "dense_prediction.weight").view(-1), A.p(dp + "dense_prediction.bias"), ya, wa)
-            loss_disc = lrows.sum()
+            loss_disc, dstash = self._disc_forward(d_ids, klens, yl, y_all, B, N, p_h, p_att, keep)
             loss = loss_disc if mode == "disc" else loss_gen + self.electra_disc_weight * loss_disc
         self._aux = {"loss_gen": loss_gen, "loss_disc": loss_disc, "counters": counters}
         if not keep:
             return loss, None
         self._pe_stale = True
-        st.dst, st.xa, st.ya, st.wa, st.hu, st.hh, st.z, st.act = dst, xa, ya, wa, hu, hh, z, act
+        st.disc = dstash
         return loss, st
 
     def _padded_word(self, W):
@@ -975,22 +1036,14 @@ class LM(nn.Module):
 
     def _electra_loss_backward(self, st, g):
         A = self._arena
-        G, D = self._G, self._D
+        G = self._G
         lin_bwd, ln_bwd = self._lin_bwd, self._ln_bwd
         with ops.stream_scope(self._split()):
             g1 = g.to(torch.float32).reshape(1)
             A.attach_grads()
-            B, N = st.dst.B, st.dst.N
+            B, N = st.disc.dst.B, st.disc.dst.N
             dev = g1.device
-            # ---- discriminator
-            dp = D + "discriminator_predictions."
-            wd = 1.0 if st.mode == "disc" else self.electra_disc_weight
-            dhh = ops.bce_head_bwd(st.hh, A.w(dp + "dense_prediction.weight").view(-1), st.z, st.ya, st.wa,
-                                   A.g(dp + "dense_prediction.weight").view(-1), A.g(dp + "dense_prediction.bias"), wd, g1)
-            dxa = lin_bwd(ops.act_bwd(dhh, st.hu, ACT_GELU), st.xa, dp + "dense.weight", dp + "dense.bias")
-            if st.act is not None:
-                dxa = torch.zeros(B * N, self._disc.d, device=dev, dtype=dxa.dtype).index_copy_(0, st.act, dxa)
-            self._backward_stack(st.dst, dxa, self._disc)
+            self._disc_backward(st.disc, 1.0 if st.mode == "disc" else self.electra_disc_weight, g1)
             if st.mode == "disc":
                 # the generator was not run: its .grad is None, as in the reference (AdamW then leaves it bit-identical).  A
                 # discriminator-only step therefore does not share an accumulation window with a generator step.
@@ -1011,31 +1064,6 @@ class LM(nn.Module):
             dxs = lin_bwd(dpre, st.xs, gp + "dense.weight", gp + "dense.bias")
             dx = torch.zeros(B * N, self._gen.d, device=dev, dtype=dxs.dtype).index_copy_(0, st.sel, dxs)
             self._backward_stack(st.gst, dx, self._gen)
-
-    def replaced_probs(self, ys, ylens):
-        """ELECTRA only.  sigmoid of the discriminator's logit at every position of `ys` as given (padding included; keys at
-        n >= ylens[b] are masked) -> float64 [B, N] on the HOST: one encoder pass, ONE device-to-host copy"""
-        assert self.electra, "replaced_probs is ELECTRA's discriminator (lm_type 'electra' / 'electra-disc')"
-        ys, _ = self._inputs(ys, None)
-        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
-        B, N = ys.shape
-        assert len(yl) == B and 1 <= min(yl) and max(yl) <= N, "ylens: one length in 1..N per row"
-        A = self._prepare()
-        dev = A.flat.device
-        D = self._D + "discriminator_predictions."
-        with torch.no_grad(), ops.stream_scope(self._split()):
-            x, _ = self._encode(h2d_i32(ys, dev), h2d_i32(yl, dev), B, N, 0.0, 0.0, False, self._disc)
-            hh = ops.gemm_nt(x, A.w(D + "dense.weight"), bias=A.p(D + "dense.bias"), act=ACT_GELU)
-            _, _, sig = ops.bce_head_fwd(hh, A.w(D + "dense_prediction.weight").view(-1), A.p(D + "dense_prediction.bias"),
-                                         want_sigmoid=True)
-        return sig.cpu().to(torch.float64).view(B, N)
-
-    def _electra_score(self, ys, ylens):
-        probs = self.replaced_probs(ys, ylens)
-        if probs.shape[0] == 1:
-            return [float(probs[0].sum())]
-        return [-float(probs[b, : int(n)].sum()) for b, n in enumerate(ylens)]
-
 
 class _ElectraLossFn(torch.autograd.Function):
     """ELECTRA's training loss (mode "both": generator + weighted discriminator; "disc": the discriminator alone) as ONE autograd node"""

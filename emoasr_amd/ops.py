@@ -1268,6 +1268,36 @@ def ce_head_fwd(x, w, bias, labels, wrow=None):
     return loss, logp, (lse, ycol, wrow)
 
 
+def ce_head_sample_ok(x, w, min_rows=None):
+    """does the sampling head (ce_head_sample_fwd) take this shape?  ce_head_ok's gates with the kernel's own V >= 64 and at least
+    min_rows rows (default CE_HEAD_MIN_ROWS)"""
+    M, K, lda = _rows(x)
+    V = w.shape[0]
+    min_rows = CE_HEAD_MIN_ROWS if min_rows is None else min_rows
+    return (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and V % 8 == 0 and V >= 64 and K % 64 == 0 and lda == K
+            and w.stride(0) == K and M >= max(1, min_rows) and M * K * 2 < (1 << 32) and V * K * 2 < (1 << 32))
+
+
+def ce_head_sample_fwd(x, w, bias, labels, wrow, seed, row0=0, min_rows=None):
+    """ce_head_fwd that also draws one sample per row in the product's epilogue -> (loss rows f32 [M], logp f32 [M], samples int32 [M],
+    ctx for ce_head_bwd).  samples[m] = argmax_v (z32[m, v] + gumbel_noise(M, V, seed, row0)[m, v]), z32 the f32 accumulator + bias,
+    ties to the lowest column: a draw from softmax(z[m]) and a function of (seed, row0 + m, v) only.  No [M, V] buffer."""
+    assert ce_head_sample_ok(x, w, min_rows), "ce_head_sample_fwd: shape outside the sampling head's gates (ops.ce_head_sample_ok)"
+    assert row0 >= 0
+    M, K, _ = _rows(_chk(x))
+    V = w.shape[0]
+    dev = x.device
+    part = torch.empty((V + 63) // 64, M, 4, device=dev, dtype=torch.float32)
+    zscr = torch.empty(M, device=dev, dtype=torch.float32)
+    ycol = torch.empty(M, device=dev, dtype=torch.int32)
+    sample = torch.empty(M, device=dev, dtype=torch.int32)
+    out = torch.empty(3, M, device=dev, dtype=torch.float32)
+    lse, logp, loss = out[0], out[1], out[2]
+    lib.call("emoasr_ce_head_sample_fwd", dt(x), M, V, K, _p(x), _p(w), _p(bias), _p(_chk(labels, torch.int32)), _p(wrow), _p(part),
+             _p(zscr), _p(ycol), _p(lse), _p(logp), _p(loss), int(seed) & (2 ** 64 - 1), int(row0), _p(sample), _stream())
+    return loss, logp, sample, (lse, ycol, wrow)
+
+
 def ce_head_bwd(x, w, bias, ctx, dw, dbias, gscale=1.0, gscale_dev=None, chunk=None, want_dx=True):
     """gradients of sum(loss rows) * gscale [* gscale_dev]: dw f32 [V, K] and dbias f32 [V] are ACCUMULATED into, -> dx [M, K] bf16.
     dz = w_row (softmax - onehot) is recomputed `chunk` rows at a time and fed to gemm_nn / gemm_tn."""

@@ -598,9 +598,17 @@ int emoasr_rnnt_head_grad(int dtype, int nrows, int V, int J, const void* h, con
  *                        part: scratch [ceil(V / 64), nrows, 2] f32; zscr: scratch [2 * nrows] f32.
  *   emoasr_ce_head_grad  dz[n, :] = s[n] * (exp(z[n, :] - lse[n]) - [v == ycol[n]]), s[n] = wrow[n] * gscale [* *gscale_dev], for
  *                        the nrows rows of one row chunk, z RECOMPUTED from x; coef: scratch [nrows, 4] f32.  The caller walks the
- *                        rows in chunks (dz chunk -> emoasr_gemm_nn / emoasr_gemm_tn), so at most one chunk of dz exists. */
+ *                        rows in chunks (dz chunk -> emoasr_gemm_nn / emoasr_gemm_tn), so at most one chunk of dz exists.
+ *   emoasr_ce_head_sample_fwd  emoasr_ce_head_fwd that also draws, in the same epilogue, one Gumbel-max sample per row:
+ *                        sample[n] = argmax_v (z32[n, v] + g(seed, row0 + n, v)), z32 the f32 accumulator + bias (not rounded to
+ *                        bf16), g the variate of emoasr_gumbel_noise, ties to the lowest column -- a draw from softmax(z[n]).
+ *                        part: scratch [ceil(V / 64), nrows, 4] f32; zscr: scratch [nrows] f32.  Same gates; (lse, ycol, wrow) feed
+ *                        emoasr_ce_head_grad as after emoasr_ce_head_fwd. */
 int emoasr_ce_head_fwd(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias, const int* labels,
                        const float* wrow, float* part, float* zscr, int* ycol, float* lse, float* logp, float* loss, void* stream);
+int emoasr_ce_head_sample_fwd(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias, const int* labels,
+                              const float* wrow, float* part, float* zscr, int* ycol, float* lse, float* logp, float* loss,
+                              uint64_t seed, long row0, int* sample, void* stream);
 int emoasr_ce_head_grad(int dtype, int nrows, int V, int K, const void* x, const void* w, const float* bias, const float* lse,
                         const int* ycol, const float* wrow, float gscale, const float* gscale_dev, float* coef, void* dz, long lddz,
                         void* stream);

@@ -1,6 +1,6 @@
 """Transformer-LM training throughput and the vocabulary head A/B (fused = no [rows, V] logits, against materialised).
 
-    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert|electra|pbert]
+    python tools/lm_bench.py [--steps 20] [--warmup 5] [--pairs 5] [--batch 100] [--leg transformer|bert|electra|pbert|pelectra]
 
 Prints one JSON line.  --leg transformer (the default):
   train_tokens_per_s   real (unpadded) tokens per second of a full training step (forward, backward, clip + AdamW) of the 12-layer
@@ -32,6 +32,16 @@ num_to_mask 35, electra_disc_weight 50), bf16:
   correct_kernels      the correction step's kernels at T' = 300 frames, 40 tokens (row_lse + ctc_token_conf + correct_fuse) against
                        the same step composed from torch ops (softmax, gather, argmax) as alternating legs in ONE process;
   correct_step         host milliseconds per corrected utterance end to end (correct_step_timing below): T' = 300, 40 tokens.
+
+--leg pelectra: P-ELECTRA (modeling/pelectra.py) with the pbert leg's generator and the electra leg's discriminator, batch 100, bf16,
+dropout 0.1:
+  step                 a full training step (train_lm.train_step) with the sampling head in the product's epilogue
+                       (PELECTRA.sample_head = "fused") against the materialised logits of the labelled rows + sample_rows
+                       ("materialised"), as alternating legs of --steps steps after --warmup in ONE process, --pairs pairs: ms per
+                       step as median and range, every pair's ratio, torch.cuda.max_memory_allocated of each path;
+  all_rows             the reference's shape of the generator's head alone on the same batch: logits of ALL B * L rows
+                       (cmlm_head(want_logits=True)) followed by sample_rows over them -- the head's time and peak memory, next to
+                       the two heads above timed alone.
 """
 import argparse
 import json
@@ -266,6 +276,78 @@ def pbert_leg(args):
     print(json.dumps(out))
 
 
+def pelectra_leg(args):
+    from emoasr_amd import ops
+    from emoasr_amd.modeling.pelectra import PELECTRA
+    from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
+    from emoasr_amd.train_lm import train_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    V, PV = 10872, 45
+    disc = dict(embedding_size=256, hidden_size=256, intermediate_size=1024, num_attention_heads=4, num_layers=12)
+    cfg = dict(lm_type="pelectra", input_layer="embed", enc_hidden_size=256, enc_num_attention_heads=4, enc_num_layers=4,
+               enc_intermediate_size=1024, dec_hidden_size=256, dec_num_attention_heads=4, dec_num_layers=4,
+               dec_intermediate_size=1024, dropout_enc_rate=0.1, dropout_dec_rate=0.1, dropout_attn_rate=0.1, mtl_ctc_weight=0,
+               lsm_prob=0, kd_weight=0, max_decode_ylen=256, vocab_size=V, src_vocab_size=PV, max_seq_len=256, eos_id=2,
+               mask_id=V - 1, phone_eos_id=2, phone_mask_id=PV - 2, blank_id=0, add_sos_eos=False, electra_disc_weight=50,
+               **{f"disc_{k}": v for k, v in disc.items()})
+    params = SimpleNamespace(**dict(cfg, learning_rate=1e-4, lr_schedule_type="lindecay", num_warmup_steps=100, weight_decay=0.01,
+                                    clip_grad_norm=5.0, accum_grad=1, log_step=10 ** 9))
+    lm = PELECTRA(params, compute_dtype=torch.bfloat16).to(dev).train()
+    opt = ScheduledOptimizer(AdamW(get_optimizer_params_nodecay(list(lm.named_parameters()), params.weight_decay), lr=0,
+                                   weight_decay=params.weight_decay), params, num_total_steps=10 ** 6)
+    data, tokens = mlm_batch(args.batch, V, V - 1, 0.3)
+    g = torch.Generator().manual_seed(1)
+    plens = (data["ylens"] * 3).clamp(max=256)      # about three phones per word
+    data["plens"] = plens
+    data["ps"] = torch.randint(3, PV - 2, (args.batch, int(plens.max())), generator=g)
+    step = lambda: train_step(lm, opt, data, params, dev, sync=False)
+    heads = ("fused", "materialised")
+    rec = {"tokens": tokens, "phones": int(plens.sum()), "rows_padded": data["ys_in"].numel(),
+           "rows_labelled": int((data["labels"] != -100).sum()), "fused_ms": [], "materialised_ms": []}
+    for _ in range(args.pairs):
+        for head in heads:
+            lm.sample_head = head
+            timed(step, args.warmup)
+            torch.cuda.reset_peak_memory_stats()
+            rec[head + "_ms"].append(round(timed(step, args.steps) / 1e3, 3))
+            rec[head + "_peak_bytes"] = torch.cuda.max_memory_allocated()
+            rec[head + "_head_taken"] = lm.last_head
+    for head in heads:
+        ms = rec[head + "_ms"]
+        rec[head + "_median_ms"], rec[head + "_min_max_ms"] = statistics.median(ms), [min(ms), max(ms)]
+    rec["pair_ratio_fused_over_materialised"] = [round(a / b, 4) for a, b in zip(rec["fused_ms"], rec["materialised_ms"])]
+    out = {"leg": "pelectra", "batch": args.batch, "dtype": "bf16", "step": rec}
+    # ---- the generator's head alone on this batch's hidden rows: the two heads above and the reference's all-rows shape
+    eng = lm.engine()
+    B, L = data["ys_in"].shape
+    x = torch.randn(B * L, 256, device=dev).to(torch.bfloat16)
+    valid = (data["labels"] != -100).view(-1)
+    sel = valid.nonzero().view(-1).to(dev)
+    lab = data["labels"].view(-1)[valid].to(torch.int32).to(dev)
+    w = torch.full((sel.numel(),), 1.0 / sel.numel(), device=dev)
+    lab_all, w_all = data["labels"].clamp(min=0).to(torch.int32).view(-1).to(dev), valid.float().to(dev)
+
+    def head(fused):
+        return lambda: eng.cmlm_head(x, sel, lab, w, False, False, sample_seed=7, sample_fused=fused)
+
+    def all_rows():
+        _, _, logits = eng.cmlm_head(x, sel, lab, w, False, True)
+        ops.sample_rows(logits, lab_all, w_all, 7)
+
+    hrec = {"rows_all": B * L}
+    for name, fn in (("fused", head(True)), ("materialised", head(False)), ("all_rows", all_rows)):
+        timed(fn, 3)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        us = [round(timed(fn, 10), 1) for _ in range(args.pairs)]
+        hrec[name + "_us"], hrec[name + "_median_us"] = us, statistics.median(us)
+        hrec[name + "_peak_bytes_above_resident"] = torch.cuda.max_memory_allocated() - base
+    out["head_alone"] = hrec
+    print(json.dumps(out))
+
+
 def correct_step_timing(args, lm, V, PV, dev):
     """host milliseconds per corrected utterance (correct.correct_step: encoder pass, both heads, greedy paths, confidences, one copy,
     the LM forward, the fusion, one copy) with the 23 M Conformer-CTC of bench.py plus a hierarchical phone head, bf16, on 1 203
@@ -327,7 +409,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=100)
-    ap.add_argument("--leg", choices=["transformer", "bert", "electra", "pbert"], default="transformer")
+    ap.add_argument("--leg", choices=["transformer", "bert", "electra", "pbert", "pelectra"], default="transformer")
     ap.add_argument("--token-rows", type=int, nargs="+", default=[16384, 65536, 262144], help="--leg bert: max_token_rows values")
     args = ap.parse_args()
     if args.leg == "bert":
@@ -336,6 +418,8 @@ def main():
         return electra_leg(args)
     if args.leg == "pbert":
         return pbert_leg(args)
+    if args.leg == "pelectra":
+        return pelectra_leg(args)
     from emoasr_amd import ops
     from emoasr_amd.modeling.lm import LM
     from emoasr_amd.optimizers import AdamW, ScheduledOptimizer, get_optimizer_params_nodecay
