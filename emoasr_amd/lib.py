@@ -282,6 +282,8 @@ SIGNATURES = {
     "emoasr_bce_head_bwd": [I, I, I, P, L, P, P, P, P, F, P, P, L, P, P, P],
     "emoasr_ctc_token_conf": [I, I, I, I, P, L, P, P, P, I, P, P, P, P],
     "emoasr_correct_fuse": [I, I, I, I, I, I, P, L, P, P, L, P, L, F, P, P, P],
+    "emoasr_edit_align": [I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P],
+    "emoasr_rescore_grid": [I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "emoasr_ctc_forward_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P],
     "emoasr_ctc_grad_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, F, P, P, P, P, P, L, P],
     "emoasr_ctc_greedy": [I, I, I, I, P, L, P, I, P, P, P, P],

@@ -46,22 +46,42 @@ def _total(pairs, cer):
     return wer, dict(tot, wer=wer)
 
 
-def compute_wers(hyps, refs, vocab=None, cer=False):
-    """corpus-level WER over id (with vocab: subword -> word) or word sequences (metrics.py:108-130)"""
+def _total_device(pairs, cer, device):
+    """_total with every pair aligned in one ops.edit_align call (csrc/rescore.hip); the same integers, so the same WER"""
+    from . import ops
+    vocab = {}
+    intern = lambda seq: [vocab.setdefault(w, len(vocab)) for w in seq]
+    hyps, refs = [], []
+    for hyp, ref in pairs:
+        hyp, ref = list(hyp) or ["<dummy>"], list(ref)      # (the empty hypothesis BEFORE the join to characters, as compute_wer)
+        if cer:
+            hyp, ref = list("".join(hyp)), list("".join(ref))
+        hyps.append(intern(hyp))
+        refs.append(intern(ref))
+    counts = ops.edit_align(hyps, refs, device=device)["counts"].astype(np.int64).sum(axis=0)
+    tot = {"n_sub": int(counts[0]), "n_ins": int(counts[1]), "n_del": int(counts[2]), "n_ref": sum(len(r) for r in refs)}
+    wer = 100.0 * (tot["n_sub"] + tot["n_ins"] + tot["n_del"]) / tot["n_ref"]
+    return wer, dict(tot, wer=wer)
+
+
+def compute_wers(hyps, refs, vocab=None, cer=False, device=None):
+    """corpus-level WER over id (with vocab: subword -> word) or word sequences (metrics.py:108-130).  With a `device` the pairs are
+    aligned there in one call (sides of at most 4096 tokens); the default is the host loop."""
     if vocab is not None:
         hyps, refs = [vocab.ids2words(h) for h in hyps], [vocab.ids2words(r) for r in refs]
-    return _total(zip(hyps, refs), cer)
+    return _total(zip(hyps, refs), cer) if device is None else _total_device(zip(hyps, refs), cer, device)
 
 
-def compute_wers_df(dfhyp, dfref=None, cer=False):
+def compute_wers_df(dfhyp, dfref=None, cer=False, device=None):
     """result TSV (columns text, reftext) or hypothesis + reference tables joined on utt_id
-    (metrics.py:133-175); missing / NaN hypotheses count as empty"""
+    (metrics.py:133-175); missing / NaN hypotheses count as empty.  `device`: as compute_wers."""
     def words(v):
         return v.split() if isinstance(v, str) else []
+    total = _total if device is None else (lambda pairs, cer: _total_device(pairs, cer, device))
     if dfref is None:
-        return _total(((words(r.text), words(r.reftext)) for r in dfhyp.itertuples()), cer)
+        return total(((words(r.text), words(r.reftext)) for r in dfhyp.itertuples()), cer)
     id2hyp = {r.utt_id: words(r.text) for r in dfhyp.itertuples()}
-    return _total(((id2hyp.get(r.utt_id, []), words(r.text)) for r in dfref.itertuples()), cer)
+    return total(((id2hyp.get(r.utt_id, []), words(r.text)) for r in dfref.itertuples()), cer)
 
 
 def wer_summary(wer, w, cer=False):

@@ -922,6 +922,92 @@ def correct_fuse(asr_logits, asr_lse, lm_logits, w, n_cols, asr_rows=None):
     return ids, val
 
 
+# ---- N-best rescoring and error-label alignment -------------------------------------------------
+ALIGN_MODES = {None: 0, "SI": 1, "SID": 2}
+EDIT_MAX_LEN = 4096
+
+
+def edit_align(hyps, refs, ref_idx=None, device="cuda", want_ops=False, label_mode=None):
+    """hyps: P int sequences; refs: int sequences; ref_idx [P]: the reference of each hypothesis (None: refs[p]) -> dict of host
+    arrays: counts int32 [P,4] = (n_sub, n_ins, n_del, dist), exactly metrics.compute_wer's; with want_ops `ops`, a list of P
+    strings over C / S / I / D; with label_mode "SI" / "SID" `labels`, a list of P strings, one letter per hypothesis token
+    (align_hyps' fold).  One upload, one emoasr_edit_align call over all pairs, one download.  An empty hypothesis is one token
+    that matches nothing.  A side of more than EDIT_MAX_LEN tokens raises; so does a pair with an empty reference (compute_wer
+    divides by its length; the kernel would count the hypothesis' tokens as insertions)."""
+    import numpy as np
+    P = len(hyps)
+    ref_idx = np.arange(P, dtype=np.int32) if ref_idx is None else np.asarray(ref_idx, dtype=np.int32)
+    assert ref_idx.shape == (P,) and (P == 0 or (ref_idx.min() >= 0 and ref_idx.max() < len(refs)))
+    mode = ALIGN_MODES[label_mode]
+    if P == 0:
+        return {"counts": np.zeros((0, 4), np.int32), "ops": [], "labels": []}
+    hlen = np.fromiter((len(h) for h in hyps), np.int64, P)
+    rlen = np.fromiter((len(r) for r in refs), np.int64, len(refs))
+    assert hlen.sum() < 2 ** 31 and rlen.sum() < 2 ** 31
+    hyp_off = np.concatenate([[0], np.cumsum(hlen)])
+    ref_off = np.concatenate([[0], np.cumsum(rlen)])
+    heff, rp = np.maximum(hlen, 1), rlen[ref_idx]
+    ops_off = np.concatenate([[0], np.cumsum(heff + rp)])
+    max_h, max_r = int(hlen.max()), int(rp.max())
+    if int(rp.min()) == 0:
+        raise ValueError(f"edit_align: pair {int(np.argmin(rp))} has an empty reference")
+    ws_need = np.zeros(P, np.int64)
+    if max_h <= EDIT_MAX_LEN and max_r <= EDIT_MAX_LEN:       # (over the limit: the call below returns the error)
+        words = 2 * ((heff + 63) // 64) * (rp + 63)             # emoasr_edit_align_ws_words, vectorised; checked against it below
+        ws_need = np.where(words > lib.size_query("emoasr_edit_align_lds_words"), words, 0)
+        k = int(np.argmax(words))
+        assert int(ws_need[k]) == lib.size_query("emoasr_edit_align_ws_words", int(rp[k]), int(hlen[k]))
+    ws_off = np.concatenate([[0], np.cumsum(ws_need)])
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+
+    flat = lambda seqs, n: np.fromiter((t for s in seqs for t in s), np.int32, n)
+    d_hyp, d_ref = up(flat(hyps, int(hyp_off[-1])), np.int32), up(flat(refs, int(ref_off[-1])), np.int32)
+    d_hoff, d_roff, d_ridx = up(hyp_off, np.int32), up(ref_off, np.int32), up(ref_idx, np.int32)
+    d_ooff, d_woff = up(ops_off[:-1], np.int64), up(ws_off, np.int64)
+    counts = torch.empty(P, 4, device=device, dtype=torch.int32)
+    status = torch.zeros(1, device=device, dtype=torch.int32)
+    d_ops = torch.empty(int(ops_off[-1]), device=device, dtype=torch.uint8) if want_ops else None
+    d_lab = torch.empty(max(int(hyp_off[-1]), 1), device=device, dtype=torch.uint8) if mode else None
+    d_ws = torch.empty(int(ws_off[-1]), device=device, dtype=torch.int64) if ws_off[-1] else None
+    with torch.cuda.device(counts.device):
+        lib.call("emoasr_edit_align", P, len(refs), max_h, max_r, _p(d_hyp), _p(d_hoff), _p(d_ref), _p(d_roff), _p(d_ridx), mode,
+                 _p(counts), _p(d_ops), _p(d_ooff), _p(d_lab), _p(d_ws), _p(d_woff), _p(status), _stream())
+    out = {"counts": counts.cpu().numpy()}
+    if int(status.item()):
+        raise lib.EmoasrHipError("emoasr_edit_align: a pair broke its declared bounds (status %d)" % int(status.item()))
+    if want_ops:
+        raw = d_ops.cpu().numpy().tobytes()
+        n_ops = heff + out["counts"][:, 2]
+        out["ops"] = [raw[int(o):int(o + n)].decode("ascii") for o, n in zip(ops_off[:-1], n_ops)]
+    if mode:
+        raw = d_lab.cpu().numpy().tobytes()
+        out["labels"] = [raw[int(a):int(b)].decode("ascii") for a, b in zip(hyp_off[:-1], hyp_off[1:])]
+    return out
+
+
+def rescore_grid(score_asr, score_lm, ylen, utt_off, counts, lm_w, len_w):
+    """score_asr / score_lm f64 [N], ylen int32 [N], utt_off int32 [U+1] (an utterance's rows are contiguous), counts int32 [N,4],
+    lm_w f64 [G1], len_w f64 [G2], all on the device -> (best int32 [G1*G2, U], totals int64 [G1*G2, 3]): per grid cell the first
+    row of each utterance with the largest (score_asr + lm_w * score_lm) + len_w * ylen (f64, each operation rounded once), and
+    the (n_sub, n_ins, n_del) of the winners summed."""
+    N, U, G1, G2 = score_asr.numel(), utt_off.numel() - 1, lm_w.numel(), len_w.numel()
+    for t in (score_asr, score_lm, lm_w, len_w):
+        assert _chk(t, torch.float64).is_contiguous() and t.dim() == 1
+    assert score_lm.numel() == N and _chk(ylen, torch.int32).numel() == N and ylen.is_contiguous()
+    assert _chk(utt_off, torch.int32).is_contiguous() and _chk(counts, torch.int32).shape == (N, 4) and counts.is_contiguous()
+    # (one synchronisation: the kernel trusts the offsets)
+    if not bool((utt_off[0] == 0) & (utt_off[-1] == N) & (utt_off[1:] >= utt_off[:-1]).all()):
+        raise ValueError(f"rescore_grid: utt_off must rise from 0 to the {N} rows")
+    best = torch.empty(G1 * G2, U, device=score_asr.device, dtype=torch.int32)
+    totals = torch.empty(G1 * G2, 3, device=score_asr.device, dtype=torch.int64)
+    with torch.cuda.device(score_asr.device):
+        lib.call("emoasr_rescore_grid", N, U, G1, G2, _p(score_asr), _p(score_lm), _p(ylen), _p(utt_off), _p(counts), _p(lm_w),
+                 _p(len_w), _p(best), _p(totals), _stream())
+    return best, totals
+
+
 # ---- knowledge distillation ---------------------------------------------------------------
 def soft_ce(logits, soft=None, src=None, hard=None, w_soft=None, w_hard=None, lsm_prob=0.0, lrow=None, want_grad=False,
             gscale=1.0, gscale_dev=None, grad=None):

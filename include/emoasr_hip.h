@@ -767,6 +767,40 @@ int emoasr_correct_fuse(int dtype_asr, int dtype_lm, int n, int V_asr, int V_lm,
                         const float* asr_lse, const int* asr_rows, long asr_nrows, const void* lm, long ld_lm, float w,
                         int* out_id, float* out_val, void* stream);
 
+/* ---- N-best rescoring and error-label alignment (asr/rescore/test_rescore_grid.py, asr/rescore/align_hyps.py) ----
+ * emoasr_edit_align: P pairs of int32 token sequences.  Hypothesis p is hyp[hyp_off[p] .. hyp_off[p+1]); its reference is sequence
+ *   r = ref_idx[p] (NULL: r = p) of the n_ref references, ref[ref_off[r] .. ref_off[r+1]), so the hypotheses of one utterance share
+ *   one reference.  Per pair, exactly compute_wer of asr/metrics.py:20-105: an empty hypothesis is one token that matches nothing;
+ *   the backtrace from (R, H) takes C when the tokens match, else I when d == left + 1, else S when d == diag + 1, else D; row 0
+ *   gives I, column 0 gives D.
+ *     counts[p] int32 [4]        = (n_sub, n_ins, n_del, dist)
+ *     ops (may be NULL)          uint8 'C' / 'S' / 'I' / 'D' in sequence order from ops[ops_off[p]]: max(H, 1) + n_del of them;
+ *                                the caller leaves R + max(H, 1) slots per pair (ops_off int64 [P])
+ *     labels (label_mode != NONE) uint8, one per hypothesis token at labels[hyp_off[p] + j] (nothing for an empty hypothesis):
+ *       EMOASR_ALIGN_SI   the ops without the deletions;
+ *       EMOASR_ALIGN_SID  align_hyps.py:43-55 as it runs: a deletion with no label before it, or after a label other than C,
+ *                         turns the next C into D; a deletion after a C is dropped.
+ *   max_hyp_len / max_ref_len are the caller's bounds on the lengths; one over EMOASR_EDIT_MAX_LEN is an error return.  The
+ *   direction codes of a pair (2 bits per cell) live in LDS up to EMOASR_EDIT_LDS_WORDS 64-bit words; a larger pair keeps them in
+ *   ws[ws_off[p] .. ws_off[p+1]) (ws 64-bit words, ws_off int64 [P+1]), emoasr_edit_align_ws_words(R, H) words of it (0: LDS; -1:
+ *   over the limit).  A pair that breaks the declared bounds, its offsets or its workspace is not computed: its counts are -1 and
+ *   bit 0 of status[0] (int32, zeroed by the caller) is set.  One wave per pair; nothing is written outside the outputs.
+ * emoasr_rescore_grid: rows k of utterance u are utt_off[u] .. utt_off[u+1]-1 (N rows, U utterances).  For cell g = a * G2 + b:
+ *     best[g][u]  = the first row of u with the largest (score_asr[k] + lm_w[a] * score_lm[k]) + len_w[b] * ylen[k], every product
+ *                   and sum rounded once to f64 (no fused multiply-add); -1 for an utterance without rows.  Scores are finite.
+ *     totals[g]   int64 [3] = (n_sub, n_ins, n_del) of counts [N][4] summed over the winners.  G1 * G2 <= 65535. */
+#define EMOASR_EDIT_MAX_LEN 4096
+#define EMOASR_EDIT_LDS_WORDS 4096
+enum { EMOASR_ALIGN_NONE = 0, EMOASR_ALIGN_SI = 1, EMOASR_ALIGN_SID = 2 };
+long emoasr_edit_align_lds_words(void);   /* EMOASR_EDIT_LDS_WORDS, for callers that size workspaces without this header */
+long emoasr_edit_align_ws_words(int ref_len, int hyp_len);
+int emoasr_edit_align(int P, int n_ref, int max_hyp_len, int max_ref_len, const int* hyp, const int* hyp_off, const int* ref,
+                      const int* ref_off, const int* ref_idx, int label_mode, int* counts, unsigned char* ops,
+                      const long* ops_off, unsigned char* labels, void* ws, const long* ws_off, int* status, void* stream);
+int emoasr_rescore_grid(int N, int U, int G1, int G2, const double* score_asr, const double* score_lm, const int* ylen,
+                        const int* utt_off, const int* counts, const double* lm_w, const double* len_w, int* best,
+                        long long* totals, void* stream);
+
 /* ---- one Conformer encoder layer, forward, sequenced on the host in C++ ---------
  * ConformerEncoderLayer.forward (asr/modeling/conformer.py:146-225) with relative-position attention:
  *   x += 0.5 * drop(FFN_macaron(LN(x)));  x += drop(RelMHA(LN(x)));  x += drop(ConvModule(LN(x)));
