@@ -1,4 +1,5 @@
-"""Decoding driver with the reference's protocol (asr/test_asr.py:36-121,226-263): one utterance per step,
+"""Decoding driver with the reference's protocol (asr/test_asr.py:36-121,226-263): one utterance per step (a loader whose
+batches hold several utterances is decoded batch by batch, its rows emitted utterance by utterance: test_step_batch),
 result rows `[utt_id, token_id, text, reftext]` (n-best: `[utt_id, score, token_id, text, reftext]`), and
 the real-time-factor measurement (wall time of `test` over `num_samples` utterances / audio seconds, mean
 over repeats).
@@ -36,6 +37,22 @@ def test_step(model, data, beam_width, len_weight, decode_ctc_weight, decode_pho
     return utt_id, hyps, scores, reftext
 
 
+def test_step_batch(model, data, beam_width, len_weight, decode_ctc_weight, decode_phone, lm, lm_weight, device):
+    """a batch of several utterances in one decode call -> [(utt_id, hyps, scores, reftext)] in batch order, each entry what test_step
+    gives for that utterance alone.  Greedy decoding takes any batch; beam_width > 1 needs a search that does (CTC without an LM:
+    the batched device search)."""
+    hyps, scores, _, _ = model.decode(data["xs"].to(device), data["xlens"], beam_width, len_weight, lm=lm,
+                                      lm_weight=lm_weight, decode_ctc_weight=decode_ctc_weight, decode_phone=decode_phone)
+    reftexts = data["ptexts"] if decode_phone else data["texts"]
+    out = []
+    for b, utt_id in enumerate(data["utt_ids"]):
+        if beam_width > 1:
+            out.append((utt_id, hyps[b], None if scores is None else scores[b], reftexts[b]))
+        else:   # greedy: one hypothesis per utterance
+            out.append((utt_id, [hyps[b]], None if scores is None else [scores[b]], reftexts[b]))
+    return out
+
+
 def test(model, dataloader, vocab, beam_width, len_weight, decode_ctc_weight, decode_phone, lm, lm_weight, device,
          eos_id=2, num_samples=-1, sample_utt_id=None, nbest=False):
     """test_asr.py:63-121 -> rows.  An utterance without any hypothesis gives token_id None and an empty text."""
@@ -62,28 +79,37 @@ def test(model, dataloader, vocab, beam_width, len_weight, decode_ctc_weight, de
 
 def _test_rows(model, dataloader, vocab, beam_width, len_weight, decode_ctc_weight, decode_phone, lm, lm_weight, device, eos_id,
                num_samples, sample_utt_id, nbest, rows, n):
-    for i, data in enumerate(dataloader):
-        if num_samples > 0 and (i + 1) > num_samples:
+    seen = 0    # utterances met so far, the skipped ones included
+    for data in dataloader:
+        if num_samples > 0 and seen >= num_samples:
             return rows
-        if sample_utt_id is not None and sample_utt_id != data["utt_ids"][0]:
+        nb = len(data["utt_ids"])
+        if sample_utt_id is not None and sample_utt_id not in data["utt_ids"]:
+            seen += nb
             continue
-        utt_id, hyps, scores, reftext = test_step(model, data, beam_width, len_weight, decode_ctc_weight, decode_phone,
-                                                  lm, lm_weight, device)
-        text = ""
-        if nbest:
-            for hyp, score in zip(hyps, scores):
-                ids = strip_eos(hyp, eos_id)
-                rows.append([utt_id, score, ints2str(ids), vocab.ids2text(ids), reftext])
-            text = vocab.ids2text(strip_eos(hyps[0], eos_id))
-        else:
-            if len(hyps) < 1:
-                token_id, text = None, ""
-                logging.warning(f"cannot decode {utt_id}")
+        step = test_step_batch if nb > 1 else (lambda *a: [test_step(*a)])
+        for utt_id, hyps, scores, reftext in step(model, data, beam_width, len_weight, decode_ctc_weight, decode_phone, lm,
+                                                  lm_weight, device):
+            if num_samples > 0 and seen >= num_samples:
+                return rows
+            seen += 1
+            if sample_utt_id is not None and sample_utt_id != utt_id:
+                continue
+            text = ""
+            if nbest:
+                for hyp, score in zip(hyps, scores):
+                    ids = strip_eos(hyp, eos_id)
+                    rows.append([utt_id, score, ints2str(ids), vocab.ids2text(ids), reftext])
+                text = vocab.ids2text(strip_eos(hyps[0], eos_id))
             else:
-                ids = strip_eos(hyps[0], eos_id)
-                token_id, text = ints2str(ids), vocab.ids2text(ids)
-            rows.append([utt_id, token_id, text, reftext])
-        logging.debug(f"{utt_id}({(i + 1):d}/{n:d}): {text}")
+                if len(hyps) < 1:
+                    token_id, text = None, ""
+                    logging.warning(f"cannot decode {utt_id}")
+                else:
+                    ids = strip_eos(hyps[0], eos_id)
+                    token_id, text = ints2str(ids), vocab.ids2text(ids)
+                rows.append([utt_id, token_id, text, reftext])
+            logging.debug(f"{utt_id}({seen:d}/{n:d}): {text}")
     return rows
 
 

@@ -24,6 +24,10 @@ Reference behaviour kept on purpose (it decides which prefixes survive):
   * when two paths reach the same prefix, probabilities are merged but the LM / length scores of the
     first path are kept (ctc.py:388-393);
   * hypotheses start with <eos> (the LM's BOS) and scores are returned best first.
+
+Without an LM (the N-best lists of `test_asr.py --nbest --beam_width N`) the search depends on nothing outside the utterance's own
+rows: ctc_prefix_beam_search_batch runs it for any number of utterances in ONE launch on the device (csrc/ctc_beam.hip:
+emoasr_ctc_beam_batch; beam_width <= 32), with the same hypotheses in the same order as the host loop.
 """
 import math
 import os
@@ -272,3 +276,69 @@ def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=Non
             for key in [q for q in lm_rows if q not in slots.slot_of]:
                 del lm_rows[key]
     return [list(p.toks) for p in live], [p.total for p in live], logits
+
+
+CTC_BEAM_BATCH_BUDGET = 1 << 27   # rows x V elements of one chunk: 512 MiB of f32 log-probabilities next to the logits
+
+
+def _search_device(logp, top, row_off_host, beam_width, blank, eos, len_weight):
+    """one launch over the utterances of row_off, ONE download (tokens, lengths, scores, counts and the status word packed into one
+    int32 array) -> (hyps, scores) per utterance"""
+    B = len(row_off_host) - 1
+    row_off = torch.tensor(row_off_host, dtype=torch.int32).to(logp.device)
+    max_frames = max([b - a for a, b in zip(row_off_host[:-1], row_off_host[1:])] + [0])
+    out_tok, out_len, out_score, out_n, status = ops.ctc_beam_batch(logp, row_off, top, beam_width, blank, eos, len_weight,
+                                                                    max_frames=max_frames)
+    W, L = beam_width, max_frames + 1
+    host = torch.cat([out_tok.view(-1), out_len.view(-1), out_score.view(torch.int32).view(-1), out_n, status]).cpu().numpy()
+    o1, o2, o3 = B * W * L, B * W * L + B * W, B * W * L + 3 * B * W
+    tok, ln = host[:o1].reshape(B, W, L), host[o1:o2].reshape(B, W)
+    score, n, st = host[o2:o3].copy().view(np.float64).reshape(B, W), host[o3:o3 + B], int(host[o3 + B])
+    if st:
+        from .. import lib
+        raise lib.EmoasrHipError(f"emoasr_ctc_beam_batch refused an utterance: {ops.ctc_beam_status_text(st)} (status {st})")
+    hyps = [[tok[b, i, :ln[b, i]].tolist() for i in range(n[b])] for b in range(B)]
+    return hyps, [[float(v) for v in score[b, :n[b]]] for b in range(B)]
+
+
+def ctc_prefix_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0.0):
+    """-> (hyps, scores, logits) for ALL utterances of the batch, no LM: hyps[b] / scores[b] are what ctc_prefix_beam_search returns
+    for utterance b alone (best first, every hypothesis starting with <eos>), logits[b] is [1, elens[b], V].
+
+    The head runs over the valid frames only (the rows of all utterances stacked), then one log-soft-max and one top-k over all
+    rows, one search launch and one download.  Utterances are taken in chunks of at most CTC_BEAM_BATCH_BUDGET = 2^27 rows x V
+    elements (an utterance larger than that goes alone), so the f32 log-probabilities of a chunk stay within 512 MiB."""
+    if not 1 <= beam_width <= ops.CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
+    eng = _engine_of(dec)
+    blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size
+    B, Tmax = eouts.shape[0], eouts.shape[1]
+    lens = [min(int(n), Tmax) for n in elens]
+    assert len(lens) == B
+    hyps, scores, logits_out = [], [], []
+    k = min(beam_width, V)
+    b0 = 0
+    with torch.no_grad():
+        while b0 < B:
+            b1, rows = b0 + 1, lens[b0]
+            while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET:
+                rows += lens[b1]
+                b1 += 1
+            row_off = [0]
+            for n in lens[b0:b1]:
+                row_off.append(row_off[-1] + n)
+            if rows:
+                x = eouts[b0, :lens[b0]] if b1 == b0 + 1 else torch.cat([eouts[b, :lens[b]] for b in range(b0, b1)])
+                logits = eng.head_logits(x.unsqueeze(0), getattr(dec, "_prefix", "decoder") + ".output")[0]      # [rows, V]
+                logp = ops.log_softmax(logits)
+                _, top, _ = ops.topk(logp, k)
+            else:
+                logits = torch.empty(0, V, device=eouts.device, dtype=eouts.dtype)
+                logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
+                top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
+            h, s = _search_device(logp, top, row_off, beam_width, blank, eos, len_weight)
+            hyps += h
+            scores += s
+            logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]
+            b0 = b1
+    return hyps, scores, logits_out

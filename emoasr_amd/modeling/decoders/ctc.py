@@ -4,6 +4,8 @@
     decoder.decode(eouts, elens, eouts_inter, beam_width, ...) -> (hyps, scores, logits, aligns)
     decoder.decode(..., decode_phone=True) -> the same through the phone head (greedy only)
     (beam_width <= 1: greedy; > 1: CTC prefix beam search with optional LM fusion, ctc.py:203-344)
+    beam_width > 1 without an LM on a batch of several utterances: the batched device search (csrc/ctc_beam.hip) -> hyps, scores
+    and logits are lists with one entry per utterance.  decoder.ctc_beam_impl = "device" sends a single utterance there too.
 
 With every auxiliary weight at 0 (the L-series configs) the head GEMM, CTC lattice and gradient run as one
 fused autograd node.  Knowledge distillation (kd_weight, ctc.py:117-127), the phone-level CTC
@@ -53,6 +55,7 @@ class CTCDecoder(nn.Module):
                 self.inter_ctc_kd_loss_fn = kd_loss()
                 self.reduce_main_loss_kd = params.reduce_main_loss_kd
                 self.forced_aligner = CTCForcedAligner(blank_id=self.blank_id)
+        self.ctc_beam_impl = "host"   # search of ONE utterance without an LM: "host" (csrc/ctc_beam_host.hip) | "device"
         self._prefix = prefix  # parameter-name prefix of this module inside the owning ASR model
         self._owner = None
 
@@ -117,6 +120,18 @@ class CTCDecoder(nn.Module):
             if lm_weight > 0:
                 logging.warning("greedy decoding: LM is not used")
             return ctc_greedy_apply(self, eouts, elens)
-        from ..ctc_beam_search import ctc_prefix_beam_search
+        from ..ctc_beam_search import ctc_prefix_beam_search, ctc_prefix_beam_search_batch
+        if self.ctc_beam_impl not in ("host", "device"):
+            raise ValueError(f"emoasr_amd: ctc_beam_impl is 'host' or 'device', not {self.ctc_beam_impl!r}")
+        no_lm = lm is None or lm_weight <= 0
+        if eouts.shape[0] > 1:
+            if not no_lm:
+                raise NotImplementedError("emoasr_amd: CTC beam search with LM fusion decodes one utterance at a time; "
+                                          "the batched search is for lm_weight == 0")
+            hyps, scores, logits = ctc_prefix_beam_search_batch(self, eouts, elens, beam_width, len_weight)
+            return hyps, scores, logits, None
+        if no_lm and self.ctc_beam_impl == "device":
+            hyps, scores, logits = ctc_prefix_beam_search_batch(self, eouts, elens, beam_width, len_weight)
+            return hyps[0], scores[0], logits[0], None
         hyps, scores, logits = ctc_prefix_beam_search(self, eouts, elens, beam_width, len_weight, lm, lm_weight)
         return hyps, scores, logits, None

@@ -1078,6 +1078,57 @@ def topk(x, k, aux=None):
     return vals, idx, aux_out
 
 
+CTC_BEAM_MAX_WIDTH = 32
+CTC_BEAM_STATUS = {1: "a top-k label outside the vocabulary", 2: "row_off not rising", 4: "more frames than max_frames",
+                   8: "workspace share short"}
+
+
+def ctc_beam_batch(logp, row_off, top, W, blank, eos, len_weight=0.0, max_frames=None):
+    """CTC prefix beam search without an LM for B utterances in one launch (csrc/ctc_beam.hip).  logp f32 [rows, V] (row stride
+    allowed): log_softmax over all frames of all utterances; row_off int32 [B+1]: utterance b owns rows row_off[b] .. row_off[b+1];
+    top int32 [rows, k], k = min(W, V): topk of logp -> device tensors (out_tok int32 [B, W, max_frames + 1], out_len int32 [B, W],
+    out_score f64 [B, W] best first, out_n int32 [B], status int32 [1]).  Only the first out_n[b] rows of an utterance and the first
+    out_len tokens of a row are defined; out_n[b] = -1 and a bit of status: that utterance was refused (CTC_BEAM_STATUS).  One
+    synchronisation here, the check of row_off (which also gives max_frames when it is not passed); the caller reads status with
+    the outputs."""
+    assert _chk(logp, torch.float32).dim() == 2 and (logp.shape[0] == 0 or logp.stride(1) == 1)
+    rows, V = logp.shape
+    ld = logp.stride(0) if rows > 1 else V
+    B = row_off.numel() - 1
+    W = int(W)
+    if not 1 <= W <= CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"ctc_beam_batch: beam width {W} is outside 1..{CTC_BEAM_MAX_WIDTH}")
+    k = min(W, V)
+    assert B >= 0 and _chk(row_off, torch.int32).is_contiguous() and row_off.dim() == 1
+    assert _chk(top, torch.int32).shape == (rows, k) and top.is_contiguous()
+    dev = logp.device
+    if B == 0:
+        return (torch.empty(0, W, 1, device=dev, dtype=torch.int32), torch.empty(0, W, device=dev, dtype=torch.int32),
+                torch.empty(0, W, device=dev, dtype=torch.float64), torch.empty(0, device=dev, dtype=torch.int32),
+                torch.zeros(1, device=dev, dtype=torch.int32))
+    # (one synchronisation: the kernel checks each utterance's own offsets, not that they cover the rows)
+    n = row_off[1:] - row_off[:-1]
+    ok, longest = torch.stack([((row_off[0] == 0) & (row_off[-1] == rows) & (n >= 0).all()).int(), n.max()]).tolist()
+    if not ok:
+        raise ValueError(f"ctc_beam_batch: row_off must rise from 0 to the {rows} rows")
+    max_frames = int(longest) if max_frames is None else int(max_frames)
+    out_tok = torch.empty(B, W, max_frames + 1, device=dev, dtype=torch.int32)
+    out_len = torch.empty(B, W, device=dev, dtype=torch.int32)
+    out_score = torch.empty(B, W, device=dev, dtype=torch.float64)
+    out_n = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    ws_bytes = lib.size_query("emoasr_ctc_beam_batch_ws_bytes", B, rows, W)
+    ws = torch.empty(ws_bytes // 8, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        lib.call("emoasr_ctc_beam_batch", B, V, W, k, _p(logp), ld, _p(row_off), _p(top), int(blank), int(eos), float(len_weight),
+                 max_frames, _p(out_tok), _p(out_len), _p(out_score), _p(out_n), _p(ws), ws_bytes, _p(status), _stream())
+    return out_tok, out_len, out_score, out_n, status
+
+
+def ctc_beam_status_text(status):
+    return ", ".join(text for bit, text in CTC_BEAM_STATUS.items() if status & bit) or "ok"
+
+
 def ctc_prefix_init(x, blank):
     T, V = x.shape
     r = torch.empty(T, 2, device=x.device, dtype=torch.float32)

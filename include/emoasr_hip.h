@@ -1133,6 +1133,32 @@ int emoasr_ctc_beam_step(emoasr_ctc_beam_t* h, const float* row, const int* top,
 int emoasr_ctc_beam_prefix(const emoasr_ctc_beam_t* h, int i, int* toks, int cap);   /* -> length of live prefix i */
 int emoasr_ctc_beam_scores(const emoasr_ctc_beam_t* h, double* total);              /* -> number of live prefixes */
 
+/* ---- CTC prefix beam search, batched, on the device (no LM) ------------------------------------------------
+ * emoasr_ctc_beam_batch: the same search for B utterances in one launch, for the case without LM fusion (the N-best lists of
+ *   `test_asr.py --nbest --beam_width N` on a CTC model).  Results equal the host search above with lm_lp = NULL: the same
+ *   hypotheses in the same order; per value the same sequence of double operations (NEG = -1e10, lse2(a, b) = m + log(exp(a - m) +
+ *   exp(b - m)) with m the larger operand, rows widened from f32, total = (asr + 0.0) + len_weight * (plain labels of the parent
+ *   + 1), nothing contracted), so the scores differ by the ulps of the device's exp / log against the host's only.
+ *     logp  f32 [rows, V] (row stride ld), emoasr_log_softmax over all frames of all utterances; utterance b owns rows
+ *           row_off[b] .. row_off[b+1] (int32 [B+1], rising from 0)
+ *     top   int32 [rows, k], emoasr_topk of logp, best first, k = min(W, V) distinct labels per row; a blank among them is skipped
+ *     out_tok int32 [B, W, max_frames + 1]; out_len int32 [B, W]; out_score f64 [B, W], best first; out_n int32 [B]: the number
+ *           of live prefixes (< W when few frames or a small V cannot fill the beam).  Every hypothesis starts with eos.  Only the
+ *           first out_n[b] rows of an utterance, and the first out_len tokens of a row, are written.  An utterance of 0 frames
+ *           gives the single prefix (eos) with score 0.0.
+ *     ws    emoasr_ctc_beam_batch_ws_bytes(B, rows, W) bytes, 8-byte aligned, any content: the per-utterance tries that give every
+ *           prefix a canonical node id (the kernel clears its share); -1 from the query: W outside the limit.
+ *   Limits: 1 <= W <= EMOASR_CTC_BEAM_MAX_WIDTH (an error return otherwise), no LM.  Ties of the total go to the candidate seen
+ *   first (live prefix i, then its stay, then its extensions in top order): std::stable_sort's order.
+ *   An utterance is not searched, gets out_n[b] = -1 and sets a bit of status[0] (int32, zeroed by the caller) when its top holds
+ *   a label outside [0, V) (bit 0), its row_off falls or is negative (bit 1), it has more than max_frames frames (bit 2) or its
+ *   share of ws is short (bit 3).  One workgroup per utterance; nothing is written outside the outputs and ws. */
+#define EMOASR_CTC_BEAM_MAX_WIDTH 32
+long emoasr_ctc_beam_batch_ws_bytes(int B, int total_rows, int W);
+int emoasr_ctc_beam_batch(int B, int V, int W, int k, const float* logp, long ld, const int* row_off, const int* top, int blank,
+                          int eos, double len_weight, int max_frames, int* out_tok, int* out_len, double* out_score, int* out_n,
+                          void* ws, long ws_bytes, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
