@@ -1,0 +1,144 @@
+"""Shallow-fusion grid search for CTC models in ONE pass over the data (asr/fusion/test_fusion_grid.py).
+
+The reference decodes the test set once per (lm_weight, len_weight) cell, 11 x 6 = 66 full decodes in 66 host processes.  Encoder,
+head, soft-max and top-k do not depend on the cell, and the searches of all cells of a batch are independent: here every batch is
+encoded once and all cells are searched in one call of ctc_prefix_beam_search_batch_lm (csrc/ctc_beam_lm.hip), each cell scored with
+metrics.compute_wers on the device.
+
+    results, best = ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device)
+    python -m emoasr_amd.fusion_grid -conf asr.yaml -ep 40 --data test.tsv --beam_width 10 --lm_conf lm.yaml --lm_ep 20
+
+results = [(lm_weight, len_weight, wer, wer_info), ...], lm_weight outer and len_weight inner as the reference builds its cells;
+best = the first cell whose WER is strictly below every earlier one's, starting from 100 (test_fusion_grid.py:51-64).  CTC models
+only: the joint CTC / attention search (decode_ctc_weight > 0) and the other decoders keep their one-cell-at-a-time paths.
+"""
+import argparse
+import logging
+import os
+
+import numpy as np
+import torch
+
+from .decode import strip_eos
+from .metrics import compute_wers, wer_summary
+
+EPS = 1e-5           # test_fusion_grid.py:17
+GRID_BATCH = 16      # utterances per decode call of the command-line tool
+
+
+def weight_lists(lm_min, lm_max, lm_step, len_min, len_max, len_step):
+    """the reference's candidates (test_fusion_grid.py:39-40), as doubles, unrounded"""
+    return np.arange(lm_min, lm_max + EPS, lm_step), np.arange(len_min, len_max + EPS, len_step)
+
+
+def require_ctc(model, decode_ctc_weight=0):
+    kind = getattr(model, "decoder_type", None)
+    if kind != "ctc":
+        raise NotImplementedError(f"emoasr_amd.fusion_grid handles CTC models only (decoder_type == 'ctc'), not {kind!r}")
+    if decode_ctc_weight > 0:
+        raise NotImplementedError("emoasr_amd.fusion_grid: decode_ctc_weight > 0 is the joint CTC / attention search, whose grid is "
+                                  "not built; CTC models only")
+
+
+def ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                    texts_out=None):
+    """-> (results, best): results = [(lm_weight, len_weight, wer, wer_info)] over lm_weights x len_weights (lm_weights outer), best =
+    (lm_weight, len_weight, wer, wer_info) of the first cell with strictly smaller WER, from (0, 0, 100, "") as the reference starts.
+    One pass over the loader: every batch is encoded once, all cells are searched in one call, a cell with lm_weight <= 0 is the search
+    without an LM (it adds nothing).  texts_out: a list that receives, per cell in the order of results, the 1-best texts."""
+    from .modeling.ctc_beam_search import ctc_prefix_beam_search_batch_lm
+    require_ctc(model, decode_ctc_weight)
+    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+    hyps_of = [[] for _ in cells]
+    refs = []
+    with torch.no_grad():
+        for data in dataloader:
+            eouts, elens, _ = model.encoder(data["xs"].to(device), data["xlens"])
+            hyps, _, _ = ctc_prefix_beam_search_batch_lm(model.decoder, eouts, elens, beam_width, lm, cells)
+            for b, reftext in enumerate(data["texts"]):
+                refs.append(reftext.split())
+                for c in range(len(cells)):
+                    best_hyp = hyps[b][c][0] if hyps[b][c] else []
+                    hyps_of[c].append(vocab.ids2text(strip_eos(best_hyp, eos_id)).split())
+    if texts_out is not None:
+        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
+    results = []
+    best = (0, 0, 100, "")
+    for c, (lm_weight, len_weight) in enumerate(cells):
+        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
+        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
+        results.append(row)
+        if wer < best[2]:
+            best = row
+    return results, best
+
+
+def log_results(results, best):
+    """the reference's log lines (test_fusion_grid.py:56-69)"""
+    for lm_weight, len_weight, _, wer_info in results:
+        logging.info(f"lm_weight: {lm_weight:.3f} len_weight: {len_weight:.3f} - {wer_info}")
+    logging.info("***** best WER:")
+    logging.info(f"lm_weight: {best[0]:.3f} len_weight: {best[1]:.3f} - {best[3]}")
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(prog="python -m emoasr_amd.fusion_grid", description=__doc__.split("\n\n")[0])
+    parser.add_argument("-conf", type=str, required=True)
+    parser.add_argument("-ep", type=str, required=True)
+    parser.add_argument("--data", type=str, default=None)
+    parser.add_argument("--data_tag", type=str, default="test")
+    parser.add_argument("--save_dir", type=str, default=None)
+    parser.add_argument("--beam_width", type=int, default=None)
+    parser.add_argument("--decode_ctc_weight", type=float, default=0)
+    parser.add_argument("--lm_min", type=float, default=0)
+    parser.add_argument("--lm_max", type=float, default=1)
+    parser.add_argument("--lm_step", type=float, default=0.1)
+    parser.add_argument("--len_min", type=float, default=0)
+    parser.add_argument("--len_max", type=float, default=5)
+    parser.add_argument("--len_step", type=float, default=1)
+    parser.add_argument("--lm_conf", type=str, default=None)
+    parser.add_argument("--lm_ep", type=str, default=None)
+    parser.add_argument("--lm_tag", type=str, default=None)
+    return parser
+
+
+def _loader(dataset, n):
+    for i in range(0, len(dataset), n):
+        yield dataset.collate_fn([dataset[j] for j in range(i, min(i + n, len(dataset)))])
+
+
+def main(args):
+    from .datasets import ASRDataset, Vocab
+    from .modeling.asr import ASR
+    from .modeling.lm import LM
+    from .rescore import load_config, model_path
+    params = load_config(args.conf)
+    require_ctc(params, args.decode_ctc_weight)
+    if not (args.lm_conf and args.lm_ep):
+        raise SystemExit("emoasr_amd.fusion_grid: shallow fusion needs --lm_conf and --lm_ep")
+    device = torch.device("cuda")
+    log_dir = args.save_dir or os.path.splitext(args.conf)[0]
+    os.makedirs(log_dir, exist_ok=True)
+    data_path = args.data or params.test_path
+    data_tag = args.data if args.data_tag == "test" and data_path != args.data and args.data else args.data_tag
+    data_tag = os.path.splitext(os.path.basename(data_tag))[0]
+    logging.basicConfig(filename=os.path.join(log_dir, f"test_fusion_grid_{data_tag}_ctc{args.decode_ctc_weight}_ep{args.ep}.log"),
+                        format="%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s", level=logging.INFO)
+    model = ASR(params, phase="test")
+    model.load_state_dict(torch.load(model_path(args.conf, args.ep), map_location="cpu"))
+    model.to(device).eval()
+    model.decoder.ctc_beam_impl = "device"
+    lm_params = load_config(args.lm_conf)
+    lm = LM(lm_params, phase="test")
+    lm.load_state_dict(torch.load(model_path(args.lm_conf, args.lm_ep), map_location="cpu"))
+    lm.to(device).eval()
+    dataset = ASRDataset(params, data_path, phase="test")
+    lm_weights, len_weights = weight_lists(args.lm_min, args.lm_max, args.lm_step, args.len_min, args.len_max, args.len_step)
+    results, best = ctc_fusion_grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), args.beam_width or params.beam_width,
+                                    lm, lm_weights, len_weights, device, eos_id=params.eos_id)
+    log_results(results, best)
+    return results, best
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -285,6 +285,9 @@ SIGNATURES = {
     "emoasr_edit_align": [I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P],
     "emoasr_rescore_grid": [I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "emoasr_ctc_beam_batch": [I, I, I, I, P, L, P, P, I, I, ctypes.c_double, I, P, P, P, P, P, L, P, P],
+    "emoasr_ctc_beam_lm_init": [I, I, I, P, P, I, I, I, P, L, P, I, P, P, P],
+    "emoasr_ctc_beam_lm_frame": [I, I, I, I, I, I, P, L, P, P, P, P, P, I, I, I, P, L, P, L, P, I, P, P, P],
+    "emoasr_ctc_beam_lm_finish": [I, I, I, I, P, P, P, P, P, L, P],
     "emoasr_ctc_forward_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P],
     "emoasr_ctc_grad_rows": [I, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, F, P, P, P, P, P, L, P],
     "emoasr_ctc_greedy": [I, I, I, I, P, L, P, I, P, P, P, P],

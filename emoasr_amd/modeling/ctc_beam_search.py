@@ -28,6 +28,11 @@ Reference behaviour kept on purpose (it decides which prefixes survive):
 Without an LM (the N-best lists of `test_asr.py --nbest --beam_width N`) the search depends on nothing outside the utterance's own
 rows: ctc_prefix_beam_search_batch runs it for any number of utterances in ONE launch on the device (csrc/ctc_beam.hip:
 emoasr_ctc_beam_batch; beam_width <= 32), with the same hypotheses in the same order as the host loop.
+
+With an LM, ctc_prefix_beam_search_batch_lm runs the searches of a whole batch -- and of all (lm_weight, len_weight) cells of a
+fusion grid over that batch -- frame by frame on the device (csrc/ctc_beam_lm.hip: one launch moves every search one frame and lists
+the prefixes that are new; one batched LM call scores them into a pool of rows the next launch reads).  Nothing but the record
+count (and, for a stateless LM, the records) comes to the host per frame.
 """
 import math
 import os
@@ -337,6 +342,134 @@ def ctc_prefix_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0.0):
                 logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
                 top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
             h, s = _search_device(logp, top, row_off, beam_width, blank, eos, len_weight)
+            hyps += h
+            scores += s
+            logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]
+            b0 = b1
+    return hyps, scores, logits_out
+
+
+CTC_BEAM_LM_POOL_BUDGET = 1 << 30   # searches x rows per search x V elements of one chunk's LM pool: 4 GiB of f32 rows
+
+
+class _StatefulPass:
+    """LM pass of a stateful LM (the RNN LM): the token, source-row and destination-row columns of the record list go to lm.step as
+    they lie on the device (lm.step chunks them by RNNLM_STEP_MAX); no per-prefix host work, no prefix is ever re-run"""
+
+    def __init__(self, lm, rows, V):
+        self.lm, self.pools = lm, lm.new_pools(rows)
+        self.logp = self.pools.logp
+        assert self.logp.shape[1] >= V, "the LM's vocabulary is smaller than the CTC head's"
+
+    def __call__(self, st, n):
+        if n:
+            self.lm.step(self.pools, n, st.rec[3], st.rec[4], st.rec[5], row_dst=st.rec[5])
+
+
+class _StatelessPass:
+    """LM pass of a stateless LM (the Transformer LM): the host keeps (search, node) -> tokens from the records (the parent's tokens
+    + the token), runs ONE lm.predict over the new prefixes of all searches, 0-padded like pad_sequence (ctc.py:243-246), and
+    copies the rows into the pool with one index_copy_"""
+
+    def __init__(self, lm, rows, V, device):
+        self.lm, self.toks = lm, {}
+        self.logp = torch.empty(rows, V, device=device, dtype=torch.float32)
+
+    def __call__(self, st, n):
+        if not n:
+            return
+        rec = st.rec[:, :n].cpu().numpy()
+        need = []
+        for s, node, parent, tok, _, _ in rec.T.tolist():
+            p = (self.toks[(s, parent)] + (tok,)) if parent >= 0 else (tok,)
+            self.toks[(s, node)] = p
+            need.append(p)
+        width = max(len(p) for p in need)
+        batch = torch.zeros(n, width, dtype=torch.int64)
+        for i, p in enumerate(need):
+            batch[i, : len(p)] = torch.tensor(p)
+        rows, _ = self.lm.predict(batch, [len(p) for p in need])
+        self.logp.index_copy_(0, st.rec[5, :n].long(), rows[:, : self.logp.shape[1]].float())
+
+
+def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weights):
+    """the frame loop over csrc/ctc_beam_lm.hip for the utterances of row_off x the weight pairs -> (hyps, scores), each
+    [utterance][pair].  init, an LM pass over the root records, then per frame one launch, one small download (the record count;
+    the stateless pass also takes the records) and one LM pass; finish and ONE download of the results."""
+    from .. import lib
+    dev = logp.device
+    B, C, W = len(row_off_host) - 1, len(weights), beam_width
+    S, V = B * C, logp.shape[1]
+    max_frames = max([b - a for a, b in zip(row_off_host[:-1], row_off_host[1:])] + [0])
+    row_off = torch.tensor(row_off_host, dtype=torch.int32).to(dev)
+    utt = torch.arange(B, dtype=torch.int32).repeat_interleave(C).to(dev)                  # search s = utterance s // C, pair s % C
+    wt = torch.tensor([[float(a) for a, _ in weights] * B, [float(b) for _, b in weights] * B], dtype=torch.float64).to(dev)
+    st = ops.ctc_beam_lm_init(row_off, utt, W, eos, max_frames)
+    rows = S * st.slots
+    lm_pass = _StatefulPass(lm, rows, V) if getattr(lm, "stateful", False) else _StatelessPass(lm, rows, V, dev)
+    lm_pass(st, int(st.rec_count.item()))
+    for t in range(max_frames):
+        ops.ctc_beam_lm_frame(st, t, logp, top, wt[0], wt[1], blank, lm_pass.logp)
+        lm_pass(st, int(st.rec_count.item()))
+    out_tok, out_len, out_score, out_n = ops.ctc_beam_lm_finish(st)
+    L = max_frames + 1
+    host = torch.cat([out_tok.view(-1), out_len.view(-1), out_score.view(torch.int32).view(-1), out_n, st.status]).cpu().numpy()
+    o1, o2, o3 = S * W * L, S * W * L + S * W, S * W * L + 3 * S * W
+    tok, ln = host[:o1].reshape(S, W, L), host[o1:o2].reshape(S, W)
+    score, n, status = host[o2:o3].copy().view(np.float64).reshape(S, W), host[o3:o3 + S], int(host[o3 + S])
+    if status:
+        raise lib.EmoasrHipError(f"emoasr_ctc_beam_lm refused a search: {ops.ctc_beam_status_text(status)} (status {status})")
+    hyps = [[[tok[b * C + c, i, :ln[b * C + c, i]].tolist() for i in range(n[b * C + c])] for c in range(C)] for b in range(B)]
+    return hyps, [[[float(v) for v in score[b * C + c, :n[b * C + c]]] for c in range(C)] for b in range(B)]
+
+
+def ctc_prefix_beam_search_batch_lm(dec, eouts, elens, beam_width, lm, weights):
+    """CTC prefix beam search WITH LM shallow fusion for all utterances of the batch and all (lm_weight, len_weight) pairs of
+    `weights` at once, on the device (csrc/ctc_beam_lm.hip).  One pair is plain batched fusion; several pairs are the cells of a
+    fusion grid, which share everything the weights do not touch.  -> (hyps, scores, logits): hyps[b][c] / scores[b][c] are what
+    ctc_prefix_beam_search returns for utterance b alone with pair c (best first, every hypothesis starting with <eos>), logits[b]
+    is [1, elens[b], V].
+
+    The acoustic side is ctc_prefix_beam_search_batch's, once per utterance whatever the number of pairs: the head over the valid
+    frames, one log-soft-max, one top-k.  Utterances are taken in chunks: the next utterance joins the chunk while (a) the chunk's
+    rows x V stay within CTC_BEAM_BATCH_BUDGET = 2^27 elements (512 MiB of f32 log-probabilities) and (b) its searches' LM pool,
+    utterances x pairs x (2 beam_width + 2) rows x V, stays within CTC_BEAM_LM_POOL_BUDGET = 2^30 elements (4 GiB); an utterance
+    that breaks either bound on its own goes alone."""
+    require_next_token_lm(lm, max([float(a) for a, _ in weights] + [0.0]))
+    if lm is None:
+        raise ValueError("ctc_prefix_beam_search_batch_lm needs an LM (without one: ctc_prefix_beam_search_batch)")
+    if not 1 <= beam_width <= ops.CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
+    weights = [(float(a), float(b)) for a, b in weights]
+    assert weights, "at least one (lm_weight, len_weight) pair"
+    eng = _engine_of(dec)
+    blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size
+    B, Tmax = eouts.shape[0], eouts.shape[1]
+    lens = [min(int(n), Tmax) for n in elens]
+    assert len(lens) == B
+    per_utt = len(weights) * ops.ctc_beam_lm_slots(beam_width) * V          # pool elements one utterance's searches need
+    hyps, scores, logits_out = [], [], []
+    k = min(beam_width, V)
+    b0 = 0
+    with torch.no_grad():
+        while b0 < B:
+            b1, rows = b0 + 1, lens[b0]
+            while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET and (b1 + 1 - b0) * per_utt <= CTC_BEAM_LM_POOL_BUDGET:
+                rows += lens[b1]
+                b1 += 1
+            row_off = [0]
+            for n in lens[b0:b1]:
+                row_off.append(row_off[-1] + n)
+            if rows:
+                x = eouts[b0, :lens[b0]] if b1 == b0 + 1 else torch.cat([eouts[b, :lens[b]] for b in range(b0, b1)])
+                logits = eng.head_logits(x.unsqueeze(0), getattr(dec, "_prefix", "decoder") + ".output")[0]      # [rows, V]
+                logp = ops.log_softmax(logits)
+                _, top, _ = ops.topk(logp, k)
+            else:
+                logits = torch.empty(0, V, device=eouts.device, dtype=eouts.dtype)
+                logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
+                top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
+            h, s = _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights)
             hyps += h
             scores += s
             logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]

@@ -5,7 +5,8 @@
     decoder.decode(..., decode_phone=True) -> the same through the phone head (greedy only)
     (beam_width <= 1: greedy; > 1: CTC prefix beam search with optional LM fusion, ctc.py:203-344)
     beam_width > 1 without an LM on a batch of several utterances: the batched device search (csrc/ctc_beam.hip) -> hyps, scores
-    and logits are lists with one entry per utterance.  decoder.ctc_beam_impl = "device" sends a single utterance there too.
+    and logits are lists with one entry per utterance.  decoder.ctc_beam_impl = "device" sends a single utterance there too, and
+    sends every search WITH an LM (lm_weight > 0, any number of utterances) to the batched fused search (csrc/ctc_beam_lm.hip).
 
 With every auxiliary weight at 0 (the L-series configs) the head GEMM, CTC lattice and gradient run as one
 fused autograd node.  Knowledge distillation (kd_weight, ctc.py:117-127), the phone-level CTC
@@ -55,7 +56,9 @@ class CTCDecoder(nn.Module):
                 self.inter_ctc_kd_loss_fn = kd_loss()
                 self.reduce_main_loss_kd = params.reduce_main_loss_kd
                 self.forced_aligner = CTCForcedAligner(blank_id=self.blank_id)
-        self.ctc_beam_impl = "host"   # search of ONE utterance without an LM: "host" (csrc/ctc_beam_host.hip) | "device"
+        # "host": one utterance (with or without an LM) through csrc/ctc_beam_host.hip, an LM with several utterances is refused;
+        # "device": one utterance without an LM through csrc/ctc_beam.hip too, any search with an LM through csrc/ctc_beam_lm.hip
+        self.ctc_beam_impl = "host"
         self._prefix = prefix  # parameter-name prefix of this module inside the owning ASR model
         self._owner = None
 
@@ -124,6 +127,12 @@ class CTCDecoder(nn.Module):
         if self.ctc_beam_impl not in ("host", "device"):
             raise ValueError(f"emoasr_amd: ctc_beam_impl is 'host' or 'device', not {self.ctc_beam_impl!r}")
         no_lm = lm is None or lm_weight <= 0
+        if not no_lm and self.ctc_beam_impl == "device":
+            from ..ctc_beam_search import ctc_prefix_beam_search_batch_lm
+            hyps, scores, logits = ctc_prefix_beam_search_batch_lm(self, eouts, elens, beam_width, lm, [(lm_weight, len_weight)])
+            if eouts.shape[0] > 1:
+                return [h[0] for h in hyps], [s[0] for s in scores], logits, None
+            return hyps[0][0], scores[0][0], logits[0], None
         if eouts.shape[0] > 1:
             if not no_lm:
                 raise NotImplementedError("emoasr_amd: CTC beam search with LM fusion decodes one utterance at a time; "

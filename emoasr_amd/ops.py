@@ -10,6 +10,7 @@ from ctypes import byref, c_void_p
 
 import os
 import threading
+from types import SimpleNamespace
 
 import torch
 
@@ -1127,6 +1128,72 @@ def ctc_beam_batch(logp, row_off, top, W, blank, eos, len_weight=0.0, max_frames
 
 def ctc_beam_status_text(status):
     return ", ".join(text for bit, text in CTC_BEAM_STATUS.items() if status & bit) or "ok"
+
+
+CTC_BEAM_STATUS.update({16: "a search names an utterance outside the batch", 32: "no free row left in a search's share of the LM pool"})
+
+
+def ctc_beam_lm_slots(W):
+    """rows of the LM pool one search of beam width W needs (2 W + 2)"""
+    return lib.size_query("emoasr_ctc_beam_lm_slots", W)
+
+
+def ctc_beam_lm_init(row_off, utt, W, eos, max_frames, slots=None):
+    """start S = len(utt) fused searches (csrc/ctc_beam_lm.hip) over the B utterances of row_off (int32 [B+1], device): utt int32
+    [S] names each search's utterance.  -> the state that ctc_beam_lm_frame / _finish take: .rec int32 [6, S W] (search, node,
+    parent node, token, src row, dst row) and .rec_count int32 [1] hold the records of the last call -- here the S roots, src = -1
+    -- whose pool rows dst the caller fills before the next call; .status int32 [1] collects the refusals (CTC_BEAM_STATUS)."""
+    W = int(W)
+    if not 1 <= W <= CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"ctc_beam_lm: beam width {W} is outside 1..{CTC_BEAM_MAX_WIDTH}")
+    assert _chk(row_off, torch.int32).is_contiguous() and row_off.dim() == 1 and _chk(utt, torch.int32).is_contiguous() and utt.dim() == 1
+    S, B, dev = utt.numel(), row_off.numel() - 1, utt.device
+    slots = ctc_beam_lm_slots(W) if slots is None else int(slots)
+    max_frames = int(max_frames)
+    ws_bytes = lib.size_query("emoasr_ctc_beam_lm_ws_bytes", S, max_frames, W)
+    st = SimpleNamespace(S=S, B=B, W=W, eos=int(eos), max_frames=max_frames, slots=slots, row_off=row_off, utt=utt, ws_bytes=ws_bytes,
+                         ws=torch.empty(max(ws_bytes // 8, 1), device=dev, dtype=torch.int64), rec_cap=max(S * W, 1),
+                         status=torch.zeros(1, device=dev, dtype=torch.int32))
+    buf = torch.zeros(1 + 6 * st.rec_cap, device=dev, dtype=torch.int32)
+    st.rec_count, st.rec = buf[:1], buf[1:].view(6, st.rec_cap)
+    if S:
+        with torch.cuda.device(dev):
+            lib.call("emoasr_ctc_beam_lm_init", S, B, W, _p(row_off), _p(utt), st.eos, max_frames, slots, _p(st.ws), ws_bytes,
+                     _p(st.rec), st.rec_cap, _p(st.rec_count), _p(st.status), _stream())
+    return st
+
+
+def ctc_beam_lm_frame(st, t, logp, top, lm_weight, len_weight, blank, lm_logp):
+    """advance every search whose utterance has a frame t by that frame.  logp f32 [rows, V], top int32 [rows, k]: as for
+    ctc_beam_batch; lm_weight / len_weight f64 [S]; lm_logp f32 [S * st.slots, >= V]: the pool whose rows the records name.  The new
+    prefixes of the frame are in st.rec[:, :st.rec_count]."""
+    assert _chk(logp, torch.float32).dim() == 2 and logp.stride(1) == 1 and _chk(lm_logp, torch.float32).dim() == 2 and lm_logp.stride(1) == 1
+    rows, V = logp.shape
+    k = min(st.W, V)
+    assert _chk(top, torch.int32).shape == (rows, k) and top.is_contiguous()
+    assert _chk(lm_weight, torch.float64).shape == (st.S,) and _chk(len_weight, torch.float64).shape == (st.S,)
+    assert lm_weight.is_contiguous() and len_weight.is_contiguous()
+    assert lm_logp.shape[0] >= st.S * st.slots and lm_logp.shape[1] >= V
+    if st.S:
+        with torch.cuda.device(logp.device):
+            lib.call("emoasr_ctc_beam_lm_frame", st.S, st.B, V, st.W, k, int(t), _p(logp), logp.stride(0) if rows > 1 else V,
+                     _p(st.row_off), _p(top), _p(st.utt), _p(lm_weight), _p(len_weight), int(blank), st.eos, st.max_frames, _p(lm_logp),
+                     lm_logp.stride(0), _p(st.ws), st.ws_bytes, _p(st.rec), st.rec_cap, _p(st.rec_count), _p(st.status), _stream())
+
+
+def ctc_beam_lm_finish(st):
+    """-> (out_tok int32 [S, W, max_frames + 1], out_len int32 [S, W], out_score f64 [S, W] best first, out_n int32 [S]; -1: the
+    search was refused, see st.status) as ctc_beam_batch returns them per utterance"""
+    dev = st.utt.device
+    out_tok = torch.empty(st.S, st.W, st.max_frames + 1, device=dev, dtype=torch.int32)
+    out_len = torch.empty(st.S, st.W, device=dev, dtype=torch.int32)
+    out_score = torch.empty(st.S, st.W, device=dev, dtype=torch.float64)
+    out_n = torch.empty(st.S, device=dev, dtype=torch.int32)
+    if st.S:
+        with torch.cuda.device(dev):
+            lib.call("emoasr_ctc_beam_lm_finish", st.S, st.W, st.max_frames, st.eos, _p(out_tok), _p(out_len), _p(out_score), _p(out_n),
+                     _p(st.ws), st.ws_bytes, _stream())
+    return out_tok, out_len, out_score, out_n
 
 
 def ctc_prefix_init(x, blank):

@@ -1159,6 +1159,50 @@ int emoasr_ctc_beam_batch(int B, int V, int W, int k, const float* logp, long ld
                           int eos, double len_weight, int max_frames, int* out_tok, int* out_len, double* out_score, int* out_n,
                           void* ws, long ws_bytes, int* status, void* stream);
 
+/* ---- CTC prefix beam search with LM shallow fusion, batched, on the device, one frame per launch -----------
+ * A *search* is one (utterance, (lm_weight, len_weight)) pair.  S searches run over B utterances; several searches may name the
+ * same utterance (the cells of a fusion grid) and share its logp / top rows, which are only read.  Results equal
+ * emoasr_ctc_beam_step fed the same f32 LM rows as lm_lp: the same hypotheses in the same order, per value the same sequence of
+ * double operations.  On top of emoasr_ctc_beam_batch's arithmetic: for live prefix i, lm_run starts at the prefix's LM term and,
+ * for j = 1..k in top order with the blank skipped, lm_run = lm_run + lm_weight * (double)lm_logp[slot_i][top[t][j-1]] (one rounded
+ * multiply, one rounded add); extension j carries the running value (the reference's `score_lm +=`, ctc.py:309-310), the stay the
+ * prefix's own term; a fold keeps the LM term and length bonus of the candidate seen first; total = (asr + lm) + len_bonus.  A
+ * search with lm_weight <= 0 reads no LM row, adds nothing and equals emoasr_ctc_beam_batch bit for bit.
+ *     utt        int32 [S]: the utterance of each search; lm_weight / len_weight f64 [S]
+ *     logp, ld, row_off, top, blank, eos, k = min(W, V): as for emoasr_ctc_beam_batch; max_frames >= the longest utterance
+ *     lm_logp    f32 [S * slots, ld_lm >= V]: the pool of LM next-token rows.  Search s owns rows s * slots .. (s + 1) * slots - 1 and
+ *                uses the first min(slots, emoasr_ctc_beam_lm_slots(W)) of them; emoasr_ctc_beam_lm_slots(W) = 2 W + 2 is enough
+ *                (<= W live after the previous frame + <= W taken at this one; the row of a prefix that left the beam returns to
+ *                the free list at the start of the NEXT frame, so this frame's records may still name it as a parent).
+ *     rec        int32 [6, rec_cap], rec_count int32 [1]: the NEW prefixes of the launch (extensions without a live twin, and the
+ *                root at init), column r = (search, node id, parent node id, token, src row, dst row) in rows 0..5; src / dst are
+ *                rows of the pool, src = -1 for the root.  The caller must fill pool row dst with the LM's next-token row after
+ *                that prefix (one LM step: token, state of src -> state of dst) before the next launch.  rec_cap >= S * W (init:
+ *                >= S).  The count is zeroed by each call; the order of records of different searches is not defined and no
+ *                result depends on it.
+ *     ws         emoasr_ctc_beam_lm_ws_bytes(S, max_frames, W) bytes, 8-byte aligned: per search its live set (id, parent, last,
+ *                n_plain, len, p_b, p_nb, lm, len_bonus, total, LM row), free list and waiting list, then its trie share.  It
+ *                carries the searches from init through the frames to finish.
+ *   emoasr_ctc_beam_lm_init    every search becomes the root (eos) with row 0 of its share; S root records.
+ *   emoasr_ctc_beam_lm_frame   advances every search whose utterance has a frame t by that frame (t = 0, 1, .. in order); one
+ *                              256-thread workgroup per search.
+ *   emoasr_ctc_beam_lm_finish  out_tok int32 [S, W, max_frames + 1], out_len int32 [S, W], out_score f64 [S, W], out_n int32 [S],
+ *                              as emoasr_ctc_beam_batch writes them per utterance.
+ *   Limits: 1 <= W <= EMOASR_CTC_BEAM_MAX_WIDTH (an error return otherwise, nothing written).  A search is retired (no further
+ *   writes, out_n = -1) and sets a bit of status[0] (int32, zeroed by the caller): bits 0-3 as emoasr_ctc_beam_batch (label outside
+ *   [0, V); falling row_off; more frames than max_frames; workspace or record list short), bit 4: utt[s] outside [0, B), bit 5: no
+ *   free row left in its share of the pool.  Nothing is written outside the outputs, rec / rec_count, status and ws. */
+long emoasr_ctc_beam_lm_ws_bytes(int S, int max_frames, int W);
+long emoasr_ctc_beam_lm_slots(int W);
+int emoasr_ctc_beam_lm_init(int S, int B, int W, const int* row_off, const int* utt, int eos, int max_frames, int slots, void* ws,
+                            long ws_bytes, int* rec, int rec_cap, int* rec_count, int* status, void* stream);
+int emoasr_ctc_beam_lm_frame(int S, int B, int V, int W, int k, int t, const float* logp, long ld, const int* row_off,
+                             const int* top, const int* utt, const double* lm_weight, const double* len_weight, int blank, int eos,
+                             int max_frames, const float* lm_logp, long ld_lm, void* ws, long ws_bytes, int* rec, int rec_cap,
+                             int* rec_count, int* status, void* stream);
+int emoasr_ctc_beam_lm_finish(int S, int W, int max_frames, int eos, int* out_tok, int* out_len, double* out_score, int* out_n,
+                              const void* ws, long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
