@@ -27,7 +27,8 @@ def build(force=False, verbose=True, variant=None, defines=()):
     objdir = os.path.join(HERE, "build") if not variant else os.path.join(HERE, "build", "variant_" + variant)
     LIB = globals()["LIB"] if not variant else os.path.join(HERE, "build", f"libemoasr_hip_{variant}.so")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h", "lstm_step.h", "gumbel.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h", "lstm_step.h", "gumbel.h",
+                                                  "ctc_beam_step.h")]
     headers.append(os.path.join(HERE, "..", "include", "emoasr_hip.h"))
     sources = SOURCES
     flags = FLAGS + ["-D" + d for d in defines]

@@ -284,26 +284,84 @@ def ctc_prefix_beam_search(dec, eouts, elens, beam_width, len_weight=0.0, lm=Non
 
 
 CTC_BEAM_BATCH_BUDGET = 1 << 27   # rows x V elements of one chunk: 512 MiB of f32 log-probabilities next to the logits
+CTC_BEAM_LM_POOL_BUDGET = 1 << 30   # searches x rows per search x V elements of one chunk's LM pool: 4 GiB of f32 rows
+
+
+def _check_width(beam_width):
+    if not 1 <= beam_width <= ops.CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
+
+
+def _chunks(dec, eouts, elens, k, admits=lambda n: True):
+    """the acoustic side of the device searches, chunk by chunk -> (b0, b1, row_off, logits, logp, top) per chunk of utterances
+    b0 .. b1: row_off the host list of their row offsets, logits [rows, V] of the head over their valid frames only (the rows of
+    all of them stacked), logp its log-soft-max, top int32 [rows, k] its top-k: one launch each.  The next utterance joins the
+    chunk while the chunk's rows x V stay within CTC_BEAM_BATCH_BUDGET and admits(utterances the chunk would then hold); an
+    utterance that breaks either bound on its own goes alone."""
+    eng = _engine_of(dec)
+    V = dec.vocab_size
+    B, Tmax = eouts.shape[0], eouts.shape[1]
+    lens = [min(int(n), Tmax) for n in elens]
+    assert len(lens) == B
+    b0 = 0
+    while b0 < B:
+        b1, rows = b0 + 1, lens[b0]
+        while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET and admits(b1 + 1 - b0):
+            rows += lens[b1]
+            b1 += 1
+        row_off = [0]
+        for n in lens[b0:b1]:
+            row_off.append(row_off[-1] + n)
+        if rows:
+            x = eouts[b0, :lens[b0]] if b1 == b0 + 1 else torch.cat([eouts[b, :lens[b]] for b in range(b0, b1)])
+            logits = eng.head_logits(x.unsqueeze(0), getattr(dec, "_prefix", "decoder") + ".output")[0]      # [rows, V]
+            logp = ops.log_softmax(logits)
+            _, top, _ = ops.topk(logp, k)
+        else:
+            logits = torch.empty(0, V, device=eouts.device, dtype=eouts.dtype)
+            logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
+            top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
+        yield b0, b1, row_off, logits, logp, top
+        b0 = b1
+
+
+def _search_chunks(chunks, search):
+    """-> (hyps, scores, logits) over all chunks: search(logp, top, row_off) gives a chunk's per-utterance hyps and scores.
+    Nothing here records a gradient: the chunk walk and the searches run under torch.no_grad()."""
+    hyps, scores, logits_out = [], [], []
+    with torch.no_grad():
+        for _, _, row_off, logits, logp, top in chunks:
+            h, s = search(logp, top, row_off)
+            hyps += h
+            scores += s
+            logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]
+    return hyps, scores, logits_out
+
+
+def _max_frames(row_off_host):
+    return max([b - a for a, b in zip(row_off_host[:-1], row_off_host[1:])] + [0])
+
+
+def _download(out_tok, out_len, out_score, out_n, status, refused):
+    """ONE download of the results of n searches (tokens, lengths, scores, counts and the status word packed into one int32 array)
+    -> (hyps, scores), each a list per search, best first; a status bit raises EmoasrHipError(`refused`: what the bits say)"""
+    n, W, L = out_tok.shape
+    host = torch.cat([out_tok.view(-1), out_len.view(-1), out_score.view(torch.int32).view(-1), out_n, status]).cpu().numpy()
+    o1, o2, o3 = n * W * L, n * W * L + n * W, n * W * L + 3 * n * W
+    tok, ln = host[:o1].reshape(n, W, L), host[o1:o2].reshape(n, W)
+    score, cnt, st = host[o2:o3].copy().view(np.float64).reshape(n, W), host[o3:o3 + n], int(host[o3 + n])
+    if st:
+        from .. import lib
+        raise lib.EmoasrHipError(f"{refused}: {ops.ctc_beam_status_text(st)} (status {st})")
+    hyps = [[tok[s, i, :ln[s, i]].tolist() for i in range(cnt[s])] for s in range(n)]
+    return hyps, [[float(v) for v in score[s, :cnt[s]]] for s in range(n)]
 
 
 def _search_device(logp, top, row_off_host, beam_width, blank, eos, len_weight):
-    """one launch over the utterances of row_off, ONE download (tokens, lengths, scores, counts and the status word packed into one
-    int32 array) -> (hyps, scores) per utterance"""
-    B = len(row_off_host) - 1
+    """one launch over the utterances of row_off, ONE download -> (hyps, scores) per utterance"""
     row_off = torch.tensor(row_off_host, dtype=torch.int32).to(logp.device)
-    max_frames = max([b - a for a, b in zip(row_off_host[:-1], row_off_host[1:])] + [0])
-    out_tok, out_len, out_score, out_n, status = ops.ctc_beam_batch(logp, row_off, top, beam_width, blank, eos, len_weight,
-                                                                    max_frames=max_frames)
-    W, L = beam_width, max_frames + 1
-    host = torch.cat([out_tok.view(-1), out_len.view(-1), out_score.view(torch.int32).view(-1), out_n, status]).cpu().numpy()
-    o1, o2, o3 = B * W * L, B * W * L + B * W, B * W * L + 3 * B * W
-    tok, ln = host[:o1].reshape(B, W, L), host[o1:o2].reshape(B, W)
-    score, n, st = host[o2:o3].copy().view(np.float64).reshape(B, W), host[o3:o3 + B], int(host[o3 + B])
-    if st:
-        from .. import lib
-        raise lib.EmoasrHipError(f"emoasr_ctc_beam_batch refused an utterance: {ops.ctc_beam_status_text(st)} (status {st})")
-    hyps = [[tok[b, i, :ln[b, i]].tolist() for i in range(n[b])] for b in range(B)]
-    return hyps, [[float(v) for v in score[b, :n[b]]] for b in range(B)]
+    outs = ops.ctc_beam_batch(logp, row_off, top, beam_width, blank, eos, len_weight, max_frames=_max_frames(row_off_host))
+    return _download(*outs, "emoasr_ctc_beam_batch refused an utterance")
 
 
 def ctc_prefix_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0.0):
@@ -313,43 +371,10 @@ def ctc_prefix_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0.0):
     The head runs over the valid frames only (the rows of all utterances stacked), then one log-soft-max and one top-k over all
     rows, one search launch and one download.  Utterances are taken in chunks of at most CTC_BEAM_BATCH_BUDGET = 2^27 rows x V
     elements (an utterance larger than that goes alone), so the f32 log-probabilities of a chunk stay within 512 MiB."""
-    if not 1 <= beam_width <= ops.CTC_BEAM_MAX_WIDTH:
-        raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
-    eng = _engine_of(dec)
-    blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size
-    B, Tmax = eouts.shape[0], eouts.shape[1]
-    lens = [min(int(n), Tmax) for n in elens]
-    assert len(lens) == B
-    hyps, scores, logits_out = [], [], []
-    k = min(beam_width, V)
-    b0 = 0
-    with torch.no_grad():
-        while b0 < B:
-            b1, rows = b0 + 1, lens[b0]
-            while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET:
-                rows += lens[b1]
-                b1 += 1
-            row_off = [0]
-            for n in lens[b0:b1]:
-                row_off.append(row_off[-1] + n)
-            if rows:
-                x = eouts[b0, :lens[b0]] if b1 == b0 + 1 else torch.cat([eouts[b, :lens[b]] for b in range(b0, b1)])
-                logits = eng.head_logits(x.unsqueeze(0), getattr(dec, "_prefix", "decoder") + ".output")[0]      # [rows, V]
-                logp = ops.log_softmax(logits)
-                _, top, _ = ops.topk(logp, k)
-            else:
-                logits = torch.empty(0, V, device=eouts.device, dtype=eouts.dtype)
-                logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
-                top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
-            h, s = _search_device(logp, top, row_off, beam_width, blank, eos, len_weight)
-            hyps += h
-            scores += s
-            logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]
-            b0 = b1
-    return hyps, scores, logits_out
-
-
-CTC_BEAM_LM_POOL_BUDGET = 1 << 30   # searches x rows per search x V elements of one chunk's LM pool: 4 GiB of f32 rows
+    _check_width(beam_width)
+    blank, eos = dec.blank_id, dec.eos_id
+    return _search_chunks(_chunks(dec, eouts, elens, min(beam_width, dec.vocab_size)),
+                          lambda logp, top, row_off: _search_device(logp, top, row_off, beam_width, blank, eos, len_weight))
 
 
 class _StatefulPass:
@@ -396,11 +421,10 @@ def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weigh
     """the frame loop over csrc/ctc_beam_lm.hip for the utterances of row_off x the weight pairs -> (hyps, scores), each
     [utterance][pair].  init, an LM pass over the root records, then per frame one launch, one small download (the record count;
     the stateless pass also takes the records) and one LM pass; finish and ONE download of the results."""
-    from .. import lib
     dev = logp.device
     B, C, W = len(row_off_host) - 1, len(weights), beam_width
     S, V = B * C, logp.shape[1]
-    max_frames = max([b - a for a, b in zip(row_off_host[:-1], row_off_host[1:])] + [0])
+    max_frames = _max_frames(row_off_host)
     row_off = torch.tensor(row_off_host, dtype=torch.int32).to(dev)
     utt = torch.arange(B, dtype=torch.int32).repeat_interleave(C).to(dev)                  # search s = utterance s // C, pair s % C
     wt = torch.tensor([[float(a) for a, _ in weights] * B, [float(b) for _, b in weights] * B], dtype=torch.float64).to(dev)
@@ -411,16 +435,8 @@ def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weigh
     for t in range(max_frames):
         ops.ctc_beam_lm_frame(st, t, logp, top, wt[0], wt[1], blank, lm_pass.logp)
         lm_pass(st, int(st.rec_count.item()))
-    out_tok, out_len, out_score, out_n = ops.ctc_beam_lm_finish(st)
-    L = max_frames + 1
-    host = torch.cat([out_tok.view(-1), out_len.view(-1), out_score.view(torch.int32).view(-1), out_n, st.status]).cpu().numpy()
-    o1, o2, o3 = S * W * L, S * W * L + S * W, S * W * L + 3 * S * W
-    tok, ln = host[:o1].reshape(S, W, L), host[o1:o2].reshape(S, W)
-    score, n, status = host[o2:o3].copy().view(np.float64).reshape(S, W), host[o3:o3 + S], int(host[o3 + S])
-    if status:
-        raise lib.EmoasrHipError(f"emoasr_ctc_beam_lm refused a search: {ops.ctc_beam_status_text(status)} (status {status})")
-    hyps = [[[tok[b * C + c, i, :ln[b * C + c, i]].tolist() for i in range(n[b * C + c])] for c in range(C)] for b in range(B)]
-    return hyps, [[[float(v) for v in score[b * C + c, :n[b * C + c]]] for c in range(C)] for b in range(B)]
+    hyps, scores = _download(*ops.ctc_beam_lm_finish(st), st.status, "emoasr_ctc_beam_lm refused a search")
+    return [hyps[b * C:(b + 1) * C] for b in range(B)], [scores[b * C:(b + 1) * C] for b in range(B)]
 
 
 def ctc_prefix_beam_search_batch_lm(dec, eouts, elens, beam_width, lm, weights):
@@ -438,40 +454,10 @@ def ctc_prefix_beam_search_batch_lm(dec, eouts, elens, beam_width, lm, weights):
     require_next_token_lm(lm, max([float(a) for a, _ in weights] + [0.0]))
     if lm is None:
         raise ValueError("ctc_prefix_beam_search_batch_lm needs an LM (without one: ctc_prefix_beam_search_batch)")
-    if not 1 <= beam_width <= ops.CTC_BEAM_MAX_WIDTH:
-        raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
+    _check_width(beam_width)
     weights = [(float(a), float(b)) for a, b in weights]
     assert weights, "at least one (lm_weight, len_weight) pair"
-    eng = _engine_of(dec)
     blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size
-    B, Tmax = eouts.shape[0], eouts.shape[1]
-    lens = [min(int(n), Tmax) for n in elens]
-    assert len(lens) == B
     per_utt = len(weights) * ops.ctc_beam_lm_slots(beam_width) * V          # pool elements one utterance's searches need
-    hyps, scores, logits_out = [], [], []
-    k = min(beam_width, V)
-    b0 = 0
-    with torch.no_grad():
-        while b0 < B:
-            b1, rows = b0 + 1, lens[b0]
-            while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET and (b1 + 1 - b0) * per_utt <= CTC_BEAM_LM_POOL_BUDGET:
-                rows += lens[b1]
-                b1 += 1
-            row_off = [0]
-            for n in lens[b0:b1]:
-                row_off.append(row_off[-1] + n)
-            if rows:
-                x = eouts[b0, :lens[b0]] if b1 == b0 + 1 else torch.cat([eouts[b, :lens[b]] for b in range(b0, b1)])
-                logits = eng.head_logits(x.unsqueeze(0), getattr(dec, "_prefix", "decoder") + ".output")[0]      # [rows, V]
-                logp = ops.log_softmax(logits)
-                _, top, _ = ops.topk(logp, k)
-            else:
-                logits = torch.empty(0, V, device=eouts.device, dtype=eouts.dtype)
-                logp = torch.empty(0, V, device=eouts.device, dtype=torch.float32)
-                top = torch.empty(0, k, device=eouts.device, dtype=torch.int32)
-            h, s = _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights)
-            hyps += h
-            scores += s
-            logits_out += [logits[a:b].unsqueeze(0) for a, b in zip(row_off[:-1], row_off[1:])]
-            b0 = b1
-    return hyps, scores, logits_out
+    return _search_chunks(_chunks(dec, eouts, elens, min(beam_width, V), lambda n: n * per_utt <= CTC_BEAM_LM_POOL_BUDGET),
+                          lambda logp, top, row_off: _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights))

@@ -1081,7 +1081,18 @@ def topk(x, k, aux=None):
 
 CTC_BEAM_MAX_WIDTH = 32
 CTC_BEAM_STATUS = {1: "a top-k label outside the vocabulary", 2: "row_off not rising", 4: "more frames than max_frames",
-                   8: "workspace share short"}
+                   8: "workspace share short", 16: "a search names an utterance outside the batch",
+                   32: "no free row left in a search's share of the LM pool"}
+
+
+def ctc_beam_status_text(status):
+    return ", ".join(text for bit, text in CTC_BEAM_STATUS.items() if status & bit) or "ok"
+
+
+def _ctc_beam_outputs(n, W, max_frames, dev):
+    """-> (out_tok int32 [n, W, max_frames + 1], out_len int32 [n, W], out_score f64 [n, W], out_n int32 [n]), uninitialised"""
+    return (torch.empty(n, W, max_frames + 1, device=dev, dtype=torch.int32), torch.empty(n, W, device=dev, dtype=torch.int32),
+            torch.empty(n, W, device=dev, dtype=torch.float64), torch.empty(n, device=dev, dtype=torch.int32))
 
 
 def ctc_beam_batch(logp, row_off, top, W, blank, eos, len_weight=0.0, max_frames=None):
@@ -1104,19 +1115,14 @@ def ctc_beam_batch(logp, row_off, top, W, blank, eos, len_weight=0.0, max_frames
     assert _chk(top, torch.int32).shape == (rows, k) and top.is_contiguous()
     dev = logp.device
     if B == 0:
-        return (torch.empty(0, W, 1, device=dev, dtype=torch.int32), torch.empty(0, W, device=dev, dtype=torch.int32),
-                torch.empty(0, W, device=dev, dtype=torch.float64), torch.empty(0, device=dev, dtype=torch.int32),
-                torch.zeros(1, device=dev, dtype=torch.int32))
+        return _ctc_beam_outputs(0, W, 0, dev) + (torch.zeros(1, device=dev, dtype=torch.int32),)
     # (one synchronisation: the kernel checks each utterance's own offsets, not that they cover the rows)
     n = row_off[1:] - row_off[:-1]
     ok, longest = torch.stack([((row_off[0] == 0) & (row_off[-1] == rows) & (n >= 0).all()).int(), n.max()]).tolist()
     if not ok:
         raise ValueError(f"ctc_beam_batch: row_off must rise from 0 to the {rows} rows")
     max_frames = int(longest) if max_frames is None else int(max_frames)
-    out_tok = torch.empty(B, W, max_frames + 1, device=dev, dtype=torch.int32)
-    out_len = torch.empty(B, W, device=dev, dtype=torch.int32)
-    out_score = torch.empty(B, W, device=dev, dtype=torch.float64)
-    out_n = torch.empty(B, device=dev, dtype=torch.int32)
+    out_tok, out_len, out_score, out_n = _ctc_beam_outputs(B, W, max_frames, dev)
     status = torch.zeros(1, device=dev, dtype=torch.int32)
     ws_bytes = lib.size_query("emoasr_ctc_beam_batch_ws_bytes", B, rows, W)
     ws = torch.empty(ws_bytes // 8, device=dev, dtype=torch.int64)
@@ -1124,13 +1130,6 @@ def ctc_beam_batch(logp, row_off, top, W, blank, eos, len_weight=0.0, max_frames
         lib.call("emoasr_ctc_beam_batch", B, V, W, k, _p(logp), ld, _p(row_off), _p(top), int(blank), int(eos), float(len_weight),
                  max_frames, _p(out_tok), _p(out_len), _p(out_score), _p(out_n), _p(ws), ws_bytes, _p(status), _stream())
     return out_tok, out_len, out_score, out_n, status
-
-
-def ctc_beam_status_text(status):
-    return ", ".join(text for bit, text in CTC_BEAM_STATUS.items() if status & bit) or "ok"
-
-
-CTC_BEAM_STATUS.update({16: "a search names an utterance outside the batch", 32: "no free row left in a search's share of the LM pool"})
 
 
 def ctc_beam_lm_slots(W):
@@ -1185,10 +1184,7 @@ def ctc_beam_lm_finish(st):
     """-> (out_tok int32 [S, W, max_frames + 1], out_len int32 [S, W], out_score f64 [S, W] best first, out_n int32 [S]; -1: the
     search was refused, see st.status) as ctc_beam_batch returns them per utterance"""
     dev = st.utt.device
-    out_tok = torch.empty(st.S, st.W, st.max_frames + 1, device=dev, dtype=torch.int32)
-    out_len = torch.empty(st.S, st.W, device=dev, dtype=torch.int32)
-    out_score = torch.empty(st.S, st.W, device=dev, dtype=torch.float64)
-    out_n = torch.empty(st.S, device=dev, dtype=torch.int32)
+    out_tok, out_len, out_score, out_n = _ctc_beam_outputs(st.S, st.W, st.max_frames, dev)
     if st.S:
         with torch.cuda.device(dev):
             lib.call("emoasr_ctc_beam_lm_finish", st.S, st.W, st.max_frames, st.eos, _p(out_tok), _p(out_len), _p(out_score), _p(out_n),

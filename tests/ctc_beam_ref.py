@@ -2,9 +2,11 @@
 
     make_rows(seed, T, V, scale, W, tie_cols=None) -> (lp f32 [T, V], top int32 [T, k]), k = min(W, V); blank 0, <eos> 2
     search(lp, top, W, len_weight)      the host search restated over label tuples, instrumented -> (hyps, scores, events)
-    search_by_ids(lp, top, W, len_weight)  the same search as the device kernel organises it: no table over label sequences, a
-                                        canonical node id per prefix from a trie keyed by (parent id, label), the merge test
-                                        q.parent == p.id and q.last == v, W rounds of arg-max -> (hyps, scores)
+    device_frame(live, row, top_t, ...)  ONE frame as the device kernels organise it (csrc/ctc_beam_step.h): no table over label
+                                        sequences, the merge test q.parent == p.id and q.last == v on canonical node ids, the
+                                        total (asr + lm) + bonus, W rounds of arg-max; the LM term and the counters are optional
+    search_by_ids(lp, top, W, len_weight)  the loop around it without an LM: node ids from a Trie keyed by (parent id, label)
+                                        -> (hyps, scores); tests/ctc_beam_lm_ref.py::search_by_slots is the loop with one
 """
 import math
 
@@ -97,69 +99,109 @@ def search(lp, top, W, len_weight=0.0, blank=BLANK, eos=EOS):
     return [list(p["toks"]) for p in live], [p["total"] if "total" in p else 0.0 for p in live], ev
 
 
+class Trie:
+    """canonical node ids: (parent id, label) -> id, the root (<eos>) being 0; tokens(id) walks the keys back to the root"""
+
+    def __init__(self):
+        self.ids, self.nodes = {}, [(-1, -1)]
+
+    def id_of(self, parent, label):
+        key = (parent, label)
+        if key not in self.ids:
+            self.ids[key] = len(self.nodes)
+            self.nodes.append(key)
+        return self.ids[key]
+
+    def tokens(self, i, eos):
+        toks = []
+        while i > 0:
+            toks.append(self.nodes[i][1])
+            i = self.nodes[i][0]
+        return [eos] + toks[::-1]
+
+
+def root():
+    """the live set before the first frame: (<eos>), holding slot 0"""
+    return dict(id=0, parent=-1, last=-1, n_plain=0, len=1, p_b=0.0, p_nb=NEG, lm=0.0, bonus=0.0, total=0.0, slot=0)
+
+
+def device_frame(live, row, top_t, k, W, len_weight, blank=BLANK, eos=EOS, lm_term=None, ev=None):
+    """one frame as csrc/ctc_beam_step.h organises it: candidates by position i (k + 1) + j, the merge test q.parent == p.id and
+    q.last == v, the fold into the one seen first (which keeps its LM term, bonus, and position), the total (asr + lm) + bonus,
+    W rounds of arg-max over rising positions -> the survivors, best first.  A survivor with id None is an extension without a
+    live twin: the caller names it (and src is its parent's slot); one that folded has its twin's id and slot.
+    lm_term(p, v): what label v adds to the running LM sum along live prefix p's candidates (None: no LM, the term stays p's).
+    ev: a Counters-like object whose fold and tie counts are kept."""
+    lp_blank = float(row[blank])
+    cand = {}                                        # position i (k + 1) + j -> candidate
+    for i, p in enumerate(live):
+        has_last = p["last"] >= 0
+        stay_b = _lse2(p["p_b"] + lp_blank, p["p_nb"] + lp_blank)
+        stay_nb = p["p_nb"] + float(row[p["last"]]) if has_last else NEG
+        cand[i * (k + 1)] = dict(p, p_b=stay_b, p_nb=stay_nb, asr=_lse2(stay_b, stay_nb), match=None)
+        lm_run = p["lm"]
+        for j in range(1, k + 1):
+            v = int(top_t[j - 1])
+            if v == blank:
+                continue
+            if lm_term is not None:
+                lm_run = lm_run + lm_term(p, v)
+            lp_v = float(row[v])
+            ext_nb = p["p_b"] + lp_v if (has_last and v == p["last"]) else _lse2(p["p_b"] + lp_v, p["p_nb"] + lp_v)
+            c = dict(id=None, parent=p["id"], last=v, n_plain=p["n_plain"] + (0 if v == eos else 1), len=p["len"] + 1,
+                     p_b=NEG, p_nb=ext_nb, asr=_lse2(NEG, ext_nb), lm=lm_run, bonus=len_weight * (p["n_plain"] + 1), slot=None,
+                     src=p["slot"])
+            c["match"] = [q for q, lq in enumerate(live) if lq["parent"] == p["id"] and lq["last"] == v]
+            cand[i * (k + 1) + j] = c
+    for pos in sorted(cand):
+        c = cand.get(pos)
+        if c is None or not c.get("match"):
+            continue
+        (q,) = c["match"]
+        z = q * (k + 1)
+        first, second = (z, pos) if z < pos else (pos, z)
+        a, b = cand[first], cand[second]
+        if ev is not None:
+            ev.folds_stay_first += z < pos
+            ev.folds_ext_first += pos < z
+            ev.folds_lm_differ += a["lm"] != b["lm"]
+        for f in ("p_b", "p_nb", "asr"):
+            a[f] = _lse2(a[f], b[f])
+        a["id"], a["slot"] = live[q]["id"], live[q]["slot"]
+        del cand[second]
+    for c in cand.values():
+        c["total"] = (c["asr"] + c["lm"]) + c["bonus"]
+    if ev is not None:
+        ranked = sorted(cand.values(), key=lambda c: c["total"], reverse=True)    # (stable; the positions are already rising)
+        for a, b in zip(ranked[:W], ranked[1:W + 1]):
+            gap = a["total"] - b["total"]
+            if gap == 0.0:
+                ev.ties += 1
+            else:
+                ev.min_gap = min(ev.min_gap, gap)
+    new = []
+    for _ in range(W):
+        best = None
+        for pos in sorted(cand):
+            if best is None or cand[pos]["total"] > cand[best]["total"]:
+                best = pos
+        if best is None:
+            break
+        new.append(cand.pop(best))
+    return new
+
+
 def search_by_ids(lp, top, W, len_weight=0.0, blank=BLANK, eos=EOS):
     """the search as csrc/ctc_beam.hip organises it -> (hyps, scores)"""
     k = top.shape[1] if top.size else min(W, lp.shape[1])
-    trie, nodes = {}, [(-1, -1)]                     # (parent id, label) -> id; id -> (parent id, label)
-    live = [dict(id=0, parent=-1, last=-1, n_plain=0, len=1, p_b=0.0, p_nb=NEG, bonus=0.0, total=0.0)]
+    trie, live = Trie(), [root()]
     for t in range(lp.shape[0]):
-        row = lp[t]
-        lp_blank = float(row[blank])
-        cand = {}                                    # position i (k + 1) + j -> candidate
-        for i, p in enumerate(live):
-            has_last = p["last"] >= 0
-            stay_b = _lse2(p["p_b"] + lp_blank, p["p_nb"] + lp_blank)
-            stay_nb = p["p_nb"] + float(row[p["last"]]) if has_last else NEG
-            cand[i * (k + 1)] = dict(p, p_b=stay_b, p_nb=stay_nb, asr=_lse2(stay_b, stay_nb), match=None)
-            for j in range(1, k + 1):
-                v = int(top[t, j - 1])
-                if v == blank:
-                    continue
-                lp_v = float(row[v])
-                ext_nb = p["p_b"] + lp_v if (has_last and v == p["last"]) else _lse2(p["p_b"] + lp_v, p["p_nb"] + lp_v)
-                c = dict(id=None, parent=p["id"], last=v, n_plain=p["n_plain"] + (0 if v == eos else 1), len=p["len"] + 1,
-                         p_b=NEG, p_nb=ext_nb, asr=_lse2(NEG, ext_nb), bonus=len_weight * (p["n_plain"] + 1))
-                c["match"] = [q for q, lq in enumerate(live) if lq["parent"] == p["id"] and lq["last"] == v]
-                cand[i * (k + 1) + j] = c
-        for pos in sorted(cand):
-            c = cand.get(pos)
-            if c is None or not c.get("match"):
-                continue
-            (q,) = c["match"]
-            s = q * (k + 1)
-            first, second = (s, pos) if s < pos else (pos, s)
-            a, b = cand[first], cand[second]
-            for f in ("p_b", "p_nb", "asr"):
-                a[f] = _lse2(a[f], b[f])
-            a["id"] = live[q]["id"]
-            del cand[second]
-        for c in cand.values():
-            c["total"] = (c["asr"] + 0.0) + c["bonus"]
-        new = []
-        for _ in range(W):
-            best = None
-            for pos in sorted(cand):
-                if best is None or cand[pos]["total"] > cand[best]["total"]:
-                    best = pos
-            if best is None:
-                break
-            new.append(cand.pop(best))
-        for c in new:
+        live = device_frame(live, lp[t], top[t], k, W, len_weight, blank, eos)
+        for c in live:
             if c["id"] is None:
-                key = (c["parent"], c["last"])
-                if key not in trie:
-                    trie[key] = len(nodes)
-                    nodes.append(key)
-                c["id"] = trie[key]
-        live = new
-    hyps = []
-    for p in live:
-        toks, i = [], p["id"]
-        while i > 0:
-            toks.append(nodes[i][1])
-            i = nodes[i][0]
-        hyps.append([eos] + toks[::-1])
-        assert len(hyps[-1]) == p["len"]
+                c["id"] = trie.id_of(c["parent"], c["last"])
+    hyps = [trie.tokens(p["id"], eos) for p in live]
+    assert all(len(h) == p["len"] for h, p in zip(hyps, live))
     return hyps, [p["total"] for p in live]
 
 

@@ -163,6 +163,39 @@ def test_every_case_equals_the_host_search(dev, case):
         assert len(got[0]) == (5 if (V, T) == (5, 1) else W)
 
 
+@pytest.mark.parametrize("case", R.expand(R.ALL_CASES), ids=_ID)
+def test_lm_weight_zero_is_the_search_without_an_lm_bit_for_bit(dev, case):
+    """one fused search with lm_weight = 0.0 (its pool holds finite rows, which it must not read into a score) against
+    emoasr_ctc_beam_batch over the same rows: tokens, lengths, counts and scores are equal as bits, and so is everything neither
+    wrote.  Both kernels run the frame of csrc/ctc_beam_step.h; this is what keeps them doing so."""
+    from emoasr_amd import lib
+    V, W, T, scale, lw, seed, tie = case
+    lp, top = R.make_rows(seed, T, V, scale, W, tie)
+    out, status, (f_tok, f_len, f_sc, f_n) = drive(dev, [(lp, top)], [(0, 0.0, lw)], W, V)
+    assert status == 0 and out[0] is not None
+    d_lp, d_top = torch.from_numpy(lp).to(dev), torch.from_numpy(top).to(dev)
+    row_off = torch.tensor([0, T], dtype=torch.int32, device=dev)
+    ws_bytes = lib.size_query("emoasr_ctc_beam_batch_ws_bytes", 1, T, W)
+    g_ws, ws = _guarded(dev, ws_bytes // 8, torch.int64, -7)
+    g_tok, tok = _guarded(dev, W * (T + 1), torch.int32, -7)
+    g_len, ln = _guarded(dev, W, torch.int32, -7)
+    g_sc, sc = _guarded(dev, W, torch.float64, -7.0)
+    g_n, n_out = _guarded(dev, 1, torch.int32, -7)
+    b_status = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        lib.call("emoasr_ctc_beam_batch", 1, V, W, min(W, V), p(d_lp), V, p(row_off), p(d_top), R.BLANK, R.EOS, lw, T, p(tok), p(ln),
+                 p(sc), p(n_out), p(ws), ws_bytes, p(b_status), None)
+    torch.cuda.synchronize()
+    for g in (g_ws, g_tok, g_len, g_sc, g_n):
+        assert bool((g[:GUARD] == -7).all()) and bool((g[-GUARD:] == -7).all())
+    assert int(b_status.item()) == 0
+    assert n_out.cpu().numpy().tolist() == f_n.tolist() == [5 if (V, T) == (5, 1) else W]
+    assert np.array_equal(ln.view(1, W).cpu().numpy(), f_len)
+    assert np.array_equal(tok.view(1, W, T + 1).cpu().numpy(), f_tok)
+    assert np.array_equal(sc.view(torch.int64).view(1, W).cpu().numpy(), f_sc.view(np.int64))
+
+
 def test_mixed_cells_of_two_utterances(dev):
     """six searches over two utterances (32 and 20 frames) with mixed weights in one launch sequence: each equals the host search;
     the lm_weight = 0 cells are bit-equal to emoasr_ctc_beam_batch; every search is bit-equal to itself run alone"""
