@@ -14,6 +14,11 @@
 // The control words (labels, source / destination slots, frame index) stay what engine._rnnt_beam_round_graph uploads; the host
 // bookkeeping (stable sort by float64 score, merge of equal label sequences, cut to the beam) is unchanged.
 //
+// The ROWS forms (emoasr_rnnt_beam_lstm_rows / _joint_rows) run the same kernels over R = S W rows of S searches in tiles of 16, one
+// tile per blockIdx.y, under control words that csrc/rnnt_beam_book.hip writes on the device: a per-row active flag (an inactive row
+// is a zero row of the staged image and writes nothing) and, for the joint, a per-row frame row of the stacked e matrix.  One row's
+// arithmetic is the 16-row kernels', so its bits do not depend on the tile or the batch it sits in.
+//
 // Numerics follow the chain: products accumulate in f32, every intermediate is rounded to the compute dtype where the chain's
 // kernels store it (gate pre-activations after each of the two products, h, the joint input); the summation ORDER inside a dot
 // product differs from the MFMA kernels', so near-ties of the top-k can differ (tests: the reference's golden hypotheses, both forms).
@@ -38,12 +43,36 @@ struct BeamLstmArgs {
   const long long *src, *dst;
   const long long* copy_src; long long* copy_dst; int copy_n;   // optional: workgroup 0 also copies copy_n words (the control record
                                                                  // from pinned host memory to its device twin, for the later launches)
+  // the ROWS form (emoasr_rnnt_beam_lstm_rows): nb rows in tiles of 16 (blockIdx.y), a per-row active flag written by the
+  // bookkeeping kernel (csrc/rnnt_beam_book.hip); nx / nslots bound the indices it hands over
+  const long long* active; long nx, nslots;
 };
 
-template <typename T>
+// ROWS: control words of tile blockIdx.y; a row that is inactive (or whose indices are outside the tables) is a zero row of
+// the staged image and writes nothing.  -> whether the tile has any row to compute (uniform; a barrier either way)
+template <bool ROWS>
+__device__ __forceinline__ bool beam_lstm_words(const BeamLstmArgs& a, int r0, int nb, long long (*cw)[16], int* act) {
+  const int tid = threadIdx.x;
+  int on = 0;
+  if (tid < nb) {
+    long long x = a.xidx[r0 + tid], sr = a.src[r0 + tid], ds = a.dst[r0 + tid];
+    on = 1;
+    if constexpr (ROWS) {
+      on = a.active[r0 + tid] != 0 && x >= 0 && x < a.nx && sr >= 0 && sr < a.nslots && ds >= 0 && ds < a.nslots;
+      if (!on) x = sr = ds = 0;
+      act[tid] = on;
+    }
+    cw[0][tid] = x; cw[1][tid] = sr; cw[2][tid] = ds;
+  }
+  if constexpr (ROWS) return __syncthreads_or(on) != 0;
+  return true;
+}
+
+template <typename T, bool ROWS>
 __global__ __launch_bounds__(BT) void rnnt_beam_lstm_kernel(const BeamLstmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nb = a.nb, nin = a.nin, H = a.H, tid = threadIdx.x, grp = tid >> 3, sub = tid & 7;
+  const int r0 = ROWS ? blockIdx.y * NBMAX : 0, nb = ROWS ? min(NBMAX, a.nb - r0) : a.nb;
+  const int nin = a.nin, H = a.H, tid = threadIdx.x, grp = tid >> 3, sub = tid & 7;
   float* xs = reinterpret_cast<float*>(smem);          // [NBMAX][nin]
   float* hs = xs + NBMAX * nin;                        // [NBMAX][H]
   float* gs = hs + NBMAX * H;                          // [NBMAX][4 UN] gate pre-activations of this workgroup's units
@@ -51,14 +80,16 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_kernel(const BeamLstmArgs a
   const T* ph = static_cast<const T*>(a.ph);
   // the control words may live in pinned HOST memory (the search's zero-copy hand-off): read each once, through LDS
   __shared__ long long cw[3][NBMAX];
-  if (tid < nb) { cw[0][tid] = a.xidx[tid]; cw[1][tid] = a.src[tid]; cw[2][tid] = a.dst[tid]; }
+  __shared__ int act[NBMAX];
+  if (!beam_lstm_words<ROWS>(a, r0, nb, cw, act)) return;
   if (blockIdx.x == 0 && a.copy_dst && tid >= 64 && tid - 64 < a.copy_n) a.copy_dst[tid - 64] = a.copy_src[tid - 64];
   __syncthreads();
   for (int i = 0; i < nb; ++i) {
     const T* xr = xtab + cw[0][i] * a.ldx;
     const T* hr = ph + cw[1][i] * (long)H;
-    for (int k = tid; k < nin; k += BT) xs[i * nin + k] = to_f32(xr[k]);
-    for (int k = tid; k < H; k += BT) hs[i * H + k] = to_f32(hr[k]);
+    const bool on = !ROWS || act[i];
+    for (int k = tid; k < nin; k += BT) xs[i * nin + k] = on ? to_f32(xr[k]) : 0.f;
+    for (int k = tid; k < H; k += BT) hs[i * H + k] = on ? to_f32(hr[k]) : 0.f;
   }
   __syncthreads();
   // row group grp <-> gate q = grp / UN (i, f, g, o), unit u0 + grp % UN
@@ -80,7 +111,7 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_kernel(const BeamLstmArgs a
   }
   __syncthreads();
   // cell update: thread <-> (hypothesis i, unit j)
-  if (tid < nb * UN) {
+  if (tid < nb * UN && (!ROWS || act[tid / UN])) {
     const int i = tid / UN, j = tid % UN, uu = blockIdx.x * UN + j;
     const float* g4 = gs + i * (4 * UN);
     const float ig = sigmoid_t<T>(g4[j]), fg = sigmoid_t<T>(g4[UN + j]), gg = tanh_t<T>(g4[2 * UN + j]), og = sigmoid_t<T>(g4[3 * UN + j]);
@@ -99,7 +130,63 @@ struct BeamJointArgs {
   const void* w_dec; const float* b_dec;    // [J][H], [J]
   const void* e_all; const long long* t;    // [Tmax][J] = w_enc . eouts + bias; frame index (device word)
   void* hj;                                 // [nb][J] joint input tanh(e_t + g)
+  const long long* active; long nslots;     // the ROWS form (emoasr_rnnt_beam_joint_rows): t is per row, a row of e_all
 };
+
+// ROWS: the words of tile blockIdx.y -- cw[i] = slot of row i, tw[i] = its row of e_all (clamped) -- as beam_lstm_words
+template <bool ROWS>
+__device__ __forceinline__ bool beam_joint_words(const BeamJointArgs& a, int r0, int nb, long long* cw, long* tw, int* act) {
+  const int tid = threadIdx.x;
+  int on = 0;
+  if (tid < nb) {
+    long long ds = a.dst[r0 + tid];
+    long t = ROWS ? a.t[r0 + tid] : *a.t;
+    t = t < 0 ? 0 : (t >= a.Tmax ? a.Tmax - 1 : t);
+    on = 1;
+    if constexpr (ROWS) {
+      on = a.active[r0 + tid] != 0 && ds >= 0 && ds < a.nslots;
+      if (!on) ds = 0;
+      act[tid] = on;
+    }
+    cw[tid] = ds; tw[tid] = t;
+  }
+  return __syncthreads_or(on) != 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(BT) void rnnt_beam_joint_rows_kernel(const BeamJointArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int r0 = blockIdx.y * NBMAX, nb = min(NBMAX, a.nb - r0);
+  const int H = a.H, J = a.J, tid = threadIdx.x, grp = tid >> 3, sub = tid & 7;
+  float* hs = reinterpret_cast<float*>(smem);   // [NBMAX][H]
+  const T* ph = static_cast<const T*>(a.ph);
+  __shared__ long long cw[NBMAX];
+  __shared__ long tw[NBMAX];
+  __shared__ int act[NBMAX];
+  if (!beam_joint_words<true>(a, r0, nb, cw, tw, act)) return;
+  for (int i = 0; i < nb; ++i) {
+    const T* hr = ph + cw[i] * (long)H;
+    for (int k = tid; k < H; k += BT) hs[i * H + k] = act[i] ? to_f32(hr[k]) : 0.f;
+  }
+  __syncthreads();
+  const int j = blockIdx.x * 32 + grp;          // 32 rows of w_dec per workgroup
+  if (j >= J) return;
+  float acc[NBMAX];
+#pragma unroll
+  for (int i = 0; i < NBMAX; ++i) acc[i] = 0.f;
+  row_dots<T>(static_cast<const T*>(a.w_dec) + (long)j * H, H, hs, H, nb, sub, acc);   // (the arithmetic of rnnt_beam_joint_kernel,
+  const float b = a.b_dec[j];                                                          // row by row)
+#pragma unroll
+  for (int i = 0; i < NBMAX; ++i) {
+    if (i < nb) {
+      const float g = rnd<T>(group_sum8(acc[i]) + b);
+      if (sub == 0 && act[i]) {
+        const float e = to_f32(static_cast<const T*>(a.e_all)[tw[i] * J + j]);
+        static_cast<T*>(a.hj)[(long)(r0 + i) * J + j] = from_f32<T>(tanh_t<T>(e + g));
+      }
+    }
+  }
+}
 
 template <typename T>
 __global__ __launch_bounds__(BT) void rnnt_beam_joint_kernel(const BeamJointArgs a) {
@@ -243,9 +330,11 @@ __global__ __launch_bounds__(64) void rnnt_beam_pick16_kernel(int V, int k, int 
 // LDS image [16][K + 8] (bf16; rows of hypotheses >= nb are zero).  The VALU form above spent its time re-reading the inputs from LDS
 // for every weight row (13 us per layer at H = 512; this form: weight-streaming latency).
 // grid = H / 16 workgroups of 4 waves: wave q = gate q (i, f, g, o) of the workgroup's 16 hidden units
+template <bool ROWS>
 __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nb = a.nb, nin = a.nin, H = a.H, tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int r0 = ROWS ? blockIdx.y * NBMAX : 0, nb = ROWS ? min(NBMAX, a.nb - r0) : a.nb;
+  const int nin = a.nin, H = a.H, tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
   const int ldx = nin + 8, ldh = H + 8;
   bf16* xs = reinterpret_cast<bf16*>(smem);              // [16][nin + 8]
   bf16* hs = xs + NBMAX * ldx;                           // [16][H + 8]
@@ -253,7 +342,8 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmA
   const bf16* xtab = static_cast<const bf16*>(a.xtab);
   const bf16* ph = static_cast<const bf16*>(a.ph);
   __shared__ long long cw[3][NBMAX];   // control words (possibly in pinned host memory): read once
-  if (tid < nb) { cw[0][tid] = a.xidx[tid]; cw[1][tid] = a.src[tid]; cw[2][tid] = a.dst[tid]; }
+  __shared__ int act[NBMAX];
+  if (!beam_lstm_words<ROWS>(a, r0, nb, cw, act)) return;
   if (blockIdx.x == 0 && a.copy_dst && tid >= 64 && tid - 64 < a.copy_n) a.copy_dst[tid - 64] = a.copy_src[tid - 64];
   __syncthreads();
   // stage the inputs: 16-byte pieces, zero rows for hypotheses >= nb
@@ -262,7 +352,7 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmA
     bf16x8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (bf16)0.f;
-    if (i < nb) v = *reinterpret_cast<const bf16x8*>(xtab + cw[0][i] * a.ldx + c);
+    if (i < nb && (!ROWS || act[i])) v = *reinterpret_cast<const bf16x8*>(xtab + cw[0][i] * a.ldx + c);
     *reinterpret_cast<bf16x8*>(xs + i * ldx + c) = v;
   }
   for (int p = tid; p < NBMAX * (H / 8); p += BT) {
@@ -270,7 +360,7 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmA
     bf16x8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (bf16)0.f;
-    if (i < nb) v = *reinterpret_cast<const bf16x8*>(ph + cw[1][i] * (long)H + c);
+    if (i < nb && (!ROWS || act[i])) v = *reinterpret_cast<const bf16x8*>(ph + cw[1][i] * (long)H + c);
     *reinterpret_cast<bf16x8*>(hs + i * ldh + c) = v;
   }
   __syncthreads();
@@ -288,13 +378,48 @@ __global__ __launch_bounds__(BT) void rnnt_beam_lstm_mfma_kernel(const BeamLstmA
     }
   }
   __syncthreads();
-  if (tid < nb * 16) {
+  if (tid < nb * 16 && (!ROWS || act[tid / 16])) {
     const int i = tid / 16, j = tid % 16, uu = u0 + j;
     const float* g4 = gs + i * 64;
     const float ig = sigmoid_t<bf16>(g4[j]), fg = sigmoid_t<bf16>(g4[16 + j]), gg = tanh_t<bf16>(g4[32 + j]), og = sigmoid_t<bf16>(g4[48 + j]);
     const float cn = fg * a.pc[cw[1][i] * (long)H + uu] + ig * gg;
     a.pc[cw[2][i] * (long)H + uu] = cn;
     static_cast<bf16*>(a.ph)[cw[2][i] * (long)H + uu] = (bf16)(og * tanh_t<bf16>(cn));
+  }
+}
+
+// the ROWS form of rnnt_beam_joint_mfma_kernel below: tile blockIdx.y, a row of e_all per hypothesis
+__global__ __launch_bounds__(BT) void rnnt_beam_joint_rows_mfma_kernel(const BeamJointArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int r0 = blockIdx.y * NBMAX, nb = min(NBMAX, a.nb - r0);
+  const int H = a.H, J = a.J, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ldh = H + 8;
+  bf16* hs = reinterpret_cast<bf16*>(smem);   // [16][H + 8]
+  const bf16* ph = static_cast<const bf16*>(a.ph);
+  __shared__ long long cw[NBMAX];
+  __shared__ long tw[NBMAX];
+  __shared__ int act[NBMAX];
+  if (!beam_joint_words<true>(a, r0, nb, cw, tw, act)) return;
+  for (int p = tid; p < NBMAX * (H / 8); p += BT) {
+    const int i = p / (H / 8), c = (p % (H / 8)) * 8;
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (bf16)0.f;
+    if (i < nb && act[i]) v = *reinterpret_cast<const bf16x8*>(ph + cw[i] * (long)H + c);
+    *reinterpret_cast<bf16x8*>(hs + i * ldh + c) = v;
+  }
+  __syncthreads();
+  const int j0 = blockIdx.x * 64 + 16 * w;
+  if (j0 >= J) return;
+  const f32x4_ d = rows16_dot(static_cast<const bf16*>(a.w_dec) + (long)j0 * H, H, H, hs, ldh, lane);
+  const int i = lane & 15;
+  if (i >= nb || !act[i]) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int j = j0 + 4 * (lane >> 4) + r;
+    const float g = rnd<bf16>(d[r] + a.b_dec[j]);
+    const float e = (float)static_cast<const bf16*>(a.e_all)[tw[i] * J + j];
+    static_cast<bf16*>(a.hj)[(long)(r0 + i) * J + j] = (bf16)tanh_t<bf16>(e + g);
   }
 }
 
@@ -350,19 +475,72 @@ extern "C" int emoasr_rnnt_beam_lstm(int dtype, int nb, int nin, int H, const vo
   if (dtype == EMO_BF16 && g_opt.rnnt_beam_mfma && H % 32 == 0 && nin % 32 == 0) {
     const size_t sm = (size_t)NBMAX * (nin + 8 + H + 8) * 2 + NBMAX * 64 * sizeof(float);
     EMO_CHECK(sm <= 64 * 1024, "rnnt_beam_lstm: nin + H = %d too wide for the LDS plan", nin + H);
-    rnnt_beam_lstm_mfma_kernel<<<H / 16, BT, sm, (hipStream_t)stream>>>(a);
+    rnnt_beam_lstm_mfma_kernel<false><<<H / 16, BT, sm, (hipStream_t)stream>>>(a);
     EMO_LAUNCH_CHECK();
     return 0;
   }
   EMO_DISPATCH(dtype, {
     static size_t set_bytes = 0;
     if (smem > 64 * 1024 && smem > set_bytes) {
-      EMO_CHECK(hipFuncSetAttribute((const void*)rnnt_beam_lstm_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess,
+      EMO_CHECK(hipFuncSetAttribute((const void*)rnnt_beam_lstm_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess,
                 "rnnt_beam_lstm: hipFuncSetAttribute(%zu) failed", smem);
       set_bytes = smem;
     }
-    rnnt_beam_lstm_kernel<T><<<H / UN, BT, smem, (hipStream_t)stream>>>(a);
+    rnnt_beam_lstm_kernel<T, false><<<H / UN, BT, smem, (hipStream_t)stream>>>(a);
   });
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+// R rows in tiles of 16 under the control words of csrc/rnnt_beam_book.hip: the same kernels, one tile per blockIdx.y
+extern "C" int emoasr_rnnt_beam_lstm_rows(int dtype, int R, int nin, int H, const void* xtab, long ldx, long nx, const long long* xidx,
+                                          const void* w_ih, const void* w_hh, const float* bias, void* ph, float* pc, long nslots,
+                                          const long long* src, const long long* dst, const long long* active, void* stream) {
+  EMO_CHECK(R >= 1 && R <= 65535 * NBMAX && nx >= 1 && nslots >= 1, "rnnt_beam_lstm_rows: R=%d nx=%ld nslots=%ld", R, nx, nslots);
+  EMO_CHECK(xidx && src && dst && active, "rnnt_beam_lstm_rows: null control words");
+  const int vec = dtype == EMO_BF16 ? 8 : 4;
+  EMO_CHECK(H % UN == 0 && nin % vec == 0 && H % vec == 0 && ldx % vec == 0, "rnnt_beam_lstm_rows: H=%d nin=%d unsupported", H, nin);
+  const size_t smem = ((size_t)NBMAX * (nin + H) + NBMAX * 4 * UN) * sizeof(float);
+  EMO_CHECK(smem <= 150 * 1024, "rnnt_beam_lstm_rows: nin + H = %d too wide for the LDS plan", nin + H);
+  BeamLstmArgs a{R, nin, H, xtab, ldx, xidx, w_ih, w_hh, bias, ph, pc, src, dst, nullptr, nullptr, 0, active, nx, nslots};
+  const unsigned tiles = (R + NBMAX - 1) / NBMAX;
+  if (dtype == EMO_BF16 && g_opt.rnnt_beam_mfma && H % 32 == 0 && nin % 32 == 0) {
+    const size_t sm = (size_t)NBMAX * (nin + 8 + H + 8) * 2 + NBMAX * 64 * sizeof(float);
+    EMO_CHECK(sm <= 64 * 1024, "rnnt_beam_lstm_rows: nin + H = %d too wide for the LDS plan", nin + H);
+    rnnt_beam_lstm_mfma_kernel<true><<<dim3(H / 16, tiles), BT, sm, (hipStream_t)stream>>>(a);
+    EMO_LAUNCH_CHECK();
+    return 0;
+  }
+  EMO_DISPATCH(dtype, {
+    static size_t set_bytes = 0;
+    if (smem > 64 * 1024 && smem > set_bytes) {
+      EMO_CHECK(hipFuncSetAttribute((const void*)rnnt_beam_lstm_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess,
+                "rnnt_beam_lstm_rows: hipFuncSetAttribute(%zu) failed", smem);
+      set_bytes = smem;
+    }
+    rnnt_beam_lstm_kernel<T, true><<<dim3(H / UN, tiles), BT, smem, (hipStream_t)stream>>>(a);
+  });
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_rnnt_beam_joint_rows(int dtype, int R, int H, int J, int e_rows, const void* ph, long nslots,
+                                           const long long* dst, const long long* active, const void* w_dec, const float* b_dec,
+                                           const void* e_all, const long long* e_row, void* hj, void* stream) {
+  EMO_CHECK(R >= 1 && R <= 65535 * NBMAX && e_rows >= 1 && nslots >= 1, "rnnt_beam_joint_rows: R=%d e_rows=%d", R, e_rows);
+  EMO_CHECK(dst && active && e_row, "rnnt_beam_joint_rows: null control words");
+  const int vec = dtype == EMO_BF16 ? 8 : 4;
+  EMO_CHECK(H % vec == 0, "rnnt_beam_joint_rows: H=%d unsupported", H);
+  const size_t smem = (size_t)NBMAX * H * sizeof(float);
+  EMO_CHECK(smem <= 64 * 1024, "rnnt_beam_joint_rows: H=%d too wide", H);
+  BeamJointArgs a{R, H, J, e_rows, ph, dst, w_dec, b_dec, e_all, e_row, hj, active, nslots};
+  const unsigned tiles = (R + NBMAX - 1) / NBMAX;
+  if (dtype == EMO_BF16 && g_opt.rnnt_beam_mfma && H % 32 == 0 && J % 16 == 0 && (size_t)NBMAX * (H + 8) * 2 <= 64 * 1024) {
+    rnnt_beam_joint_rows_mfma_kernel<<<dim3((J + 63) / 64, tiles), BT, (size_t)NBMAX * (H + 8) * 2, (hipStream_t)stream>>>(a);
+    EMO_LAUNCH_CHECK();
+    return 0;
+  }
+  EMO_DISPATCH(dtype, (rnnt_beam_joint_rows_kernel<T><<<dim3((J + 31) / 32, tiles), BT, smem, (hipStream_t)stream>>>(a)));
   EMO_LAUNCH_CHECK();
   return 0;
 }

@@ -518,6 +518,140 @@ class RNNTDecoder:
                 return [hyp for hyp, _, _ in beams], [score for _, score, _ in beams]
             return [hyp for hyp, _, _ in beams]
 
+    _BEAM_BATCH_CAP = 64   # searches per launch chain: S W <= 1024 rows, S (E + 1) W state slots per layer (25 MB at H = 512, W = 16)
+
+    def rnnt_beam_device_ok(self, beam_width, num_expands=3):
+        """does the model fit the batched search's round kernels?  (the limits of the fused round, _rnnt_beam_round_graph, and of
+        the bookkeeping kernel: beam_width <= 16, beam_width <= V - 1)"""
+        A, H, nl = self.arena, self.r_H, self.r_nl
+        V_ = A.w("decoder.output.weight").shape[0]
+        nin_max = max(A.w(f"decoder.rnns.{l}.weight_ih_l0").shape[1] for l in range(nl)) if nl else 0
+        fits = V_ * 4 <= 60 * 1024 and 16 * H * 4 <= 64 * 1024 and (self.dtype == torch.bfloat16 or nin_max + H <= 2368)
+        return nl >= 1 and fits and 1 <= beam_width <= min(ops.RNNT_BEAM_MAX_WIDTH, V_ - 1) and 1 <= num_expands <= ops.RNNT_BEAM_MAX_EXPANDS
+
+    def rnnt_beam_search_batch(self, eouts, elens, beam_width, blank, eos, num_expands=3):
+        """alignment-length synchronous beam search for a BATCH (rnn_transducer.py:242-325 per utterance; the reference asserts a
+        batch of one): eouts [B, Tmax, d], utterance b is searched over its own elens[b] frames -> (hyps[b][n], scores[b][n]),
+        best first, hypotheses with the leading <sos>, float64 scores.  The bookkeeping runs on the device
+        (csrc/rnnt_beam_book.hip): one frame -- num_expands rounds of (LSTM layers, joint, output product, pick, book) over all
+        S W rows -- is captured once per (S, W) and replayed max(elens) times without a synchronisation in between.  Batches above
+        _BEAM_BATCH_CAP are searched in chunks.  A model outside the round kernels' limits is searched utterance by utterance
+        through rnnt_beam_search."""
+        elens = [int(v) for v in elens]
+        B = eouts.shape[0]
+        assert len(elens) == B and all(0 <= n <= eouts.shape[1] for n in elens), (elens, tuple(eouts.shape))
+        with self._scope():
+            self.arena.refresh_shadow()
+        hyps, scores = [], []
+        if not self.rnnt_beam_device_ok(beam_width, num_expands):
+            for b in range(B):
+                if elens[b] == 0:
+                    h, s = [[eos]], [0.0]
+                else:
+                    h, s = self.rnnt_beam_search(eouts[b:b + 1, :elens[b]], beam_width, blank, eos, num_expands, return_scores=True)
+                hyps.append(h)
+                scores.append([float(v) for v in s])
+            return hyps, scores
+        for b0 in range(0, B, self._BEAM_BATCH_CAP):
+            h, s = self._rnnt_beam_search_device(eouts[b0:b0 + self._BEAM_BATCH_CAP], elens[b0:b0 + self._BEAM_BATCH_CAP], beam_width,
+                                                 blank, eos, num_expands)
+            hyps += h
+            scores += s
+        return hyps, scores
+
+    def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total):
+        """static buffers of S searches of width W over <= st.rows frames in all, and ONE FRAME of all of them (E rounds of
+        LSTM layers, joint, output product, pick, book) captured as a HIP graph.  The warm-up runs the body with every search
+        finished (no frames): every row is inactive, no state is touched."""
+        from .. import lib
+        tab = self.__dict__.setdefault("_beam_batch_static", {})
+        key = (S, W, blank, eos, E)
+        st = tab.get(key)
+        if st is not None and st.rows >= total:
+            return st
+        A, J, H, nl = self.arena, self.r_J, self.r_H, self.r_nl
+        dev = A.flat.device
+        V_ = A.w("decoder.output.weight").shape[0]
+        st = _Stash()
+        st.rows = 1024
+        while st.rows < total:
+            st.rows *= 2
+        st.R, st.nslots = S * W, S * (E + 1) * W
+        R = st.R
+        st.ph = [torch.zeros(st.nslots, H, device=dev, dtype=self.dtype) for _ in range(nl)]
+        st.pc = [torch.zeros(st.nslots, H, device=dev, dtype=torch.float32) for _ in range(nl)]
+        st.e = torch.zeros(st.rows, J, device=dev, dtype=self.dtype)
+        st.ctl = torch.zeros(5, R, device=dev, dtype=torch.int64)
+        st.rec = torch.zeros(R, 1 + 2 * W, device=dev, dtype=torch.float32)
+        st.hj = torch.zeros(R, J, device=dev, dtype=self.dtype)
+        st.row_off = torch.zeros(S + 1, device=dev, dtype=torch.int32)
+        st.ws = torch.empty(lib.size_query("emoasr_rnnt_beam_ws_bytes", S, st.rows, W, E), device=dev, dtype=torch.uint8)
+        st.status = torch.zeros(1, device=dev, dtype=torch.int32)
+        st.bias = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(nl)]   # (refreshed per search)
+
+        def body():
+            with self._scope():
+                dtc = ops.dt(st.ph[0])
+                p_lab, p_src, p_dst, p_act, p_row = (c_void_p(st.ctl.data_ptr() + 8 * R * i) for i in range(5))
+                emb = A.w("decoder.embed.weight")
+                w_out, b_out = A.w("decoder.output.weight"), A.p("decoder.output.bias")
+                for _ in range(E):
+                    xtab, ldx, nx, xidx = emb, emb.shape[1], emb.shape[0], p_lab
+                    for l in range(nl):
+                        name = f"decoder.rnns.{l}"
+                        w_ih, w_hh = A.w(name + ".weight_ih_l0"), A.w(name + ".weight_hh_l0")
+                        lib.call("emoasr_rnnt_beam_lstm_rows", dtc, R, w_ih.shape[1], H, ops._p(xtab), ldx, nx, xidx, ops._p(w_ih),
+                                 ops._p(w_hh), ops._p(st.bias[l]), ops._p(st.ph[l]), ops._p(st.pc[l]), st.nslots, p_src, p_dst, p_act,
+                                 ops._stream())
+                        xtab, ldx, nx, xidx = st.ph[l], H, st.nslots, p_dst
+                    lib.call("emoasr_rnnt_beam_joint_rows", dtc, R, H, J, st.rows, ops._p(st.ph[nl - 1]), st.nslots, p_dst, p_act,
+                             ops._p(A.w("decoder.w_dec.weight")), ops._p(A.p("decoder.w_dec.bias")), ops._p(st.e), p_row,
+                             ops._p(st.hj), ops._stream())
+                    logits = ops.gemm_nt(st.hj, w_out, bias=b_out)
+                    lib.call("emoasr_rnnt_beam_pick", dtc, R, V_, W, blank, ops._p(logits), logits.stride(0), ops._p(st.rec),
+                             st.rec.stride(0), ops._stream())
+                    ops.rnnt_beam_book(st.row_off, W, E, V_, eos, st.rec, st.ctl, st.ws, st.status)
+
+        ops.rnnt_beam_start(st.row_off, W, E, V_, eos, st.ctl, st.ws, st.status)   # (row_off all zero: every search finished)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()   # warm-up outside the capture (allocator, lazy initialisation)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        st.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(st.graph):
+            body()
+        tab[key] = st
+        return st
+
+    def _rnnt_beam_search_device(self, eouts, elens, W, blank, eos, E):
+        """one chunk of rnnt_beam_search_batch: S = len(elens) <= _BEAM_BATCH_CAP searches"""
+        with self._scope(), torch.no_grad():
+            A, nl = self.arena, self.r_nl
+            S, total, longest = len(elens), sum(elens), max(elens)
+            V_ = A.w("decoder.output.weight").shape[0]
+            st = self._rnnt_beam_frame_graph(S, W, blank, eos, E, total)
+            offs = [0]
+            for b in range(S):
+                # w_enc . eouts + b per utterance, as the single-utterance forms compute it (a row's bits then do not depend on
+                # the batch it came in)
+                if elens[b]:
+                    st.e[offs[-1]:offs[-1] + elens[b]].copy_(ops.gemm_nt(eouts[b, :elens[b]], A.w("decoder.w_enc.weight"),
+                                                                         bias=A.p("decoder.w_enc.bias")))
+                offs.append(offs[-1] + elens[b])
+            st.row_off.copy_(torch.tensor(offs, dtype=torch.int32))
+            for l in range(nl):
+                st.bias[l].copy_(self._lstm_bias(f"decoder.rnns.{l}"))
+                st.ph[l].view(S, -1, self.r_H)[:, 0].zero_()    # slot 0 of every search's region: the zero state it starts from
+                st.pc[l].view(S, -1, self.r_H)[:, 0].zero_()
+            st.status.zero_()
+            ops.rnnt_beam_start(st.row_off, W, E, V_, eos, st.ctl, st.ws, st.status)
+            for _ in range(longest):
+                st.graph.replay()
+            hyps, scores, _ = ops.rnnt_beam_finish(st.row_off, W, E, V_, eos, longest * (E - 1), st.ws, st.status)
+            return hyps, scores
+
     def _rnnt_beam_search_chain(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
         """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359).
 

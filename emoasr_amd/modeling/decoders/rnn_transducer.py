@@ -2,16 +2,20 @@
 
     decoder(eouts, elens, eouts_inter, ys, ylens, ys_in, ys_out) -> (loss, loss_dict, logits [B,T,L+1,V])
     decoder.decode(eouts, elens, beam_width=1, ...)              -> (hyps, None, None, None)
+    decoder.decode(eouts [B > 1], elens, beam_width > 1)         -> (hyps[b][n], scores[b][n], None, None)
 
 The transducer loss is the HIP lattice kernel (`emoasr_rnnt_forward/_grad`) -- the reference calls the
 third-party warp_rnnt package here (rnn_transducer.py:106-115).  beam_width <= 1: time-synchronous greedy
 search; > 1: alignment-length synchronous beam search (:242-325, batch size 1, hypotheses keep the leading
 <sos>, LM arguments unused -- all as in the reference).  Like the reference, decode() discards
-scores/logits/aligns (:339-346).
+scores/logits/aligns (:339-346) for one utterance.  Several utterances with beam_width > 1 (the reference asserts a batch of one)
+go to the batched search with the bookkeeping on the device (engine.rnnt_beam_search_batch): every utterance is searched over its
+own elens[b] frames and the N-best lists come back with their scores; decoder.rnnt_beam_impl = "device" sends a single utterance
+there too (default "host": the search with the host bookkeeping, unchanged).
 """
 import torch.nn as nn
 
-from ..functions import rnnt_apply, rnnt_beam_apply, rnnt_greedy_apply, rnnt_prediction_stacked
+from ..functions import rnnt_apply, rnnt_beam_apply, rnnt_beam_batch_apply, rnnt_greedy_apply, rnnt_prediction_stacked
 from ...criteria import RNNTAlignDistillLoss, RNNTWordDistillLoss
 from .ctc import CTCDecoder
 from .rnnt_aligner import RNNTForcedAligner
@@ -52,6 +56,9 @@ class RNNTDecoder(nn.Module):
         # training, and forming them costs 0.9 GB per micro-batch at the L4 sizes: in train mode they are None unless this is set
         # (or distillation needs them); eval-mode forward returns them as the reference does
         self.return_logits = False
+        # beam_width > 1 on ONE utterance: "host" (the expansion round on the device, the bookkeeping on the host; no scores) or
+        # "device" (the batched search, which several utterances always take).  A plain attribute: not a parameter, not saved.
+        self.rnnt_beam_impl = "host"
         self._owner = None
 
     def prediction_stacked(self, ys_in_list, ylens_list):
@@ -77,6 +84,15 @@ class RNNTDecoder(nn.Module):
     def decode(self, eouts, elens, eouts_inter=None, beam_width=1, len_weight=0, lm=None, lm_weight=0,
                decode_ctc_weight=0, decode_phone=False):
         if beam_width > 1:
+            if self.rnnt_beam_impl not in ("host", "device"):
+                raise ValueError(f"emoasr_amd: rnnt_beam_impl is 'host' or 'device', not {self.rnnt_beam_impl!r}")
+            if self.rnnt_beam_impl == "device" and beam_width > 16:   # (asked for by name: no quiet detour through the host forms)
+                raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' takes beam_width <= 16, not {beam_width}")
+            if eouts.size(0) > 1 or self.rnnt_beam_impl == "device":
+                hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width)
+                if eouts.size(0) == 1:
+                    return hyps[0], scores[0], None, None
+                return hyps, scores, None, None
             return self._beam_search(eouts, elens, beam_width, len_weight, lm, lm_weight), None, None, None
         if decode_ctc_weight == 1:
             self.ctc._owner = self._owner

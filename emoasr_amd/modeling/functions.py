@@ -608,3 +608,8 @@ def rnnt_greedy_apply(dec, eouts, elens):
 
 def rnnt_beam_apply(dec, eouts, beam_width):
     return _engine_of(dec).rnnt_beam_search(eouts, beam_width, dec.blank_id, dec.eos_id)
+
+
+def rnnt_beam_batch_apply(dec, eouts, elens, beam_width):
+    """-> (hyps[b][n], scores[b][n]): every utterance searched over its own elens[b] frames"""
+    return _engine_of(dec).rnnt_beam_search_batch(eouts, _host_list(elens), beam_width, dec.blank_id, dec.eos_id)

@@ -1744,3 +1744,53 @@ def attn_step(qkv, kcache, vcache, pos, H):
     lib.call("emoasr_attn_step", nb, d, H, kcache.shape[1], _p(_chk(qkv, torch.bfloat16)), _p(kcache), _p(vcache), _p(pos), _p(out),
              _stream())
     return out
+
+
+# ---- batched transducer beam search with the bookkeeping on the device (csrc/rnnt_beam_book.hip) --------------------------------
+RNNT_BEAM_MAX_WIDTH, RNNT_BEAM_MAX_EXPANDS = 16, 15
+RNNT_BEAM_STATUS = {1: "a picked label outside 1 .. V - 1", 2: "row_off not rising", 4: "a hypothesis longer than the output row",
+                    8: "workspace too short for the searches' states and tries", 32: "no free state slot in a search's region"}
+
+
+def rnnt_beam_start(row_off, W, num_expands, V, eos, ctl, ws, status, ws_bytes=None):
+    """every search of row_off (int32 [S + 1], device) at [(<sos>)], score 0, slot 0; writes the control words ctl (int64 [5, S W])
+    of round 0.  ws: uint8 workspace of emoasr_rnnt_beam_ws_bytes(S, row_off[-1], W, num_expands) bytes (ws_bytes: what to tell
+    the kernels instead of its size)."""
+    S = row_off.numel() - 1
+    if not 1 <= int(W) <= RNNT_BEAM_MAX_WIDTH:
+        raise ValueError(f"rnnt_beam: beam width {W} is outside 1..{RNNT_BEAM_MAX_WIDTH}")
+    assert _chk(row_off, torch.int32).is_contiguous() and _chk(ctl, torch.int64).is_contiguous() and ctl.numel() == 5 * S * W
+    with torch.cuda.device(ws.device):
+        lib.call("emoasr_rnnt_beam_start", S, int(W), int(num_expands), int(V), int(eos), _p(row_off), _p(ctl), _p(ws),
+                 ws.numel() if ws_bytes is None else int(ws_bytes), _p(status), _stream())
+
+
+def rnnt_beam_book(row_off, W, num_expands, V, eos, rec, ctl, ws, status, ws_bytes=None):
+    """one round's bookkeeping from the records rec (f32 [S W, >= 1 + 2 W]: what emoasr_rnnt_beam_pick wrote for the rows of ctl)
+    and the next round's control words into ctl"""
+    S = row_off.numel() - 1
+    assert _chk(rec, torch.float32).shape[0] == S * W and rec.stride(1) == 1 and ctl.numel() == 5 * S * W
+    with torch.cuda.device(ws.device):
+        lib.call("emoasr_rnnt_beam_book", S, int(W), int(num_expands), int(V), int(eos), _p(row_off), _p(rec), rec.stride(0), _p(ctl),
+                 _p(ws), ws.numel() if ws_bytes is None else int(ws_bytes), _p(status), _stream())
+
+
+def rnnt_beam_finish(row_off, W, num_expands, V, eos, Lmax, ws, status, ws_bytes=None):
+    """-> (hyps[s][n] with the leading <sos>, float64 scores[s][n], out_n list) best first; one download.  RuntimeError naming the
+    cause when a search was refused (RNNT_BEAM_STATUS; its out_n is -1)."""
+    S, dev = row_off.numel() - 1, ws.device
+    out_tok, out_len, out_score, out_n = _ctc_beam_outputs(S, int(W), int(Lmax), dev)
+    with torch.cuda.device(dev):
+        lib.call("emoasr_rnnt_beam_finish", S, int(W), int(num_expands), int(V), int(eos), _p(row_off), int(Lmax), _p(out_tok),
+                 _p(out_len), _p(out_score), _p(out_n), _p(ws), ws.numel() if ws_bytes is None else int(ws_bytes), _p(status),
+                 _stream())
+    n, st = out_n.tolist(), int(status.item())
+    if st or min(n, default=0) < 0:
+        why = ", ".join(text for bit, text in RNNT_BEAM_STATUS.items() if st & bit) or f"status {st}"
+        err = RuntimeError(f"rnnt_beam: refused {sum(1 for v in n if v < 0)} of {S} searches: {why}")
+        err.out_n = n
+        raise err
+    tok, lens, score = out_tok.cpu().numpy(), out_len.cpu().numpy(), out_score.cpu().numpy()
+    hyps = [[tok[s, i, :lens[s, i]].tolist() for i in range(n[s])] for s in range(S)]
+    scores = [[float(score[s, i]) for i in range(n[s])] for s in range(S)]
+    return hyps, scores, n

@@ -662,6 +662,44 @@ int emoasr_rnnt_beam_joint(int dtype, int nb, int H, int J, int Tmax, const void
 int emoasr_rnnt_beam_pick(int dtype, int nb, int V, int k, int blank, const void* logits, long ldl, float* out, long ldo,
                           void* stream);
 
+/* ---- batched transducer beam search with the bookkeeping on the device (csrc/rnnt_beam_book.hip, csrc/rnnt_beam.hip;
+ * engine.rnnt_beam_search_batch): S searches of W <= 16 rows each, R = S W rows per launch, no host round trip between rounds.
+ * Control words ctl: int64 [5][R], row s W + i: last label, source slot, destination slot, active flag, row of the search's current
+ * frame in the stacked [sum of T, J] matrix w_enc . eouts + b.  row_off: int32 [S + 1], the frames before search s in that matrix.
+ * Search s owns the slots s (E + 1) W .. (s + 1)(E + 1) W - 1 of the state pools (E = num_expands <= 15); slot s (E + 1) W must
+ * hold the zero state when the search starts.
+ *   emoasr_rnnt_beam_lstm_rows / _joint_rows: emoasr_rnnt_beam_lstm / _joint over R rows in tiles of 16 (one tile per blockIdx.y),
+ *       row by row the same arithmetic.  A row whose active flag is 0 (or whose indices are outside nx / nslots) is a zero row of
+ *       the staged image: it writes no pool slot and no row of hj.  hj is [R][J]; e_row (int64 [R]) names each row's row of e_all.
+ *   emoasr_rnnt_beam_ws_bytes: the workspace of S searches over total_frames frames in all: S fixed states of
+ *       EMOASR_RNNT_BEAM_STATE_BYTES, then 32 bytes per trie node, W total_frames (num_expands - 1) + S nodes.  -1 outside the limits.
+ *   emoasr_rnnt_beam_start : every search at [(<sos> = eos)], score 0, slot 0, frame 0, round 0; writes the control words of round 0
+ *   emoasr_rnnt_beam_book  : after the pick kernel of a round (rec: f32 [R][ldr], ldr >= 1 + 2 W, k = W): the round's bookkeeping
+ *       (rnn_transducer.py:264-321, 348-359: blank extensions to the frame list, grown candidates, stable order by double score,
+ *       merge of equal label sequences by log-add, cut to W; after round num_expands - 1 the same on the frame list, next frame)
+ *       and the next round's control words.  A search whose frames are used up keeps its beams; its rows stay inactive.
+ *   emoasr_rnnt_beam_finish: out_tok int32 [S][W][Lmax + 1], out_len [S][W], out_score f64 [S][W], out_n [S], best first, as
+ *       emoasr_ctc_beam_batch writes them; hypotheses keep the leading <sos>.
+ * Refusals (workspace short, a label outside 1 .. V - 1, offsets not rising, a hypothesis longer than Lmax + 1) are OR-ed into
+ * *status (the bits of the CTC searches: 1 label, 2 offsets, 4 too long, 8 workspace, 32 no slot), the search stops and finish
+ * gives out_n[s] = -1. */
+#define EMOASR_RNNT_BEAM_MAX_WIDTH 16
+#define EMOASR_RNNT_BEAM_MAX_EXPANDS 15
+#define EMOASR_RNNT_BEAM_STATE_BYTES 8736
+int emoasr_rnnt_beam_lstm_rows(int dtype, int R, int nin, int H, const void* xtab, long ldx, long nx, const long long* xidx,
+                               const void* w_ih, const void* w_hh, const float* bias, void* ph, float* pc, long nslots,
+                               const long long* src, const long long* dst, const long long* active, void* stream);
+int emoasr_rnnt_beam_joint_rows(int dtype, int R, int H, int J, int e_rows, const void* ph, long nslots, const long long* dst,
+                                const long long* active, const void* w_dec, const float* b_dec, const void* e_all,
+                                const long long* e_row, void* hj, void* stream);
+long emoasr_rnnt_beam_ws_bytes(int S, int total_frames, int W, int num_expands);
+int emoasr_rnnt_beam_start(int S, int W, int num_expands, int V, int eos, const int* row_off, long long* ctl, void* ws,
+                           long ws_bytes, int* status, void* stream);
+int emoasr_rnnt_beam_book(int S, int W, int num_expands, int V, int eos, const int* row_off, const float* rec, long ldr,
+                          long long* ctl, void* ws, long ws_bytes, int* status, void* stream);
+int emoasr_rnnt_beam_finish(int S, int W, int num_expands, int V, int eos, const int* row_off, int Lmax, int* out_tok, int* out_len,
+                            double* out_score, int* out_n, void* ws, long ws_bytes, int* status, void* stream);
+
 /* ---- one step of the RNN LM for the hypotheses of a beam search (csrc/rnnlm.hip; lm/modeling/rnn.py:62-81, RNNLM.predict): L + 2
  * launches -- one per LSTM layer, emoasr_gemm_nt for the vocabulary head, a log-softmax.  1 <= nb <= 32 rows.  Row i reads the
  * embedding of ids[i] (int32), the state (h, c) of every layer from the slot pools ph [L][slots][H] (compute dtype) / pc
