@@ -577,3 +577,83 @@ extern "C" int emoasr_joint_beam_graph_launch(int slot, int part, void* stream) 
   if (e != hipSuccess) { emo_set_error("hipGraphLaunch: %s", hipGetErrorString(e)); return 1; }
   return 0;
 }
+
+// ---- the joint search for S utterances at once (kernels in csrc/decode_batch.hip) ------------------
+extern "C" size_t emoasr_decode_step_group_ws_bytes(int dtype, int nb, int d, int H, int F, int V) {
+  return emoasr_decode_step_ws_bytes(dtype, nb, d, H, F, V);
+}
+
+// the launch chain of emoasr_transformer_decoder_step (never the cooperative kernel) with the grouped cross-attention
+extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const emoasr_decoder_layer_t* layers,
+                                                     const emoasr_decoder_step_group_t* g, void* stream) {
+  EMO_CHECK(layers && g && g->moff, "decoder_step_group: missing arguments");
+  const emoasr_decoder_step_t* io = &g->d;
+  EMO_CHECK(io->ws && io->kv && io->logits_last && io->kcache && io->vcache && io->pos && io->klens, "decoder_step_group: missing arguments");
+  const int nb = io->nb, Lmax = io->Lmax, dd = io->dd, H = io->H, F = io->F;
+  EMO_CHECK(g->S >= 1 && g->W >= 1 && g->W <= 32 && nb == g->S * g->W, "decoder_step_group: %d rows for %d searches of width %d (1..32)", nb,
+            g->S, g->W);
+  EMO_CHECK(Lmax > 0 && dd % H == 0, "decoder_step_group: bad dims Lmax=%d dd=%d H=%d", Lmax, dd, H);
+  const size_t esz = dtype == EMO_BF16 ? 2 : 4;
+  hipStream_t s = (hipStream_t)stream;
+  Bump ws{(char*)io->ws, io->ws_bytes};
+  void* x = ws.take(nb * dd * esz);
+  void* x2 = ws.take(nb * dd * esz);
+  void* h = ws.take(nb * dd * esz);
+  void* o = ws.take(nb * dd * esz);
+  void* q = ws.take(nb * dd * esz);
+  void* qkv = ws.take((size_t)nb * 3 * dd * esz);
+  void* act = ws.take((size_t)nb * F * esz);
+  float* lse = (float*)ws.take((size_t)nb * H * 4);
+  EMO_CHECK(ws.ok, "decoder_step_group: scratch too small (%zu bytes given)", io->ws_bytes);
+  EMO_DISPATCH(dtype, (step_embed_kernel<T><<<cdiv((long)nb * dd, 256), 256, 0, s>>>(nb, dd, io->ids, (const T*)io->embed, io->pe,
+                                                                                      io->emb_scale, io->pos, (T*)x)));
+  const size_t layer_bytes = (size_t)nb * Lmax * dd * esz;
+  for (int li = 0; li < nl; ++li) {
+    const emoasr_decoder_layer_t& Ly = layers[li];
+    char* kc = (char*)io->kcache + li * layer_bytes;
+    char* vc = (char*)io->vcache + li * layer_bytes;
+    if (emoasr_layernorm_fwd(dtype, nb, dd, x, Ly.ln1.g, Ly.ln1.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
+    if (linear(dtype, nb, 3 * dd, dd, h, dd, Ly.qkv, qkv, EMOASR_ACT_NONE, nullptr, stream)) return 1;
+    EMO_DISPATCH(dtype, (kv_append_kernel<T><<<cdiv((long)nb * dd, 256), 256, 0, s>>>(nb, dd, Lmax, (const T*)qkv, (T*)kc, (T*)vc, io->pos)));
+    if (attn_cached(dtype, nb, Lmax, dd, H, qkv, kc, vc, io->klens, o, lse, stream)) return 1;
+    if (linear(dtype, nb, dd, dd, o, dd, Ly.out, x2, EMOASR_ACT_NONE, x, stream)) return 1;
+    if (emoasr_layernorm_fwd(dtype, nb, dd, x2, Ly.ln2.g, Ly.ln2.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
+    if (linear(dtype, nb, dd, dd, h, dd, Ly.q2, q, EMOASR_ACT_NONE, nullptr, stream)) return 1;
+    if (emoasr_attn_step_group(dtype, g->S, g->W, dd, H, q, io->kv[li], g->moff, o, stream)) return 1;
+    if (linear(dtype, nb, dd, dd, o, dd, Ly.out2, x, EMOASR_ACT_NONE, x2, stream)) return 1;
+    if (emoasr_layernorm_fwd(dtype, nb, dd, x, Ly.ln3.g, Ly.ln3.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
+    if (linear(dtype, nb, F, dd, h, dd, Ly.w1, act, EMOASR_ACT_RELU, nullptr, stream)) return 1;
+    if (linear(dtype, nb, dd, F, act, F, Ly.w2, x2, EMOASR_ACT_NONE, x, stream)) return 1;
+    void* t = x; x = x2; x2 = t;
+  }
+  if (emoasr_layernorm_fwd(dtype, nb, dd, x, io->ln_out.g, io->ln_out.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
+  EMO_LAUNCH_CHECK();
+  return linear(dtype, nb, io->V, dd, h, dd, io->out, io->logits_last, EMOASR_ACT_NONE, nullptr, stream);
+}
+
+extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream) {
+  EMO_CHECK(js && js->dec_layers, "joint_beam_batch_step: missing arguments");
+  const emoasr_decoder_step_t& d = js->dec.d;
+  const emoasr_bert_step_t& l = js->lm;
+  const emoasr_beam_update_t& u = js->upd.u;
+  const int nb = d.nb, V = d.V, W = js->dec.W;
+  const bool use_lm = js->lm_nl > 0;
+  EMO_CHECK(u.bw == W && js->upd.S == js->dec.S, "joint_beam_batch_step: the update's %d x %d searches against the decoder's %d x %d", js->upd.S,
+            u.bw, js->dec.S, W);
+  EMO_CHECK(!use_lm || (l.nb == nb && l.raw_logits), "joint_beam_batch_step: the LM step runs on the same %d rows and leaves raw logits", nb);
+  if (emoasr_beam_cache_gather(dtype, js->dec_nl, nb, d.Lmax, d.dd, js->dec_k_prev, js->dec_v_prev, d.kcache, d.vcache, js->parent,
+                               d.pos, stream)) return 1;
+  if (emoasr_transformer_decoder_step_group(dtype, js->dec_nl, js->dec_layers, &js->dec, stream)) return 1;
+  if (use_lm) {
+    if (emoasr_beam_cache_gather(dtype, js->lm_nl, nb, l.Lmax, l.d, js->lm_k_prev, js->lm_v_prev, l.kcache, l.vcache, js->parent,
+                                 l.pos, stream)) return 1;
+    if (emoasr_bert_lm_step(dtype, js->lm_nl, js->lm_layers, &l, stream)) return 1;
+  }
+  if (emoasr_beam_scores_topk(dtype, nb, V, u.cw, d.logits_last, V, use_lm ? l.logp : nullptr, use_lm ? V : 0, use_lm ? u.mu : 0.f,
+                              (float*)u.vals, (int*)u.cands, (float*)u.lm_at, stream)) return 1;
+  if (u.psi) {
+    if (emoasr_ctc_prefix_score_ragged(nb, W, js->Tmax, V, u.cw, js->ctc_x, js->dec.moff, js->states_prev, u.cw, js->parent, u.n_pcand,
+                                       u.n_last, u.n_outlen, u.cands, js->blank, u.eos, (float*)u.psi, js->states_cur, stream)) return 1;
+  }
+  return emoasr_beam_update_batch(&js->upd, stream);
+}

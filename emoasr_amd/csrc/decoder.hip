@@ -369,13 +369,17 @@ __device__ __forceinline__ float np_logaddexp(float a, float b) {
 // but everything it consumes is not: per chunk of 64 frames the lanes fetch the parent state and the two
 // emission columns (one memory round trip per chunk instead of four per frame) and compute phi; lane 0 then
 // runs the 64 dependent steps out of LDS and the lanes write the new state rows back coalesced.
+// RAGGED (the batched joint search): row m belongs to search m / W, whose emissions are the rows xoff[s] .. xoff[s + 1] - 1 of x;
+// every state is a [Tn = Tmax, 2] slot of which the search uses its first T_s rows.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void ctc_prefix_kernel(int Tn, int V, int cw, const float* __restrict__ x,
                                                         const float* __restrict__ prev_states, int cw_prev,
                                                         const int* __restrict__ parent, const int* __restrict__ pcand,
                                                         const float* __restrict__ init_state,
                                                         const int* __restrict__ last, const int* __restrict__ out_len,
                                                         const int* __restrict__ cands, int blank, int eos,
-                                                        float* __restrict__ log_psi, float* __restrict__ states) {
+                                                        float* __restrict__ log_psi, float* __restrict__ states,
+                                                        const int* __restrict__ xoff, int W) {
   __shared__ float s_rn[64], s_rb[64];
   const int m = blockIdx.x / cw, c = blockIdx.x % cw, lane = threadIdx.x;
   const float* rp = prev_states ? prev_states + ((long)parent[m] * cw_prev + pcand[m]) * Tn * 2 : init_state;
@@ -383,6 +387,11 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(int Tn, int V, int cw, c
   const int olen = out_len[m];
   const bool same = olen > 0 && tok == last[m];
   float* r = states + ((long)m * cw + c) * Tn * 2;
+  if constexpr (RAGGED) {   // (after the slots are addressed with the common stride)
+    const int s = m / W;
+    x += (long)xoff[s] * V;
+    Tn = xoff[s + 1] - xoff[s];
+  }
   const int start = olen > 1 ? olen : 1;
   // rows before `start` keep their initial value: LOG_0, except r[0][0] = x[0][tok] for an empty prefix
   for (int t = lane; t < start && t < Tn; t += 64) {
@@ -438,9 +447,18 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(int Tn, int V, int cw, c
 }
 
 // initial state: r[t,1] = running sum of the blank log-probs (float32, step by step), r[t,0] = LOG_0
+template <bool RAGGED>
 __global__ void ctc_prefix_init_kernel(int Tn, int V, const float* __restrict__ x, int blank,
-                                       float* __restrict__ r) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+                                       float* __restrict__ r, const int* __restrict__ xoff, long r_stride) {
+  if (threadIdx.x != 0) return;
+  if constexpr (RAGGED) {   // one block per search: its own frames, its own state slot
+    const int s = blockIdx.x;
+    x += (long)xoff[s] * V;
+    Tn = xoff[s + 1] - xoff[s];
+    r += s * r_stride;
+  } else {
+    if (blockIdx.x != 0) return;
+  }
   float acc = 0.f;
   for (int t = 0; t < Tn; ++t) {
     acc = t == 0 ? x[blank] : acc + x[(long)t * V + blank];
@@ -495,7 +513,7 @@ extern "C" int emoasr_beam_scores_topk(int dtype, int M, int V, int k, const voi
 }
 
 extern "C" int emoasr_ctc_prefix_init(int T, int V, const float* x, int blank, float* r, void* stream) {
-  ctc_prefix_init_kernel<<<1, 64, 0, (hipStream_t)stream>>>(T, V, x, blank, r);
+  ctc_prefix_init_kernel<false><<<1, 64, 0, (hipStream_t)stream>>>(T, V, x, blank, r, nullptr, 0);
   EMO_LAUNCH_CHECK();
   return 0;
 }
@@ -507,9 +525,32 @@ extern "C" int emoasr_ctc_prefix_score(int nb, int T, int V, int cw, const float
   if (nb == 0) return 0;
   EMO_CHECK(cw >= 1 && cw <= 1024, "ctc_prefix_score: cw=%d", cw);
   EMO_CHECK(prev_states || init_state, "ctc_prefix_score: no previous state");
-  ctc_prefix_kernel<<<nb * cw, 64, 0, (hipStream_t)stream>>>(T, V, cw, x, prev_states, cw_prev, parent, pcand,
+  ctc_prefix_kernel<false><<<nb * cw, 64, 0, (hipStream_t)stream>>>(T, V, cw, x, prev_states, cw_prev, parent, pcand,
                                                                      init_state, last, out_len, cands, blank, eos,
-                                                                     log_psi, states);
+                                                                     log_psi, states, nullptr, 1);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the ragged twins (batched joint search): S searches of W rows each, x the stacked emissions [sum T_s, V] ----
+extern "C" int emoasr_ctc_prefix_init_ragged(int S, int V, const float* x, const int* xoff, int blank, float* r, long r_stride,
+                                             void* stream) {
+  EMO_CHECK(S >= 1 && x && xoff && r, "ctc_prefix_init_ragged: missing arguments");
+  ctc_prefix_init_kernel<true><<<S, 64, 0, (hipStream_t)stream>>>(0, V, x, blank, r, xoff, r_stride);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_ctc_prefix_score_ragged(int nb, int W, int Tmax, int V, int cw, const float* x, const int* xoff,
+                                              const float* prev_states, int cw_prev, const int* parent, const int* pcand,
+                                              const int* last, const int* out_len, const int* cands, int blank, int eos,
+                                              float* log_psi, float* states, void* stream) {
+  if (nb == 0) return 0;
+  EMO_CHECK(W >= 1 && W <= 32 && nb % W == 0, "ctc_prefix_score_ragged: %d rows in groups of %d (1..32)", nb, W);
+  EMO_CHECK(cw >= 1 && cw <= 32, "ctc_prefix_score_ragged: cw=%d outside 1..32", cw);
+  EMO_CHECK(x && xoff && prev_states && Tmax >= 1, "ctc_prefix_score_ragged: missing arguments");
+  ctc_prefix_kernel<true><<<nb * cw, 64, 0, (hipStream_t)stream>>>(Tmax, V, cw, x, prev_states, cw_prev, parent, pcand, nullptr,
+                                                                    last, out_len, cands, blank, eos, log_psi, states, xoff, W);
   EMO_LAUNCH_CHECK();
   return 0;
 }

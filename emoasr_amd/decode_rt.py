@@ -75,6 +75,35 @@ class DecoderStepRuntime:
         self.T, self.beam = T, beam_width
         self.kmem = h2d_i32([T] * beam_width, eouts.device)
 
+    def begin_batch(self, eouts, elens, rows_cap=0):
+        """the batched search's memory: the valid frames of all utterances stacked [sum T_s, d] and projected ONCE per layer into
+        kv_group[l] [>= max(sum T_s, rows_cap), 2*dd] (no per-beam replica: emoasr_attn_step_group reads a search's rows for all
+        its beams; the buffers are kept and reused while they are large enough, so that captured steps may point at them);
+        moff_host: the first row of every utterance.  -> the stacked memory [sum T_s, d]"""
+        eng, A = self.eng, self.eng.arena
+        self._params()
+        elens = [int(n) for n in elens]
+        S, d, dd = eouts.shape[0], eouts.shape[2], eng.dd
+        if len(elens) != S or any(n < 1 or n > eouts.shape[1] for n in elens):
+            raise ValueError(f"begin_batch: every utterance needs 1 <= elens[b] <= {eouts.shape[1]} frames, got {elens}")
+        offs = [0]
+        for n in elens:
+            offs.append(offs[-1] + n)
+        lib.call("emoasr_group_offsets_check", S, (ctypes.c_int * (S + 1))(*offs))
+        mem = torch.cat([eouts[b, :elens[b]] for b in range(S)], 0) if S > 1 else eouts[0, :elens[0]].contiguous()
+        rows = max(offs[-1], int(rows_cap))
+        kvg = getattr(self, "kv_group", None)
+        if kvg is None or kvg[0].shape[0] < rows or kvg[0].dtype != mem.dtype or kvg[0].device != mem.device:
+            kvg = self.kv_group = [torch.zeros(rows, 2 * dd, device=mem.device, dtype=mem.dtype) for _ in range(eng.dnl)]
+            self.kv_group_ptrs = (ctypes.c_void_p * eng.dnl)(*[k.data_ptr() for k in kvg])
+        for li in range(eng.dnl):
+            ca = f"decoder.transformers.{li}.src_attn"
+            wkv = A.w_span(ca + ".linear_k.weight", ca + ".linear_v.weight", (2 * dd, d))
+            bkv = A.p_span(ca + ".linear_k.bias", ca + ".linear_v.bias", (2 * dd,))
+            ops.gemm_nt(mem, wkv, out=kvg[li][:offs[-1]], bias=bkv)  # [sum T_s, 2dd]
+        self.moff_host = offs
+        return mem
+
     def step(self, ys_in):
         """ys_in: CPU int64 [nb, L] -> logits of the last position [nb, V] (compute dtype)"""
         eng, A = self.eng, self.eng.arena

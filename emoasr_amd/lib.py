@@ -132,6 +132,22 @@ class JointStep(Structure):
                 ("states_prev", c_void_p), ("states_cur", c_void_p), ("upd", BeamUpdate)]
 
 
+class BeamUpdateBatch(Structure):
+    _fields_ = [("u", BeamUpdate), ("S", c_int), ("max_pos", c_int), ("pos", c_void_p), ("ctl", c_void_p)]
+
+
+class DecoderStepGroup(Structure):
+    _fields_ = [("d", DecoderStep), ("S", c_int), ("W", c_int), ("moff", c_void_p)]
+
+
+class JointBatchStep(Structure):
+    _fields_ = [("dec_nl", c_int), ("dec_layers", POINTER(DecoderLayer)), ("dec", DecoderStepGroup),
+                ("lm_nl", c_int), ("lm_layers", POINTER(BertLayer)), ("lm", BertStep),
+                ("dec_k_prev", c_void_p), ("dec_v_prev", c_void_p), ("lm_k_prev", c_void_p), ("lm_v_prev", c_void_p),
+                ("parent", c_void_p), ("ctc_x", c_void_p), ("Tmax", c_int), ("blank", c_int),
+                ("states_prev", c_void_p), ("states_cur", c_void_p), ("upd", BeamUpdateBatch)]
+
+
 class FfnParams(Structure):
     _fields_ = [("ln_g", c_void_p), ("ln_b", c_void_p), ("w1", c_void_p), ("b1", c_void_p),
                 ("w2", c_void_p), ("b2", c_void_p)]
@@ -239,6 +255,13 @@ SIGNATURES = {
     "emoasr_joint_beam_step_parts": [I, POINTER(JointStep), I, P],
     "emoasr_joint_beam_graph_build": [I, POINTER(JointStep), I, I, P],
     "emoasr_joint_beam_graph_launch": [I, I, P],
+    "emoasr_attn_step_group": [I, I, I, I, I, P, P, P, P, P],
+    "emoasr_group_offsets_check": [I, POINTER(c_int)],
+    "emoasr_beam_update_batch": [POINTER(BeamUpdateBatch), P],
+    "emoasr_ctc_prefix_init_ragged": [I, I, P, P, I, P, L, P],
+    "emoasr_ctc_prefix_score_ragged": [I, I, I, I, I, P, P, P, I, P, P, P, P, P, I, I, P, P, P],
+    "emoasr_transformer_decoder_step_group": [I, I, POINTER(DecoderLayer), POINTER(DecoderStepGroup), P],
+    "emoasr_joint_beam_batch_step": [I, POINTER(JointBatchStep), P],
     "emoasr_attn_dropmask": [I, POINTER(AttnArgs), P, I, P],
     "emoasr_attn_fwd": [I, POINTER(AttnArgs), P],
     "emoasr_attn_bwd": [I, POINTER(AttnArgs), P],

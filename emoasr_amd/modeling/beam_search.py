@@ -156,3 +156,24 @@ def joint_beam_search(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_w
             beams = alive
     results = sorted(results, key=lambda r: r["score"], reverse=True)
     return [r["hyp"] for r in results], [r["score"] for r in results], None, None
+
+
+def joint_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
+    """the joint search for every utterance of a batch: eouts [B, Tmax, d], utterance b over its own elens[b] frames ->
+    (hyps, scores, None, None), hyps[b] / scores[b] the lists joint_beam_search returns for eouts[b:b+1, :elens[b]].
+    The batched device search (beam_search_device.joint_beam_search_device_batch: all searches in lockstep) takes it when it
+    can; a stateful LM (the RNN LM), beam_width or a candidate width above 32, and the switches that force the host
+    bookkeeping fall back to one joint_beam_search per utterance."""
+    require_next_token_lm(lm, lm_weight)
+    lens = [int(n) for n in elens]
+    if len(lens) != eouts.shape[0] or any(n < 1 for n in lens):
+        raise ValueError(f"joint beam search: every utterance needs at least one encoder frame, got elens {lens}")
+    from . import beam_search_device as bsd
+    if bsd.batch_device_ok(dec, beam_width, lm, lm_weight, decode_ctc_weight):
+        return bsd.joint_beam_search_device_batch(dec, eouts, lens, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+    hyps, scores = [], []
+    for b, n in enumerate(lens):
+        h, s, _, _ = joint_beam_search(dec, eouts[b:b + 1, :n], elens[b:b + 1], beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+        hyps.append(h)
+        scores.append(s)
+    return hyps, scores, None, None

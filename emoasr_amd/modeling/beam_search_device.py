@@ -8,6 +8,9 @@ flag back:
   * candidate selection, CTC prefix re-scoring, the per-beam and global prunes, <eos> handling and the result list are
     device kernels (emoasr_beam_update: numpy-float32 candidate scores, double hypothesis scores, stable orders);
   * the token sequences are rebuilt once, at the end, from the per-step (parent, token) history.
+
+joint_beam_search_device_batch (second half of this file) runs the same search for S utterances in lockstep: rows s * W ..
+s * W + W - 1 belong to utterance s, one captured step serves them all.
 """
 import ctypes
 import gc
@@ -306,3 +309,309 @@ def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=Non
         results.append(dict(hyp=toks[::-1], score=float(rs[k])))
     results = sorted(results, key=lambda r: r["score"], reverse=True)
     return [r["hyp"] for r in results], [r["score"] for r in results], None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The same search for S utterances at once.  A search is one utterance; S searches of width W occupy
+# rows s * W .. s * W + W - 1 of every per-hypothesis array and step in lockstep: one captured step serves all of them, a
+# finished search keeps its rows (computed and ignored).  Kernels: csrc/decode_batch.hip (grouped cross-attention over the
+# unreplicated memories, one bookkeeping workgroup per search), the ragged CTC prefix scorer (csrc/decoder.hip) and the
+# chain emoasr_joint_beam_batch_step (csrc/decode_rt.hip).
+# ---------------------------------------------------------------------------------------------------------------------------
+MAX_ROWS = 1024                     # S * W rows of one chunk
+CACHE_BUDGET_BYTES = 8 << 30        # the self-attention cache pools of one chunk (decoder + LM, both halves of the ping-pong)
+
+
+def batch_cache_bytes(nb, Lmax, dnl, dd, lnl, ld, esz):
+    """bytes of the cache pools of nb rows: K and V, two halves (previous / current step), every layer, Lmax positions"""
+    return 2 * 2 * nb * Lmax * (dnl * dd + lnl * ld) * esz
+
+
+def batch_chunk_capacity(W, Lmax, dnl, dd, lnl, ld, esz, budget=None, max_rows=None):
+    """S_max: the most searches of width W one chunk holds -- S_max * W <= MAX_ROWS rows and batch_cache_bytes(S_max * W, ...)
+    <= CACHE_BUDGET_BYTES; never below one search"""
+    budget = CACHE_BUDGET_BYTES if budget is None else budget
+    max_rows = MAX_ROWS if max_rows is None else max_rows
+    per_search = batch_cache_bytes(W, Lmax, dnl, dd, lnl, ld, esz)
+    return max(1, min(max_rows // W, budget // per_search))
+
+
+def batch_device_ok(dec, beam_width, lm, lm_weight, decode_ctc_weight):
+    """whether the batched device search takes this configuration (else: utterance by utterance through joint_beam_search)"""
+    use_ctc = decode_ctc_weight > 0
+    cw = min(dec.vocab_size, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if use_ctc else beam_width
+    if os.environ.get("EMOASR_DEVICE_BEAM", "1") == "0" or os.environ.get("EMOASR_CPP_DECODE", "1") == "0":
+        return False   # the switches that force the host bookkeeping
+    if not (1 <= beam_width <= 32 and 1 <= cw <= 32 and beam_width <= dec.vocab_size):
+        return False
+    return lm is None or lm_weight <= 0 or hasattr(lm, "predict_device")
+
+
+class _BatchBuffers:
+    """device buffers of one (S, W, cw, Lmax, model sizes, frame capacities) configuration, reused across calls: the captured
+    steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`)."""
+
+    def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc):
+        nb = S * W
+        self.rows_cap, self.Tcap = rows_cap, Tcap
+        i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
+        f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        # pack: res_score (double [nb]) | state [S, 4] | res_step [nb] | res_parent [nb] | hist_parent [Lmax, nb] | hist_token [Lmax, nb]
+        n = [2 * nb, 4 * S, nb, nb, Lmax * nb, Lmax * nb]
+        self.pack = i32(sum(n))
+        o = [0]
+        for v in n:
+            o.append(o[-1] + v)
+        self.pack_off = o
+        part = lambda k: self.pack[o[k]:o[k + 1]]
+        self.res_score = part(0).view(torch.float64)
+        self.state, self.res_step, self.res_parent = part(1).view(S, 4), part(2), part(3)
+        self.hist_parent, self.hist_token = part(4).view(Lmax, nb), part(5).view(Lmax, nb)
+        self.pos, self.ctl = i32(1), i32(1)
+        self.ids, self.parent, self.pcand = i32(nb), i32(nb), i32(nb)
+        self.last, self.outlen, self.klens = i32(nb), i32(nb), i32(nb)
+        self.score = torch.zeros(nb, device=dev, dtype=torch.float64)
+        self.score_ctc = f32(nb)
+        self.vals, self.cands, self.lm_at, self.psi = f32(nb, cw), i32(nb, cw), f32(nb, cw), f32(nb, cw)
+        self.logits = torch.zeros(nb, V, device=dev, dtype=dtype)
+        self.lm_logp = f32(nb, V) if lnl else None
+        self.dec_k = torch.zeros(2, dnl, nb, Lmax, dd, device=dev, dtype=dtype)
+        self.dec_v = torch.zeros_like(self.dec_k)
+        self.lm_k = torch.zeros(2, max(lnl, 1), nb, Lmax, max(ld, 1), device=dev, dtype=dtype) if lnl else None
+        self.lm_v = torch.zeros_like(self.lm_k) if lnl else None
+        self.moff = i32(S + 1)
+        self.ctc_x = f32(rows_cap, V) if use_ctc else None
+        self.states = f32(2, nb, cw, Tcap, 2) if use_ctc else None
+        self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
+        self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured structs point at)
+
+
+def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, decode_ctc_weight):
+    """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable)"""
+    V, eos, blank = dec.vocab_size, dec.eos_id, dec.blank_id
+    dev = eouts.device
+    S, W = len(elens), bw
+    nb = S * W
+    use_ctc = decode_ctc_weight > 0
+    use_lm = lm is not None and lm_weight > 0
+    cw = min(V, int(bw * CTC_BEAM_WIDTH_RATIO)) if use_ctc else bw
+    max_steps = dec.max_decode_ylen
+    Lmax = max_steps + 1
+    A = eng.arena
+    bstream = getattr(eng, "_beam_stream", None)
+    if bstream is None:
+        bstream = eng._beam_stream = torch.cuda.Stream(device=dev)
+    caller = torch.cuda.current_stream()
+    bstream.wait_stream(caller)
+    # the launch chains only: the cooperative step kernels (csrc/decode_coop.hip, <= 16 rows) are not part of the batched step
+    with torch.no_grad(), torch.cuda.stream(bstream), ops.stream_scope(), lib.options(decode_coop=0):
+        rt = getattr(eng, "_dec_rt", None)
+        if rt is None:
+            rt = eng._dec_rt = DecoderStepRuntime(eng)
+        dec_layers = rt._params()
+        total, longest = sum(elens), max(elens)
+        rows_cap = (total + 1023) // 1024 * 1024
+        Tcap = (longest + 63) // 64 * 64
+        mem = rt.begin_batch(eouts, elens, rows_cap)   # (raises ValueError for an utterance without frames)
+        dtype = A.shadow.dtype
+        dd, dh, F = eng.dd, eng.dh, rt._F
+        lnl = ld = lH = lF = 0
+        lm_guard = None
+        if use_lm:
+            lmrt = getattr(lm, "_step_rt", None)
+            if lmrt is None:
+                lmrt = lm._step_rt = LMStepRuntime(lm)
+            LA, lm_layers = lmrt._params()
+            P = lm.params
+            lnl, ld, lH, lF = P.num_layers, P.hidden_size, P.num_attention_heads, P.intermediate_size
+            assert P.vocab_size == V and LA.shadow.dtype == dtype
+            assert lm._pe.shape[0] >= Lmax, "LM position table shorter than max_decode_ylen + 1"
+            lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._pe.data_ptr())
+        # one set of buffers is kept: reused while the sizes match and the frame capacities suffice
+        key = (str(dev), dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, use_ctc)
+        cache = getattr(eng, "_beam_batch_bufs", None)
+        if cache is not None and cache[0] == key and cache[1].rows_cap >= rows_cap and cache[1].Tcap >= Tcap:
+            Bf = cache[1]
+            rows_cap, Tcap = Bf.rows_cap, Bf.Tcap
+        else:
+            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc)
+            eng._beam_batch_bufs = (key, Bf)
+        # ---- this call's inputs, into the buffers the captured steps read ----
+        Bf.moff.copy_(h2d_i32(rt.moff_host, dev))
+        if use_ctc:
+            ctc_logits = eng.head_logits(mem.unsqueeze(0), "decoder.ctc.output")
+            Bf.ctc_x[:total].copy_(ops.log_softmax(ctc_logits.view(total, V)))
+
+        def reset(done):
+            Bf.state.copy_(h2d_i32([[0, 1, 0, done]] * S, dev))
+            Bf.pos.zero_(); Bf.ctl.fill_(done)
+            Bf.ids.fill_(eos); Bf.last.fill_(eos)
+            Bf.parent.copy_(torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(W) * W)
+            Bf.pcand.zero_(); Bf.outlen.zero_(); Bf.klens.fill_(1)
+            Bf.score.zero_(); Bf.score_ctc.zero_()
+
+        lam, mu = float(decode_ctc_weight), float(lm_weight)
+        gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), lm_guard, tuple(k.data_ptr() for k in rt.kv_group), lam, mu if use_lm else 0.0,
+                float(len_weight), eos, blank, id(Bf))
+        if Bf.graphs is None or Bf.graphs[0] != gkey:
+            dt_code = ops.dt(Bf.logits)
+            ws_dec = torch.empty(lib.size_query("emoasr_decode_step_group_ws_bytes", dt_code, nb, dd, dh, F, V), device=dev, dtype=torch.uint8)
+            ws_lm = torch.empty(lib.size_query("emoasr_decode_step_ws_bytes", dt_code, nb, max(ld, 8), max(lH, 1), max(lF, 8), V),
+                                device=dev, dtype=torch.uint8) if use_lm else None
+            pe_dec = eng._abs_table(Lmax, dev, dd)
+            steps = []
+            for cur in (0, 1):
+                prev = cur ^ 1
+                js = lib.JointBatchStep()
+                js.dec_nl, js.dec_layers = eng.dnl, dec_layers
+                js.dec.S, js.dec.W, js.dec.moff = S, W, Bf.moff.data_ptr()
+                d = js.dec.d
+                d.nb, d.Lmax, d.T, d.dd, d.H, d.F, d.V = nb, Lmax, Tcap, dd, dh, F, V
+                d.ids, d.pos, d.klens = Bf.ids.data_ptr(), Bf.pos.data_ptr(), Bf.klens.data_ptr()
+                d.embed, d.pe, d.emb_scale = A.w("decoder.embed.weight").data_ptr(), pe_dec.data_ptr(), math.sqrt(dd)
+                d.kmem, d.kv = None, ctypes.cast(rt.kv_group_ptrs, ctypes.POINTER(ctypes.c_void_p))
+                d.kcache, d.vcache = Bf.dec_k[cur].data_ptr(), Bf.dec_v[cur].data_ptr()
+                _ln(d.ln_out, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"))
+                _lin(d.out, A.w("decoder.output.weight"), A.p("decoder.output.bias"))
+                d.logits_last, d.ws, d.ws_bytes = Bf.logits.data_ptr(), ws_dec.data_ptr(), ws_dec.numel()
+                js.dec_k_prev, js.dec_v_prev = Bf.dec_k[prev].data_ptr(), Bf.dec_v[prev].data_ptr()
+                js.lm_nl = lnl if use_lm else 0
+                if use_lm:
+                    js.lm_layers = lm_layers
+                    l = js.lm
+                    pre, cp = "lm.transformer.bert.", "lm.transformer.cls.predictions."
+                    l.nb, l.Lmax, l.d, l.H, l.F, l.V = nb, Lmax, ld, lH, lF, V
+                    l.ids, l.pos, l.klens = Bf.ids.data_ptr(), Bf.pos.data_ptr(), Bf.klens.data_ptr()
+                    l.word_emb, l.pe = LA.w(pre + "embeddings.word_embeddings.weight").data_ptr(), lm._pe.data_ptr()
+                    _ln(l.ln_emb, LA.p(pre + "embeddings.LayerNorm.weight"), LA.p(pre + "embeddings.LayerNorm.bias"))
+                    l.kcache, l.vcache = Bf.lm_k[cur].data_ptr(), Bf.lm_v[cur].data_ptr()
+                    _lin(l.transform, LA.w(cp + "transform.dense.weight"), LA.p(cp + "transform.dense.bias"))
+                    _ln(l.ln_transform, LA.p(cp + "transform.LayerNorm.weight"), LA.p(cp + "transform.LayerNorm.bias"))
+                    l.out_bias, l.logp = LA.p(cp + "bias").data_ptr(), Bf.lm_logp.data_ptr()
+                    l.raw_logits = 1   # emoasr_beam_scores_topk does both log-softmaxes
+                    l.ws, l.ws_bytes = ws_lm.data_ptr(), ws_lm.numel()
+                    js.lm_k_prev, js.lm_v_prev = Bf.lm_k[prev].data_ptr(), Bf.lm_v[prev].data_ptr()
+                js.parent = Bf.parent.data_ptr()
+                js.Tmax, js.blank = Tcap, blank
+                if use_ctc:
+                    js.ctc_x = Bf.ctc_x.data_ptr()
+                    js.states_prev, js.states_cur = Bf.states[prev].data_ptr(), Bf.states[cur].data_ptr()
+                ub = js.upd
+                ub.S, ub.max_pos, ub.pos, ub.ctl = S, max_steps, Bf.pos.data_ptr(), Bf.ctl.data_ptr()
+                u = ub.u
+                u.bw, u.cw, u.eos = W, cw, eos
+                u.one_minus_lam, u.lam = float(np.float32(1 - lam)), float(np.float32(lam))
+                u.mu = float(np.float32(mu)) if use_lm else 0.0
+                u.len_weight = float(len_weight)
+                u.vals, u.cands = Bf.vals.data_ptr(), Bf.cands.data_ptr()
+                u.lm_at = Bf.lm_at.data_ptr() if (use_lm and use_ctc) else None
+                u.psi = Bf.psi.data_ptr() if use_ctc else None
+                u.score, u.score_ctc = Bf.score.data_ptr(), Bf.score_ctc.data_ptr()
+                u.n_ids, u.n_parent, u.n_pcand = Bf.ids.data_ptr(), Bf.parent.data_ptr(), Bf.pcand.data_ptr()
+                u.n_last, u.n_outlen, u.n_klens = Bf.last.data_ptr(), Bf.outlen.data_ptr(), Bf.klens.data_ptr()
+                u.hist_parent, u.hist_token = Bf.hist_parent.data_ptr(), Bf.hist_token.data_ptr()
+                u.res_score, u.res_step, u.res_parent = Bf.res_score.data_ptr(), Bf.res_step.data_ptr(), Bf.res_parent.data_ptr()
+                u.state = Bf.state.data_ptr()
+                u.host_mirror = Bf.mirror_host.data_ptr()
+                steps.append(js)
+            # warm-up with every search marked finished (the bookkeeping returns at once, the networks run on valid rows):
+            # every kernel's lazy one-time setup happens outside the capture.  Then each step is captured once: a linear
+            # chain on one stream.
+            reset(1)
+            for k in (0, 1):
+                lib.call("emoasr_joint_beam_batch_step", dt_code, ctypes.byref(steps[k]), ops._stream())
+            torch.cuda.current_stream().synchronize()
+            graphs = []
+            for k in (0, 1):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
+                    lib.call("emoasr_joint_beam_batch_step", dt_code, ctypes.byref(steps[k]), ops._stream())
+                graphs.append(g)
+            Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group))
+        graphs = Bf.graphs[1]
+        reset(0)
+        if use_ctc:   # (after the warm-up, whose steps write both halves of the scorer states)
+            # step 0 reads "previous" = half 1 at (the search's row 0, candidate 0)
+            ops.ctc_prefix_init_ragged(Bf.ctc_x, Bf.moff, blank, Bf.states[1], W * cw * Tcap * 2)
+        mirror = Bf.mirror_host.numpy()
+        mirror[:] = (0, 0)
+        main = torch.cuda.current_stream()
+        main.synchronize()     # (the mirror is host memory: the reset above must not race the first step's store)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(main)
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            # steps are issued one ahead of the mirror they depend on: a step replayed after the end changes nothing
+            for i in range(max_steps):
+                graphs[i & 1].replay()
+                if i >= 1:
+                    spins, t_wait = 0, None
+                    while mirror[0] < i and mirror[1] < S:
+                        _yield()
+                        spins += 1
+                        if spins & 0xFFF == 0:   # a lost launch / a faulted device must surface, not spin forever
+                            now = time.perf_counter()
+                            t_wait = now if t_wait is None else t_wait
+                            if now - t_wait > _STEP_DEADLINE_S:
+                                raise RuntimeError(f"batched beam search: step {i - 1} did not report within {_STEP_DEADLINE_S:.0f} s "
+                                                   f"(stream idle: {main.query()}; last library error: {lib.load().emoasr_last_error().decode()!r})")
+                    if mirror[1] >= S:
+                        break
+            ev1.record(main)
+            main.synchronize()
+        finally:
+            if gc_was_on:
+                gc.enable()
+        n_done = int(mirror[0])
+        stats = getattr(eng, "_beam_batch_stats", None)   # running totals for tools/joint_beam_bench.py
+        if stats is None:
+            stats = eng._beam_batch_stats = {"steps": 0, "loop_s": 0.0, "utts": 0, "calls": 0}
+        stats["steps"] += n_done; stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
+        host = Bf.pack.cpu().numpy()      # the one download
+    caller.wait_stream(bstream)
+    o = Bf.pack_off
+    rs = host[o[0]:o[1]].view(np.float64)
+    state = host[o[1]:o[2]].reshape(S, 4)
+    rstep, rpar = host[o[2]:o[3]], host[o[3]:o[4]]
+    hp, ht = host[o[4]:o[5]].reshape(Lmax, S, W), host[o[5]:o[6]].reshape(Lmax, S, W)
+    hyps, scores = [], []
+    for s in range(S):
+        results = []
+        for k in range(int(state[s, 2])):
+            toks, slot = [], int(rpar[s * W + k])
+            for p in range(int(rstep[s * W + k]) - 1, -1, -1):
+                toks.append(int(ht[p, s, slot]))
+                slot = int(hp[p, s, slot])
+            results.append((toks[::-1], float(rs[s * W + k])))
+        results = sorted(results, key=lambda r: r[1], reverse=True)
+        hyps.append([r[0] for r in results])
+        scores.append([r[1] for r in results])
+    return hyps, scores
+
+
+def joint_beam_search_device_batch(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
+    """joint_beam_search_device for every utterance of the batch: eouts [B, Tmax, d], utterance b over its own elens[b] >= 1
+    frames -> (hyps, scores, None, None) with hyps[b] / scores[b] what the single search returns for eouts[b:b+1, :elens[b]]
+    (hypotheses best first).  The batch is searched in chunks of at most batch_chunk_capacity searches."""
+    require_next_token_lm(lm, lm_weight)
+    eng = _engine_of(dec)
+    elens = [int(n) for n in elens]
+    B = eouts.shape[0]
+    if len(elens) != B or any(n < 1 for n in elens):
+        raise ValueError(f"joint_beam_search_device_batch: every utterance needs at least one frame, got elens {elens}")
+    use_ctc = decode_ctc_weight > 0
+    use_lm = lm is not None and lm_weight > 0
+    cw = min(dec.vocab_size, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if use_ctc else beam_width
+    assert 1 <= beam_width <= 32 and 1 <= cw <= 32, "device beam bookkeeping handles up to 32 beams x 32 candidates"
+    assert not use_lm or hasattr(lm, "predict_device"), "the batched search fuses the Transformer LM only"
+    esz = 2 if eouts.dtype == torch.bfloat16 else 4
+    lnl, ld = (lm.params.num_layers, lm.params.hidden_size) if use_lm else (0, 0)
+    cap = batch_chunk_capacity(beam_width, dec.max_decode_ylen + 1, eng.dnl, eng.dd, lnl, ld, esz)
+    hyps, scores = [], []
+    for b0 in range(0, B, cap):
+        n = elens[b0:b0 + cap]
+        h, s = _batch_search_chunk(dec, eng, eouts[b0:b0 + cap, :max(n)], n, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+        hyps += h
+        scores += s
+    return hyps, scores, None, None

@@ -30,6 +30,9 @@ class TransformerDecoder(nn.Module):
         self.blank_id = params.blank_id
         self.eos_id = params.eos_id
         self.max_decode_ylen = params.max_decode_ylen
+        # the joint search of ONE utterance: "single" (joint_beam_search) or "batch" (the batched device search with one search in it;
+        # DESIGN.md section 21).  Several utterances always take the batched search.
+        self.joint_beam_impl = "single"
         self._owner = None
 
     def forward(self, eouts, elens, eouts_inter=None, ys=None, ylens=None, ys_in=None, ys_out=None,
@@ -54,5 +57,16 @@ class TransformerDecoder(nn.Module):
         if decode_ctc_weight == 1:
             self.ctc._owner = self._owner
             return self.ctc.decode(eouts, elens, beam_width=1)
-        from ..beam_search import joint_beam_search
-        return joint_beam_search(self, eouts, elens, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+        from .. import beam_search as bs
+        if self.joint_beam_impl not in ("single", "batch"):
+            raise ValueError(f"joint_beam_impl {self.joint_beam_impl!r}: 'single' or 'batch'")
+        B = eouts.shape[0]
+        if B == 1 and self.joint_beam_impl == "single":
+            return bs.joint_beam_search(self, eouts, elens, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+        # a batch: N-best lists per utterance (one utterance through "batch": that utterance's lists, the single search's return shape)
+        hyps, scores, _, _ = bs.joint_beam_search_batch(self, eouts, elens, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+        if B == 1:
+            return hyps[0], scores[0], None, None
+        if beam_width == 1:   # what decode.test_step_batch expects of a greedy batch: one hypothesis (or none) per utterance
+            return [h[0] if h else [] for h in hyps], [s[0] if s else None for s in scores], None, None
+        return hyps, scores, None, None

@@ -1211,6 +1211,38 @@ def ctc_prefix_score(x, cands, last, out_len, blank, eos, prev_states=None, pare
     return log_psi, states
 
 
+def ctc_prefix_init_ragged(x, xoff, blank, out, stride):
+    """x f32 [sum T_s, V], xoff int32 [S + 1] (device): search s's initial state into out.view(-1)[s * stride:][: 2 T_s]"""
+    S = xoff.numel() - 1
+    lib.call("emoasr_ctc_prefix_init_ragged", S, x.shape[1], _p(_chk(x, torch.float32)), _p(xoff), blank, _p(out), stride, _stream())
+
+
+def ctc_prefix_score_ragged(x, xoff, W, Tmax, cands, last, out_len, blank, eos, prev_states, parent, pcand, log_psi=None, states=None):
+    """the ragged twin of ctc_prefix_score: row m of cands [nb, cw] belongs to search m // W, which runs over the rows
+    xoff[s] .. xoff[s + 1] - 1 of x; prev_states / states [nb, cw, Tmax, 2], parent the GLOBAL row -> (log_psi, states)"""
+    nb, cw = cands.shape
+    V = x.shape[1]
+    if log_psi is None:
+        log_psi = torch.empty(nb, cw, device=x.device, dtype=torch.float32)
+    if states is None:
+        states = torch.zeros(nb, cw, Tmax, 2, device=x.device, dtype=torch.float32)
+    lib.call("emoasr_ctc_prefix_score_ragged", nb, W, Tmax, V, cw, _p(_chk(x, torch.float32)), _p(xoff), _p(prev_states),
+             prev_states.shape[1], _p(parent), _p(pcand), _p(last), _p(out_len), _p(cands), blank, eos, _p(log_psi), _p(states),
+             _stream())
+    return log_psi, states
+
+
+def attn_step_group(q, kv, moff, W, H):
+    """single-query cross-attention of S searches of W hypotheses: q [S * W, dd], kv [sum T_s, 2 dd] (K | V) the searches' stacked
+    memories, moff int32 [S + 1] (device) -> out [S * W, dd]"""
+    nb, dd = q.shape
+    S = moff.numel() - 1
+    assert nb == S * W and kv.shape[1] == 2 * dd and kv.dtype == q.dtype and q.is_contiguous() and kv.is_contiguous()
+    out = torch.empty_like(q)
+    lib.call("emoasr_attn_step_group", dt(q), S, W, dd, H, _p(_chk(q)), _p(_chk(kv)), _p(moff), _p(out), _stream())
+    return out
+
+
 # ---- RNN-T -------------------------------------------------------------------------------------
 DACT_TANH_OUT = 5
 DACT_MUL = 6            # epilogue dact: multiply by the saved factor (ACT_SAVE_DACT forward)

@@ -1114,6 +1114,61 @@ int emoasr_joint_beam_step_parts(int dtype, const emoasr_joint_step_t* js, int p
 int emoasr_joint_beam_graph_build(int dtype, const emoasr_joint_step_t* js, int slot, int part, void* stream);
 int emoasr_joint_beam_graph_launch(int slot, int part, void* stream);
 
+/* ---- the joint search for S utterances at once (csrc/decode_batch.hip, csrc/decode_rt.hip).  A search is
+ * one utterance; S searches of width W occupy rows s * W .. s * W + W - 1 of every per-hypothesis array (nb = S * W rows) and
+ * all live searches are at the same output position.  A finished search keeps its rows: they are computed and ignored. */
+/* Single-query cross-attention of every search's W hypotheses against that search's own memory: q [S * W, dd], kv the
+ * projected memories stacked over the searches [sum T_s, 2 dd] (K in the first dd columns, V in the second), moff
+ * (device int32 [S + 1]) the first row of every search, out [S * W, dd].  1 <= W <= 32, dd / H in {32, 64, 128}, T_s >= 1.
+ * A row's result does not depend on S or on the other searches.  emoasr_group_offsets_check verifies a HOST copy of the
+ * offsets (rising, T_s >= 1) before they are uploaded. */
+int emoasr_attn_step_group(int dtype, int S, int W, int dd, int H, const void* q, const void* kv, const int* moff, void* out,
+                           void* stream);
+int emoasr_group_offsets_check(int S, const int* moff_host);
+/* emoasr_beam_update for S searches, one workgroup each: u's arrays hold nb = S * bw rows (vals / cands / psi / lm_at
+ * [nb, cw]), u.state is state[S], hist_parent / hist_token are [max_pos][S][bw], the results of search s are at s * bw.
+ * n_parent is a GLOBAL row (s * bw + parent); n_pcand, the history and res_parent are local to the search.  *pos is the shared
+ * output position: a one-thread launch after the S workgroups advances it once per live step, sets ctl[0] when every search
+ * has finished and writes u.host_mirror = {pos, finished searches} (payload first, position last).  A step replayed after
+ * ctl[0] is set, or at pos >= max_pos, changes nothing. */
+typedef struct emoasr_beam_update_batch {
+  emoasr_beam_update_t u;
+  int S, max_pos;
+  int* pos;
+  int* ctl;
+} emoasr_beam_update_batch_t;
+int emoasr_beam_update_batch(const emoasr_beam_update_batch_t* b, void* stream);
+/* The ragged twins of emoasr_ctc_prefix_init / emoasr_ctc_prefix_score: x the stacked emissions [sum T_s, V], xoff (device
+ * int32 [S + 1]); row m belongs to search m / W and runs over that search's T_s frames; states [nb, cw, Tmax, 2].  The init
+ * writes search s's initial state to r + s * r_stride. */
+int emoasr_ctc_prefix_init_ragged(int S, int V, const float* x, const int* xoff, int blank, float* r, long r_stride, void* stream);
+int emoasr_ctc_prefix_score_ragged(int nb, int W, int Tmax, int V, int cw, const float* x, const int* xoff,
+                                   const float* prev_states, int cw_prev, const int* parent, const int* pcand, const int* last,
+                                   const int* out_len, const int* cands, int blank, int eos, float* log_psi, float* states,
+                                   void* stream);
+/* The launch chain of emoasr_transformer_decoder_step on nb = S * W rows with emoasr_attn_step_group in place of the
+ * cross-attention: d.kv[l] is layer l's STACKED memory projection [sum T_s, 2 dd]; d.T and d.kmem are not read. */
+typedef struct emoasr_decoder_step_group {
+  emoasr_decoder_step_t d;
+  int S, W;
+  const int* moff;
+} emoasr_decoder_step_group_t;
+size_t emoasr_decode_step_group_ws_bytes(int dtype, int nb, int d, int H, int F, int V);
+int emoasr_transformer_decoder_step_group(int dtype, int nl, const emoasr_decoder_layer_t* layers,
+                                          const emoasr_decoder_step_group_t* io, void* stream);
+/* One output step of all S searches as a linear chain on one stream: cache gathers, decoder step, LM step
+ * (emoasr_bert_lm_step on nb rows), emoasr_beam_scores_topk, the ragged CTC scorer (xoff = dec.moff), the batched update. */
+typedef struct emoasr_joint_batch_step {
+  int dec_nl; const emoasr_decoder_layer_t* dec_layers; emoasr_decoder_step_group_t dec;
+  int lm_nl; const emoasr_bert_layer_t* lm_layers; emoasr_bert_step_t lm;
+  const void *dec_k_prev, *dec_v_prev, *lm_k_prev, *lm_v_prev;
+  const int* parent;
+  const float* ctc_x; int Tmax; int blank;
+  const float* states_prev; float* states_cur;
+  emoasr_beam_update_batch_t upd;
+} emoasr_joint_batch_step_t;
+int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream);
+
 /* ---- optimizer (asr/train_asr.py:84-92, torch.optim.Adam semantics) ---------- */
 /* out[0] += sum x^2 */
 int emoasr_sqnorm(long n, const float* x, float* out, void* stream);
