@@ -44,9 +44,11 @@ def test_step_batch(model, data, beam_width, len_weight, decode_ctc_weight, deco
     hyps, scores, _, _ = model.decode(data["xs"].to(device), data["xlens"], beam_width, len_weight, lm=lm,
                                       lm_weight=lm_weight, decode_ctc_weight=decode_ctc_weight, decode_phone=decode_phone)
     reftexts = data["ptexts"] if decode_phone else data["texts"]
+    # (the LAS decoder returns N-best lists at beam width 1 too, except through its CTC greedy route)
+    lists = beam_width > 1 or (decode_ctc_weight != 1 and getattr(getattr(model, "decoder", None), "batch_nbest_lists", False))
     out = []
     for b, utt_id in enumerate(data["utt_ids"]):
-        if beam_width > 1:
+        if lists:
             out.append((utt_id, hyps[b], None if scores is None else scores[b], reftexts[b]))
         else:   # greedy: one hypothesis per utterance
             out.append((utt_id, [hyps[b]], None if scores is None else [scores[b]], reftexts[b]))

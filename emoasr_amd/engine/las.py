@@ -5,11 +5,77 @@ context).  Per position: one recurrent product of [ctx | h] against [W_ih[:, E:]
 residual, the cell kernel, the query projection, the attention step (csrc/las.hip).  Hoisted: the embedding gather and its input
 product, the key projection, LSTM layers 1.. as whole-sequence layers (recurrence.py), intermed + tanh and the vocabulary head.
 Time-major throughout; the logits are transposed to [B, L, V] at the end."""
+import ctypes
+import gc
+
 import torch
 
-from .. import ops
+from .. import lib, ops
 from ..recurrence import lstm_stack_bwd, lstm_stack_fwd
 from .arena import _Stash, _cfg, h2d_i32, h2d_pack
+
+
+LAS_BEAM_MAX_ROWS = 1024            # S * W rows of one chunk of the batched search
+LAS_BEAM_POOL_BUDGET_BYTES = 2 << 30    # the two attention-weight pools of one chunk
+
+
+def las_beam_pool_bytes(nb, Tmax):
+    """bytes of the attention-weight pools of nb rows: two halves (source / destination of a step), Tmax f32 per row"""
+    return 2 * nb * Tmax * 4
+
+
+def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None):
+    """S_max: the most searches of width W one chunk of las_beam_search_batch holds -- S_max * W <= LAS_BEAM_MAX_ROWS rows and
+    las_beam_pool_bytes(S_max * W, Tmax) <= LAS_BEAM_POOL_BUDGET_BYTES; never below one search"""
+    budget = LAS_BEAM_POOL_BUDGET_BYTES if budget is None else budget
+    max_rows = LAS_BEAM_MAX_ROWS if max_rows is None else max_rows
+    return max(1, min(max_rows // W, budget // las_beam_pool_bytes(W, Tmax)))
+
+
+class _LasBeamBuffers:
+    """device buffers of one (S, W, max_len, frame capacities) configuration of the batched search, reused across calls: the
+    captured steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`, laid out
+    as modeling/beam_search_device.py:batch_pack_sizes)."""
+
+    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, pack_sizes):
+        nb = S * W
+        self.rows_cap, self.Tcap = rows_cap, Tcap
+        i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
+        f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        cdt = lambda *s: torch.zeros(*s, device=dev, dtype=dt)
+        self.pack = i32(sum(pack_sizes))
+        o = [0]
+        for v in pack_sizes:
+            o.append(o[-1] + v)
+        self.pack_off = o
+        part = lambda k: self.pack[o[k]:o[k + 1]]
+        self.res_score = part(0).view(torch.float64)
+        self.state, self.res_step, self.res_parent = part(1).view(S, 4), part(2), part(3)
+        self.hist_parent, self.hist_token = part(4).view(Lmax, nb), part(5).view(Lmax, nb)
+        self.pos, self.ctl = i32(1), i32(1)
+        self.ids, self.parent, self.pcand = i32(nb), i32(nb), i32(nb)
+        self.last, self.outlen, self.klens = i32(nb), i32(nb), i32(nb)
+        self.score = torch.zeros(nb, device=dev, dtype=torch.float64)
+        self.score_ctc = f32(nb)
+        self.vals, self.cands = f32(nb, W), i32(nb, W)
+        self.moff = i32(S + 1)
+        self.pk, self.eo = cdt(rows_cap, AD), cdt(rows_cap, D)
+        nu = max(NL - 1, 1)
+        self.pools = []
+        for _ in range(2):   # take turns as source and destination of a step
+            P = _Stash()
+            P.xc, P.c0 = cdt(nb, D + H), f32(nb, H)
+            P.hu, P.cu = cdt(nu, nb, H), f32(nu, nb, H)
+            P.aw = f32(nb, Tcap)
+            self.pools.append(P)
+        # the parents' rows of the small state arrays, gathered for the step (emoasr_las_state_gather)
+        self.g_xc, self.g_c0, self.g_hu, self.g_cu = cdt(nb, D + H), f32(nb, H), cdt(nu, nb, H), f32(nu, nb, H)
+        self.gact = cdt(nb, 4 * H)
+        self.scores = f32(nb, Tcap)
+        self.wcat = cdt(4 * H, D + H)
+        self.bias = f32(NL, 4 * H)
+        self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
+        self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured steps point at)
 
 
 class LASDecoder:
@@ -280,3 +346,168 @@ class LASDecoder:
                 beams = extend
             results = sorted(results, key=lambda x: x["score"], reverse=True)
             return [r["hyp"] for r in results], [r["score"] for r in results]
+
+    # ------------------------------------------------------------------ the same search for S utterances at once
+    def _las_batch_step(self, Bf, k, S, W, D, gather, upd):
+        """one token for all S * W rows: pool k is the source, pool 1 - k the destination.  A linear chain of launches on the
+        current stream, no host round trip: the state gather, the networks on the existing operators, the grouped attention,
+        log-softmax + top-W and the batched bookkeeping (emoasr_beam_update_batch, which writes the next step's ids / parents)."""
+        A, E, H, NL, I = self.arena, self.l_E, self.l_H, self.l_nl, self.l_I
+        nb = S * W
+        src, dst = Bf.pools[k], Bf.pools[1 - k]
+        lib.call("emoasr_las_state_gather", ctypes.byref(gather[k]), ops._stream())
+        emb = ops.embed_fwd(Bf.ids.view(nb, 1), A.w("decoder.embed.weight"), None, 1.0).view(nb, E)
+        gates = ops.gemm_nt(emb, A.w("decoder.rnns.0.weight_ih")[:, :E], bias=Bf.bias[0])
+        gates = ops.gemm_nt(Bf.g_xc, Bf.wcat, residual=gates, res_scale=1.0)
+        h = dst.xc[:, D:]
+        ops.lstm_cell_fwd(gates, Bf.g_c0, h, dst.c0, Bf.gact)
+        pq = ops.gemm_nt(h, A.w("decoder.score.w_query.weight"), bias=A.p("decoder.score.w_query.bias"))
+        ops.las_attend_group(self._las_weights(), Bf.pk, Bf.eo, Bf.moff, pq, src.aw, Bf.parent, Bf.state, W, dst.aw, dst.xc[:, :D],
+                             Bf.scores)
+        x = h
+        for l in range(1, NL):
+            name = f"decoder.rnns.{l}"
+            g = ops.gemm_nt(x, A.w(name + ".weight_ih"), bias=Bf.bias[l])
+            g = ops.gemm_nt(Bf.g_hu[l - 1], A.w(name + ".weight_hh"), residual=g, res_scale=1.0)
+            ops.lstm_cell_fwd(g, Bf.g_cu[l - 1], dst.hu[l - 1], dst.cu[l - 1], Bf.gact)
+            x = dst.hu[l - 1]
+        w_i = A.w("decoder.intermed.weight")
+        e = ops.gemm_nt(dst.xc[:, :D], w_i[:, :D], bias=A.p("decoder.intermed.bias"))
+        g = ops.gemm_nt(x, w_i[:, D:])
+        hgen = ops.joint_tanh(e.view(nb, 1, I), g.view(nb, 1, I)).view(nb, I)
+        logits = ops.gemm_nt(hgen, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"), out_f32=True)
+        logp = ops.log_softmax(logits)
+        V = logp.shape[1]
+        lib.call("emoasr_topk", nb, V, W, ops._p(logp), V, None, 0, ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
+        lib.call("emoasr_beam_update_batch", ctypes.byref(upd), ops._stream())
+
+    def _las_beam_chunk(self, eouts, elens, W, len_weight, eos, max_len):
+        """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable)"""
+        from ..modeling import beam_search_device as bsd   # (imports this package: resolved at call time)
+        A, E, H, NL, AD = self.arena, self.l_E, self.l_H, self.l_nl, self.l_A
+        dev, dt = eouts.device, self.dtype
+        S, D = len(elens), eouts.shape[2]
+        nb = S * W
+        V = A.p("decoder.output.bias").numel()
+        bstream = getattr(self, "_beam_stream", None)   # its own stream: the legacy default stream cannot be captured
+        if bstream is None:
+            bstream = self._beam_stream = torch.cuda.Stream(device=dev)
+        caller = torch.cuda.current_stream()
+        bstream.wait_stream(caller)
+        with torch.no_grad(), torch.cuda.stream(bstream), self._scope():
+            moff, offs = ops.las_group_offsets(elens, dev)
+            total, longest = offs[-1], max(elens)
+            rows_cap = (total + 1023) // 1024 * 1024
+            Tcap = (longest + 63) // 64 * 64
+            key = (str(dev), dt, S, W, max_len, V, E, H, NL, D, AD)
+            cache = getattr(self, "_las_beam_bufs", None)
+            if cache is not None and cache[0] == key and cache[1].rows_cap >= rows_cap and cache[1].Tcap >= Tcap:
+                Bf = cache[1]
+            else:
+                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, bsd.batch_pack_sizes(S, W, max_len))
+                self._las_beam_bufs = (key, Bf)
+            # ---- this call's inputs, into the buffers the captured steps read ----
+            Bf.moff.copy_(moff)
+            mem = torch.cat([eouts[b, :elens[b]] for b in range(S)], 0).to(dt) if S > 1 else eouts[0, :elens[0]].to(dt).contiguous()
+            Bf.eo[:total].copy_(mem)
+            # the key projection: ONE product over all stacked frames
+            ops.gemm_nt(mem, A.w("decoder.score.w_key.weight"), bias=A.p("decoder.score.w_key.bias"), out=Bf.pk[:total])
+            Bf.wcat.copy_(torch.cat([A.w("decoder.rnns.0.weight_ih")[:, E:], A.w("decoder.rnns.0.weight_hh")], dim=1))
+            for l in range(NL):
+                Bf.bias[l].copy_(self._las_bias(l))
+
+            def reset(done):
+                Bf.state.copy_(h2d_i32([[0, 1, 0, done]] * S, dev))
+                Bf.pos.zero_(); Bf.ctl.fill_(done)
+                Bf.ids.fill_(eos); Bf.last.fill_(eos)
+                Bf.parent.copy_(torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(W) * W)
+                Bf.pcand.zero_(); Bf.outlen.zero_(); Bf.klens.fill_(1)
+                Bf.score.zero_(); Bf.score_ctc.zero_()
+                P = Bf.pools[0]   # step 0 reads its parents' rows here: zeros, so the general step is the first step too
+                P.xc.zero_(); P.c0.zero_(); P.hu.zero_(); P.cu.zero_(); P.aw.zero_()
+
+            gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), float(len_weight), eos, id(Bf), ops.dt(Bf.pk))
+            if Bf.graphs is None or Bf.graphs[0] != gkey:
+                ub = lib.BeamUpdateBatch()
+                ub.S, ub.max_pos, ub.pos, ub.ctl = S, max_len, Bf.pos.data_ptr(), Bf.ctl.data_ptr()
+                u = ub.u
+                u.bw, u.cw, u.eos = W, W, eos                  # attention only: psi and lm_at stay NULL
+                u.one_minus_lam, u.lam, u.mu, u.len_weight = 1.0, 0.0, 0.0, float(len_weight)
+                u.vals, u.cands = Bf.vals.data_ptr(), Bf.cands.data_ptr()
+                u.score, u.score_ctc = Bf.score.data_ptr(), Bf.score_ctc.data_ptr()
+                u.n_ids, u.n_parent, u.n_pcand = Bf.ids.data_ptr(), Bf.parent.data_ptr(), Bf.pcand.data_ptr()
+                u.n_last, u.n_outlen, u.n_klens = Bf.last.data_ptr(), Bf.outlen.data_ptr(), Bf.klens.data_ptr()
+                u.hist_parent, u.hist_token = Bf.hist_parent.data_ptr(), Bf.hist_token.data_ptr()
+                u.res_score, u.res_step, u.res_parent = Bf.res_score.data_ptr(), Bf.res_step.data_ptr(), Bf.res_parent.data_ptr()
+                u.state = Bf.state.data_ptr()
+                u.host_mirror = Bf.mirror_host.data_ptr()      # pinned: the tail kernel writes it, the host polls it
+                gather = []
+                for k in (0, 1):
+                    P = Bf.pools[k]
+                    pairs = [(P.xc, Bf.g_xc), (P.c0, Bf.g_c0)]
+                    for l in range(NL - 1):
+                        pairs += [(P.hu[l], Bf.g_hu[l]), (P.cu[l], Bf.g_cu[l])]
+                    gather.append(ops.las_state_gather_args(pairs, Bf.parent, Bf.state, W))
+                # warm-up with every search marked finished (the new kernels and the bookkeeping return at once, the networks
+                # run on the rows as they are): every kernel's lazy one-time setup happens outside the capture.  Then each
+                # step is captured once: a linear chain on one stream.
+                reset(1)
+                for k in (0, 1):
+                    self._las_batch_step(Bf, k, S, W, D, gather, ub)
+                torch.cuda.current_stream().synchronize()
+                graphs = []
+                for k in (0, 1):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
+                        self._las_batch_step(Bf, k, S, W, D, gather, ub)
+                    graphs.append(g)
+                Bf.graphs = (gkey, graphs, (ub, gather))
+            graphs = Bf.graphs[1]
+            reset(0)
+            mirror = Bf.mirror_host.numpy()
+            mirror[:] = (0, 0)
+            main = torch.cuda.current_stream()
+            main.synchronize()     # (the mirror is host memory: the reset above must not race the first step's store)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record(main)
+            gc_was_on = gc.isenabled()
+            gc.disable()           # (a collection in the middle of the loop stalls a step for milliseconds)
+            try:
+                # steps are issued one ahead of the mirror they depend on: a step replayed after the end changes nothing
+                for i in range(max_len):
+                    graphs[i & 1].replay()
+                    if i >= 1 and bsd.batch_step_reported(mirror, i, S, main):
+                        break
+                ev1.record(main)
+                main.synchronize()
+            finally:
+                if gc_was_on:
+                    gc.enable()
+            stats = getattr(self, "_las_beam_stats", None)   # running totals for tools/las_beam_bench.py
+            if stats is None:
+                stats = self._las_beam_stats = {"steps": 0, "loop_s": 0.0, "utts": 0, "calls": 0}
+            stats["steps"] += int(mirror[0]); stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
+            host = Bf.pack.cpu().numpy()      # the one download
+        caller.wait_stream(bstream)
+        return bsd.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len)
+
+    def las_beam_search_batch(self, eouts, elens, beam_width, len_weight, eos, max_len):
+        """las_beam_search for every utterance of the batch: eouts [B, Tmax, D], utterance b over its own
+        elens[b] >= 1 frames (frames past them are never read) -> (hyps, scores) with hyps[b] / scores[b] what las_beam_search
+        returns for eouts[b:b+1, :elens[b]].  All searches of a chunk step in lockstep on the device: per step one captured chain
+        of launches, no host round trip, one download at the end.  Chunks hold at most las_beam_chunk_capacity searches."""
+        W = int(beam_width)
+        elens = [int(n) for n in elens]
+        B, T = eouts.shape[0], eouts.shape[1]
+        if len(elens) != B or any(n < 1 or n > T for n in elens):
+            raise ValueError(f"las_beam_search_batch: every utterance needs 1 <= elens[b] <= {T} frames, got elens {elens}")
+        V = self.arena.p("decoder.output.bias").numel()
+        assert 1 <= W <= 32 and W <= V, "the batched LAS search handles beams of 1..32 hypotheses, at most the vocabulary"
+        cap = las_beam_chunk_capacity(W, (max(elens) + 63) // 64 * 64)
+        hyps, scores = [], []
+        for b0 in range(0, B, cap):
+            n = elens[b0:b0 + cap]
+            h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len)
+            hyps += h
+            scores += s
+        return hyps, scores

@@ -213,6 +213,26 @@ class LasAttend(Structure):
                 ("dw_score", c_void_p), ("dw_conv", c_void_p), ("db_conv", c_void_p), ("dfilt", c_void_p)]
 
 
+class LasAttendGroup(Structure):
+    _fields_ = [("S", c_int), ("W", c_int), ("A", c_int), ("D", c_int), ("Tmax", c_int), ("rows", c_int),
+                ("pk", c_void_p), ("eouts", c_void_p), ("moff", c_void_p), ("pq", c_void_p), ("aw_src", c_void_p),
+                ("parent", c_void_p), ("state", c_void_p),
+                ("filt", c_void_p), ("w_conv", c_void_p), ("b_conv", c_void_p), ("w_score", c_void_p),
+                ("scores", c_void_p), ("aw_dst", c_void_p), ("ctx", c_void_p), ("ctx_ld", c_long)]
+
+
+LAS_GATHER_MAX = 16
+
+
+class LasGatherItem(Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_bytes", c_long)]
+
+
+class LasStateGather(Structure):
+    _fields_ = [("S", c_int), ("W", c_int), ("n", c_int), ("parent", c_void_p), ("state", c_void_p),
+                ("item", LasGatherItem * LAS_GATHER_MAX)]
+
+
 P, I, L, F, U64 = c_void_p, c_int, c_long, c_float, c_uint64
 
 # name -> argtypes (every function returns int status); mirrors include/emoasr_hip.h
@@ -302,6 +322,8 @@ SIGNATURES = {
     "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],
     "emoasr_las_attend_bwd": [I, POINTER(LasAttend), P],
     "emoasr_las_dropmask": [POINTER(LasAttend), P, P],
+    "emoasr_las_attend_group": [I, POINTER(LasAttendGroup), P],
+    "emoasr_las_state_gather": [POINTER(LasStateGather), P],
     "emoasr_mlm_expand": [I, I, I, P, P, P, I, I, I, I, P, P, P, P, P],
     "emoasr_sample_rows": [I, I, I, P, L, P, P, U64, L, P, P, P, P],
     "emoasr_gumbel_noise": [I, I, U64, L, P, L, P],

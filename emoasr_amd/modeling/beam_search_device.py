@@ -357,7 +357,7 @@ class _BatchBuffers:
         i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         # pack: res_score (double [nb]) | state [S, 4] | res_step [nb] | res_parent [nb] | hist_parent [Lmax, nb] | hist_token [Lmax, nb]
-        n = [2 * nb, 4 * S, nb, nb, Lmax * nb, Lmax * nb]
+        n = batch_pack_sizes(S, W, Lmax)
         self.pack = i32(sum(n))
         o = [0]
         for v in n:
@@ -545,19 +545,8 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             # steps are issued one ahead of the mirror they depend on: a step replayed after the end changes nothing
             for i in range(max_steps):
                 graphs[i & 1].replay()
-                if i >= 1:
-                    spins, t_wait = 0, None
-                    while mirror[0] < i and mirror[1] < S:
-                        _yield()
-                        spins += 1
-                        if spins & 0xFFF == 0:   # a lost launch / a faulted device must surface, not spin forever
-                            now = time.perf_counter()
-                            t_wait = now if t_wait is None else t_wait
-                            if now - t_wait > _STEP_DEADLINE_S:
-                                raise RuntimeError(f"batched beam search: step {i - 1} did not report within {_STEP_DEADLINE_S:.0f} s "
-                                                   f"(stream idle: {main.query()}; last library error: {lib.load().emoasr_last_error().decode()!r})")
-                    if mirror[1] >= S:
-                        break
+                if i >= 1 and batch_step_reported(mirror, i, S, main):
+                    break
             ev1.record(main)
             main.synchronize()
         finally:
@@ -570,7 +559,35 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
         stats["steps"] += n_done; stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
         host = Bf.pack.cpu().numpy()      # the one download
     caller.wait_stream(bstream)
-    o = Bf.pack_off
+    return batch_nbest_from_pack(host, Bf.pack_off, S, W, Lmax)
+
+
+def batch_pack_sizes(S, W, Lmax):
+    """int32 words of the parts of the ONE allocation the host reads back after a batched search: res_score (double [nb]) |
+    state [S, 4] | res_step [nb] | res_parent [nb] | hist_parent [Lmax, nb] | hist_token [Lmax, nb]"""
+    nb = S * W
+    return [2 * nb, 4 * S, nb, nb, Lmax * nb, Lmax * nb]
+
+
+def batch_step_reported(mirror, i, S, main):
+    """wait until emoasr_beam_update_batch's pinned mirror {position, finished searches} shows step i - 1 -> whether every search
+    has finished"""
+    spins, t_wait = 0, None
+    while mirror[0] < i and mirror[1] < S:
+        _yield()
+        spins += 1
+        if spins & 0xFFF == 0:   # a lost launch / a faulted device must surface, not spin forever
+            now = time.perf_counter()
+            t_wait = now if t_wait is None else t_wait
+            if now - t_wait > _STEP_DEADLINE_S:
+                raise RuntimeError(f"batched beam search: step {i - 1} did not report within {_STEP_DEADLINE_S:.0f} s "
+                                   f"(stream idle: {main.query()}; last library error: {lib.load().emoasr_last_error().decode()!r})")
+    return mirror[1] >= S
+
+
+def batch_nbest_from_pack(host, o, S, W, Lmax):
+    """the downloaded pack (batch_pack_sizes; o: the parts' offsets) -> (hyps[s], scores[s]): the token sequences rebuilt from
+    the (parent, token) history, each search's results sorted by score (stable)"""
     rs = host[o[0]:o[1]].view(np.float64)
     state = host[o[1]:o[2]].reshape(S, 4)
     rstep, rpar = host[o[2]:o[3]], host[o[3]:o[4]]

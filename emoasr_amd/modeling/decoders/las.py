@@ -9,16 +9,20 @@ The sub-modules carry the reference's names (nn.LSTMCell `rnns`, `score.w_key / 
 csrc/las.hip.  As in the reference, the attention weights are dropped with p = 0.1 in train mode -- AttentionLoc's constructor
 default, which LASDecoder never overrides and no config field reaches (`decoder.score.dropout_attn_rate` is the attribute).
 
-decode(): `decode_ctc_weight == 1` is CTC greedy; otherwise batch size 1 and the reference's beam search (las.py:176-287).  The
+decode(): `decode_ctc_weight == 1` is CTC greedy; otherwise the reference's beam search (las.py:176-287).  The
 reference's `lm`, `lm_weight` and intermediate `decode_ctc_weight` branches are `pass`: the arguments are accepted and their values
 ignored here too (as RNNTDecoder does with its LM arguments).  A search that never emits <eos> returns ([], [], None, None).
+The reference takes one utterance; here a batch of several returns (hyps[b], scores[b], None, None), utterance b searched over its
+own elens[b] frames -- N-best lists at every beam width, beam 1 included (one-element lists; [] / [] for a search that never
+ends).  `las_beam_impl`: "single" searches one utterance with the host bookkeeping (engine/las.py:las_beam_search) and a batch
+with the lockstep device search (las_beam_search_batch); "batch" sends one utterance there too.
 
 Supported sizes (16-byte accesses): embedding_size, enc_hidden_size, dec_hidden_size, attn_dim and dec_intermediate_size are
 multiples of 8, attn_dim <= 512 (one 8-channel group per lane of the attention kernel); batch and lengths are free.
 """
 import torch.nn as nn
 
-from ..functions import las_beam_apply, las_decoder_apply
+from ..functions import las_beam_apply, las_beam_batch_apply, las_decoder_apply
 from .ctc import CTCDecoder
 
 LAS_FIELDS = ("vocab_size", "embedding_size", "enc_hidden_size", "dec_hidden_size", "dec_num_layers", "attn_dim",
@@ -46,6 +50,8 @@ class AttentionLoc(nn.Module):
 
 
 class LASDecoder(nn.Module):
+    batch_nbest_lists = True   # decode() of a batch returns a LIST of hypotheses per utterance at beam width 1 too (decode.py)
+
     def __init__(self, params, phase="train"):
         super().__init__()
         for f in LAS_FIELDS:
@@ -78,6 +84,7 @@ class LASDecoder(nn.Module):
         self.blank_id = getattr(params, "blank_id", 0)
         self.eos_id = params.eos_id
         self.max_decode_ylen = params.max_decode_ylen
+        self.las_beam_impl = "single"   # "batch": one utterance goes through the batched device search too
         self._owner = None
 
     def forward(self, eouts, elens, eouts_inter=None, ys=None, ylens=None, ys_in=None, ys_out=None, soft_labels=None,
@@ -96,6 +103,12 @@ class LASDecoder(nn.Module):
         if decode_ctc_weight == 1:
             self.ctc._owner = self._owner
             return self.ctc.decode(eouts, elens, beam_width=1)
-        assert eouts.size(0) == 1   # las.py:196
-        hyps, scores = las_beam_apply(self, eouts, beam_width, len_weight)
+        if self.las_beam_impl not in ("single", "batch"):
+            raise ValueError(f"las_beam_impl {self.las_beam_impl!r}: 'single' or 'batch'")
+        if eouts.size(0) == 1 and self.las_beam_impl == "single":   # las.py:196: the reference's one utterance, all its frames
+            hyps, scores = las_beam_apply(self, eouts, beam_width, len_weight)
+            return hyps, scores, None, None
+        hyps, scores = las_beam_batch_apply(self, eouts, elens, beam_width, len_weight)
+        if eouts.size(0) == 1:   # one utterance through "batch": the single search's return shape
+            return hyps[0], scores[0], None, None
         return hyps, scores, None, None

@@ -406,6 +406,28 @@ def las_beam_apply(dec, eouts, beam_width, len_weight):
     return _engine_of(dec).las_beam_search(eouts, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
 
 
+LAS_BATCH_MAX_BEAM = 32   # rows of a search in csrc/las_beam.hip and in emoasr_beam_update_batch
+
+
+def las_beam_batch_apply(dec, eouts, elens, beam_width, len_weight, batched=True):
+    """LASDecoder.decode's beam search for every utterance of the batch, utterance b over its own elens[b] frames
+    -> (hyps[b], scores[b]).  batched: all utterances in lockstep on the device (engine/las.py:las_beam_search_batch); beams wider
+    than 32 or than the vocabulary, and batched=False, run las_beam_search once per utterance."""
+    eng = _engine_of(dec)
+    elens = [int(n) for n in elens]
+    B, T = eouts.shape[0], eouts.shape[1]
+    if len(elens) != B or any(n < 1 or n > T for n in elens):
+        raise ValueError(f"LASDecoder.decode: every utterance needs 1 <= elens[b] <= {T} frames, got elens {elens}")
+    if batched and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
+        return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+    hyps, scores = [], []
+    for b in range(B):
+        h, s = eng.las_beam_search(eouts[b:b + 1, :elens[b]], beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+        hyps.append(h)
+        scores.append(s)
+    return hyps, scores
+
+
 class _CMLMDecoderFn(torch.autograd.Function):
     """the conditional masked LM decoder (decoders/transformer.py:102-105,127-128): bidirectional self-attention over ylens keys,
     MaskedLMLoss on the labelled rows"""

@@ -1692,6 +1692,72 @@ def las_attend_bwd(W, pk, pq, aw_prev, eouts, elens, drop_p, seed, step, aw, ctx
     lib.call("emoasr_las_attend_bwd", dt(pq), byref(a), _stream())
 
 
+def las_group_offsets(elens, device):
+    """frame counts of S searches -> (moff int32 [S + 1] on the device, the host list): the row offsets of their stacked frames,
+    checked on the host (rising, T_s >= 1: emoasr_group_offsets_check) before the upload"""
+    offs = [0]
+    for n in elens:
+        offs.append(offs[-1] + int(n))
+    S = len(offs) - 1
+    lib.call("emoasr_group_offsets_check", S, (ctypes.c_int * (S + 1))(*offs))
+    t = torch.tensor(offs, dtype=torch.int32)
+    return t.pin_memory().to(device, non_blocking=True), offs
+
+
+def _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores):
+    nb, A = pq.shape
+    S = moff.numel() - 1
+    rows, D = eouts.shape
+    Tmax = aw_src.shape[1]
+    assert nb == S * width and A == W.A and pk.shape == (rows, A) and pk.dtype == pq.dtype == eouts.dtype == ctx.dtype
+    assert pq.is_contiguous() and pk.is_contiguous() and eouts.is_contiguous()
+    for t in (aw_src, aw_dst, scores):
+        assert _chk(t, torch.float32).is_contiguous() and t.shape == (nb, Tmax)
+    assert _chk(parent, torch.int32).numel() == nb and _chk(moff, torch.int32).is_contiguous()
+    assert _chk(state, torch.int32).is_contiguous() and state.numel() == 4 * S
+    assert ctx.shape == (nb, D) and ctx.stride(1) == 1
+    a = lib.LasAttendGroup()
+    a.S, a.W, a.A, a.D, a.Tmax, a.rows = S, width, A, D, Tmax, rows
+    a.pk, a.eouts, a.moff, a.pq = _chk(pk).data_ptr(), _chk(eouts).data_ptr(), moff.data_ptr(), _chk(pq).data_ptr()
+    a.aw_src, a.parent, a.state = aw_src.data_ptr(), parent.data_ptr(), state.data_ptr()
+    a.filt, a.w_conv, a.b_conv, a.w_score = W.filt.data_ptr(), W.w_conv.data_ptr(), W.b_conv.data_ptr(), W.w_score.data_ptr()
+    a.scores, a.aw_dst, a.ctx, a.ctx_ld = scores.data_ptr(), aw_dst.data_ptr(), ctx.data_ptr(), ctx.stride(0)
+    return a
+
+
+def las_attend_group(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores):
+    """one position of the location-aware attention for S searches of `width` rows (include/emoasr_hip.h:
+    emoasr_las_attend_group_t): pk [sum T_s, A] / eouts [sum T_s, D] stacked over the searches, moff int32 [S + 1] (device,
+    las_group_offsets), pq [S * width, A], aw_src f32 [S * width, Tmax] read at the PARENT's row (parent int32, global rows),
+    state int32 [S, 4] of emoasr_beam_update_batch; writes aw_dst, ctx (a view with a row stride is written in place) and the
+    scratch `scores` -- for the live rows only"""
+    a = _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores)
+    lib.call("emoasr_las_attend_group", dt(pq), byref(a), _stream())
+
+
+def las_state_gather_args(pairs, parent, state, width):
+    """the pointer table of las_state_gather: pairs of (src, dst) arrays [S * width, ...] with contiguous rows"""
+    S = state.numel() // 4
+    g = lib.LasStateGather()
+    g.S, g.W, g.n = S, width, len(pairs)
+    assert _chk(parent, torch.int32).numel() == S * width and _chk(state, torch.int32).is_contiguous()
+    g.parent, g.state = parent.data_ptr(), state.data_ptr()
+    if len(pairs) > lib.LAS_GATHER_MAX:
+        raise lib.EmoasrHipError(f"las_state_gather: {len(pairs)} arrays (1..{lib.LAS_GATHER_MAX})")
+    for k, (src, dst) in enumerate(pairs):
+        assert _chk(src).shape == _chk(dst).shape and src.dtype == dst.dtype and src.shape[0] == S * width
+        assert src.is_contiguous() and dst.is_contiguous()
+        g.item[k].src, g.item[k].dst = src.data_ptr(), dst.data_ptr()
+        g.item[k].row_bytes = src[0].numel() * src.element_size()
+    return g
+
+
+def las_state_gather(pairs, parent, state, width):
+    """dst[r] = src[parent[r]] for every live row r of every (src, dst) pair, ONE launch (exact copies; dead rows untouched)"""
+    g = las_state_gather_args(pairs, parent, state, width)
+    lib.call("emoasr_las_state_gather", byref(g), _stream())
+
+
 def las_dropmask(B, T, drop_p, seed, step, device="cuda"):
     """the keep mask las_attend_fwd / _bwd derive at (seed, step): uint8 [B,T], 1 = kept (for tests)"""
     a = lib.LasAttend()

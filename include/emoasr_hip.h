@@ -1169,6 +1169,46 @@ typedef struct emoasr_joint_batch_step {
 } emoasr_joint_batch_step_t;
 int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream);
 
+/* ---- the LAS beam search for S utterances at once (csrc/las_beam.hip).  Rows as above: search s owns
+ * rows s * W .. s * W + W - 1; `state` is the array emoasr_beam_update_batch keeps, `parent` its n_parent (GLOBAL rows).  A row at
+ * or past its search's n_alive, and every row of a search that is done, is SKIPPED: nothing of it is read (its parent may hold
+ * anything) and nothing is written for it.  A live row whose parent lies outside its own search is read from the search's row 0. */
+/* One decoder position of the location-aware attention (emoasr_las_attend_fwd's arithmetic with drop_p = 0) for all rows:
+ * pk [sum T_s, A] / eouts [sum T_s, D] the searches' stacked key projections / encoder frames (once per utterance), moff (device
+ * int32 [S + 1]) their first rows, pq [S * W, A]; aw_src / aw_dst f32 [S * W, Tmax] the previous weights (read at the PARENT's row,
+ * frames 0 .. T_s - 1) and the new ones (written at the row's own), scores f32 [S * W, Tmax] scratch, ctx rows of stride ctx_ld.
+ * Tmax >= every T_s.  Score pass: one workgroup per (32-frame tile of a search, search) -- the filter and the tile of pk are fetched
+ * once for all live rows; context pass: one workgroup per (64 context columns, search) -- every eouts tile is fetched once for the
+ * W rows.  Tiles count from the search's own first frame: a row's bits do not depend on S or on the other searches.
+ * 1 <= W <= 32, A % 8 == 0, A <= 512, D % 8 == 0, ctx_ld % 8 == 0. */
+typedef struct emoasr_las_attend_group {
+  int S, W, A, D, Tmax;
+  int rows;                      /* sum T_s: a search whose frames do not lie inside [0, rows) or exceed Tmax is skipped */
+  const void* pk;
+  const void* eouts;
+  const int* moff;
+  const void* pq;
+  const float* aw_src;
+  const int* parent;
+  const emoasr_beam_state_t* state;
+  const float *filt, *w_conv, *b_conv, *w_score;
+  float* scores;
+  float* aw_dst;
+  void* ctx; long ctx_ld;
+} emoasr_las_attend_group_t;
+int emoasr_las_attend_group(int dtype, const emoasr_las_attend_group_t* a, void* stream);
+/* Parent row -> child row for the small state arrays of a step, one launch: item k copies row_bytes (a multiple of 16, both
+ * pointers 16-byte aligned) from src + parent[r] * row_bytes to dst + r * row_bytes for every live row r.  Exact copies. */
+#define EMOASR_LAS_GATHER_MAX 16
+typedef struct emoasr_las_gather_item { const void* src; void* dst; long row_bytes; } emoasr_las_gather_item_t;
+typedef struct emoasr_las_state_gather {
+  int S, W, n;
+  const int* parent;
+  const emoasr_beam_state_t* state;
+  emoasr_las_gather_item_t item[EMOASR_LAS_GATHER_MAX];
+} emoasr_las_state_gather_t;
+int emoasr_las_state_gather(const emoasr_las_state_gather_t* g, void* stream);
+
 /* ---- optimizer (asr/train_asr.py:84-92, torch.optim.Adam semantics) ---------- */
 /* out[0] += sum x^2 */
 int emoasr_sqnorm(long n, const float* x, float* out, void* stream);
