@@ -87,6 +87,21 @@ __global__ __launch_bounds__(256) void glu_fwd_kernel(long n, int C, const T* __
     out[i] = from_f32<T>(a * sigmoid_t<T>(g));
   }
 }
+// glu_fwd_kernel over [B, Tn, 2C] with the frames at and past lens[b] written as zeros: the depthwise convolution that follows then
+// sees an utterance inside a padded batch as it sees it alone (zero padding past its end)
+template <typename T>
+__global__ __launch_bounds__(256) void glu_fwd_masked_kernel(long n, int Tn, int C, const T* __restrict__ in,
+                                                             const int* __restrict__ lens, T* __restrict__ out) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long m = i / C; const int c = i % C;
+    float v = 0.f;
+    if ((int)(m % Tn) < lens[m / Tn]) {
+      const float a = to_f32(in[m * 2 * C + c]), g = to_f32(in[m * 2 * C + C + c]);
+      v = a * sigmoid_t<T>(g);
+    }
+    out[i] = from_f32<T>(v);
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void glu_bwd_kernel(long n, int C, const T* __restrict__ in,
                                                       const T* __restrict__ dout, T* __restrict__ din) {
@@ -243,6 +258,15 @@ extern "C" int emoasr_glu_fwd(int dtype, int M, int C, const void* in, void* out
   if (n == 0) return 0;
   EMO_DISPATCH(dtype, (glu_fwd_kernel<T><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(n, C, (const T*)in,
                                                                                      (T*)out)));
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int emoasr_glu_fwd_masked(int dtype, int B, int Tn, int C, const void* in, const int* lens, void* out, void* stream) {
+  const long n = (long)B * Tn * C;
+  if (n == 0) return 0;
+  EMO_CHECK(B > 0 && Tn > 0 && C > 0 && in && lens && out, "glu_fwd_masked: B=%d T=%d C=%d or a null argument", B, Tn, C);
+  EMO_DISPATCH(dtype, (glu_fwd_masked_kernel<T><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(n, Tn, C, (const T*)in, lens,
+                                                                                            (T*)out)));
   EMO_LAUNCH_CHECK();
   return 0;
 }

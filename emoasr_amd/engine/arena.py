@@ -285,8 +285,9 @@ def h2d_pack(arrays, device):
 
 
 def h2d_i32(values, device):
-    """small host array -> int32 device tensor through pinned memory (asynchronous H2D)"""
+    """small host array -> int32 device tensor through pinned memory (asynchronous H2D); a tensor already on a device is converted
+    where it lies"""
     t = torch.as_tensor(values, dtype=torch.int32)
-    if torch.device(device).type == "cpu":
+    if torch.device(device).type == "cpu" or t.is_cuda:
         return t
     return t.pin_memory().to(device, non_blocking=True)

@@ -79,6 +79,11 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
         # Conformer layers sequenced in C++ (EMOASR_CPP_LAYER=0: one FFI call per kernel from Python)
         self._cpp_layers = os.environ.get("EMOASR_CPP_LAYER", "1") != "0"
         self._layer_rt = None
+        # inference only, off by default (the reference never masks padded frames): the convolution module reads zeros at the frames
+        # past an utterance's end, so an utterance inside a padded batch gets the output it gets alone.  Every other kernel of the
+        # stack is row-wise or masked by the lengths already.  Takes the per-kernel path (the C++ layer call has no such form).
+        self.mask_padding = False
+        self._conv_lens = None
         # EMOASR_WGRAD_SIDE=1: run them on a side stream (measured slower on MI355X: 13.97 vs 13.62 ms/step)
         self._side_wgrads = os.environ.get("EMOASR_WGRAD_SIDE", "0") != "0"
         self._side, self._inflight = None, []
@@ -188,7 +193,8 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
             st.B, st.T2, st.F2, st.M, st.elens = B, T2, F2, M, elens
             st.layers = []
             st.s_pe = s_pe
-        if self._cpp_layers and self.conformer and self.rel and not self.attn_store_scores:
+        self._conv_lens = elens if self.mask_padding and not training and not stash else None
+        if self._cpp_layers and self.conformer and self.rel and not self.attn_store_scores and self._conv_lens is None:
             # one C-ABI call per layer (csrc/layer.hip); intermediates land in per-layer workspaces and
             # become tensors only when the backward sweep asks for them (layer_rt.LayerStash)
             if self._layer_rt is None:
@@ -209,6 +215,7 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
                     st.layers.append(ls)
                 if li + 1 == self.inter_layer:
                     x_inter = x
+        self._conv_lens = None
         # the intermediate branch goes through the SAME final LayerNorm (encoders/transformer.py:104-107)
         self.eouts_inter = None
         if self.inter_layer > 0:
@@ -311,7 +318,10 @@ class CTCEngine(TransformerDecoder, RNNTDecoder, RNNEncoder, LASDecoder):
         rm, rv = self._buffers(bn + ".running_mean"), self._buffers(bn + ".running_var")
         wdk, bd = wd.view(d, wd.shape[-1]), A.p(name + ".depthwise_conv.bias")
         fused = self._conv_fused and g.dtype == torch.bfloat16  # GLU inside the convolution's staging pass (convfused.hip)
-        gl = None if fused else ops.glu_fwd(g)
+        if self._conv_lens is not None:      # (mask_padding: the GLU writes zeros past every utterance's end)
+            fused, gl = False, ops.glu_fwd_masked(g, B, T, self._conv_lens)
+        else:
+            gl = None if fused else ops.glu_fwd(g)
         if fused:
             c, bmean, bvar = ops.glu_dwconv_fwd(g, B, T, wdk, bd, rm, rv, 0.1, self._buffers(bn + ".num_batches_tracked"),
                                                 training)

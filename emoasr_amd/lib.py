@@ -287,6 +287,7 @@ SIGNATURES = {
     "emoasr_attn_bwd": [I, POINTER(AttnArgs), P],
     "emoasr_attn_bwd_fused": [I, POINTER(AttnArgs), P, ctypes.c_size_t, P],
     "emoasr_glu_fwd": [I, I, I, P, P, P],
+    "emoasr_glu_fwd_masked": [I, I, I, I, P, P, P, P],
     "emoasr_glu_bwd": [I, I, I, P, P, P, P],
     "emoasr_dwconv_fwd": [I, I, I, I, I, P, P, P, P, P],
     "emoasr_dwconv_bwd_x": [I, I, I, I, I, P, P, P, P],
@@ -332,6 +333,8 @@ SIGNATURES = {
     "emoasr_bce_head_bwd": [I, I, I, P, L, P, P, P, P, F, P, P, L, P, P, P],
     "emoasr_ctc_token_conf": [I, I, I, I, P, L, P, P, P, I, P, P, P, P],
     "emoasr_correct_fuse": [I, I, I, I, I, I, P, L, P, P, L, P, L, F, P, P, P],
+    "emoasr_correct_mask_grid": [I, I, I, P, P, P, P, P, I, I, P, P, P, P, P],
+    "emoasr_correct_fuse_grid": [I, I, I, I, I, I, P, L, P, P, L, P, L, P, I, P, P, P],
     "emoasr_edit_align": [I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P],
     "emoasr_rescore_grid": [I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "emoasr_ctc_beam_batch": [I, I, I, I, P, L, P, P, I, I, ctypes.c_double, I, P, P, P, P, P, L, P, P],

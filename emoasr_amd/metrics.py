@@ -72,6 +72,39 @@ def compute_wers(hyps, refs, vocab=None, cer=False, device=None):
     return _total(zip(hyps, refs), cer) if device is None else _total_device(zip(hyps, refs), cer, device)
 
 
+def compute_wers_cells(cells, refs, device=None):
+    """cells[c][u]: the word hypothesis of utterance u in cell c of a grid; refs[u] its reference -> [(wer, dict)] per cell, what
+    compute_wers(cells[c], refs, device=device) gives.  Cells of a grid share most hypotheses: every distinct (utterance, hypothesis)
+    pair is aligned ONCE (with a `device` all of them in one ops.edit_align call, the alignment compute_wers runs there; an
+    utterance's hypotheses share its reference) and a cell's totals are the sums over its pairs."""
+    n_ref = sum(len(r) for r in refs)
+    index = [{} for _ in refs]       # per utterance: hypothesis -> its number among the utterance's distinct hypotheses
+    for cell in cells:
+        assert len(cell) == len(refs)
+        for u, hyp in enumerate(cell):
+            index[u].setdefault(tuple(hyp), len(index[u]))
+    pairs = [(u, hyp) for u, seen in enumerate(index) for hyp in seen]
+    counts = {}
+    if device is None:
+        for u, hyp in pairs:
+            w = compute_wer(hyp, refs[u])[1]
+            counts[u, hyp] = (w["n_sub"], w["n_ins"], w["n_del"])
+    elif pairs:
+        from . import ops
+        vocab = {}
+        intern = lambda seq: [vocab.setdefault(w, len(vocab)) for w in seq]
+        got = ops.edit_align([intern(list(hyp) or ["<dummy>"]) for _, hyp in pairs], [intern(r) for r in refs],
+                             ref_idx=[u for u, _ in pairs], device=device)["counts"]
+        counts = {p: tuple(int(v) for v in got[i, :3]) for i, p in enumerate(pairs)}
+    out = []
+    for cell in cells:
+        s = np.sum([counts[u, tuple(hyp)] for u, hyp in enumerate(cell)], axis=0) if len(cell) else np.zeros(3)
+        tot = {"n_sub": int(s[0]), "n_ins": int(s[1]), "n_del": int(s[2]), "n_ref": n_ref}
+        wer = 100.0 * (tot["n_sub"] + tot["n_ins"] + tot["n_del"]) / n_ref
+        out.append((wer, dict(tot, wer=wer)))
+    return out
+
+
 def compute_wers_df(dfhyp, dfref=None, cer=False, device=None):
     """result TSV (columns text, reftext) or hypothesis + reference tables joined on utt_id
     (metrics.py:133-175); missing / NaN hypotheses count as empty.  `device`: as compute_wers."""

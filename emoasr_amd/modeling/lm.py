@@ -779,6 +779,39 @@ class LM(_StackOps, nn.Module):
         loss = _LMLossFn.apply(self, ys, yl, labels.contiguous(), *A.params)
         return loss, {"loss_total": loss}
 
+    def logits_at(self, ys, ylens, rows):
+        """masked LM (lm_type "bert"), inputs that already lie on the device: ys int [S, Lw] (device), ylens [S] (host, each >= 1),
+        rows int [n] (device): flat positions s * Lw + j of ys -> logits [n, V] (f32) of those positions.  The
+        stack runs on all tokens, in chunks of MAX_TOKEN_ROWS token rows (sequences x padded length); the transform and the
+        vocabulary product run on the n gathered rows alone.  Nothing is copied to the host."""
+        assert not self.causal and not self.electra, "logits_at is the masked LM's (lm_type='bert')"
+        P = self.params
+        A = self._prepare()
+        dev = A.flat.device
+        assert ys.is_cuda and rows.is_cuda and ys.dim() == 2, "logits_at takes device tensors (forward takes host ids)"
+        S, Lw = ys.shape
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        assert len(yl) == S and min(yl) >= 1 and max(yl) <= min(Lw, P.max_seq_len), f"ylens in [1, {min(Lw, P.max_seq_len)}]"
+        Lp = min((max(yl) + 7) // 8 * 8, Lw, P.max_seq_len)     # (the padding is masked by the key lengths)
+        n = rows.numel()
+        with torch.no_grad(), ops.stream_scope(self._split()):
+            W = A.w(self._PRE + "embeddings.word_embeddings.weight")
+            if n == 0:
+                return torch.empty(0, W.shape[0], device=dev, dtype=torch.float32)
+            ids = ys[:, :Lp].to(torch.int32).contiguous()
+            r = rows.to(torch.int64)
+            r = (r // Lw) * Lp + r % Lw
+            klens = h2d_i32(yl, dev)
+            chunk = max(1, self.MAX_TOKEN_ROWS // Lp)
+            h = None
+            for s0 in range(0, S, chunk):
+                s1 = min(s0 + chunk, S)
+                x, _ = self._encode(ids[s0:s1], klens[s0:s1], s1 - s0, Lp, 0.0, 0.0, False)
+                g = x.index_select(0, (r - s0 * Lp).clamp_(0, (s1 - s0) * Lp - 1))
+                h = g if h is None else torch.where(((r >= s0 * Lp) & (r < s1 * Lp)).unsqueeze(1), g, h)
+            t2, _ = self._transform(h, False)
+            return ops.gemm_nt(t2, W, bias=A.p(self._CP + "bias"), out_f32=t2.dtype != torch.float32)
+
     def _loss_forward(self, ys, yl, labels, keep):
         A = self._arena
         dev = A.flat.device

@@ -16,6 +16,7 @@ import logging
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .asr import F32X3
 from .decoders.ctc import CTCDecoder
 from .decoders.transformer import TransformerDecoder
@@ -106,6 +107,45 @@ class P2W(nn.Module):
         if self.return_logits:
             return loss, loss_dict, logits
         return loss, loss_dict
+
+    def logits_at(self, ys, ylens, rows, ps, plens):
+        """lm_type "pbert", inputs that already lie on the device: ps int [B, Pw] (device) with plens [B] (host, each >= 1); ys int
+        [S, Lw] (device), S a multiple of B, sequence s over the phones of utterance s % B; ylens [S] (host, each >= 1); rows int
+        [n] (device): flat positions s * Lw + j of ys -> logits [n, V] (compute dtype) of those positions.  The phone encoder runs
+        ONCE over the B utterances and its output is indexed per sequence; the decoder stack runs on all tokens, in chunks of
+        LM.MAX_TOKEN_ROWS token rows; the final LayerNorm and the vocabulary product run on the n gathered rows alone (the row
+        selection of engine.cmlm_head).  Nothing is copied to the host."""
+        from .lm import LM
+        if self.decoder_type != "bert":
+            raise NotImplementedError("emoasr_amd: P2W.logits_at needs the masked-LM decoder (lm_type='pbert')")
+        assert ys.is_cuda and rows.is_cuda and ps.is_cuda and ys.dim() == 2 and ps.dim() == 2, "logits_at takes device tensors"
+        B, S, Lw = ps.shape[0], ys.shape[0], ys.shape[1]
+        yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+        pl = [int(v) for v in (plens.tolist() if torch.is_tensor(plens) else plens)]
+        assert S % B == 0 and len(yl) == S and len(pl) == B, "ys: a whole number of copies of the batch"
+        assert min(yl) >= 1 and max(yl) <= Lw and min(pl) >= 1 and max(pl) <= ps.shape[1], "ylens in [1, Lw], plens in [1, Pw]"
+        L, n = max(yl), rows.numel()
+        eng = self.engine()
+        with torch.no_grad():
+            if n == 0:
+                return torch.empty(0, self.vocab_size, device=ys.device, dtype=self.compute_dtype)
+            eouts, _, elens_dev, _ = eng.forward(ps[:, :max(pl)].to(torch.int32).contiguous(), pl, False, stash=False)
+            ids = ys[:, :L].to(torch.int32).contiguous()
+            r = rows.to(torch.int64)
+            r = (r // Lw) * L + r % Lw
+            chunk = max(1, LM.MAX_TOKEN_ROWS // L)
+            h = None
+            for s0 in range(0, S, chunk):
+                s1 = min(s0 + chunk, S)
+                utt = torch.arange(s0, s1, device=ys.device) % B
+                x, _ = eng.dec_forward(eouts.index_select(0, utt), elens_dev.index_select(0, utt), ids[s0:s1], yl[s0:s1], False, False,
+                                       causal=False, head=False)
+                g = x.index_select(0, (r - s0 * L).clamp_(0, (s1 - s0) * L - 1))
+                h = g if h is None else torch.where(((r >= s0 * L) & (r < s1 * L)).unsqueeze(1), g, h)
+            with eng._scope():
+                A = eng.arena
+                y, _, _ = ops.layernorm_fwd(h, A.p("decoder.norm.weight"), A.p("decoder.norm.bias"), 1e-12, False)
+                return eng.head_logits(y.view(1, n, -1), "decoder.output")[0]
 
     def decode(self, ps, plens=None):
         """greedy hypotheses of the CTC head over the phone encoder (lm_type "pctc")"""

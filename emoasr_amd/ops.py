@@ -496,6 +496,15 @@ def glu_fwd(x):
     return out
 
 
+def glu_fwd_masked(x, B, T, lens):
+    """glu_fwd of x [B*T, 2C] with zeros at the frames t >= lens[b] (lens int32 [B] on the device) -> [B*T, C]"""
+    M, C2, ld = _rows(_chk(x))
+    assert M == B * T and ld == C2 and _chk(lens, torch.int32).numel() == B and lens.is_contiguous()
+    out = torch.empty(M, C2 // 2, device=x.device, dtype=x.dtype)
+    lib.call("emoasr_glu_fwd_masked", dt(x), B, T, C2 // 2, _p(x), _p(lens), _p(out), _stream())
+    return out
+
+
 def glu_bwd(x, dout):
     M, C2, ld = _rows(_chk(x))
     din = torch.empty_like(x)
@@ -920,6 +929,55 @@ def correct_fuse(asr_logits, asr_lse, lm_logits, w, n_cols, asr_rows=None):
     val = torch.empty(n, device=lm_logits.device, dtype=torch.float32)
     lib.call("emoasr_correct_fuse", _DT[asr_logits.dtype], _DT[lm_logits.dtype], n, Va, Vl, int(n_cols), _p(asr_logits), lda,
              _p(asr_lse), _p(asr_rows), R, _p(lm_logits), ldl, float(w), _p(ids), _p(val), _stream())
+    return ids, val
+
+
+CORRECT_MAX_WEIGHTS = 16     # EMO_CORRECT_MAX_WEIGHTS: weights per emoasr_correct_fuse_grid launch
+
+
+def correct_mask_grid(hyp, ntok, conf, frame, ths, mask_id, pad_id=0):
+    """hyp int32 [B,T] the collapsed greedy ids; ntok int32 [B], conf f32 [B,T], frame int32 [B,T] as ctc_token_conf leaves them; ths
+    f32 [NT] (device) -> (ys int32 [NT,B,T], num_masked int32 [NT,B], lm_rows int32 [NT*B*T], asr_rows int32 [NT*B*T]): ys[k,b,j] =
+    mask_id where conf[b,j] < ths[k] (strictly), hyp[b,j] otherwise, pad_id from ntok[b] on.  The first num_masked.sum() entries of
+    the two lists are the masked positions in (threshold, utterance, token) order: lm_rows = (k * B + b) * T + j, the row of
+    ys.view(-1), and asr_rows = b * T + frame[b,j], the recogniser's row; the rest is unset.  The order comes from a scan over the
+    counts, so it is a fixed function of the inputs."""
+    B, T = _chk(hyp, torch.int32).shape
+    NT = _chk(ths, torch.float32).numel()
+    assert hyp.is_contiguous() and ths.is_contiguous() and _chk(ntok, torch.int32).numel() == B and ntok.is_contiguous()
+    assert _chk(conf, torch.float32).shape == (B, T) and conf.is_contiguous()
+    assert _chk(frame, torch.int32).shape == (B, T) and frame.is_contiguous()
+    assert T >= 1 and NT * B * T < 2 ** 31
+    dev = hyp.device
+    ys = torch.empty(NT, B, T, device=dev, dtype=torch.int32)
+    num_masked = torch.empty(NT, B, device=dev, dtype=torch.int32)
+    lm_rows = torch.empty(NT * B * T, device=dev, dtype=torch.int32)
+    asr_rows = torch.empty(NT * B * T, device=dev, dtype=torch.int32)
+    lib.call("emoasr_correct_mask_grid", B, T, NT, _p(hyp), _p(ntok), _p(conf), _p(frame), _p(ths), int(mask_id), int(pad_id),
+             _p(ys), _p(num_masked), _p(lm_rows), _p(asr_rows), _stream())
+    return ys, num_masked, lm_rows, asr_rows
+
+
+def correct_fuse_grid(asr_logits, asr_lse, lm_logits, weights, n_cols, asr_rows=None):
+    """correct_fuse for every weight of `weights` (host floats in [0, 1]) in one read of the two rows -> (ids int32 [NW,n], values f32
+    [NW,n]); row k is correct_fuse(..., weights[k], ...) bit for bit.  One launch per CORRECT_MAX_WEIGHTS weights."""
+    R, Va, lda = _rows(_chk(asr_logits))
+    n, Vl, ldl = _rows(_chk(lm_logits))
+    assert asr_logits.dim() == 2 and lm_logits.dim() == 2 and asr_logits.dtype in _DT and lm_logits.dtype in _DT
+    assert _chk(asr_lse, torch.float32).numel() == R and asr_lse.is_contiguous()
+    if asr_rows is not None:
+        assert _chk(asr_rows, torch.int32).numel() == n and asr_rows.is_contiguous()
+    else:
+        assert R >= n
+    w = torch.as_tensor([float(v) for v in weights], dtype=torch.float32)
+    NW = w.numel()
+    ids = torch.empty(NW, n, device=lm_logits.device, dtype=torch.int32)
+    val = torch.empty(NW, n, device=lm_logits.device, dtype=torch.float32)
+    for k0 in range(0, NW, CORRECT_MAX_WEIGHTS):
+        k1 = min(k0 + CORRECT_MAX_WEIGHTS, NW)
+        lib.call("emoasr_correct_fuse_grid", _DT[asr_logits.dtype], _DT[lm_logits.dtype], n, Va, Vl, int(n_cols), _p(asr_logits),
+                 lda, _p(asr_lse), _p(asr_rows), R, _p(lm_logits), ldl, _p(w[k0:k1]), k1 - k0, _p(ids[k0:k1]), _p(val[k0:k1]),
+                 _stream())
     return ids, val
 
 

@@ -317,6 +317,9 @@ int emoasr_attn_bwd_fused(int dtype, const emoasr_attn_t* a, void* ws, size_t ws
 /* out[M,C] = in[M,:C] * sigmoid(in[M,C:2C]) */
 int emoasr_glu_fwd(int dtype, int M, int C, const void* in, void* out, void* stream);
 int emoasr_glu_bwd(int dtype, int M, int C, const void* in, const void* dout, void* din, void* stream);
+/* emoasr_glu_fwd over in [B,T,2C] with zeros at the frames t >= lens[b] (lens int32 [B]): inference on a padded batch whose
+ * depthwise convolution must see every utterance as it sees it alone (zero padding past its own end) */
+int emoasr_glu_fwd_masked(int dtype, int B, int T, int C, const void* in, const int* lens, void* out, void* stream);
 /* depthwise Conv1d over time, channels-last x[B,T,C], w f32 [C,K], zero padding (K-1)/2 */
 int emoasr_dwconv_fwd(int dtype, int B, int T, int C, int K, const void* x, const float* w,
                       const float* bias, void* y, void* stream);
@@ -804,6 +807,28 @@ int emoasr_ctc_token_conf(int dtype, int B, int T, int V, const void* logits, lo
 int emoasr_correct_fuse(int dtype_asr, int dtype_lm, int n, int V_asr, int V_lm, int n_cols, const void* asr, long ld_asr,
                         const float* asr_lse, const int* asr_rows, long asr_nrows, const void* lm, long ld_lm, float w,
                         int* out_id, float* out_val, void* stream);
+/* The grid of thresholds and weights (one recogniser pass, one LM pass per threshold, one fuse launch for all weights).
+ * emoasr_correct_mask_grid: hyp int32 [B,T] the collapsed greedy ids; ntok [B], conf [B,T], frame [B,T] as emoasr_ctc_token_conf
+ *   leaves them; ths f32 [NT] on the device.  For threshold k and utterance b (the pair k * B + b):
+ *     ys[k,b,j]        = mask_id where j < ntok[b] and conf[b,j] < ths[k] (strictly), hyp[b,j] for the other j < ntok[b], pad_id from
+ *                        ntok[b] on (ys int32 [NT,B,T]: Lmax = T);
+ *     num_masked[k,b]  = the number of masked tokens of the pair (int32 [NT,B]);
+ *     lm_rows, asr_rows (int32, room for NT * B * T entries; sum(num_masked) are written): the masked positions in (threshold,
+ *                        utterance, token) order; lm_rows[i] = (k * B + b) * T + j is the position's row of ys viewed flat, so it
+ *                        names (k, b, j) as well; asr_rows[i] = b * T + frame[b,j] its recogniser row.
+ *   A pair's place in the lists is the sum of the counts before it (a scan, no atomics): the lists are a fixed function of the
+ *   inputs.  ntok[b] is clamped to [0, T]; NT * B * T <= 2^31 - 1.  One wave per pair, two launches.
+ * emoasr_correct_fuse_grid: emoasr_correct_fuse for the NW weights `weights` (f32 [NW] on the HOST, each in [0, 1]; 1 <= NW <=
+ *   EMO_CORRECT_MAX_WEIGHTS per launch): out_id / out_val are [NW, n], row k what emoasr_correct_fuse gives for w = weights[k], bit
+ *   for bit.  Both rows are read once: exp(a[v] - lse_a) and exp(l[v] - lse_l) are formed once per column, every weight keeps its
+ *   own running (value, column).  Same dtypes, strides and alignment rules as emoasr_correct_fuse. */
+#define EMO_CORRECT_MAX_WEIGHTS 16
+int emoasr_correct_mask_grid(int B, int T, int NT, const int* hyp, const int* ntok, const float* conf, const int* frame,
+                             const float* ths, int mask_id, int pad_id, int* ys, int* num_masked, int* lm_rows, int* asr_rows,
+                             void* stream);
+int emoasr_correct_fuse_grid(int dtype_asr, int dtype_lm, int n, int V_asr, int V_lm, int n_cols, const void* asr, long ld_asr,
+                             const float* asr_lse, const int* asr_rows, long asr_nrows, const void* lm, long ld_lm,
+                             const float* weights, int NW, int* out_id, float* out_val, void* stream);
 
 /* ---- N-best rescoring and error-label alignment (asr/rescore/test_rescore_grid.py, asr/rescore/align_hyps.py) ----
  * emoasr_edit_align: P pairs of int32 token sequences.  Hypothesis p is hyp[hyp_off[p] .. hyp_off[p+1]); its reference is sequence
