@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libemoasr_hip.so")
 SOURCES = ["api.hip", "gemm.hip", "layernorm.hip", "elementwise.hip", "convmodule.hip",
-           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "decode_batch.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_beam.hip", "rnnt_beam_book.hip", "rnnlm.hip", "ctc_beam_host.hip", "ctc_beam.hip", "ctc_beam_lm.hip", "mlm.hip", "electra.hip", "correct.hip", "las.hip", "las_beam.hip", "rescore.hip"]
+           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "decode_batch.hip", "decode_grid.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_beam.hip", "rnnt_beam_book.hip", "rnnlm.hip", "ctc_beam_host.hip", "ctc_beam.hip", "ctc_beam_lm.hip", "mlm.hip", "electra.hip", "correct.hip", "las.hip", "las_beam.hip", "rescore.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-Wno-unused-value", "-Wno-comment",
          "-ffp-contract=off"]
 
@@ -28,7 +28,9 @@ def build(force=False, verbose=True, variant=None, defines=()):
     LIB = globals()["LIB"] if not variant else os.path.join(HERE, "build", f"libemoasr_hip_{variant}.so")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h", "lstm_step.h", "gumbel.h",
-                                                  "ctc_beam_step.h")]
+                                                  "ctc_beam_step.h", "attn_group.h", "attn_group_body.h",
+                                                  "beam_score_step.h", "beam_scores_topk_body.h", "ctc_prefix_body.h", "beam_update_batch.h",
+                                                  "beam_update_batch_body.h")]
     headers.append(os.path.join(HERE, "..", "include", "emoasr_hip.h"))
     sources = SOURCES
     flags = FLAGS + ["-D" + d for d in defines]

@@ -583,9 +583,10 @@ extern "C" size_t emoasr_decode_step_group_ws_bytes(int dtype, int nb, int d, in
   return emoasr_decode_step_ws_bytes(dtype, nb, d, H, F, V);
 }
 
-// the launch chain of emoasr_transformer_decoder_step (never the cooperative kernel) with the grouped cross-attention
-extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const emoasr_decoder_layer_t* layers,
-                                                     const emoasr_decoder_step_group_t* g, void* stream) {
+// the launch chain of emoasr_transformer_decoder_step (never the cooperative kernel) with the grouped cross-attention; cells:
+// the fusion grid's table of row groups (emoasr_attn_step_cells over g->moff = the UTTERANCES' first rows), or NULL
+static int decoder_step_group_chain(int dtype, int nl, const emoasr_decoder_layer_t* layers, const emoasr_decoder_step_group_t* g,
+                                    const emoasr_joint_grid_step_t* cells, void* stream) {
   EMO_CHECK(layers && g && g->moff, "decoder_step_group: missing arguments");
   const emoasr_decoder_step_t* io = &g->d;
   EMO_CHECK(io->ws && io->kv && io->logits_last && io->kcache && io->vcache && io->pos && io->klens, "decoder_step_group: missing arguments");
@@ -619,7 +620,12 @@ extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const em
     if (linear(dtype, nb, dd, dd, o, dd, Ly.out, x2, EMOASR_ACT_NONE, x, stream)) return 1;
     if (emoasr_layernorm_fwd(dtype, nb, dd, x2, Ly.ln2.g, Ly.ln2.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
     if (linear(dtype, nb, dd, dd, h, dd, Ly.q2, q, EMOASR_ACT_NONE, nullptr, stream)) return 1;
-    if (emoasr_attn_step_group(dtype, g->S, g->W, dd, H, q, io->kv[li], g->moff, o, stream)) return 1;
+    if (cells) {
+      if (emoasr_attn_step_cells(dtype, cells->n_groups, cells->group_rows, nb, cells->U, dd, H, q, io->kv[li], g->moff, cells->groups, o,
+                                 stream)) return 1;
+    } else if (emoasr_attn_step_group(dtype, g->S, g->W, dd, H, q, io->kv[li], g->moff, o, stream)) {
+      return 1;
+    }
     if (linear(dtype, nb, dd, dd, o, dd, Ly.out2, x, EMOASR_ACT_NONE, x2, stream)) return 1;
     if (emoasr_layernorm_fwd(dtype, nb, dd, x, Ly.ln3.g, Ly.ln3.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
     if (linear(dtype, nb, F, dd, h, dd, Ly.w1, act, EMOASR_ACT_RELU, nullptr, stream)) return 1;
@@ -629,6 +635,11 @@ extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const em
   if (emoasr_layernorm_fwd(dtype, nb, dd, x, io->ln_out.g, io->ln_out.b, 1e-12f, h, nullptr, nullptr, stream)) return 1;
   EMO_LAUNCH_CHECK();
   return linear(dtype, nb, io->V, dd, h, dd, io->out, io->logits_last, EMOASR_ACT_NONE, nullptr, stream);
+}
+
+extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const emoasr_decoder_layer_t* layers,
+                                                     const emoasr_decoder_step_group_t* g, void* stream) {
+  return decoder_step_group_chain(dtype, nl, layers, g, nullptr, stream);
 }
 
 extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream) {
@@ -656,4 +667,38 @@ extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_
                                        u.n_last, u.n_outlen, u.cands, js->blank, u.eos, (float*)u.psi, js->states_cur, stream)) return 1;
   }
   return emoasr_beam_update_batch(&js->upd, stream);
+}
+
+// ---- the fusion grid of the joint search (kernels in csrc/decode_grid.hip) ------------------------------
+// emoasr_joint_beam_batch_step with a search = (utterance, lm_weight): the same linear chain with the four cell kernels in
+// place of their scalar twins.
+extern "C" int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_step_t* gs, void* stream) {
+  EMO_CHECK(gs && gs->js.dec_layers && gs->sutt && gs->groups && gs->mu && gs->mu_row, "joint_beam_grid_step: missing arguments");
+  const emoasr_joint_batch_step_t* js = &gs->js;
+  const emoasr_decoder_step_t& d = js->dec.d;
+  const emoasr_bert_step_t& l = js->lm;
+  const emoasr_beam_update_t& u = js->upd.u;
+  const int nb = d.nb, V = d.V, W = js->dec.W;
+  const bool use_lm = js->lm_nl > 0;
+  EMO_CHECK(u.bw == W && js->upd.S == js->dec.S, "joint_beam_grid_step: the update's %d x %d searches against the decoder's %d x %d", js->upd.S,
+            u.bw, js->dec.S, W);
+  EMO_CHECK(gs->U >= 1 && gs->U <= js->dec.S, "joint_beam_grid_step: %d utterances for %d searches", gs->U, js->dec.S);
+  EMO_CHECK(u.len_weight == 0.0, "joint_beam_grid_step: the grid searches at len_weight 0 (the host expands the length weights)");
+  EMO_CHECK(!use_lm || (l.nb == nb && l.raw_logits), "joint_beam_grid_step: the LM step runs on the same %d rows and leaves raw logits", nb);
+  if (emoasr_beam_cache_gather(dtype, js->dec_nl, nb, d.Lmax, d.dd, js->dec_k_prev, js->dec_v_prev, d.kcache, d.vcache, js->parent,
+                               d.pos, stream)) return 1;
+  if (decoder_step_group_chain(dtype, js->dec_nl, js->dec_layers, &js->dec, gs, stream)) return 1;
+  if (use_lm) {
+    if (emoasr_beam_cache_gather(dtype, js->lm_nl, nb, l.Lmax, l.d, js->lm_k_prev, js->lm_v_prev, l.kcache, l.vcache, js->parent,
+                                 l.pos, stream)) return 1;
+    if (emoasr_bert_lm_step(dtype, js->lm_nl, js->lm_layers, &l, stream)) return 1;
+  }
+  if (emoasr_beam_scores_topk_rows(dtype, nb, V, u.cw, d.logits_last, V, use_lm ? l.logp : nullptr, use_lm ? V : 0, gs->mu_row,
+                                   (float*)u.vals, (int*)u.cands, (float*)u.lm_at, stream)) return 1;
+  if (u.psi) {
+    if (emoasr_ctc_prefix_score_cells(nb, W, js->Tmax, V, u.cw, js->ctc_x, js->dec.moff, gs->sutt, js->states_prev, u.cw, js->parent,
+                                      u.n_pcand, u.n_last, u.n_outlen, u.cands, js->blank, u.eos, (float*)u.psi, js->states_cur,
+                                      stream)) return 1;
+  }
+  return emoasr_beam_update_cells(&js->upd, gs->mu, stream);
 }

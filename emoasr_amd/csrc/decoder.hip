@@ -6,6 +6,7 @@
 // eps/(V-1) on every other class, summed over t < ylens[b], optional /ylen and /B).
 #include "common.h"
 #include "../../include/emoasr_hip.h"
+#include "beam_score_step.h"
 
 namespace {
 
@@ -178,199 +179,15 @@ __global__ __launch_bounds__(256) void topk_kernel(int V, int k, const float* __
   }
 }
 
-#define EMO_DPP_I(old_, v_, ctrl_, rmask_) __builtin_amdgcn_update_dpp((old_), (v_), (ctrl_), (rmask_), 0xf, false)
-// wave-wide max / min through DPP moves: quad swaps, half-row and row mirrors, the GFX9 row broadcasts; the result of lane 63
-__device__ __forceinline__ float topk_wave_max(float v) {
-#define EMO_STEP(ctrl_, rm_) v = fmaxf(v, __builtin_bit_cast(float, EMO_DPP_I(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), ctrl_, rm_)))
-  EMO_STEP(0xB1, 0xf); EMO_STEP(0x4E, 0xf); EMO_STEP(0x141, 0xf); EMO_STEP(0x140, 0xf); EMO_STEP(0x142, 0xa); EMO_STEP(0x143, 0xc);
-#undef EMO_STEP
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ int topk_wave_min(int v) {
-#define EMO_STEP(ctrl_, rm_) v = min(v, EMO_DPP_I(v, v, ctrl_, rm_))
-  EMO_STEP(0xB1, 0xf); EMO_STEP(0x4E, 0xf); EMO_STEP(0x141, 0xf); EMO_STEP(0x140, 0xf); EMO_STEP(0x142, 0xa); EMO_STEP(0x143, 0xc);
-#undef EMO_STEP
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// log-softmax of the decoder row + mu * log-softmax of the LM row + top-k, one launch, one workgroup of 1024 threads per
-// hypothesis (the beam search never needs the full score rows: three launches and ~130 us per step become one of ~20 us).
-//   s[v] = (dec[v] - lse(dec)) + mu * (lm[v] - lse(lm));  vals / idx = the k largest s (ties -> lowest index);
-//   lm_at = lm[idx] - lse(lm).   lm == NULL: no LM term.
-// Selection: every thread keeps the best of its own strided elements; a round is one wave reduction + one barrier, then
-// only the owner of the winner rescans its elements.
+// The bodies of the kernels below are csrc/beam_scores_topk_body.h and csrc/ctc_prefix_body.h (shared with csrc/decode_grid.hip).
 template <typename T>
 __global__ __launch_bounds__(1024) void beam_scores_topk_kernel(int V, int k, const T* __restrict__ dec, long ldd,
                                                                 const float* __restrict__ lm, long ldl, float mu,
                                                                 float* __restrict__ vals, int* __restrict__ idx,
                                                                 float* __restrict__ lm_at, int lm_lds) {
-  extern __shared__ float sbuf[];      // [V] the decoder row (f32), later the scores | [16][k] x 2 survivors | (lm_lds) [V] the LM row
-  __shared__ float red4[4][16];
-  const long m = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const T* drow = dec + m * ldd;
-  const float* lrow = lm ? lm + m * ldl : nullptr;
-  // Both rows go to LDS first, four strided elements of each per thread and trip (8 loads in flight): read where they are used,
-  // inside three loops of ~V / 1024 dependent trips each, the rows cost ~30 global round trips -- most of the kernel's 41 us.
-  // A thread only ever reads back the elements it staged itself (v = tid mod 1024), so no barrier is needed.
-  float* slm = (lrow && lm_lds) ? sbuf + V + 32 * k : nullptr;
-  for (int v0 = tid; v0 < V; v0 += 4096) {
-    float a[4], b[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = v0 + 1024 * u;
-      a[u] = v < V ? to_f32(drow[v]) : 0.f;
-      b[u] = (slm && v < V) ? lrow[v] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = v0 + 1024 * u;
-      if (v < V) { sbuf[v] = a[u]; if (slm) slm[v] = b[u]; }
-    }
-  }
-  const float* lsrc = slm ? slm : lrow;   // (LM row too long for LDS: read from global memory as before)
-  // ---- the two log-sum-exps ----
-  float mxd = -INFINITY, mxl = -INFINITY;
-  for (int v = tid; v < V; v += 1024) {
-    mxd = fmaxf(mxd, sbuf[v]);
-    if (lrow) mxl = fmaxf(mxl, lsrc[v]);
-  }
-  for (int o = 32; o > 0; o >>= 1) { mxd = fmaxf(mxd, __shfl_xor(mxd, o)); mxl = fmaxf(mxl, __shfl_xor(mxl, o)); }
-  if (lane == 0) { red4[0][wave] = mxd; red4[1][wave] = mxl; }
-  __syncthreads();
-  mxd = red4[0][0]; mxl = red4[1][0];
-  for (int w = 1; w < 16; ++w) { mxd = fmaxf(mxd, red4[0][w]); mxl = fmaxf(mxl, red4[1][w]); }
-  float sd = 0.f, sl = 0.f;
-  for (int v = tid; v < V; v += 1024) {
-    sd += expf(sbuf[v] - mxd);
-    if (lrow) sl += expf(lsrc[v] - mxl);
-  }
-  for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o); sl += __shfl_xor(sl, o); }
-  if (lane == 0) { red4[2][wave] = sd; red4[3][wave] = sl; }
-  __syncthreads();
-  sd = 0.f; sl = 0.f;
-  for (int w = 0; w < 16; ++w) { sd += red4[2][w]; sl += red4[3][w]; }
-  const float lsed = mxd + logf(sd), lsel = lrow ? mxl + logf(sl) : 0.f;
-  // ---- scores; local best of this thread's elements ----
-  // Two levels, so that a round costs no workgroup barrier: every wave selects the k best of its own lanes' elements (a round = two
-  // DPP reductions -- the maximum, then the lowest index among the lanes that hold it -- and a rescan of the lanes' elements),
-  // then wave 0 merges the 16 x k survivors the same way.  The elements being rescanned sit in REGISTERS (V <= 16 K, k <= 32;
-  // beyond that the LDS copies are walked): a rescan loop over LDS with a run-time trip count waits ~130 cycles per element for
-  // one useful lane, which -- not the reductions, the barrier or the global loads -- was 2 us per round (42 us at k = 15).
-  constexpr int NE = 16, NM = 8;
-  const bool e_regs = V <= NE * 1024;
-  float lb = -INFINITY; int li = 0x7fffffff;
-  float e[NE];
-  if (e_regs) {
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int v = tid + 1024 * u;
-      e[u] = -INFINITY;
-      if (v < V) {
-        float r = sbuf[v] - lsed;
-        if (lrow) r += mu * (lsrc[v] - lsel);
-        e[u] = r;
-        if (r > lb) { lb = r; li = v; }   // ascending v: ties keep the lower index
-      }
-    }
-  } else {
-    for (int v = tid; v < V; v += 1024) {
-      float r = sbuf[v] - lsed;
-      if (lrow) r += mu * (lsrc[v] - lsel);
-      sbuf[v] = r;
-      if (r > lb) { lb = r; li = v; }
-    }
-  }
-  float* cand_v = sbuf + V;                              // [16][k] survivors of the waves (dynamic LDS after the score row)
-  int* cand_i = reinterpret_cast<int*>(cand_v + 16 * k);
-  for (int j = 0; j < k; ++j) {
-    const float best = topk_wave_max(lb);
-    const int bi = topk_wave_min(lb == best ? li : 0x7fffffff);
-    if (lane == 0) { cand_v[wave * k + j] = best; cand_i[wave * k + j] = bi; }
-    if (e_regs) {   // every lane: drop the winner if it is mine, take the best of what is left
-      lb = -INFINITY; li = 0x7fffffff;
-#pragma unroll
-      for (int u = 0; u < NE; ++u) {
-        if (tid + 1024 * u == bi) e[u] = -INFINITY;
-        if (e[u] > lb) { lb = e[u]; li = tid + 1024 * u; }
-      }
-    } else if (bi != 0x7fffffff && (bi & 1023) == tid) {
-      sbuf[bi] = -INFINITY;
-      lb = -INFINITY; li = 0x7fffffff;
-      for (int v = tid; v < V; v += 1024) {
-        const float c = sbuf[v];
-        if (c > lb) { lb = c; li = v; }
-      }
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-    // lane owns survivors lane, lane + 64, ... of the 16 k (indices are unique; -inf / 0x7fffffff entries are never picked)
-    const int n = 16 * k;
-    const bool m_regs = n <= NM * 64;
-    float cv[NM]; int ci[NM];
-#pragma unroll
-    for (int u = 0; u < NM; ++u) {
-      const int c = lane + 64 * u;
-      cv[u] = (m_regs && c < n) ? cand_v[c] : -INFINITY;
-      ci[u] = (m_regs && c < n) ? cand_i[c] : 0x7fffffff;
-    }
-    float mb = -INFINITY; int mi = 0x7fffffff;
-    auto rescan = [&]() {
-      mb = -INFINITY; mi = 0x7fffffff;
-      if (m_regs) {
-#pragma unroll
-        for (int u = 0; u < NM; ++u)
-          if (cv[u] > mb || (cv[u] == mb && ci[u] < mi)) { mb = cv[u]; mi = ci[u]; }
-      } else {
-        for (int c = lane; c < n; c += 64) {
-          const float xv = cand_v[c];
-          const int xi = cand_i[c];
-          if (xv > mb || (xv == mb && xi < mi)) { mb = xv; mi = xi; }
-        }
-      }
-    };
-    rescan();
-    for (int j = 0; j < k; ++j) {
-      const float best = topk_wave_max(mb);
-      int bi = topk_wave_min(mb == best ? mi : 0x7fffffff);
-      if (bi != 0x7fffffff) {
-        if (m_regs) {
-#pragma unroll
-          for (int u = 0; u < NM; ++u)
-            if (ci[u] == bi) { cv[u] = -INFINITY; ci[u] = 0x7fffffff; }
-        } else {
-          for (int c = lane; c < n; c += 64)
-            if (cand_i[c] == bi) { cand_v[c] = -INFINITY; cand_i[c] = 0x7fffffff; }
-        }
-        rescan();
-      }
-      if (bi == 0x7fffffff) bi = 0;
-      if (lane == 0) {
-        vals[m * k + j] = best;
-        idx[m * k + j] = bi;
-        if (lm_at) lm_at[m * k + j] = lrow ? lsrc[bi] - lsel : 0.f;   // (from the LDS copy: a global load here was a round trip per round)
-      }
-    }
-  }
+#include "beam_scores_topk_body.h"
 }
 
-#define EMO_LOG0 (-1e10f)
-__device__ __forceinline__ float np_logaddexp(float a, float b) {
-  // numpy.logaddexp semantics for finite inputs
-  const float d = a - b;
-  return d > 0.f ? a + log1pf(expf(-d)) : b + log1pf(expf(d));
-}
-
-// One wave per (beam m, candidate c).  x: CTC log-probs [T, V].
-// r_prev: the parent's state [T,2]: prev_states + (parent[m]*cw_prev + pcand[m]) * T*2, or init_state
-// when prev_states == NULL.  Outputs log_psi [nb, cw] and states [nb, cw, T, 2].
-// The recursion over t is sequential (and kept in the reference's float32 operation order: ctc_score.py:47-76),
-// but everything it consumes is not: per chunk of 64 frames the lanes fetch the parent state and the two
-// emission columns (one memory round trip per chunk instead of four per frame) and compute phi; lane 0 then
-// runs the 64 dependent steps out of LDS and the lanes write the new state rows back coalesced.
-// RAGGED (the batched joint search): row m belongs to search m / W, whose emissions are the rows xoff[s] .. xoff[s + 1] - 1 of x;
-// every state is a [Tn = Tmax, 2] slot of which the search uses its first T_s rows.
 template <bool RAGGED>
 __global__ __launch_bounds__(64) void ctc_prefix_kernel(int Tn, int V, int cw, const float* __restrict__ x,
                                                         const float* __restrict__ prev_states, int cw_prev,
@@ -380,73 +197,11 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(int Tn, int V, int cw, c
                                                         const int* __restrict__ cands, int blank, int eos,
                                                         float* __restrict__ log_psi, float* __restrict__ states,
                                                         const int* __restrict__ xoff, int W) {
-  __shared__ float s_rn[64], s_rb[64];
-  const int m = blockIdx.x / cw, c = blockIdx.x % cw, lane = threadIdx.x;
-  const float* rp = prev_states ? prev_states + ((long)parent[m] * cw_prev + pcand[m]) * Tn * 2 : init_state;
-  const int tok = cands[m * cw + c];
-  const int olen = out_len[m];
-  const bool same = olen > 0 && tok == last[m];
-  float* r = states + ((long)m * cw + c) * Tn * 2;
-  if constexpr (RAGGED) {   // (after the slots are addressed with the common stride)
-    const int s = m / W;
-    x += (long)xoff[s] * V;
-    Tn = xoff[s + 1] - xoff[s];
-  }
-  const int start = olen > 1 ? olen : 1;
-  // rows before `start` keep their initial value: LOG_0, except r[0][0] = x[0][tok] for an empty prefix
-  for (int t = lane; t < start && t < Tn; t += 64) {
-    r[2 * t] = (t == 0 && olen == 0) ? x[tok] : EMO_LOG0;
-    r[2 * t + 1] = EMO_LOG0;
-  }
-  // The three recursions have one shape, v <- logaddexp(v, a_t) + b_t:
-  //   lane 0: r^n   a = phi_t            b = x_t[tok]
-  //   lane 1: psi   a = phi_t + x_t[tok] b = 0
-  //   lane 2: r^b   a = r^n_{t-1}        b = x_t[blank]     (a comes from lane 0, one step behind)
-  // so lanes 0..2 run them in lockstep: one logaddexp per frame on the critical path instead of three.
-  const float v0 = (start == 1 && olen == 0) ? x[tok] : EMO_LOG0;
-  float v = lane == 2 ? EMO_LOG0 : v0;  // rn = psi = v0, rb = LOG_0
-  for (int t0 = start; t0 < Tn; t0 += 64) {
-    const int t = t0 + lane;
-    // lane i keeps frame t0 + i's inputs in registers; the recurrence lanes fetch them with v_readlane (the LDS copies they used
-    // to read cost a ~130-cycle round trip per frame on top of the dependent exp / log chain: 53 us at T' 285)
-    float my_phi = 0.f, my_x = 0.f, my_xb = 0.f;
-    if (t < Tn) {
-      const float pn = rp[2 * (t - 1)], pb = rp[2 * (t - 1) + 1];
-      my_phi = same ? pb : np_logaddexp(pn, pb);
-      my_x = x[(long)t * V + tok];
-      my_xb = x[(long)t * V + blank];
-    }
-    const int n = min(64, Tn - t0);
-    for (int i = 0; i < n; ++i) {
-      const float rn_prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-      const float phi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_phi), i));
-      const float xt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_x), i));
-      const float xbl = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_xb), i));
-      const float a = lane == 0 ? phi : (lane == 1 ? phi + xt : rn_prev);
-      const float bb = lane == 0 ? xt : (lane == 1 ? 0.f : xbl);
-      if (lane < 3) {
-        // same formula as np_logaddexp with the hardware exp / log (v_exp_f32, v_log_f32): |error| < 1e-7 in
-        // absolute terms per step against scores of magnitude 10..100 (the library expf / log1pf pair is ~4x
-        // the latency of this loop's critical path)
-        const float d = v - a;
-        v = (d > 0.f ? v + __logf(1.f + __expf(-d)) : a + __logf(1.f + __expf(d))) + bb;
-      }
-      if (lane == 0) s_rn[i] = v;
-      if (lane == 2) s_rb[i] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (t < Tn) { r[2 * t] = s_rn[lane]; r[2 * t + 1] = s_rb[lane]; }
-    __builtin_amdgcn_wave_barrier();
-  }
-  float psi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 1));
-  if (lane == 0) {
-    if (tok == eos) psi = np_logaddexp(rp[2 * (Tn - 1)], rp[2 * (Tn - 1) + 1]);
-    if (tok == blank) psi = EMO_LOG0;
-    log_psi[m * cw + c] = psi;
-  }
+#define EMO_CTC_FRAMES_OF(s) s
+#include "ctc_prefix_body.h"
+#undef EMO_CTC_FRAMES_OF
 }
 
-// initial state: r[t,1] = running sum of the blank log-probs (float32, step by step), r[t,0] = LOG_0
 template <bool RAGGED>
 __global__ void ctc_prefix_init_kernel(int Tn, int V, const float* __restrict__ x, int blank,
                                        float* __restrict__ r, const int* __restrict__ xoff, long r_stride) {
@@ -459,12 +214,7 @@ __global__ void ctc_prefix_init_kernel(int Tn, int V, const float* __restrict__ 
   } else {
     if (blockIdx.x != 0) return;
   }
-  float acc = 0.f;
-  for (int t = 0; t < Tn; ++t) {
-    acc = t == 0 ? x[blank] : acc + x[(long)t * V + blank];
-    r[2 * t] = EMO_LOG0;
-    r[2 * t + 1] = acc;
-  }
+  EMO_CTC_PREFIX_INIT_ROWS(Tn, V, x, blank, r)
 }
 
 }  // namespace
@@ -494,10 +244,9 @@ extern "C" int emoasr_beam_scores_topk(int dtype, int M, int V, int k, const voi
                                        float mu, float* vals, int* idx, float* lm_at, void* stream) {
   if (M == 0) return 0;
   EMO_CHECK(k >= 1 && k <= V, "beam_scores_topk: k=%d V=%d", k, V);
-  int bytes = V * 4 + 16 * k * 8;   // the score row + the 16 waves' k survivors (value, index)
-  EMO_CHECK((size_t)bytes <= 150 * 1024, "beam_scores_topk: V=%d, k=%d too large for the LDS plan", V, k);
-  const int lm_lds = lm && (size_t)bytes + (size_t)V * 4 <= 150 * 1024;   // the LM row staged in LDS as well
-  if (lm_lds) bytes += V * 4;
+  int lm_lds = 0;   // the LM row staged in LDS as well
+  const int bytes = beam_scores_topk_lds_bytes(V, k, lm != nullptr, &lm_lds);
+  EMO_CHECK(bytes > 0, "beam_scores_topk: V=%d, k=%d too large for the LDS plan", V, k);
   if (dtype == EMO_BF16) {
     if (bytes > 60 * 1024) hipFuncSetAttribute((const void*)beam_scores_topk_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     beam_scores_topk_kernel<bf16><<<M, 1024, bytes, (hipStream_t)stream>>>(V, k, (const bf16*)dec, ldd, lm, ldl, mu, vals, idx, lm_at, lm_lds);

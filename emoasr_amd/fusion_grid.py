@@ -1,4 +1,4 @@
-"""Shallow-fusion grid search for CTC models in ONE pass over the data (asr/fusion/test_fusion_grid.py).
+"""Shallow-fusion grid search for CTC and attention models in ONE pass over the data (asr/fusion/test_fusion_grid.py).
 
 The reference decodes the test set once per (lm_weight, len_weight) cell, 11 x 6 = 66 full decodes in 66 host processes.  Encoder,
 head, soft-max and top-k do not depend on the cell, and the searches of all cells of a batch are independent: here every batch is
@@ -9,8 +9,11 @@ metrics.compute_wers on the device.
     python -m emoasr_amd.fusion_grid -conf asr.yaml -ep 40 --data test.tsv --beam_width 10 --lm_conf lm.yaml --lm_ep 20
 
 results = [(lm_weight, len_weight, wer, wer_info), ...], lm_weight outer and len_weight inner as the reference builds its cells;
-best = the first cell whose WER is strictly below every earlier one's, starting from 100 (test_fusion_grid.py:51-64).  CTC models
-only: the joint CTC / attention search (decode_ctc_weight > 0) and the other decoders keep their one-cell-at-a-time paths.
+best = the first cell whose WER is strictly below every earlier one's, starting from 100 (test_fusion_grid.py:51-64).
+
+Attention models (decoder_type == "transformer", any --decode_ctc_weight) go through joint_fusion_grid: one encoder pass and one
+joint_beam_search_device_grid call per batch -- every distinct lm_weight is searched once, the len_weights are an expansion of the
+finished hypotheses' scores.  The RNN-T and LAS searches ignore the LM in the reference: no grid for them.
 """
 import argparse
 import logging
@@ -73,6 +76,55 @@ def ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_we
     return results, best
 
 
+def joint_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                      texts_out=None):
+    """ctc_fusion_grid for an attention model (decoder_type == "transformer"): -> (results, best) with the same cell order and the
+    same rule for best.  One encoder pass and one joint_beam_search_device_grid call per batch; decode_ctc_weight == 1 is greedy
+    CTC whatever the weights: decoded once per batch, every cell gets that result."""
+    from .modeling.beam_search_device import joint_beam_search_device_grid
+    kind = getattr(model, "decoder_type", None)
+    if kind != "transformer":
+        raise NotImplementedError(f"emoasr_amd.fusion_grid.joint_fusion_grid handles decoder_type == 'transformer', not {kind!r}")
+    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+    hyps_of = [[] for _ in cells]
+    refs = []
+    with torch.no_grad():
+        for data in dataloader:
+            eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
+            if decode_ctc_weight == 1:
+                greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
+                best_of = lambda b, c: greedy[b]
+            else:
+                hyps, _ = joint_beam_search_device_grid(model.decoder, eouts, elens, beam_width, lm, [a for a in lm_weights],
+                                                        [b for b in len_weights], decode_ctc_weight)
+                best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
+            for b, reftext in enumerate(data["texts"]):
+                refs.append(reftext.split())
+                for c in range(len(cells)):
+                    hyps_of[c].append(vocab.ids2text(strip_eos(best_of(b, c), eos_id)).split())
+    if texts_out is not None:
+        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
+    results = []
+    best = (0, 0, 100, "")
+    for c, (lm_weight, len_weight) in enumerate(cells):
+        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
+        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
+        results.append(row)
+        if wer < best[2]:
+            best = row
+    return results, best
+
+
+def grid_of(kind):
+    """the grid function of a decoder type: "ctc" -> ctc_fusion_grid, "transformer" -> joint_fusion_grid; the transducer and LAS
+    searches ignore the LM in the reference (there is nothing to tune): refused"""
+    if kind == "ctc":
+        return ctc_fusion_grid
+    if kind == "transformer":
+        return joint_fusion_grid
+    raise NotImplementedError(f"emoasr_amd.fusion_grid handles decoder_type 'ctc' and 'transformer', not {kind!r}")
+
+
 def log_results(results, best):
     """the reference's log lines (test_fusion_grid.py:56-69)"""
     for lm_weight, len_weight, _, wer_info in results:
@@ -113,7 +165,10 @@ def main(args):
     from .modeling.lm import LM
     from .rescore import load_config, model_path
     params = load_config(args.conf)
-    require_ctc(params, args.decode_ctc_weight)
+    kind = getattr(params, "decoder_type", None)
+    grid = grid_of(kind)
+    if kind == "ctc":
+        require_ctc(params, args.decode_ctc_weight)
     if not (args.lm_conf and args.lm_ep):
         raise SystemExit("emoasr_amd.fusion_grid: shallow fusion needs --lm_conf and --lm_ep")
     device = torch.device("cuda")
@@ -127,15 +182,16 @@ def main(args):
     model = ASR(params, phase="test")
     model.load_state_dict(torch.load(model_path(args.conf, args.ep), map_location="cpu"))
     model.to(device).eval()
-    model.decoder.ctc_beam_impl = "device"
+    if kind == "ctc":
+        model.decoder.ctc_beam_impl = "device"
     lm_params = load_config(args.lm_conf)
     lm = LM(lm_params, phase="test")
     lm.load_state_dict(torch.load(model_path(args.lm_conf, args.lm_ep), map_location="cpu"))
     lm.to(device).eval()
     dataset = ASRDataset(params, data_path, phase="test")
     lm_weights, len_weights = weight_lists(args.lm_min, args.lm_max, args.lm_step, args.len_min, args.len_max, args.len_step)
-    results, best = ctc_fusion_grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), args.beam_width or params.beam_width,
-                                    lm, lm_weights, len_weights, device, eos_id=params.eos_id)
+    results, best = grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), args.beam_width or params.beam_width,
+                         lm, lm_weights, len_weights, device, eos_id=params.eos_id, decode_ctc_weight=args.decode_ctc_weight)
     log_results(results, best)
     return results, best
 

@@ -148,6 +148,11 @@ class JointBatchStep(Structure):
                 ("states_prev", c_void_p), ("states_cur", c_void_p), ("upd", BeamUpdateBatch)]
 
 
+class JointGridStep(Structure):
+    _fields_ = [("js", JointBatchStep), ("U", c_int), ("n_groups", c_int), ("group_rows", c_int),
+                ("sutt", c_void_p), ("groups", c_void_p), ("mu", c_void_p), ("mu_row", c_void_p)]
+
+
 class FfnParams(Structure):
     _fields_ = [("ln_g", c_void_p), ("ln_b", c_void_p), ("w1", c_void_p), ("b1", c_void_p),
                 ("w2", c_void_p), ("b2", c_void_p)]
@@ -282,6 +287,13 @@ SIGNATURES = {
     "emoasr_ctc_prefix_score_ragged": [I, I, I, I, I, P, P, P, I, P, P, P, P, P, I, I, P, P, P],
     "emoasr_transformer_decoder_step_group": [I, I, POINTER(DecoderLayer), POINTER(DecoderStepGroup), P],
     "emoasr_joint_beam_batch_step": [I, POINTER(JointBatchStep), P],
+    "emoasr_attn_step_cells": [I, I, I, I, I, I, I, P, P, P, P, P, P],
+    "emoasr_cell_groups_check": [I, POINTER(c_int), I, I, I],
+    "emoasr_beam_scores_topk_rows": [I, I, I, I, P, L, P, L, P, P, P, P, P],
+    "emoasr_ctc_prefix_init_cells": [I, I, I, P, P, P, I, P, L, P],
+    "emoasr_ctc_prefix_score_cells": [I, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, I, P, P, P],
+    "emoasr_beam_update_cells": [POINTER(BeamUpdateBatch), P, P],
+    "emoasr_joint_beam_grid_step": [I, POINTER(JointGridStep), P],
     "emoasr_attn_dropmask": [I, POINTER(AttnArgs), P, I, P],
     "emoasr_attn_fwd": [I, POINTER(AttnArgs), P],
     "emoasr_attn_bwd": [I, POINTER(AttnArgs), P],

@@ -319,6 +319,7 @@ def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=Non
 # chain emoasr_joint_beam_batch_step (csrc/decode_rt.hip).
 # ---------------------------------------------------------------------------------------------------------------------------
 MAX_ROWS = 1024                     # S * W rows of one chunk
+GRID_BUFFER_SETS = 3                # buffer sets the fusion grid keeps (one per chunk shape)
 CACHE_BUDGET_BYTES = 8 << 30        # the self-attention cache pools of one chunk (decoder + LM, both halves of the ping-pong)
 
 
@@ -351,7 +352,7 @@ class _BatchBuffers:
     """device buffers of one (S, W, cw, Lmax, model sizes, frame capacities) configuration, reused across calls: the captured
     steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`)."""
 
-    def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc):
+    def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid=False):
         nb = S * W
         self.rows_cap, self.Tcap = rows_cap, Tcap
         i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
@@ -383,17 +384,32 @@ class _BatchBuffers:
         self.ctc_x = f32(rows_cap, V) if use_ctc else None
         self.states = f32(2, nb, cw, Tcap, 2) if use_ctc else None
         self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
+        if grid:   # the fusion grid: search -> utterance, the LM weight of every search / row, the attention's row groups [<= S, 3]
+            self.sutt, self.groups = i32(S), i32(3 * S)
+            self.mu, self.mu_row = f32(S), f32(nb)
         self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured structs point at)
 
 
-def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, decode_ctc_weight):
-    """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable)"""
+def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, decode_ctc_weight, grid=None, sort=True):
+    """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable; sort=False: in
+    the order the search found them).
+    grid = (sutt, mus, cells_per_group): the fusion grid's chunk (section 24) -- the U = len(elens) utterances are encoded,
+    projected and soft-maxed once, search s runs over utterance sutt[s] (consecutive per utterance) with the LM weight mus[s] > 0
+    through emoasr_joint_beam_grid_step; lm_weight is not read and len_weight must be 0."""
     V, eos, blank = dec.vocab_size, dec.eos_id, dec.blank_id
     dev = eouts.device
-    S, W = len(elens), bw
+    U, W = len(elens), bw
+    S = len(grid[0]) if grid else U
     nb = S * W
     use_ctc = decode_ctc_weight > 0
-    use_lm = lm is not None and lm_weight > 0
+    use_lm = lm is not None and (lm_weight > 0 or grid is not None)
+    if grid:
+        sutt, mus, cells_per_group = grid
+        assert lm is not None and len(mus) == S and all(m > 0 for m in mus) and len_weight == 0
+        assert all(0 <= u < U for u in sutt) and all(a <= b for a, b in zip(sutt, sutt[1:])), sutt
+        groups, group_rows = ops.cell_groups(sutt, W, cells_per_group)
+        flat_groups = [v for g in groups for v in g]
+        lib.call("emoasr_cell_groups_check", len(groups), (ctypes.c_int * len(flat_groups))(*flat_groups), group_rows, nb, U)
     cw = min(V, int(bw * CTC_BEAM_WIDTH_RATIO)) if use_ctc else bw
     max_steps = dec.max_decode_ylen
     Lmax = max_steps + 1
@@ -428,16 +444,33 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             assert lm._pe.shape[0] >= Lmax, "LM position table shorter than max_decode_ylen + 1"
             lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._pe.data_ptr())
         # one set of buffers is kept: reused while the sizes match and the frame capacities suffice
-        key = (str(dev), dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, use_ctc)
+        key = (str(dev), dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, use_ctc, grid is not None)
         cache = getattr(eng, "_beam_batch_bufs", None)
+        if grid:      # the grid alternates between a few chunk shapes (and the search without the LM): one set of buffers each
+            sets = getattr(eng, "_beam_grid_bufs", None)
+            if sets is None:
+                sets = eng._beam_grid_bufs = {}
+            cache = (key, sets[key]) if key in sets else None
         if cache is not None and cache[0] == key and cache[1].rows_cap >= rows_cap and cache[1].Tcap >= Tcap:
             Bf = cache[1]
             rows_cap, Tcap = Bf.rows_cap, Bf.Tcap
+        elif grid:
+            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, True)
+            sets.pop(key, None)
+            while len(sets) >= GRID_BUFFER_SETS:
+                sets.pop(next(iter(sets)))
+            sets[key] = Bf
         else:
-            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc)
+            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid is not None)
             eng._beam_batch_bufs = (key, Bf)
         # ---- this call's inputs, into the buffers the captured steps read ----
-        Bf.moff.copy_(h2d_i32(rt.moff_host, dev))
+        Bf.moff[:U + 1].copy_(h2d_i32(rt.moff_host, dev))
+        if grid:
+            Bf.sutt.copy_(h2d_i32(list(sutt), dev))
+            Bf.groups[:len(flat_groups)].copy_(h2d_i32(flat_groups, dev))
+            mu32 = np.asarray(mus, dtype=np.float32)        # rounded as emoasr_beam_update_t.mu is
+            Bf.mu.copy_(torch.from_numpy(mu32).to(dev))
+            Bf.mu_row.copy_(torch.from_numpy(np.repeat(mu32, W)).to(dev))
         if use_ctc:
             ctc_logits = eng.head_logits(mem.unsqueeze(0), "decoder.ctc.output")
             Bf.ctc_x[:total].copy_(ops.log_softmax(ctc_logits.view(total, V)))
@@ -451,8 +484,11 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             Bf.score.zero_(); Bf.score_ctc.zero_()
 
         lam, mu = float(decode_ctc_weight), float(lm_weight)
+        if grid:    # the weights are device data; the groups' count and width are part of the captured launches
+            mu = 0.0
         gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), lm_guard, tuple(k.data_ptr() for k in rt.kv_group), lam, mu if use_lm else 0.0,
-                float(len_weight), eos, blank, id(Bf))
+                float(len_weight), eos, blank, id(Bf), (U, len(groups), group_rows) if grid else None)
+        step_fn = "emoasr_joint_beam_grid_step" if grid else "emoasr_joint_beam_batch_step"
         if Bf.graphs is None or Bf.graphs[0] != gkey:
             dt_code = ops.dt(Bf.logits)
             ws_dec = torch.empty(lib.size_query("emoasr_decode_step_group_ws_bytes", dt_code, nb, dd, dh, F, V), device=dev, dtype=torch.uint8)
@@ -462,7 +498,14 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             steps = []
             for cur in (0, 1):
                 prev = cur ^ 1
-                js = lib.JointBatchStep()
+                if grid:
+                    gs = lib.JointGridStep()
+                    js = gs.js
+                    gs.U, gs.n_groups, gs.group_rows = U, len(groups), group_rows
+                    gs.sutt, gs.groups = Bf.sutt.data_ptr(), Bf.groups.data_ptr()
+                    gs.mu, gs.mu_row = Bf.mu.data_ptr(), Bf.mu_row.data_ptr()
+                else:
+                    js = lib.JointBatchStep()
                 js.dec_nl, js.dec_layers = eng.dnl, dec_layers
                 js.dec.S, js.dec.W, js.dec.moff = S, W, Bf.moff.data_ptr()
                 d = js.dec.d
@@ -501,7 +544,7 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 u = ub.u
                 u.bw, u.cw, u.eos = W, cw, eos
                 u.one_minus_lam, u.lam = float(np.float32(1 - lam)), float(np.float32(lam))
-                u.mu = float(np.float32(mu)) if use_lm else 0.0
+                u.mu = float(np.float32(mu)) if use_lm else 0.0      # (the grid: mu[s] on the device)
                 u.len_weight = float(len_weight)
                 u.vals, u.cands = Bf.vals.data_ptr(), Bf.cands.data_ptr()
                 u.lm_at = Bf.lm_at.data_ptr() if (use_lm and use_ctc) else None
@@ -513,26 +556,29 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 u.res_score, u.res_step, u.res_parent = Bf.res_score.data_ptr(), Bf.res_step.data_ptr(), Bf.res_parent.data_ptr()
                 u.state = Bf.state.data_ptr()
                 u.host_mirror = Bf.mirror_host.data_ptr()
-                steps.append(js)
+                steps.append(gs if grid else js)
             # warm-up with every search marked finished (the bookkeeping returns at once, the networks run on valid rows):
             # every kernel's lazy one-time setup happens outside the capture.  Then each step is captured once: a linear
             # chain on one stream.
             reset(1)
             for k in (0, 1):
-                lib.call("emoasr_joint_beam_batch_step", dt_code, ctypes.byref(steps[k]), ops._stream())
+                lib.call(step_fn, dt_code, ctypes.byref(steps[k]), ops._stream())
             torch.cuda.current_stream().synchronize()
             graphs = []
             for k in (0, 1):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
-                    lib.call("emoasr_joint_beam_batch_step", dt_code, ctypes.byref(steps[k]), ops._stream())
+                    lib.call(step_fn, dt_code, ctypes.byref(steps[k]), ops._stream())
                 graphs.append(g)
             Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group))
         graphs = Bf.graphs[1]
         reset(0)
         if use_ctc:   # (after the warm-up, whose steps write both halves of the scorer states)
             # step 0 reads "previous" = half 1 at (the search's row 0, candidate 0)
-            ops.ctc_prefix_init_ragged(Bf.ctc_x, Bf.moff, blank, Bf.states[1], W * cw * Tcap * 2)
+            if grid:
+                ops.ctc_prefix_init_cells(Bf.ctc_x, Bf.moff[:U + 1], Bf.sutt, blank, Bf.states[1], W * cw * Tcap * 2)
+            else:
+                ops.ctc_prefix_init_ragged(Bf.ctc_x, Bf.moff, blank, Bf.states[1], W * cw * Tcap * 2)
         mirror = Bf.mirror_host.numpy()
         mirror[:] = (0, 0)
         main = torch.cuda.current_stream()
@@ -559,7 +605,7 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
         stats["steps"] += n_done; stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
         host = Bf.pack.cpu().numpy()      # the one download
     caller.wait_stream(bstream)
-    return batch_nbest_from_pack(host, Bf.pack_off, S, W, Lmax)
+    return batch_nbest_from_pack(host, Bf.pack_off, S, W, Lmax, sort)
 
 
 def batch_pack_sizes(S, W, Lmax):
@@ -585,9 +631,9 @@ def batch_step_reported(mirror, i, S, main):
     return mirror[1] >= S
 
 
-def batch_nbest_from_pack(host, o, S, W, Lmax):
+def batch_nbest_from_pack(host, o, S, W, Lmax, sort=True):
     """the downloaded pack (batch_pack_sizes; o: the parts' offsets) -> (hyps[s], scores[s]): the token sequences rebuilt from
-    the (parent, token) history, each search's results sorted by score (stable)"""
+    the (parent, token) history, each search's results sorted by score (stable); sort=False: in the order they were found"""
     rs = host[o[0]:o[1]].view(np.float64)
     state = host[o[1]:o[2]].reshape(S, 4)
     rstep, rpar = host[o[2]:o[3]], host[o[3]:o[4]]
@@ -601,7 +647,8 @@ def batch_nbest_from_pack(host, o, S, W, Lmax):
                 toks.append(int(ht[p, s, slot]))
                 slot = int(hp[p, s, slot])
             results.append((toks[::-1], float(rs[s * W + k])))
-        results = sorted(results, key=lambda r: r[1], reverse=True)
+        if sort:
+            results = sorted(results, key=lambda r: r[1], reverse=True)
         hyps.append([r[0] for r in results])
         scores.append([r[1] for r in results])
     return hyps, scores
@@ -632,3 +679,120 @@ def joint_beam_search_device_batch(dec, eouts, elens, beam_width, len_weight=0, 
         hyps += h
         scores += s
     return hyps, scores, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The shallow-fusion grid of the joint search: every (lm_weight, len_weight) cell of every utterance
+# from ONE call.  len_weight never touches the search (it is added to a finished hypothesis' score only), so a cell's N-best
+# list is the result set of its lm_weight's search, rescored and stably re-sorted on the host; the searches of the distinct
+# positive lm_weights of an utterance share its frames (csrc/decode_grid.hip).
+# ---------------------------------------------------------------------------------------------------------------------------
+# searches of one utterance per cross-attention workgroup (None: ops.cell_groups' 32 // W).  Packing wins for the kernel alone only
+# where it saves a round of workgroups, and does not beat 1 inside the grid call: the default is 1
+GRID_CELLS_PER_GROUP = 1
+
+
+def grid_cell_plan(lm_weights, len_weights, has_lm=True):
+    """-> (search_weights, cells): search_weights the distinct lm_weights to search in order of first appearance, every weight
+    <= 0 (and every weight without an LM) folded into ONE entry 0.0, the search without the LM; cells[c] = (index into
+    search_weights, index into len_weights) for the cells in lm_weight-outer, len_weight-inner order.  Weights are compared as
+    doubles, unrounded: 0.30000000000000004 and 0.3 are two searches."""
+    search_weights, index, cells = [], {}, []
+    for a in lm_weights:
+        a = float(a)
+        a = a if (has_lm and a > 0) else 0.0
+        if a not in index:
+            index[a] = len(search_weights)
+            search_weights.append(a)
+        cells += [(index[a], j) for j in range(len(len_weights))]
+    return search_weights, cells
+
+
+def grid_chunk_plan(n_utts, n_weights, cap):
+    """chunks of at most cap searches for n_utts utterances of n_weights searches each -> [[(utterance, first weight, count)]]:
+    whole utterances per chunk while an utterance fits a chunk; an utterance with more searches than a chunk is cut into
+    pieces of cap (each piece forms that utterance's memory projection again)"""
+    assert n_weights >= 1 and cap >= 1
+    chunks, cur, room = [], [], cap
+    for b in range(n_utts):
+        k0 = 0
+        while k0 < n_weights:
+            left = n_weights - k0
+            if left > room and (cur and (left <= cap or k0 == 0)):   # does not fit behind what the chunk holds: a new chunk
+                chunks.append(cur)
+                cur, room = [], cap
+            n = min(left, room)
+            cur.append((b, k0, n))
+            k0 += n
+            room -= n
+            if room == 0:
+                chunks.append(cur)
+                cur, room = [], cap
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
+def expand_len_weights(hyps, scores, len_weights):
+    """the results of ONE search at len_weight 0 in the order the search found them -> per len_weight w (hyps, scores): every score
+    + w * (len(hyp) + 2) in double -- what emoasr_beam_update_batch writes as cscore + len_weight * (double)(pos + 2), the library
+    being compiled without contraction of the multiply-add -- sorted by score with the stable order of batch_nbest_from_pack"""
+    out = []
+    for w in len_weights:
+        w = float(w)
+        sc = [float(s) + w * float(len(h) + 2) for h, s in zip(hyps, scores)]
+        order = sorted(range(len(sc)), key=lambda i: sc[i], reverse=True)
+        out.append(([hyps[i] for i in order], [sc[i] for i in order]))
+    return out
+
+
+def joint_beam_search_device_grid(dec, eouts, elens, beam_width, lm, lm_weights, len_weights, decode_ctc_weight=0):
+    """the joint search of every utterance for every (lm_weight, len_weight) cell -> (hyps, scores): hyps[b][c] / scores[b][c] what
+    joint_beam_search_device_batch returns for utterance b with cell c's weights (cells in lm_weight-outer, len_weight-inner
+    order).  Distinct lm_weights are searched once, at len_weight 0; weights <= 0 are one search without the LM."""
+    lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
+    weights, cells = grid_cell_plan(lm_weights, len_weights, lm is not None)
+    require_next_token_lm(lm, max(weights))
+    elens = [int(n) for n in elens]
+    B = eouts.shape[0]
+    if len(elens) != B or any(n < 1 for n in elens):
+        raise ValueError(f"joint_beam_search_device_grid: every utterance needs at least one frame, got elens {elens}")
+    found = [[None] * len(weights) for _ in range(B)]     # [b][k] -> (hyps, scores) of search k at len_weight 0
+    if not batch_device_ok(dec, beam_width, lm, max(weights), decode_ctc_weight):
+        from .beam_search import joint_beam_search_batch
+        for k, a in enumerate(weights):
+            h, s = joint_beam_search_batch(dec, eouts, elens, beam_width, 0, lm, a, decode_ctc_weight)[:2]
+            for b in range(B):
+                found[b][k] = (h[b], s[b])
+    else:
+        eng = _engine_of(dec)
+        esz = 2 if eouts.dtype == torch.bfloat16 else 4
+        Lmax = dec.max_decode_ylen + 1
+        positive = [k for k, a in enumerate(weights) if a > 0]
+        if len(positive) < len(weights):      # the search without the LM: the batched search as it is, no LM launches
+            k = weights.index(0.0)
+            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, 0, 0, esz)
+            for b0 in range(0, B, cap):
+                n = elens[b0:b0 + cap]
+                h, s = _batch_search_chunk(dec, eng, eouts[b0:b0 + cap, :max(n)], n, beam_width, 0, None, 0, decode_ctc_weight, sort=False)
+                for i in range(len(n)):
+                    found[b0 + i][k] = (h[i], s[i])
+        if positive:
+            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, lm.params.num_layers, lm.params.hidden_size, esz)
+            for chunk in grid_chunk_plan(B, len(positive), cap):
+                utts = sorted({b for b, _, _ in chunk})
+                local = {b: i for i, b in enumerate(utts)}
+                n = [elens[b] for b in utts]
+                sutt = [local[b] for b, _, cnt in chunk for _ in range(cnt)]
+                ks = [positive[k0 + j] for _, k0, cnt in chunk for j in range(cnt)]
+                sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
+                h, s = _batch_search_chunk(dec, eng, sub, n, beam_width, 0, lm, 0, decode_ctc_weight,
+                                           grid=(sutt, [weights[k] for k in ks], GRID_CELLS_PER_GROUP), sort=False)
+                for i, (u, k) in enumerate(zip(sutt, ks)):
+                    found[utts[u]][k] = (h[i], s[i])
+    hyps, scores = [], []
+    for b in range(B):
+        per_search = [expand_len_weights(h, s, len_weights) for h, s in found[b]]
+        hyps.append([per_search[k][j][0] for k, j in cells])
+        scores.append([per_search[k][j][1] for k, j in cells])
+    return hyps, scores

@@ -1301,6 +1301,74 @@ def attn_step_group(q, kv, moff, W, H):
     return out
 
 
+# ---- the fusion grid of the joint search (csrc/decode_grid.hip): a search is an (utterance, lm_weight) pair ----
+def cell_groups(sutt, W, cells_per_group=None):
+    """the row groups of emoasr_attn_step_cells for searches of width W over the utterances sutt[s] (searches of one utterance
+    consecutive): up to cells_per_group (default 32 // W, at least 1) consecutive searches of ONE utterance per group
+    -> ([(first row, rows, utterance)], the most rows of a group)"""
+    cpg = max(1, 32 // W) if cells_per_group is None else int(cells_per_group)
+    assert 1 <= W <= 32 and 1 <= cpg and cpg * W <= max(32, W), (W, cpg)
+    groups, s, S = [], 0, len(sutt)
+    while s < S:
+        n = 1
+        while n < cpg and s + n < S and sutt[s + n] == sutt[s]:
+            n += 1
+        groups.append((s * W, n * W, int(sutt[s])))
+        s += n
+    return groups, max(g[1] for g in groups)
+
+
+def attn_step_cells(q, kv, moff, groups, group_rows, H, out=None):
+    """emoasr_attn_step_group for searches that share utterances: q [nb, dd], kv [sum T_u, 2 dd], moff int32 [U + 1] (device),
+    groups a HOST list of (first row, rows, utterance) covering the nb rows (cell_groups) -> out [nb, dd]"""
+    import ctypes
+    nb, dd = q.shape
+    U, G = moff.numel() - 1, len(groups)
+    assert kv.shape[1] == 2 * dd and kv.dtype == q.dtype and q.is_contiguous() and kv.is_contiguous()
+    flat = [int(v) for g in groups for v in g]
+    lib.call("emoasr_cell_groups_check", G, (ctypes.c_int * (3 * G))(*flat), group_rows, nb, U)
+    table = torch.tensor(flat, dtype=torch.int32).to(q.device)
+    out = torch.empty_like(q) if out is None else out
+    lib.call("emoasr_attn_step_cells", dt(q), G, group_rows, nb, U, dd, H, _p(_chk(q)), _p(_chk(kv)), _p(moff), _p(table), _p(out),
+             _stream())
+    return out
+
+
+def beam_scores_topk_rows(dec, lm, mu_row, k):
+    """emoasr_beam_scores_topk with one weight per row: dec [M, V] (compute dtype), lm f32 [M, V] or None, mu_row f32 [M]
+    -> (vals f32 [M, k], idx int32 [M, k], lm_at f32 [M, k])"""
+    M, V = dec.shape
+    vals = torch.empty(M, k, device=dec.device, dtype=torch.float32)
+    idx = torch.empty(M, k, device=dec.device, dtype=torch.int32)
+    lm_at = torch.empty(M, k, device=dec.device, dtype=torch.float32)
+    lib.call("emoasr_beam_scores_topk_rows", dt(dec), M, V, k, _p(_chk(dec)), V, _p(lm), V if lm is not None else 0,
+             _p(_chk(mu_row, torch.float32)) if mu_row is not None else None, _p(vals), _p(idx), _p(lm_at), _stream())
+    return vals, idx, lm_at
+
+
+def ctc_prefix_init_cells(x, xoff, sutt, blank, out, stride):
+    """x f32 [sum T_u, V], xoff int32 [U + 1], sutt int32 [S] (device): the initial state of utterance sutt[s] into
+    out.view(-1)[s * stride:][: 2 T_u] for every search s (computed once per utterance)"""
+    lib.call("emoasr_ctc_prefix_init_cells", sutt.numel(), xoff.numel() - 1, x.shape[1], _p(_chk(x, torch.float32)), _p(xoff), _p(sutt),
+             blank, _p(out), stride, _stream())
+
+
+def ctc_prefix_score_cells(x, xoff, sutt, W, Tmax, cands, last, out_len, blank, eos, prev_states, parent, pcand, log_psi=None,
+                           states=None):
+    """ctc_prefix_score_ragged with search m // W over the frames of utterance sutt[m // W] -> (log_psi, states)"""
+    nb, cw = cands.shape
+    V = x.shape[1]
+    assert sutt.numel() * W == nb
+    if log_psi is None:
+        log_psi = torch.empty(nb, cw, device=x.device, dtype=torch.float32)
+    if states is None:
+        states = torch.zeros(nb, cw, Tmax, 2, device=x.device, dtype=torch.float32)
+    lib.call("emoasr_ctc_prefix_score_cells", nb, W, Tmax, V, cw, _p(_chk(x, torch.float32)), _p(xoff), _p(sutt), _p(prev_states),
+             prev_states.shape[1], _p(parent), _p(pcand), _p(last), _p(out_len), _p(cands), blank, eos, _p(log_psi), _p(states),
+             _stream())
+    return log_psi, states
+
+
 # ---- RNN-T -------------------------------------------------------------------------------------
 DACT_TANH_OUT = 5
 DACT_MUL = 6            # epilogue dact: multiply by the saved factor (ACT_SAVE_DACT forward)

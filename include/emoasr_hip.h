@@ -1194,6 +1194,44 @@ typedef struct emoasr_joint_batch_step {
 } emoasr_joint_batch_step_t;
 int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream);
 
+/* ---- the fusion grid of the joint search (csrc/decode_grid.hip, csrc/decode_rt.hip).  A search is an
+ * (utterance, lm_weight) pair.  Rows as above: search s owns rows s * W .. s * W + W - 1.  sutt (device int32 [S]) is the
+ * utterance of every search, searches of one utterance are consecutive; moff / xoff (device int32 [U + 1]) are the first frames
+ * of the U UTTERANCES, whose frames are stored once.  Every kernel gives a row the bits its scalar twin above gives it on
+ * that row's search (the twin run with one offset entry per search over replicated frames, and with the search's weight). */
+/* emoasr_attn_step_group with one workgroup per (group, head): groups (device int32 [G, 3]) = {first row, rows, utterance} of up
+ * to max_rows <= 32 consecutive rows whose searches share one utterance; q / out [nb, dd].  Rows of a group beyond its count, and
+ * the rows of an entry that does not fit (rows outside 0 .. nb, more than max_rows rounded up to 8, utterance outside 0 .. U - 1)
+ * are never written.  emoasr_cell_groups_check verifies a HOST copy of the table: the groups cover rows 0 .. nb - 1 once, in
+ * order. */
+int emoasr_attn_step_cells(int dtype, int G, int max_rows, int nb, int U, int dd, int H, const void* q, const void* kv,
+                           const int* moff, const int* groups, void* out, void* stream);
+int emoasr_cell_groups_check(int G, const int* groups_host, int max_rows, int nb, int U);
+/* emoasr_beam_scores_topk with the weight of row m in mu_row[m] (device f32 [M]; not read when lm == NULL) */
+int emoasr_beam_scores_topk_rows(int dtype, int M, int V, int k, const void* dec, long ldd, const float* lm, long ldl,
+                                 const float* mu_row, float* vals, int* idx, float* lm_at, void* stream);
+/* The ragged CTC scorer pair with search s over the frames of utterance sutt[s].  The init computes an utterance's initial
+ * state once and writes it to r + s * r_stride of each of its searches. */
+int emoasr_ctc_prefix_init_cells(int S, int U, int V, const float* x, const int* xoff, const int* sutt, int blank, float* r,
+                                 long r_stride, void* stream);
+int emoasr_ctc_prefix_score_cells(int nb, int W, int Tmax, int V, int cw, const float* x, const int* xoff, const int* sutt,
+                                  const float* prev_states, int cw_prev, const int* parent, const int* pcand, const int* last,
+                                  const int* out_len, const int* cands, int blank, int eos, float* log_psi, float* states,
+                                  void* stream);
+/* emoasr_beam_update_batch with the LM weight of search s in mu[s] (device f32 [S], rounded as u.mu is); u.mu is not read */
+int emoasr_beam_update_cells(const emoasr_beam_update_batch_t* b, const float* mu, void* stream);
+/* One output step of all S searches: the linear chain of emoasr_joint_beam_batch_step with the kernels above.  js.dec.moff holds
+ * the U utterances' offsets, js.dec.S the searches; js.upd.u.len_weight must be 0 (a result's score is then its hypothesis
+ * score; the caller adds len_weight * (position + 2) in double for every length weight of the grid); mu_row [S * W] repeats
+ * mu[s] for the rows of search s. */
+typedef struct emoasr_joint_grid_step {
+  emoasr_joint_batch_step_t js;
+  int U, n_groups, group_rows;                   /* utterances; rows of `groups`; the most rows of a group */
+  const int* sutt; const int* groups;
+  const float* mu; const float* mu_row;
+} emoasr_joint_grid_step_t;
+int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_step_t* gs, void* stream);
+
 /* ---- the LAS beam search for S utterances at once (csrc/las_beam.hip).  Rows as above: search s owns
  * rows s * W .. s * W + W - 1; `state` is the array emoasr_beam_update_batch keeps, `parent` its n_parent (GLOBAL rows).  A row at
  * or past its search's n_alive, and every row of a search that is done, is SKIPPED: nothing of it is read (its parent may hold
