@@ -326,10 +326,15 @@ class RNNTDecoder:
             aligns.append(align[:na].tolist())
         return hyps, aligns
 
-    def rnnt_beam_search(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
+    def rnnt_beam_search(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False, lm=None, lm_weight=0,
+                         len_weight=0):
         """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359): the expansion round as a
         replayed HIP graph (_rnnt_beam_search_graph) unless EMOASR_RNNT_BEAM_GRAPH=0 or the utterance does not fit its static
-        buffers; then the launch chain below.  return_scores: (hyps, float64 scores) instead of hyps (tests compare the two forms)."""
+        buffers; then the launch chain below.  return_scores: (hyps, float64 scores) instead of hyps (tests compare the two forms).
+        lm with lm_weight > 0: shallow fusion (DESIGN.md section 25) through the launch chain, the only host form that fuses;
+        without it lm_weight and len_weight are not read."""
+        if lm is not None and lm_weight > 0:
+            return self._rnnt_beam_search_chain(eouts, beam_width, blank, eos, num_expands, return_scores, lm, lm_weight, len_weight)
         T = eouts.shape[1]
         if (os.environ.get("EMOASR_RNNT_BEAM_GRAPH", "1") != "0" and beam_width <= 16
                 and (T * num_expands + 2) * beam_width + 1 <= self._BEAM_POOL - 16 and T <= self._BEAM_TMAX):
@@ -520,28 +525,76 @@ class RNNTDecoder:
 
     _BEAM_BATCH_CAP = 64   # searches per launch chain: S W <= 1024 rows, S (E + 1) W state slots per layer (25 MB at H = 512, W = 16)
 
-    def rnnt_beam_device_ok(self, beam_width, num_expands=3):
+    _BEAM_POOL_BUDGET = 256 << 20   # bytes of state pools (prediction network + LM) one chunk of fused searches may hold
+
+    def rnnt_beam_lm_why_not(self, lm):
+        """why the batched device search cannot fuse this LM (None: it can).  The LM's LSTM layers run through
+        emoasr_rnnt_beam_lstm_rows beside the prediction network's and csrc/rnnt_beam_lm.hip ranks the candidates: an RNN LM
+        (lm_type == "rnn") of the engine's compute dtype and product mode, its layer sizes inside that kernel's LDS plans, its
+        vocabulary at least the model's"""
+        if getattr(lm, "lm_type", None) != "rnn":
+            return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
+        V_ = self.arena.w("decoder.output.weight").shape[0]
+        if lm.compute_dtype != self.dtype or lm.compute_dtype not in (torch.float32, torch.bfloat16) or bool(lm.f32_split) != bool(self.split):
+            return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {self.dtype} ({bool(self.split)})"
+        vec, wide = (8, 1904) if self.dtype == torch.bfloat16 else (4, 2368)
+        if lm.L < 1 or lm.H % 8 or lm.H % vec or lm.E % vec or max(lm.E, lm.H) + lm.H > wide or 16 * lm.H * 4 > 64 * 1024:
+            return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnt_beam_lstm_rows' limits"
+        if lm.V < V_:
+            return f"the LM's vocabulary ({lm.V}) is smaller than the model's ({V_})"
+        return None
+
+    def rnnt_beam_device_ok(self, beam_width, num_expands=3, lm=None):
         """does the model fit the batched search's round kernels?  (the limits of the fused round, _rnnt_beam_round_graph, and of
-        the bookkeeping kernel: beam_width <= 16, beam_width <= V - 1)"""
+        the bookkeeping kernel: beam_width <= 16, beam_width <= V - 1; with an LM to fuse, rnnt_beam_lm_why_not as well)"""
         A, H, nl = self.arena, self.r_H, self.r_nl
         V_ = A.w("decoder.output.weight").shape[0]
         nin_max = max(A.w(f"decoder.rnns.{l}.weight_ih_l0").shape[1] for l in range(nl)) if nl else 0
         fits = V_ * 4 <= 60 * 1024 and 16 * H * 4 <= 64 * 1024 and (self.dtype == torch.bfloat16 or nin_max + H <= 2368)
+        if lm is not None and self.rnnt_beam_lm_why_not(lm) is not None:
+            return False
         return nl >= 1 and fits and 1 <= beam_width <= min(ops.RNNT_BEAM_MAX_WIDTH, V_ - 1) and 1 <= num_expands <= ops.RNNT_BEAM_MAX_EXPANDS
 
-    def rnnt_beam_search_batch(self, eouts, elens, beam_width, blank, eos, num_expands=3):
+    def rnnt_beam_chunk_capacity(self, W, E, lm=None):
+        """searches per launch chain: _BEAM_BATCH_CAP, and with an LM no more than hold their state pools -- (E + 1) W slots per
+        search of (h in the compute dtype, c in f32) per layer of both networks -- inside _BEAM_POOL_BUDGET; never below one"""
+        if lm is None:
+            return self._BEAM_BATCH_CAP
+        esz = 2 if self.dtype == torch.bfloat16 else 4
+        per_search = (E + 1) * W * (esz + 4) * (self.r_nl * self.r_H + lm.L * lm.H)
+        return max(1, min(self._BEAM_BATCH_CAP, self._BEAM_POOL_BUDGET // per_search))
+
+    @staticmethod
+    def rnnt_len_expand(hyps, scores, len_weight):
+        """the finish of a fused search: final = score + len_weight * len(hyp) in doubles (the hypothesis with its leading <sos>,
+        decoders/transformer.py:274), then a stable descending re-sort"""
+        w = float(len_weight)
+        sc = [float(s) + w * float(len(h)) for h, s in zip(hyps, scores)]
+        order = sorted(range(len(sc)), key=lambda i: -sc[i])
+        return [hyps[i] for i in order], [sc[i] for i in order]
+
+    def rnnt_beam_search_batch(self, eouts, elens, beam_width, blank, eos, num_expands=3, lm=None, lm_weights=None, len_weights=None):
         """alignment-length synchronous beam search for a BATCH (rnn_transducer.py:242-325 per utterance; the reference asserts a
         batch of one): eouts [B, Tmax, d], utterance b is searched over its own elens[b] frames -> (hyps[b][n], scores[b][n]),
         best first, hypotheses with the leading <sos>, float64 scores.  The bookkeeping runs on the device
         (csrc/rnnt_beam_book.hip): one frame -- num_expands rounds of (LSTM layers, joint, output product, pick, book) over all
         S W rows -- is captured once per (S, W) and replayed max(elens) times without a synchronisation in between.  Batches above
         _BEAM_BATCH_CAP are searched in chunks.  A model outside the round kernels' limits is searched utterance by utterance
-        through rnnt_beam_search."""
+        through rnnt_beam_search.
+
+        lm_weights (a list; None: the call above, unchanged): the shallow-fusion GRID ->
+        (hyps[b][cell][n], scores[b][cell][n]), cells in lm_weight-outer, len_weight-inner order (len_weights None: [0]).  A search
+        is an (utterance, lm_weight) pair: every distinct positive lm_weight of an utterance is searched once with the LM's LSTM
+        stepped beside the prediction network's, all weights <= 0 (or no LM) are ONE search on the chain above.  The len_weights
+        are a host expansion of a fused search's results (rnnt_len_expand); the search without the LM does not read them.  An LM
+        or a width the device form cannot take is searched utterance by utterance through the host form."""
         elens = [int(v) for v in elens]
         B = eouts.shape[0]
         assert len(elens) == B and all(0 <= n <= eouts.shape[1] for n in elens), (elens, tuple(eouts.shape))
         with self._scope():
             self.arena.refresh_shadow()
+        if lm_weights is not None:
+            return self._rnnt_beam_search_grid(eouts, elens, beam_width, blank, eos, num_expands, lm, lm_weights, len_weights)
         hyps, scores = [], []
         if not self.rnnt_beam_device_ok(beam_width, num_expands):
             for b in range(B):
@@ -559,13 +612,59 @@ class RNNTDecoder:
             scores += s
         return hyps, scores
 
-    def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total):
+    def _rnnt_beam_search_grid(self, eouts, elens, W, blank, eos, E, lm, lm_weights, len_weights):
+        """rnnt_beam_search_batch with lm_weights: plan the searches, run them in chunks, expand the cells"""
+        from ..modeling.beam_search_device import grid_cell_plan
+        from ..modeling.lm import require_next_token_lm
+        len_weights = [0.0] if len_weights is None else [float(v) for v in len_weights]
+        weights, cells = grid_cell_plan([float(a) for a in lm_weights], len_weights, lm is not None)
+        require_next_token_lm(lm, max(weights))
+        B = len(elens)
+        found = [[None] * len(weights) for _ in range(B)]      # [b][k] -> (hyps, scores) of search k, before the len_weight
+        positive = [k for k, a in enumerate(weights) if a > 0]
+        if len(positive) < len(weights):                       # the search without the LM: the call as it was
+            k = weights.index(0.0)
+            h, s = self.rnnt_beam_search_batch(eouts, elens, W, blank, eos, E)
+            for b in range(B):
+                found[b][k] = (h[b], s[b])
+        if positive and not self.rnnt_beam_device_ok(W, E, lm):
+            for b in range(B):
+                for k in positive:
+                    if elens[b] == 0:
+                        found[b][k] = ([[eos]], [0.0])
+                    else:
+                        h, s = self._rnnt_beam_search_chain(eouts[b:b + 1, :elens[b]], W, blank, eos, E, True, lm, weights[k], 0)
+                        found[b][k] = (h, [float(v) for v in s])
+        elif positive:
+            pairs = [(b, k) for b in range(B) for k in positive]
+            cap = self.rnnt_beam_chunk_capacity(W, E, lm)
+            for p0 in range(0, len(pairs), cap):
+                chunk = pairs[p0:p0 + cap]
+                h, s = self._rnnt_beam_search_device(eouts, elens, W, blank, eos, E, lm, [weights[k] for _, k in chunk],
+                                                     [b for b, _ in chunk])
+                for i, (b, k) in enumerate(chunk):
+                    found[b][k] = (h[i], s[i])
+        hyps, scores = [], []
+        for b in range(B):
+            per_cell = [self.rnnt_len_expand(*found[b][k], len_weights[j]) if weights[k] > 0 else found[b][k] for k, j in cells]
+            hyps.append([c[0] for c in per_cell])
+            scores.append([c[1] for c in per_cell])
+        return hyps, scores
+
+    def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total, lm=None):
         """static buffers of S searches of width W over <= st.rows frames in all, and ONE FRAME of all of them (E rounds of
         LSTM layers, joint, output product, pick, book) captured as a HIP graph.  The warm-up runs the body with every search
-        finished (no frames): every row is inactive, no state is touched."""
+        finished (no frames): every row is inactive, no state is touched.
+        lm (an RNN LM that rnnt_beam_lm_why_not passes, _prepare()d by the caller): the fused frame -- every round but the last runs
+        the LM's LSTM layers under the same control words on pools lh / lc beside ph / pc, gathers the top layer's h, forms the LM's
+        logits and ranks the candidates with emoasr_rnnt_beam_pick_lm under the per-search weights st.mu; the last round of a frame
+        grows no candidate and stays the chain without the LM.  Keyed by the LM's identity, sizes and parameter addresses."""
         from .. import lib
         tab = self.__dict__.setdefault("_beam_batch_static", {})
         key = (S, W, blank, eos, E)
+        if lm is not None:
+            LA = lm._arena
+            key += (id(lm), lm.V, lm.E, lm.H, lm.L, LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._bias[0].data_ptr())
         st = tab.get(key)
         if st is not None and st.rows >= total:
             return st
@@ -588,6 +687,19 @@ class RNNTDecoder:
         st.ws = torch.empty(lib.size_query("emoasr_rnnt_beam_ws_bytes", S, st.rows, W, E), device=dev, dtype=torch.uint8)
         st.status = torch.zeros(1, device=dev, dtype=torch.int32)
         st.bias = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(nl)]   # (refreshed per search)
+        if lm is not None:
+            st.lh = [torch.zeros(st.nslots, lm.H, device=dev, dtype=self.dtype) for _ in range(lm.L)]
+            st.lc = [torch.zeros(st.nslots, lm.H, device=dev, dtype=torch.float32) for _ in range(lm.L)]
+            st.lmh = torch.zeros(R, lm.H, device=dev, dtype=self.dtype)
+            st.mu = torch.zeros(S, device=dev, dtype=torch.float32)
+
+        def lstm_layers(dtc, emb, weights, bias, ph, pc, Hl, p_lab, p_src, p_dst, p_act):
+            xtab, ldx, nx, xidx = emb, emb.shape[1], emb.shape[0], p_lab
+            for l, (w_ih, w_hh) in enumerate(weights):
+                lib.call("emoasr_rnnt_beam_lstm_rows", dtc, R, w_ih.shape[1], Hl, ops._p(xtab), ldx, nx, xidx, ops._p(w_ih),
+                         ops._p(w_hh), ops._p(bias[l]), ops._p(ph[l]), ops._p(pc[l]), st.nslots, p_src, p_dst, p_act,
+                         ops._stream())
+                xtab, ldx, nx, xidx = ph[l], Hl, st.nslots, p_dst
 
         def body():
             with self._scope():
@@ -595,21 +707,28 @@ class RNNTDecoder:
                 p_lab, p_src, p_dst, p_act, p_row = (c_void_p(st.ctl.data_ptr() + 8 * R * i) for i in range(5))
                 emb = A.w("decoder.embed.weight")
                 w_out, b_out = A.w("decoder.output.weight"), A.p("decoder.output.bias")
-                for _ in range(E):
-                    xtab, ldx, nx, xidx = emb, emb.shape[1], emb.shape[0], p_lab
-                    for l in range(nl):
-                        name = f"decoder.rnns.{l}"
-                        w_ih, w_hh = A.w(name + ".weight_ih_l0"), A.w(name + ".weight_hh_l0")
-                        lib.call("emoasr_rnnt_beam_lstm_rows", dtc, R, w_ih.shape[1], H, ops._p(xtab), ldx, nx, xidx, ops._p(w_ih),
-                                 ops._p(w_hh), ops._p(st.bias[l]), ops._p(st.ph[l]), ops._p(st.pc[l]), st.nslots, p_src, p_dst, p_act,
-                                 ops._stream())
-                        xtab, ldx, nx, xidx = st.ph[l], H, st.nslots, p_dst
+                weights = [(A.w(f"decoder.rnns.{l}.weight_ih_l0"), A.w(f"decoder.rnns.{l}.weight_hh_l0")) for l in range(nl)]
+                for v in range(E):
+                    fuse = lm is not None and v < E - 1
+                    lstm_layers(dtc, emb, weights, st.bias, st.ph, st.pc, H, p_lab, p_src, p_dst, p_act)
+                    if fuse:
+                        LA = lm._arena
+                        lstm_layers(dtc, LA.w("lm.embed.weight"), [lm._w(l) for l in range(lm.L)], lm._bias, st.lh, st.lc, lm.H,
+                                    p_lab, p_src, p_dst, p_act)
                     lib.call("emoasr_rnnt_beam_joint_rows", dtc, R, H, J, st.rows, ops._p(st.ph[nl - 1]), st.nslots, p_dst, p_act,
                              ops._p(A.w("decoder.w_dec.weight")), ops._p(A.p("decoder.w_dec.bias")), ops._p(st.e), p_row,
                              ops._p(st.hj), ops._stream())
                     logits = ops.gemm_nt(st.hj, w_out, bias=b_out)
-                    lib.call("emoasr_rnnt_beam_pick", dtc, R, V_, W, blank, ops._p(logits), logits.stride(0), ops._p(st.rec),
-                             st.rec.stride(0), ops._stream())
+                    if fuse:
+                        lib.call("emoasr_rnnt_beam_gather_rows", dtc, R, lm.H, ops._p(st.lh[lm.L - 1]), st.nslots, p_dst, p_act,
+                                 ops._p(st.lmh), ops._stream())
+                        lm_logits = ops.gemm_nt(st.lmh, LA.w("lm.output.weight"), bias=LA.p("lm.output.bias"))
+                        lib.call("emoasr_rnnt_beam_pick_lm", dtc, R, V_, lm.V, W, blank, W, ops._p(logits), logits.stride(0),
+                                 ops._p(lm_logits), lm_logits.stride(0), ops._p(st.mu), p_act, ops._p(st.rec), st.rec.stride(0),
+                                 ops._stream())
+                    else:
+                        lib.call("emoasr_rnnt_beam_pick", dtc, R, V_, W, blank, ops._p(logits), logits.stride(0), ops._p(st.rec),
+                                 st.rec.stride(0), ops._stream())
                     ops.rnnt_beam_book(st.row_off, W, E, V_, eos, st.rec, st.ctl, st.ws, st.status)
 
         ops.rnnt_beam_start(st.row_off, W, E, V_, eos, st.ctl, st.ws, st.status)   # (row_off all zero: every search finished)
@@ -625,26 +744,40 @@ class RNNTDecoder:
         tab[key] = st
         return st
 
-    def _rnnt_beam_search_device(self, eouts, elens, W, blank, eos, E):
-        """one chunk of rnnt_beam_search_batch: S = len(elens) <= _BEAM_BATCH_CAP searches"""
+    def _rnnt_beam_search_device(self, eouts, elens, W, blank, eos, E, lm=None, mus=None, sutt=None):
+        """one chunk of rnnt_beam_search_batch: S <= _BEAM_BATCH_CAP searches, one per utterance -- or, with sutt, search s over
+        utterance sutt[s] (the same utterance several times in a row: its rows of w_enc . eouts + b are replicated per search, so
+        the frame offsets keep rising and the bookkeeping is what it was).  lm, mus: the fused chain with the LM weight mus[s] of
+        search s (f32-rounded on the device; 0 ranks by the model alone, through the same launches)."""
         with self._scope(), torch.no_grad():
             A, nl = self.arena, self.r_nl
-            S, total, longest = len(elens), sum(elens), max(elens)
+            sutt = list(range(len(elens))) if sutt is None else list(sutt)
+            lens = [elens[b] for b in sutt]
+            S, total, longest = len(lens), sum(lens), max(lens)
             V_ = A.w("decoder.output.weight").shape[0]
-            st = self._rnnt_beam_frame_graph(S, W, blank, eos, E, total)
-            offs = [0]
-            for b in range(S):
+            if lm is not None:
+                assert len(mus) == S and self.rnnt_beam_lm_why_not(lm) is None
+                lm._prepare()      # (compute-dtype weights current, bias_ih + bias_hh rebuilt in place)
+            st = self._rnnt_beam_frame_graph(S, W, blank, eos, E, total, lm)
+            offs, rows_of = [0], {}
+            for b in sutt:
                 # w_enc . eouts + b per utterance, as the single-utterance forms compute it (a row's bits then do not depend on
-                # the batch it came in)
+                # the batch it came in); formed once for the consecutive searches of an utterance
                 if elens[b]:
-                    st.e[offs[-1]:offs[-1] + elens[b]].copy_(ops.gemm_nt(eouts[b, :elens[b]], A.w("decoder.w_enc.weight"),
-                                                                         bias=A.p("decoder.w_enc.bias")))
+                    if b not in rows_of:
+                        rows_of = {b: ops.gemm_nt(eouts[b, :elens[b]], A.w("decoder.w_enc.weight"), bias=A.p("decoder.w_enc.bias"))}
+                    st.e[offs[-1]:offs[-1] + elens[b]].copy_(rows_of[b])
                 offs.append(offs[-1] + elens[b])
             st.row_off.copy_(torch.tensor(offs, dtype=torch.int32))
             for l in range(nl):
                 st.bias[l].copy_(self._lstm_bias(f"decoder.rnns.{l}"))
                 st.ph[l].view(S, -1, self.r_H)[:, 0].zero_()    # slot 0 of every search's region: the zero state it starts from
                 st.pc[l].view(S, -1, self.r_H)[:, 0].zero_()
+            if lm is not None:
+                st.mu.copy_(torch.tensor([float(m) for m in mus], dtype=torch.float32))
+                for l in range(lm.L):
+                    st.lh[l].view(S, -1, lm.H)[:, 0].zero_()
+                    st.lc[l].view(S, -1, lm.H)[:, 0].zero_()
             st.status.zero_()
             ops.rnnt_beam_start(st.row_off, W, E, V_, eos, st.ctl, st.ws, st.status)
             for _ in range(longest):
@@ -652,8 +785,46 @@ class RNNTDecoder:
             hyps, scores, _ = ops.rnnt_beam_finish(st.row_off, W, E, V_, eos, longest * (E - 1), st.ws, st.status)
             return hyps, scores
 
-    def _rnnt_beam_search_chain(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False):
+    def _rnnt_lm_rows(self, lm, live, rows, states, V):
+        """shallow fusion, host form: the LM's log-probability row (f32 [V] on the device: log_softmax over the LM's vocabulary,
+        cut to the model's) of every live hypothesis, from lm.predict -- the stateful one-step call for the RNN LM (the state
+        after a label sequence is kept per label tuple; a hypothesis' parent was live one round earlier), the whole prefix for
+        the Transformer LM -- cached per label tuple in rows / states -> [nb, V]"""
+        todo = []
+        for hyp, _, _ in live:
+            key = tuple(hyp)
+            if key not in rows and key not in todo:
+                todo.append(key)
+        if todo:
+            if getattr(lm, "stateful", False):
+                prev = None
+                if any(len(k) > 1 for k in todo):
+                    zero = lm.zero_states(1, self.arena.flat.device)
+                    parts = [states[k[:-1]] if len(k) > 1 else zero for k in todo]
+                    prev = (torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1))
+                logp, (h, c) = lm.predict(torch.tensor([[k[-1]] for k in todo]), [1] * len(todo), prev)
+                for i, k in enumerate(todo):
+                    states[k] = (h[:, i:i + 1].clone(), c[:, i:i + 1].clone())
+            else:
+                n = max(len(k) for k in todo)
+                ys = torch.zeros(len(todo), n, dtype=torch.int64)
+                for i, k in enumerate(todo):
+                    ys[i, :len(k)] = torch.tensor(k)
+                logp, _ = lm.predict(ys, [len(k) for k in todo], None)
+            assert logp.shape[1] >= V, f"the LM's vocabulary ({logp.shape[1]}) is smaller than the model's ({V})"
+            for i, k in enumerate(todo):
+                rows[k] = logp[i, :V].to(torch.float32).clone()
+        return torch.stack([rows[tuple(hyp)] for hyp, _, _ in live])
+
+    def _rnnt_beam_search_chain(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False, lm=None, lm_weight=0,
+                                len_weight=0):
         """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359).
+
+        lm with lm_weight > 0: shallow fusion (the reference's search takes the arguments and never reads
+        them).  The non-blank candidates of a live hypothesis are the beam_width best v >= 1 of f = lp + mu * lq in torch f32 (mu
+        rounded to f32, product and sum rounded separately), lq the LM's row for the hypothesis' label sequence (_rnnt_lm_rows); the
+        blank extension takes no LM term; at the end score + len_weight * len(hyp) and a stable re-sort (rnnt_len_expand).  A
+        masked LM is refused.  Without an LM (or lm_weight <= 0) neither weight is read.
 
         eouts [1,T,d].  Per frame up to `num_expands` rounds; each round is one batched prediction-network
         step over the live hypotheses (every hypothesis keeps the LSTM state from before its last label, as
@@ -672,6 +843,12 @@ class RNNTDecoder:
             zero = ([torch.zeros(1, H, device=dev, dtype=cdt) for _ in range(nl)],
                     [torch.zeros(1, H, device=dev, dtype=torch.float32) for _ in range(nl)])
             beams = [([eos], 0.0, (zero, 0))]  # (hyp, score, (state tensors, row))
+            fuse = lm is not None and lm_weight > 0
+            if fuse:
+                from ..modeling.lm import require_next_token_lm
+                require_next_token_lm(lm, lm_weight)
+                mu = torch.tensor(float(lm_weight), device=dev, dtype=torch.float32)
+                lm_rows, lm_states = {}, {}
 
             def merge(cands):
                 seen = {}
@@ -713,7 +890,10 @@ class RNNTDecoder:
                     if last:
                         host = lp[:, blank].cpu().double().numpy().reshape(nb, 1)
                     else:
-                        vals, idx, _ = ops.topk(lp[:, 1:], beam_width)
+                        cand = lp
+                        if fuse:   # two f32 roundings: the product, then the sum (csrc/rnnt_beam_lm.hip does the same)
+                            cand = lp + mu * self._rnnt_lm_rows(lm, live, lm_rows, lm_states, lp.shape[1])
+                        vals, idx, _ = ops.topk(cand[:, 1:], beam_width)
                         host = torch.cat([lp[:, blank:blank + 1], vals, idx.to(torch.float32)], 1).cpu().double().numpy()
                     for i, (hyp, score, st) in enumerate(live):
                         frame_out.append((hyp, score + float(host[i, 0]), st))
@@ -728,6 +908,9 @@ class RNNTDecoder:
                     live = merge(grown)[:beam_width]
                 frame_out.sort(key=lambda c: -c[1])
                 beams = merge(frame_out)[:beam_width]
+            hyps, scores = [hyp for hyp, _, _ in beams], [score for _, score, _ in beams]
+            if fuse:
+                hyps, scores = self.rnnt_len_expand(hyps, scores, len_weight)
             if return_scores:
-                return [hyp for hyp, _, _ in beams], [score for _, score, _ in beams]
-            return [hyp for hyp, _, _ in beams]
+                return hyps, scores
+            return hyps

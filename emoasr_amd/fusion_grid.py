@@ -13,7 +13,9 @@ best = the first cell whose WER is strictly below every earlier one's, starting 
 
 Attention models (decoder_type == "transformer", any --decode_ctc_weight) go through joint_fusion_grid: one encoder pass and one
 joint_beam_search_device_grid call per batch -- every distinct lm_weight is searched once, the len_weights are an expansion of the
-finished hypotheses' scores.  The RNN-T and LAS searches ignore the LM in the reference: no grid for them.
+finished hypotheses' scores.  Transducer models (decoder_type == "rnn_transducer") go through
+rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25).  The LAS
+search ignores the LM, in the reference and here: no grid for it.
 """
 import argparse
 import logging
@@ -115,14 +117,56 @@ def joint_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_
     return results, best
 
 
+def rnnt_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                     texts_out=None):
+    """joint_fusion_grid for a transducer model (decoder_type == "rnn_transducer"): -> (results, best) with the same cell order and
+    the same rule for best.  One encoder pass and one engine.rnnt_beam_search_batch grid call per batch: every distinct positive
+    lm_weight of an utterance is one search with the RNN LM stepped beside the prediction network, the len_weights are a host
+    expansion.  decode_ctc_weight == 1 is greedy CTC whatever the weights, as in joint_fusion_grid."""
+    from .modeling.functions import rnnt_fusion_grid_apply
+    kind = getattr(model, "decoder_type", None)
+    if kind != "rnn_transducer":
+        raise NotImplementedError(f"emoasr_amd.fusion_grid.rnnt_fusion_grid handles decoder_type == 'rnn_transducer', not {kind!r}")
+    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+    hyps_of = [[] for _ in cells]
+    refs = []
+    with torch.no_grad():
+        for data in dataloader:
+            eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
+            if decode_ctc_weight == 1:
+                greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
+                best_of = lambda b, c: greedy[b]
+            else:
+                hyps, _ = rnnt_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)
+                best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
+            for b, reftext in enumerate(data["texts"]):
+                refs.append(reftext.split())
+                for c in range(len(cells)):
+                    hyps_of[c].append(vocab.ids2text(strip_eos(best_of(b, c), eos_id)).split())
+    if texts_out is not None:
+        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
+    results = []
+    best = (0, 0, 100, "")
+    for c, (lm_weight, len_weight) in enumerate(cells):
+        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
+        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
+        results.append(row)
+        if wer < best[2]:
+            best = row
+    return results, best
+
+
 def grid_of(kind):
-    """the grid function of a decoder type: "ctc" -> ctc_fusion_grid, "transformer" -> joint_fusion_grid; the transducer and LAS
-    searches ignore the LM in the reference (there is nothing to tune): refused"""
+    """the grid function of a decoder type: "ctc" -> ctc_fusion_grid, "transformer" -> joint_fusion_grid, "rnn_transducer" ->
+    rnnt_fusion_grid; the LAS search ignores the LM in the reference and here (there is nothing to tune): refused"""
     if kind == "ctc":
         return ctc_fusion_grid
     if kind == "transformer":
         return joint_fusion_grid
-    raise NotImplementedError(f"emoasr_amd.fusion_grid handles decoder_type 'ctc' and 'transformer', not {kind!r}")
+    if kind == "rnn_transducer":
+        return rnnt_fusion_grid
+    raise NotImplementedError(f"emoasr_amd.fusion_grid handles decoder_type 'ctc' and 'transformer' (and 'rnn_transducer'), "
+                              f"not {kind!r}")
 
 
 def log_results(results, best):

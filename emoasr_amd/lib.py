@@ -331,6 +331,8 @@ SIGNATURES = {
     "emoasr_rnnt_beam_start": [I, I, I, I, I, P, P, P, L, P, P],
     "emoasr_rnnt_beam_book": [I, I, I, I, I, P, P, L, P, P, L, P, P],
     "emoasr_rnnt_beam_finish": [I, I, I, I, I, P, I, P, P, P, P, P, L, P, P],
+    "emoasr_rnnt_beam_pick_lm": [I, I, I, I, I, I, I, P, L, P, L, P, P, P, L, P],
+    "emoasr_rnnt_beam_gather_rows": [I, I, I, P, L, P, P, P, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
     "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],
     "emoasr_las_attend_bwd": [I, POINTER(LasAttend), P],

@@ -7,16 +7,23 @@
 The transducer loss is the HIP lattice kernel (`emoasr_rnnt_forward/_grad`) -- the reference calls the
 third-party warp_rnnt package here (rnn_transducer.py:106-115).  beam_width <= 1: time-synchronous greedy
 search; > 1: alignment-length synchronous beam search (:242-325, batch size 1, hypotheses keep the leading
-<sos>, LM arguments unused -- all as in the reference).  Like the reference, decode() discards
+<sos> -- as in the reference).  Like the reference, decode() discards
 scores/logits/aligns (:339-346) for one utterance.  Several utterances with beam_width > 1 (the reference asserts a batch of one)
 go to the batched search with the bookkeeping on the device (engine.rnnt_beam_search_batch): every utterance is searched over its
 own elens[b] frames and the N-best lists come back with their scores; decoder.rnnt_beam_impl = "device" sends a single utterance
 there too (default "host": the search with the host bookkeeping, unchanged).
+
+Shallow fusion (the reference's search takes lm / lm_weight and never reads them): with lm is not None and
+lm_weight > 0 the non-blank candidates are ranked by log p_asr + lm_weight * log p_lm and a finished hypothesis' score gains
+len_weight * len(hyp).  Several utterances, or rnnt_beam_impl = "device", fuse the RNN LM on the device (returns as above);
+one utterance with "host" takes the host form (any next-token LM; no scores).  "device" with an LM the device form cannot take is a
+ValueError.  Without an LM, or with lm_weight <= 0, neither weight is read.
 """
 import torch.nn as nn
 
 from ..functions import rnnt_apply, rnnt_beam_apply, rnnt_beam_batch_apply, rnnt_greedy_apply, rnnt_prediction_stacked
 from ...criteria import RNNTAlignDistillLoss, RNNTWordDistillLoss
+from ..lm import require_next_token_lm
 from .ctc import CTCDecoder
 from .rnnt_aligner import RNNTForcedAligner
 
@@ -88,8 +95,19 @@ class RNNTDecoder(nn.Module):
                 raise ValueError(f"emoasr_amd: rnnt_beam_impl is 'host' or 'device', not {self.rnnt_beam_impl!r}")
             if self.rnnt_beam_impl == "device" and beam_width > 16:   # (asked for by name: no quiet detour through the host forms)
                 raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' takes beam_width <= 16, not {beam_width}")
+            fuse = lm is not None and lm_weight > 0    # shallow fusion; without it lm_weight and len_weight are not read
+            if fuse:
+                require_next_token_lm(lm, lm_weight)
+                if self.rnnt_beam_impl == "device" and getattr(lm, "lm_type", None) != "rnn":   # (by name: no quiet detour)
+                    raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' fuses the RNN LM (lm_type 'rnn') only, not lm_type "
+                                     f"{getattr(lm, 'lm_type', None)!r}; rnnt_beam_impl = 'host' takes any next-token LM")
             if eouts.size(0) > 1 or self.rnnt_beam_impl == "device":
-                hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width)
+                if fuse:
+                    hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width, lm, [float(lm_weight)], [float(len_weight)],
+                                                         require_device=self.rnnt_beam_impl == "device")
+                    hyps, scores = [h[0] for h in hyps], [s[0] for s in scores]
+                else:
+                    hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width)
                 if eouts.size(0) == 1:
                     return hyps[0], scores[0], None, None
                 return hyps, scores, None, None
@@ -106,4 +124,4 @@ class RNNTDecoder(nn.Module):
 
     def _beam_search(self, eouts, elens, beam_width=1, len_weight=0, lm=None, lm_weight=0):
         assert eouts.size(0) == 1  # rnn_transducer.py:251
-        return rnnt_beam_apply(self, eouts, beam_width)
+        return rnnt_beam_apply(self, eouts, beam_width, lm, lm_weight, len_weight)

@@ -628,10 +628,25 @@ def rnnt_greedy_apply(dec, eouts, elens):
     return eng.rnnt_greedy(eouts, _host_list(elens), dec.blank_id, dec.eos_id, dec.max_seq_len)
 
 
-def rnnt_beam_apply(dec, eouts, beam_width):
-    return _engine_of(dec).rnnt_beam_search(eouts, beam_width, dec.blank_id, dec.eos_id)
+def rnnt_beam_apply(dec, eouts, beam_width, lm=None, lm_weight=0, len_weight=0):
+    return _engine_of(dec).rnnt_beam_search(eouts, beam_width, dec.blank_id, dec.eos_id, lm=lm, lm_weight=lm_weight,
+                                            len_weight=len_weight)
 
 
-def rnnt_beam_batch_apply(dec, eouts, elens, beam_width):
-    """-> (hyps[b][n], scores[b][n]): every utterance searched over its own elens[b] frames"""
-    return _engine_of(dec).rnnt_beam_search_batch(eouts, _host_list(elens), beam_width, dec.blank_id, dec.eos_id)
+def rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm=None, lm_weights=None, len_weights=None, require_device=False):
+    """-> (hyps[b][n], scores[b][n]): every utterance searched over its own elens[b] frames; with lm_weights the shallow-fusion
+    grid (hyps[b][cell][n], scores[b][cell][n]: engine.rnnt_beam_search_batch).  require_device: a ValueError naming the reason
+    where the device form cannot fuse this LM, instead of the host form"""
+    eng = _engine_of(dec)
+    if require_device and lm is not None and lm_weights is not None and any(float(a) > 0 for a in lm_weights):
+        why = eng.rnnt_beam_lm_why_not(lm)
+        if why is not None:
+            raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' cannot fuse this LM: {why}")
+    return eng.rnnt_beam_search_batch(eouts, _host_list(elens), beam_width, dec.blank_id, dec.eos_id, lm=lm, lm_weights=lm_weights,
+                                      len_weights=len_weights)
+
+
+def rnnt_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_weights):
+    """the transducer search of every utterance for every (lm_weight, len_weight) cell -> (hyps[b][cell][n], scores[b][cell][n]),
+    cells in lm_weight-outer, len_weight-inner order"""
+    return rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm, [float(a) for a in lm_weights], [float(b) for b in len_weights])

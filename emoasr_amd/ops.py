@@ -2018,3 +2018,41 @@ def rnnt_beam_finish(row_off, W, num_expands, V, eos, Lmax, ws, status, ws_bytes
     hyps = [[tok[s, i, :lens[s, i]].tolist() for i in range(n[s])] for s in range(S)]
     scores = [[float(score[s, i]) for i in range(n[s])] for s in range(S)]
     return hyps, scores, n
+
+
+# ---- RNN-LM shallow fusion inside the batched transducer search (csrc/rnnt_beam_lm.hip) -------------------------------------------
+def rnnt_beam_pick(logits, k, blank, out):
+    """out[r] (f32, row stride >= 1 + 2 k) = { log_softmax(logits[r])[blank], the k best of log_softmax(logits[r])[1:], their indices
+    relative to column 1 as floats } (emoasr_rnnt_beam_pick)"""
+    R, V, ldl = _rows(_chk(logits))
+    assert _chk(out, torch.float32).shape[0] == R and out.stride(1) == 1
+    lib.call("emoasr_rnnt_beam_pick", dt(logits), R, V, int(k), int(blank), _p(logits), ldl, _p(out), out.stride(0), _stream())
+    return out
+
+
+def rnnt_beam_pick_lm(logits, lm_logits, mu, W, k, blank, out, active=None):
+    """the fused record of emoasr_rnnt_beam_pick_lm: candidates ranked by log_softmax(logits[r])[v] + mu[r // W] *
+    log_softmax(lm_logits[r])[v]; logits [R, V] and lm_logits [R, V_lm >= V] of one dtype (row strides allowed), mu f32 [>= ceil(R / W)],
+    active int64 [R] or None; rows with active == 0 leave out untouched"""
+    R, V, ldl = _rows(_chk(logits))
+    Rl, V_lm, ldlm = _rows(_chk(lm_logits, logits.dtype))
+    assert Rl == R and _chk(out, torch.float32).shape[0] == R and out.stride(1) == 1
+    assert _chk(mu, torch.float32).is_contiguous() and mu.numel() * int(W) >= R, (mu.shape, W, R)
+    assert active is None or (_chk(active, torch.int64).is_contiguous() and active.numel() == R)
+    lib.call("emoasr_rnnt_beam_pick_lm", dt(logits), R, V, V_lm, int(k), int(blank), int(W), _p(logits), ldl, _p(lm_logits), ldlm,
+             _p(mu), _p(active), _p(out), out.stride(0), _stream())
+    return out
+
+
+def rnnt_beam_gather_rows(pool, dst, active=None, out=None):
+    """out[r] = pool[dst[r]] for an active row whose slot lies inside the pool, a zero row otherwise (emoasr_rnnt_beam_gather_rows);
+    pool [nslots, H] contiguous, dst / active int64 [R]"""
+    nslots, H = pool.shape
+    R = dst.numel()
+    assert _chk(pool).is_contiguous() and _chk(dst, torch.int64).is_contiguous()
+    assert active is None or (_chk(active, torch.int64).is_contiguous() and active.numel() == R)
+    if out is None:
+        out = torch.empty(R, H, device=pool.device, dtype=pool.dtype)
+    assert _chk(out, pool.dtype).is_contiguous() and tuple(out.shape) == (R, H)
+    lib.call("emoasr_rnnt_beam_gather_rows", dt(pool), R, H, _p(pool), nslots, _p(dst), _p(active), _p(out), _stream())
+    return out

@@ -703,6 +703,23 @@ int emoasr_rnnt_beam_book(int S, int W, int num_expands, int V, int eos, const i
 int emoasr_rnnt_beam_finish(int S, int W, int num_expands, int V, int eos, const int* row_off, int Lmax, int* out_tok, int* out_len,
                             double* out_score, int* out_n, void* ws, long ws_bytes, int* status, void* stream);
 
+/* ---- RNN-LM shallow fusion inside the batched transducer search (csrc/rnnt_beam_lm.hip; engine.rnnt_beam_search_batch with lm=).
+ * The LM's LSTM states live in pools beside ph / pc under the same slot numbers and are stepped by emoasr_rnnt_beam_lstm_rows under
+ * the same control words; these two entry points are what a fused round adds.
+ *   emoasr_rnnt_beam_gather_rows: out[r] = pool[dst[r]] (H values of the compute dtype) for an active row with 0 <= dst[r] < nslots,
+ *       a zero row otherwise (active == NULL: every row is active).  out is [R][H].
+ *   emoasr_rnnt_beam_pick_lm    : emoasr_rnnt_beam_pick with f[v] = lp[v] + mu * lq[v] in place of lp[v] for the candidates v in
+ *       1 .. V - 1: lp = log_softmax(logits[r, :V]), lq = log_softmax(lm_logits[r, :V_lm])[:V], V_lm >= V, mu = mu[r / W] (one f32 per
+ *       search), the product and the sum rounded to f32 separately.  out[r] = { lp[blank], the k best f (descending, ties -> lowest
+ *       index), their indices relative to column 1 as floats }, ldo >= 1 + 2 k, k < V.  mu = 0 gives emoasr_rnnt_beam_pick's record
+ *       bit for bit.  A row with active[r] == 0 writes nothing (active == NULL: every row is active).  Both logit matrices are of the
+ *       compute dtype. */
+int emoasr_rnnt_beam_pick_lm(int dtype, int R, int V, int V_lm, int k, int blank, int W, const void* logits, long ldl,
+                             const void* lm_logits, long ldlm, const float* mu, const long long* active, float* out, long ldo,
+                             void* stream);
+int emoasr_rnnt_beam_gather_rows(int dtype, int R, int H, const void* pool, long nslots, const long long* dst,
+                                 const long long* active, void* out, void* stream);
+
 /* ---- one step of the RNN LM for the hypotheses of a beam search (csrc/rnnlm.hip; lm/modeling/rnn.py:62-81, RNNLM.predict): L + 2
  * launches -- one per LSTM layer, emoasr_gemm_nt for the vocabulary head, a log-softmax.  1 <= nb <= 32 rows.  Row i reads the
  * embedding of ids[i] (int32), the state (h, c) of every layer from the slot pools ph [L][slots][H] (compute dtype) / pc
