@@ -642,25 +642,47 @@ extern "C" int emoasr_transformer_decoder_step_group(int dtype, int nl, const em
   return decoder_step_group_chain(dtype, nl, layers, g, nullptr, stream);
 }
 
-extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream) {
-  EMO_CHECK(js && js->dec_layers, "joint_beam_batch_step: missing arguments");
+// The step of all S searches in three parts, shared by the Transformer-LM and the RNN-LM chains: the decoder (its cache gather and
+// step; cells: the fusion grid's row groups or NULL), one of the two LM steps, and the tail (scores + top-cw, the CTC scorer, the
+// update) over the LM's raw f32 logits lm [nb][ldl] (NULL: no LM).
+static int joint_batch_checks(const char* who, const emoasr_joint_batch_step_t* js) {
+  const emoasr_beam_update_t& u = js->upd.u;
+  const int nb = js->dec.d.nb;
+  EMO_CHECK(u.bw == js->dec.W && js->upd.S == js->dec.S, "%s: the update's %d x %d searches against the decoder's %d x %d", who, js->upd.S, u.bw,
+            js->dec.S, js->dec.W);
+  EMO_CHECK(js->lm_nl <= 0 || (js->lm.nb == nb && js->lm.raw_logits), "%s: the LM step runs on the same %d rows and leaves raw logits", who, nb);
+  return 0;
+}
+
+static int joint_batch_decoder(int dtype, const emoasr_joint_batch_step_t* js, const emoasr_joint_grid_step_t* cells, void* stream) {
   const emoasr_decoder_step_t& d = js->dec.d;
+  if (emoasr_beam_cache_gather(dtype, js->dec_nl, d.nb, d.Lmax, d.dd, js->dec_k_prev, js->dec_v_prev, d.kcache, d.vcache, js->parent,
+                               d.pos, stream)) return 1;
+  return decoder_step_group_chain(dtype, js->dec_nl, js->dec_layers, &js->dec, cells, stream);
+}
+
+static int joint_batch_bert_lm(int dtype, const emoasr_joint_batch_step_t* js, void* stream) {
   const emoasr_bert_step_t& l = js->lm;
+  const int nb = js->dec.d.nb;
+  if (emoasr_beam_cache_gather(dtype, js->lm_nl, nb, l.Lmax, l.d, js->lm_k_prev, js->lm_v_prev, l.kcache, l.vcache, js->parent,
+                               l.pos, stream)) return 1;
+  return emoasr_bert_lm_step(dtype, js->lm_nl, js->lm_layers, &l, stream);
+}
+
+static int joint_batch_rnn_lm_checks(const char* who, const emoasr_joint_batch_step_t* js, const emoasr_rnnlm_rows_t* rl) {
+  const emoasr_decoder_step_t& d = js->dec.d;
+  EMO_CHECK(rl, "%s: missing arguments", who);
+  EMO_CHECK(js->lm_nl == 0, "%s: the Transformer LM (lm_nl = %d) and the RNN LM in one chain", who, js->lm_nl);
+  EMO_CHECK(rl->R == d.nb && rl->V == d.V && rl->logits && rl->ldl >= d.V, "%s: the LM step runs on the same %d rows over the same %d tokens",
+            who, d.nb, d.V);
+  return 0;
+}
+
+static int joint_batch_tail(int dtype, const emoasr_joint_batch_step_t* js, const float* lm, long ldl, void* stream) {
+  const emoasr_decoder_step_t& d = js->dec.d;
   const emoasr_beam_update_t& u = js->upd.u;
   const int nb = d.nb, V = d.V, W = js->dec.W;
-  const bool use_lm = js->lm_nl > 0;
-  EMO_CHECK(u.bw == W && js->upd.S == js->dec.S, "joint_beam_batch_step: the update's %d x %d searches against the decoder's %d x %d", js->upd.S,
-            u.bw, js->dec.S, W);
-  EMO_CHECK(!use_lm || (l.nb == nb && l.raw_logits), "joint_beam_batch_step: the LM step runs on the same %d rows and leaves raw logits", nb);
-  if (emoasr_beam_cache_gather(dtype, js->dec_nl, nb, d.Lmax, d.dd, js->dec_k_prev, js->dec_v_prev, d.kcache, d.vcache, js->parent,
-                               d.pos, stream)) return 1;
-  if (emoasr_transformer_decoder_step_group(dtype, js->dec_nl, js->dec_layers, &js->dec, stream)) return 1;
-  if (use_lm) {
-    if (emoasr_beam_cache_gather(dtype, js->lm_nl, nb, l.Lmax, l.d, js->lm_k_prev, js->lm_v_prev, l.kcache, l.vcache, js->parent,
-                                 l.pos, stream)) return 1;
-    if (emoasr_bert_lm_step(dtype, js->lm_nl, js->lm_layers, &l, stream)) return 1;
-  }
-  if (emoasr_beam_scores_topk(dtype, nb, V, u.cw, d.logits_last, V, use_lm ? l.logp : nullptr, use_lm ? V : 0, use_lm ? u.mu : 0.f,
+  if (emoasr_beam_scores_topk(dtype, nb, V, u.cw, d.logits_last, V, lm, lm ? ldl : 0, lm ? u.mu : 0.f,
                               (float*)u.vals, (int*)u.cands, (float*)u.lm_at, stream)) return 1;
   if (u.psi) {
     if (emoasr_ctc_prefix_score_ragged(nb, W, js->Tmax, V, u.cw, js->ctc_x, js->dec.moff, js->states_prev, u.cw, js->parent, u.n_pcand,
@@ -669,31 +691,44 @@ extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_
   return emoasr_beam_update_batch(&js->upd, stream);
 }
 
+extern "C" int emoasr_joint_beam_batch_step(int dtype, const emoasr_joint_batch_step_t* js, void* stream) {
+  EMO_CHECK(js && js->dec_layers, "joint_beam_batch_step: missing arguments");
+  const bool use_lm = js->lm_nl > 0;
+  if (joint_batch_checks("joint_beam_batch_step", js)) return 1;
+  if (joint_batch_decoder(dtype, js, nullptr, stream)) return 1;
+  if (use_lm && joint_batch_bert_lm(dtype, js, stream)) return 1;
+  return joint_batch_tail(dtype, js, use_lm ? js->lm.logp : nullptr, js->dec.d.V, stream);
+}
+
+// the same chain with the stateful RNN LM: its step over the chain's rows, addressed by js->parent
+extern "C" int emoasr_joint_beam_batch_step_rnnlm(int dtype, const emoasr_joint_batch_step_t* js, const emoasr_rnnlm_rows_t* rl,
+                                                  void* stream) {
+  EMO_CHECK(js && js->dec_layers, "joint_beam_batch_step_rnnlm: missing arguments");
+  if (joint_batch_checks("joint_beam_batch_step_rnnlm", js)) return 1;
+  if (joint_batch_rnn_lm_checks("joint_beam_batch_step_rnnlm", js, rl)) return 1;
+  if (joint_batch_decoder(dtype, js, nullptr, stream)) return 1;
+  if (emoasr_rnnlm_step_rows(dtype, rl, js->dec.d.ids, js->parent, stream)) return 1;
+  return joint_batch_tail(dtype, js, rl->logits, rl->ldl, stream);
+}
+
 // ---- the fusion grid of the joint search (kernels in csrc/decode_grid.hip) ------------------------------
 // emoasr_joint_beam_batch_step with a search = (utterance, lm_weight): the same linear chain with the four cell kernels in
 // place of their scalar twins.
-extern "C" int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_step_t* gs, void* stream) {
-  EMO_CHECK(gs && gs->js.dec_layers && gs->sutt && gs->groups && gs->mu && gs->mu_row, "joint_beam_grid_step: missing arguments");
+static int joint_grid_checks(const char* who, const emoasr_joint_grid_step_t* gs) {
+  EMO_CHECK(gs && gs->js.dec_layers && gs->sutt && gs->groups && gs->mu && gs->mu_row, "%s: missing arguments", who);
+  const emoasr_joint_batch_step_t* js = &gs->js;
+  if (joint_batch_checks(who, js)) return 1;
+  EMO_CHECK(gs->U >= 1 && gs->U <= js->dec.S, "%s: %d utterances for %d searches", who, gs->U, js->dec.S);
+  EMO_CHECK(js->upd.u.len_weight == 0.0, "%s: the grid searches at len_weight 0 (the host expands the length weights)", who);
+  return 0;
+}
+
+static int joint_grid_tail(int dtype, const emoasr_joint_grid_step_t* gs, const float* lm, long ldl, void* stream) {
   const emoasr_joint_batch_step_t* js = &gs->js;
   const emoasr_decoder_step_t& d = js->dec.d;
-  const emoasr_bert_step_t& l = js->lm;
   const emoasr_beam_update_t& u = js->upd.u;
   const int nb = d.nb, V = d.V, W = js->dec.W;
-  const bool use_lm = js->lm_nl > 0;
-  EMO_CHECK(u.bw == W && js->upd.S == js->dec.S, "joint_beam_grid_step: the update's %d x %d searches against the decoder's %d x %d", js->upd.S,
-            u.bw, js->dec.S, W);
-  EMO_CHECK(gs->U >= 1 && gs->U <= js->dec.S, "joint_beam_grid_step: %d utterances for %d searches", gs->U, js->dec.S);
-  EMO_CHECK(u.len_weight == 0.0, "joint_beam_grid_step: the grid searches at len_weight 0 (the host expands the length weights)");
-  EMO_CHECK(!use_lm || (l.nb == nb && l.raw_logits), "joint_beam_grid_step: the LM step runs on the same %d rows and leaves raw logits", nb);
-  if (emoasr_beam_cache_gather(dtype, js->dec_nl, nb, d.Lmax, d.dd, js->dec_k_prev, js->dec_v_prev, d.kcache, d.vcache, js->parent,
-                               d.pos, stream)) return 1;
-  if (decoder_step_group_chain(dtype, js->dec_nl, js->dec_layers, &js->dec, gs, stream)) return 1;
-  if (use_lm) {
-    if (emoasr_beam_cache_gather(dtype, js->lm_nl, nb, l.Lmax, l.d, js->lm_k_prev, js->lm_v_prev, l.kcache, l.vcache, js->parent,
-                                 l.pos, stream)) return 1;
-    if (emoasr_bert_lm_step(dtype, js->lm_nl, js->lm_layers, &l, stream)) return 1;
-  }
-  if (emoasr_beam_scores_topk_rows(dtype, nb, V, u.cw, d.logits_last, V, use_lm ? l.logp : nullptr, use_lm ? V : 0, gs->mu_row,
+  if (emoasr_beam_scores_topk_rows(dtype, nb, V, u.cw, d.logits_last, V, lm, lm ? ldl : 0, gs->mu_row,
                                    (float*)u.vals, (int*)u.cands, (float*)u.lm_at, stream)) return 1;
   if (u.psi) {
     if (emoasr_ctc_prefix_score_cells(nb, W, js->Tmax, V, u.cw, js->ctc_x, js->dec.moff, gs->sutt, js->states_prev, u.cw, js->parent,
@@ -701,4 +736,22 @@ extern "C" int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_st
                                       stream)) return 1;
   }
   return emoasr_beam_update_cells(&js->upd, gs->mu, stream);
+}
+
+extern "C" int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_step_t* gs, void* stream) {
+  if (joint_grid_checks("joint_beam_grid_step", gs)) return 1;
+  const emoasr_joint_batch_step_t* js = &gs->js;
+  const bool use_lm = js->lm_nl > 0;
+  if (joint_batch_decoder(dtype, js, gs, stream)) return 1;
+  if (use_lm && joint_batch_bert_lm(dtype, js, stream)) return 1;
+  return joint_grid_tail(dtype, gs, use_lm ? js->lm.logp : nullptr, js->dec.d.V, stream);
+}
+
+extern "C" int emoasr_joint_beam_grid_step_rnnlm(int dtype, const emoasr_joint_grid_step_t* gs, const emoasr_rnnlm_rows_t* rl, void* stream) {
+  if (joint_grid_checks("joint_beam_grid_step_rnnlm", gs)) return 1;
+  const emoasr_joint_batch_step_t* js = &gs->js;
+  if (joint_batch_rnn_lm_checks("joint_beam_grid_step_rnnlm", js, rl)) return 1;
+  if (joint_batch_decoder(dtype, js, gs, stream)) return 1;
+  if (emoasr_rnnlm_step_rows(dtype, rl, js->dec.d.ids, js->parent, stream)) return 1;
+  return joint_grid_tail(dtype, gs, rl->logits, rl->ldl, stream);
 }

@@ -16,6 +16,13 @@
 // of v_mfma_f32_16x16x32_bf16; the hypotheses are one or two 16-row B tiles from a zero-padded LDS image (the layout of
 // rnnt_beam_lstm_mfma_kernel, whose one-tile form this extends).  f32 (and f32x3) and bf16 shapes off the 32-wide k step: the VALU form.
 //
+// emoasr_rnnlm_step_rows is the same step for any number of rows in one call: the SAME kernel bodies compiled
+// with ROWS = true take their tile of 16 / 32 rows from blockIdx.y and form the control words themselves from the batched joint
+// search's arrays -- input row ids[r], source slot src_base + parent[r] (a parent outside the call's rows: the zero state), destination
+// slot dst_base + r -- so that no host-made index list is needed between two captured steps.  A row's arithmetic does not depend on
+// its tile or on the other rows: it gets the bits emoasr_rnnlm_step gives it.  The head's raw f32 logits are the output (the joint
+// search's score kernel forms the log-softmax).
+//
 // Rounding follows the sequence forward (emoasr_amd/recurrence.py): products accumulate in f32, the input projection + bias is rounded
 // to the compute dtype, the recurrent product is added to it and rounded again, h is stored in the compute dtype, c in f32.
 #include <math.h>
@@ -38,13 +45,25 @@ struct LmLayerArgs {
   void* ph; float* pc;                // this layer's state pools [slots][H] (T / f32)
   const int *src, *dst;
   void* hrow;                         // top layer: compact [nb][H] copy of the new h (else NULL)
+  // ROWS: nb rows in tiles on blockIdx.y; xidx = ids (layer 0) or NULL (the layer below's new h at dst_base + r)
+  const int* parent; int src_base, dst_base;
 };
 
 // control words of one call, read once: index of the input row / source slot (-1: zeros) / destination slot (-1: dropped).
 // Out-of-range indices are turned into -1 here, so no later access leaves its array.
-__device__ __forceinline__ void load_cw(const LmLayerArgs& a, int (*cw)[NBMAX], int tid) {
-  if (tid < a.nb) {
-    const int x = a.xidx[tid], s = a.src[tid], d = a.dst[tid];
+// ROWS: the words of rows r0 .. r0 + nb - 1 formed from (ids, parent, src_base, dst_base)
+template <bool ROWS>
+__device__ __forceinline__ void load_cw(const LmLayerArgs& a, int (*cw)[NBMAX], int tid, int r0, int nb) {
+  if (tid < nb) {
+    int x, s, d;
+    if constexpr (ROWS) {
+      const int r = r0 + tid, p = a.parent[r];
+      d = a.dst_base + r;
+      x = a.xidx ? a.xidx[r] : d;
+      s = (p >= 0 && p < a.nb) ? a.src_base + p : -1;
+    } else {
+      x = a.xidx[tid]; s = a.src[tid]; d = a.dst[tid];
+    }
     cw[0][tid] = (x >= 0 && x < a.xrows) ? x : -1;
     cw[1][tid] = (s >= 0 && s < a.slots) ? s : -1;
     cw[2][tid] = (d >= 0 && d < a.slots) ? d : -1;
@@ -52,8 +71,8 @@ __device__ __forceinline__ void load_cw(const LmLayerArgs& a, int (*cw)[NBMAX], 
 }
 
 template <typename T>
-__device__ __forceinline__ void cell_store(const LmLayerArgs& a, const int (*cw)[NBMAX], int i, int uu, float g_i, float g_f, float g_g,
-                                           float g_o) {
+__device__ __forceinline__ void cell_store(const LmLayerArgs& a, const int (*cw)[NBMAX], int i, int hi, int uu, float g_i, float g_f,
+                                           float g_g, float g_o) {
   const float ig = sigmoid_t<T>(g_i), fg = sigmoid_t<T>(g_f), gg = tanh_t<T>(g_g), og = sigmoid_t<T>(g_o);
   const int s = cw[1][i], d = cw[2][i];
   const float cn = fg * (s >= 0 ? a.pc[(long)s * a.H + uu] : 0.f) + ig * gg;
@@ -62,21 +81,22 @@ __device__ __forceinline__ void cell_store(const LmLayerArgs& a, const int (*cw)
     a.pc[(long)d * a.H + uu] = cn;
     static_cast<T*>(a.ph)[(long)d * a.H + uu] = h;
   }
-  if (a.hrow) static_cast<T*>(a.hrow)[(long)i * a.H + uu] = h;
+  if (a.hrow) static_cast<T*>(a.hrow)[(long)hi * a.H + uu] = h;   // hi: the row of the call (its tile's first row + i)
 }
 
 // ---- VALU form: grid = H / UN workgroups; row group grp <-> gate grp / UN, unit u0 + grp % UN; NB = 16 or 32 rows of LDS
-template <typename T, int NB>
+template <typename T, int NB, bool ROWS>
 __global__ __launch_bounds__(BT) void rnnlm_layer_kernel(const LmLayerArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nb = a.nb, nin = a.nin, H = a.H, tid = threadIdx.x, grp = tid >> 3, sub = tid & 7;
+  const int r0 = ROWS ? blockIdx.y * NB : 0, nb = ROWS ? min(NB, a.nb - r0) : a.nb;
+  const int nin = a.nin, H = a.H, tid = threadIdx.x, grp = tid >> 3, sub = tid & 7;
   float* xs = reinterpret_cast<float*>(smem);          // [NB][nin]
   float* hs = xs + NB * nin;                           // [NB][H]
   float* gs = hs + NB * H;                             // [NB][4 UN]
   const T* xtab = static_cast<const T*>(a.xtab);
   const T* ph = static_cast<const T*>(a.ph);
   __shared__ int cw[3][NBMAX];
-  load_cw(a, cw, tid);
+  load_cw<ROWS>(a, cw, tid, r0, nb);
   __syncthreads();
   for (int i = 0; i < nb; ++i) {
     const int x = cw[0][i], s = cw[1][i];
@@ -104,7 +124,7 @@ __global__ __launch_bounds__(BT) void rnnlm_layer_kernel(const LmLayerArgs a) {
   for (int e = tid; e < nb * UN; e += BT) {
     const int i = e / UN, j = e % UN;
     const float* g4 = gs + i * (4 * UN);
-    cell_store<T>(a, cw, i, blockIdx.x * UN + j, g4[j], g4[UN + j], g4[2 * UN + j], g4[3 * UN + j]);
+    cell_store<T>(a, cw, i, r0 + i, blockIdx.x * UN + j, g4[j], g4[UN + j], g4[2 * UN + j], g4[3 * UN + j]);
   }
 }
 
@@ -128,11 +148,12 @@ __device__ __forceinline__ void rows16_dot_tiles(const bf16* __restrict__ wrow0,
   }
 }
 
-template <int NT>
+template <int NT, bool ROWS>
 __global__ __launch_bounds__(BT) void rnnlm_layer_mfma_kernel(const LmLayerArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NR = 16 * NT;
-  const int nb = a.nb, nin = a.nin, H = a.H, tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int r0 = ROWS ? blockIdx.y * NR : 0, nb = ROWS ? min(NR, a.nb - r0) : a.nb;
+  const int nin = a.nin, H = a.H, tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
   const int ldx = nin + 8, ldh = H + 8;
   bf16* xs = reinterpret_cast<bf16*>(smem);                 // [NR][nin + 8]
   bf16* hs = xs + NR * ldx;                                 // [NR][H + 8]
@@ -140,7 +161,7 @@ __global__ __launch_bounds__(BT) void rnnlm_layer_mfma_kernel(const LmLayerArgs 
   const bf16* xtab = static_cast<const bf16*>(a.xtab);
   const bf16* ph = static_cast<const bf16*>(a.ph);
   __shared__ int cw[3][NBMAX];
-  load_cw(a, cw, tid);
+  load_cw<ROWS>(a, cw, tid, r0, nb);
   __syncthreads();
   // stage the inputs in 16-byte pieces; zero rows for hypotheses >= nb, absent input rows and the zero state
   for (int p = tid; p < NR * (nin / 8); p += BT) {
@@ -179,7 +200,7 @@ __global__ __launch_bounds__(BT) void rnnlm_layer_mfma_kernel(const LmLayerArgs 
   for (int e = tid; e < nb * 16; e += BT) {
     const int i = e / 16, j = e % 16;
     const float* g4 = gs + i * 64;
-    cell_store<bf16>(a, cw, i, u0 + j, g4[j], g4[16 + j], g4[32 + j], g4[48 + j]);
+    cell_store<bf16>(a, cw, i, r0 + i, u0 + j, g4[j], g4[16 + j], g4[32 + j], g4[48 + j]);
   }
 }
 
@@ -225,17 +246,20 @@ int set_lds(K kernel, size_t bytes, size_t* granted) {
   return 0;
 }
 
+// ROWS: a.nb rows in tiles of 16 (a.nb <= 16: one tile) or 32 on blockIdx.y
+template <bool ROWS>
 int launch_layer(int dtype, const LmLayerArgs& a, hipStream_t s) {
   const int two = a.nb > 16;
+  const unsigned tiles = ROWS ? (a.nb + (two ? 32 : 16) - 1) / (two ? 32 : 16) : 1;
   if (mfma_ok(dtype, a.nin, a.H)) {
     const size_t sm = mfma_lds(two ? 2 : 1, a.nin, a.H);
     static size_t g1 = 0, g2 = 0;
     if (two) {
-      if (set_lds(rnnlm_layer_mfma_kernel<2>, sm, &g2)) return 1;
-      rnnlm_layer_mfma_kernel<2><<<a.H / 16, BT, sm, s>>>(a);
+      if (set_lds(rnnlm_layer_mfma_kernel<2, ROWS>, sm, &g2)) return 1;
+      rnnlm_layer_mfma_kernel<2, ROWS><<<dim3(a.H / 16, tiles), BT, sm, s>>>(a);
     } else {
-      if (set_lds(rnnlm_layer_mfma_kernel<1>, sm, &g1)) return 1;
-      rnnlm_layer_mfma_kernel<1><<<a.H / 16, BT, sm, s>>>(a);
+      if (set_lds(rnnlm_layer_mfma_kernel<1, ROWS>, sm, &g1)) return 1;
+      rnnlm_layer_mfma_kernel<1, ROWS><<<dim3(a.H / 16, tiles), BT, sm, s>>>(a);
     }
     EMO_LAUNCH_CHECK();
     return 0;
@@ -244,11 +268,11 @@ int launch_layer(int dtype, const LmLayerArgs& a, hipStream_t s) {
   EMO_DISPATCH(dtype, {
     static size_t g1 = 0, g2 = 0;
     if (two) {
-      if (set_lds(rnnlm_layer_kernel<T, 32>, sm, &g2)) return 1;
-      rnnlm_layer_kernel<T, 32><<<a.H / UN, BT, sm, s>>>(a);
+      if (set_lds(rnnlm_layer_kernel<T, 32, ROWS>, sm, &g2)) return 1;
+      rnnlm_layer_kernel<T, 32, ROWS><<<dim3(a.H / UN, tiles), BT, sm, s>>>(a);
     } else {
-      if (set_lds(rnnlm_layer_kernel<T, 16>, sm, &g1)) return 1;
-      rnnlm_layer_kernel<T, 16><<<a.H / UN, BT, sm, s>>>(a);
+      if (set_lds(rnnlm_layer_kernel<T, 16, ROWS>, sm, &g1)) return 1;
+      rnnlm_layer_kernel<T, 16, ROWS><<<dim3(a.H / UN, tiles), BT, sm, s>>>(a);
     }
   });
   EMO_LAUNCH_CHECK();
@@ -291,7 +315,8 @@ extern "C" int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, 
     a.pc = pc + (size_t)l * slots * H;
     a.src = src; a.dst = dst;
     a.hrow = l == L - 1 ? hrow : nullptr;
-    if (launch_layer(dtype, a, s)) return 1;
+    a.parent = nullptr; a.src_base = a.dst_base = 0;
+    if (launch_layer<false>(dtype, a, s)) return 1;
   }
   emoasr_epilogue_t ep = {};
   ep.bias = b_out; ep.alpha = 1.f; ep.res_scale = 1.f; ep.out_f32 = 1;
@@ -299,4 +324,46 @@ extern "C" int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, 
   rnnlm_logp_kernel<<<nb, BT, 0, s>>>(V, logits, V, logp, ldlogp, logp_rows, row_dst);
   EMO_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- the step for R rows of the batched joint search ---------------------------------------------------------
+constexpr int ROWS_MAX = 65535 * 16;   // tiles on blockIdx.y
+
+extern "C" int emoasr_rnnlm_step_rows_supported(int dtype, int L, int E, int H) { return emoasr_rnnlm_step_supported(dtype, NBMAX, L, E, H); }
+
+extern "C" long emoasr_rnnlm_step_rows_ws_bytes(int dtype, int R, int H) {
+  const size_t es = dtype == EMO_BF16 ? 2 : 4;
+  return R >= 1 && H >= 1 ? (long)align256((size_t)R * H * es) : 0;
+}
+
+extern "C" int emoasr_rnnlm_step_rows(int dtype, const emoasr_rnnlm_rows_t* rl, const int* ids, const int* parent, void* stream) {
+  EMO_CHECK(rl && ids && parent, "rnnlm_step_rows: missing arguments");
+  const int L = rl->L, E = rl->E, H = rl->H, V = rl->V, R = rl->R, slots = rl->slots;
+  EMO_CHECK(emoasr_rnnlm_step_rows_supported(dtype, L, E, H), "rnnlm_step_rows: L=%d E=%d H=%d outside the kernel's shape plan", L, E, H);
+  EMO_CHECK(R >= 1 && R <= ROWS_MAX && V >= 1 && rl->ldl >= V, "rnnlm_step_rows: R=%d V=%d ldl=%ld", R, V, rl->ldl);
+  EMO_CHECK(rl->emb && rl->w_ih && rl->w_hh && rl->bias && rl->w_out && rl->ph && rl->pc && rl->logits, "rnnlm_step_rows: missing operands");
+  // both slot ranges inside the pools, and apart: another workgroup may still be staging a source slot
+  const long sb = rl->src_base, db = rl->dst_base;
+  EMO_CHECK(sb >= 0 && db >= 0 && sb + R <= slots && db + R <= slots && (sb + R <= db || db + R <= sb),
+            "rnnlm_step_rows: source slots %ld.. and destination slots %ld.. of %d rows in pools of %d slots", sb, db, R, slots);
+  EMO_CHECK(rl->ws && rl->ws_bytes >= emoasr_rnnlm_step_rows_ws_bytes(dtype, R, H), "rnnlm_step_rows: workspace of %ld bytes is too small",
+            rl->ws_bytes);
+  const size_t es = dtype == EMO_BF16 ? 2 : 4;
+  hipStream_t s = (hipStream_t)stream;
+  for (int l = 0; l < L; ++l) {
+    LmLayerArgs a;
+    a.nb = R; a.H = H; a.slots = slots;
+    if (l == 0) { a.nin = E; a.xrows = V; a.xtab = rl->emb; a.ldx = E; a.xidx = ids; }
+    else { a.nin = H; a.xrows = slots; a.xtab = static_cast<char*>(rl->ph) + (size_t)(l - 1) * slots * H * es; a.ldx = H; a.xidx = nullptr; }
+    a.w_ih = rl->w_ih[l]; a.w_hh = rl->w_hh[l]; a.bias = rl->bias[l];
+    a.ph = static_cast<char*>(rl->ph) + (size_t)l * slots * H * es;
+    a.pc = rl->pc + (size_t)l * slots * H;
+    a.src = a.dst = nullptr;
+    a.parent = parent; a.src_base = rl->src_base; a.dst_base = rl->dst_base;
+    a.hrow = l == L - 1 ? rl->ws : nullptr;
+    if (launch_layer<true>(dtype, a, s)) return 1;
+  }
+  emoasr_epilogue_t ep = {};
+  ep.bias = rl->b_out; ep.alpha = 1.f; ep.res_scale = 1.f; ep.out_f32 = 1;
+  return emoasr_gemm_nt(dtype, R, V, H, rl->ws, H, rl->w_out, H, rl->logits, rl->ldl, &ep, stream);
 }

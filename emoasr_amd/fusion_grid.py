@@ -13,7 +13,8 @@ best = the first cell whose WER is strictly below every earlier one's, starting 
 
 Attention models (decoder_type == "transformer", any --decode_ctc_weight) go through joint_fusion_grid: one encoder pass and one
 joint_beam_search_device_grid call per batch -- every distinct lm_weight is searched once, the len_weights are an expansion of the
-finished hypotheses' scores.  Transducer models (decoder_type == "rnn_transducer") go through
+finished hypotheses' scores; with an RNN LM the tool sets decoder.joint_rnnlm_impl = "device", so that the LM is
+stepped inside that search (section 26).  Transducer models (decoder_type == "rnn_transducer") go through
 rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25).  The LAS
 search ignores the LM, in the reference and here: no grid for it.
 """
@@ -169,6 +170,22 @@ def grid_of(kind):
                               f"not {kind!r}")
 
 
+def set_joint_rnnlm_impl(decoder, beam_width, lm, decode_ctc_weight):
+    """an attention model with a stateful LM (the RNN LM): decoder.joint_rnnlm_impl = "device", every distinct lm_weight searched in one
+    pass with the LM stepped on the device -- unless beam_search_device.batch_rnnlm_why_not gives a reason: that
+    reason is logged and the switch stays "host" (one host search per utterance and weight).  -> the value set"""
+    from .modeling.beam_search_device import batch_rnnlm_why_not
+    impl = "host"
+    if getattr(lm, "stateful", False):
+        why = batch_rnnlm_why_not(decoder, beam_width, lm, decode_ctc_weight)
+        if why is None:
+            impl = "device"
+        else:
+            logging.info(f"joint_rnnlm_impl stays 'host' (one host search per utterance and lm_weight): {why}")
+    decoder.joint_rnnlm_impl = impl
+    return impl
+
+
 def log_results(results, best):
     """the reference's log lines (test_fusion_grid.py:56-69)"""
     for lm_weight, len_weight, _, wer_info in results:
@@ -232,9 +249,12 @@ def main(args):
     lm = LM(lm_params, phase="test")
     lm.load_state_dict(torch.load(model_path(args.lm_conf, args.lm_ep), map_location="cpu"))
     lm.to(device).eval()
+    beam_width = args.beam_width or params.beam_width
+    if kind == "transformer":
+        set_joint_rnnlm_impl(model.decoder, beam_width, lm, args.decode_ctc_weight)
     dataset = ASRDataset(params, data_path, phase="test")
     lm_weights, len_weights = weight_lists(args.lm_min, args.lm_max, args.lm_step, args.len_min, args.len_max, args.len_step)
-    results, best = grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), args.beam_width or params.beam_width,
+    results, best = grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), beam_width,
                          lm, lm_weights, len_weights, device, eos_id=params.eos_id, decode_ctc_weight=args.decode_ctc_weight)
     log_results(results, best)
     return results, best

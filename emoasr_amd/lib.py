@@ -153,6 +153,13 @@ class JointGridStep(Structure):
                 ("sutt", c_void_p), ("groups", c_void_p), ("mu", c_void_p), ("mu_row", c_void_p)]
 
 
+class RnnlmRows(Structure):
+    _fields_ = [("L", c_int), ("E", c_int), ("H", c_int), ("V", c_int), ("R", c_int), ("emb", c_void_p),
+                ("w_ih", c_void_p), ("w_hh", c_void_p), ("bias", c_void_p), ("w_out", c_void_p), ("b_out", c_void_p),
+                ("ph", c_void_p), ("pc", c_void_p), ("slots", c_int), ("src_base", c_int), ("dst_base", c_int),
+                ("logits", c_void_p), ("ldl", c_long), ("ws", c_void_p), ("ws_bytes", c_long)]
+
+
 class FfnParams(Structure):
     _fields_ = [("ln_g", c_void_p), ("ln_b", c_void_p), ("w1", c_void_p), ("b1", c_void_p),
                 ("w2", c_void_p), ("b2", c_void_p)]
@@ -294,6 +301,8 @@ SIGNATURES = {
     "emoasr_ctc_prefix_score_cells": [I, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, I, P, P, P],
     "emoasr_beam_update_cells": [POINTER(BeamUpdateBatch), P, P],
     "emoasr_joint_beam_grid_step": [I, POINTER(JointGridStep), P],
+    "emoasr_joint_beam_batch_step_rnnlm": [I, POINTER(JointBatchStep), POINTER(RnnlmRows), P],
+    "emoasr_joint_beam_grid_step_rnnlm": [I, POINTER(JointGridStep), POINTER(RnnlmRows), P],
     "emoasr_attn_dropmask": [I, POINTER(AttnArgs), P, I, P],
     "emoasr_attn_fwd": [I, POINTER(AttnArgs), P],
     "emoasr_attn_bwd": [I, POINTER(AttnArgs), P],
@@ -334,6 +343,7 @@ SIGNATURES = {
     "emoasr_rnnt_beam_pick_lm": [I, I, I, I, I, I, I, P, L, P, L, P, P, P, L, P],
     "emoasr_rnnt_beam_gather_rows": [I, I, I, P, L, P, P, P, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
+    "emoasr_rnnlm_step_rows": [I, POINTER(RnnlmRows), P, P, P],
     "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],
     "emoasr_las_attend_bwd": [I, POINTER(LasAttend), P],
     "emoasr_las_dropmask": [POINTER(LasAttend), P, P],

@@ -11,7 +11,8 @@ log-probabilities, log-softmax + fusion, top-k candidate selection, CTC prefix s
 (beam, candidate) with the scorer states kept on the device.  Host side: one small D2H per step
 (candidate ids/scores), then the reference's own list bookkeeping (sort, prune, finish).
 
-A stateful LM (the RNN LM, modeling/rnnlm.py) always takes the host-bookkeeping path: every beam carries the slot of its LM state
+A stateful LM (the RNN LM, modeling/rnnlm.py) takes the host-bookkeeping path here (the batched device search steps it on the device
+under decoder.joint_rnnlm_impl = "device"): every beam carries the slot of its LM state
 (the LSTM run over hyp[:-1], as the reference's `lm_states`, decoders/transformer.py:190,223-253), an output step is ONE LM step
 for all beams from the parents' slots into the other half of a double-buffered slot pool.
 """
@@ -162,8 +163,9 @@ def joint_beam_search_batch(dec, eouts, elens, beam_width, len_weight=0, lm=None
     """the joint search for every utterance of a batch: eouts [B, Tmax, d], utterance b over its own elens[b] frames ->
     (hyps, scores, None, None), hyps[b] / scores[b] the lists joint_beam_search returns for eouts[b:b+1, :elens[b]].
     The batched device search (beam_search_device.joint_beam_search_device_batch: all searches in lockstep) takes it when it
-    can; a stateful LM (the RNN LM), beam_width or a candidate width above 32, and the switches that force the host
-    bookkeeping fall back to one joint_beam_search per utterance."""
+    can; a stateful LM (the RNN LM) under dec.joint_rnnlm_impl = "host", beam_width or a candidate width above 32, and the switches
+    that force the host bookkeeping fall back to one joint_beam_search per utterance.  joint_rnnlm_impl = "device" steps the RNN LM
+    inside the batched device search and raises ValueError where that form cannot take the configuration."""
     require_next_token_lm(lm, lm_weight)
     lens = [int(n) for n in elens]
     if len(lens) != eouts.shape[0] or any(n < 1 for n in lens):

@@ -316,7 +316,9 @@ def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=Non
 # rows s * W .. s * W + W - 1 of every per-hypothesis array and step in lockstep: one captured step serves all of them, a
 # finished search keeps its rows (computed and ignored).  Kernels: csrc/decode_batch.hip (grouped cross-attention over the
 # unreplicated memories, one bookkeeping workgroup per search), the ragged CTC prefix scorer (csrc/decoder.hip) and the
-# chain emoasr_joint_beam_batch_step (csrc/decode_rt.hip).
+# chain emoasr_joint_beam_batch_step (csrc/decode_rt.hip).  A stateful LM (the RNN LM) under decoder.joint_rnnlm_impl = "device" is
+# stepped inside the same chain: emoasr_rnnlm_step_rows over all S * W rows, its state in a double-buffered
+# slot pool addressed by the chain's own parent array, through emoasr_joint_beam_batch_step_rnnlm / _grid_step_rnnlm.
 # ---------------------------------------------------------------------------------------------------------------------------
 MAX_ROWS = 1024                     # S * W rows of one chunk
 GRID_BUFFER_SETS = 3                # buffer sets the fusion grid keeps (one per chunk shape)
@@ -337,8 +339,53 @@ def batch_chunk_capacity(W, Lmax, dnl, dd, lnl, ld, esz, budget=None, max_rows=N
     return max(1, min(max_rows // W, budget // per_search))
 
 
+def joint_rnnlm_impl(dec):
+    """the decoder's switch for a stateful LM in the batched searches: "host" (default) or "device"; anything else is refused"""
+    impl = getattr(dec, "joint_rnnlm_impl", "host")
+    if impl not in ("host", "device"):
+        raise ValueError(f"emoasr_amd: joint_rnnlm_impl is 'host' or 'device', not {impl!r}")
+    return impl
+
+
+def batch_rnnlm_why_not(dec, beam_width, lm, decode_ctc_weight):
+    """why the batched device search cannot fuse this LM through emoasr_rnnlm_step_rows (None: it can)"""
+    if getattr(lm, "lm_type", None) != "rnn":
+        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
+    V = dec.vocab_size
+    if lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
+        return f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
+    eng = _engine_of(dec)
+    if lm.compute_dtype != eng.dtype or bool(lm.f32_split) != bool(eng.split):
+        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
+    code = lib.F32X3 if lm.f32_split else {torch.float32: lib.F32, torch.bfloat16: lib.BF16}.get(lm.compute_dtype)
+    if code is None or lib.size_query("emoasr_rnnlm_step_rows_supported", code, lm.L, lm.E, lm.H) != 1:
+        return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnlm_step_rows' shape plan"
+    cw = min(V, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if decode_ctc_weight > 0 else beam_width
+    if not (1 <= beam_width <= 32 and 1 <= cw <= 32 and beam_width <= V):
+        return f"beam_width {beam_width} (candidate width {cw}, vocabulary {V}) is outside the device bookkeeping's 32 beams x 32 candidates"
+    for env in ("EMOASR_DEVICE_BEAM", "EMOASR_CPP_DECODE"):
+        if os.environ.get(env, "1") == "0":
+            return f"{env}=0 forces the host bookkeeping"
+    return None
+
+
+def rnnlm_on_device(dec, beam_width, lm, lm_weight, decode_ctc_weight):
+    """does a stateful LM go through the batched device search?  Exactly when the decoder's joint_rnnlm_impl says "device" -- then a
+    configuration the device form cannot take is a ValueError naming the reason, never a quiet detour through the host form.  False
+    without an LM to fuse and for an LM without state (the Transformer LM: the switch does not touch it)."""
+    impl = joint_rnnlm_impl(dec)
+    if lm is None or lm_weight <= 0 or not getattr(lm, "stateful", False) or impl != "device":
+        return False
+    why = batch_rnnlm_why_not(dec, beam_width, lm, decode_ctc_weight)
+    if why is not None:
+        raise ValueError(f"emoasr_amd: joint_rnnlm_impl = 'device' cannot fuse this LM: {why}")
+    return True
+
+
 def batch_device_ok(dec, beam_width, lm, lm_weight, decode_ctc_weight):
     """whether the batched device search takes this configuration (else: utterance by utterance through joint_beam_search)"""
+    if rnnlm_on_device(dec, beam_width, lm, lm_weight, decode_ctc_weight):
+        return True
     use_ctc = decode_ctc_weight > 0
     cw = min(dec.vocab_size, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if use_ctc else beam_width
     if os.environ.get("EMOASR_DEVICE_BEAM", "1") == "0" or os.environ.get("EMOASR_CPP_DECODE", "1") == "0":
@@ -352,7 +399,7 @@ class _BatchBuffers:
     """device buffers of one (S, W, cw, Lmax, model sizes, frame capacities) configuration, reused across calls: the captured
     steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`)."""
 
-    def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid=False):
+    def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid=False, rnn=None):
         nb = S * W
         self.rows_cap, self.Tcap = rows_cap, Tcap
         i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
@@ -375,7 +422,10 @@ class _BatchBuffers:
         self.score_ctc = f32(nb)
         self.vals, self.cands, self.lm_at, self.psi = f32(nb, cw), i32(nb, cw), f32(nb, cw), f32(nb, cw)
         self.logits = torch.zeros(nb, V, device=dev, dtype=dtype)
-        self.lm_logp = f32(nb, V) if lnl else None
+        self.lm_logp = f32(nb, V) if (lnl or rnn) else None
+        # a stateful LM (rnn = (L, H); section 26): slot pools of two halves (previous / current step), no K / V pools
+        self.lm_h = torch.zeros(rnn[0], 2 * nb, rnn[1], device=dev, dtype=dtype) if rnn else None
+        self.lm_c = f32(rnn[0], 2 * nb, rnn[1]) if rnn else None
         self.dec_k = torch.zeros(2, dnl, nb, Lmax, dd, device=dev, dtype=dtype)
         self.dec_v = torch.zeros_like(self.dec_k)
         self.lm_k = torch.zeros(2, max(lnl, 1), nb, Lmax, max(ld, 1), device=dev, dtype=dtype) if lnl else None
@@ -433,7 +483,13 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
         dd, dh, F = eng.dd, eng.dh, rt._F
         lnl = ld = lH = lF = 0
         lm_guard = None
-        if use_lm:
+        rnn = None      # a stateful LM: (L, H) of its slot pools
+        if use_lm and getattr(lm, "stateful", False):
+            LA = lm._prepare()       # (arena bound, compute-dtype weights and the summed biases current: before the capture)
+            assert lm.V == V and LA.shadow.dtype == dtype
+            rnn = (lm.L, lm.H)
+            lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr()) + tuple(b.data_ptr() for b in lm._bias)
+        elif use_lm:
             lmrt = getattr(lm, "_step_rt", None)
             if lmrt is None:
                 lmrt = lm._step_rt = LMStepRuntime(lm)
@@ -444,7 +500,7 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             assert lm._pe.shape[0] >= Lmax, "LM position table shorter than max_decode_ylen + 1"
             lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._pe.data_ptr())
         # one set of buffers is kept: reused while the sizes match and the frame capacities suffice
-        key = (str(dev), dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, use_ctc, grid is not None)
+        key = (str(dev), dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, use_ctc, grid is not None, rnn)
         cache = getattr(eng, "_beam_batch_bufs", None)
         if grid:      # the grid alternates between a few chunk shapes (and the search without the LM): one set of buffers each
             sets = getattr(eng, "_beam_grid_bufs", None)
@@ -455,13 +511,13 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             Bf = cache[1]
             rows_cap, Tcap = Bf.rows_cap, Bf.Tcap
         elif grid:
-            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, True)
+            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, True, rnn)
             sets.pop(key, None)
             while len(sets) >= GRID_BUFFER_SETS:
                 sets.pop(next(iter(sets)))
             sets[key] = Bf
         else:
-            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid is not None)
+            Bf = _BatchBuffers(dev, dtype, S, W, cw, Lmax, V, eng.dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid is not None, rnn)
             eng._beam_batch_bufs = (key, Bf)
         # ---- this call's inputs, into the buffers the captured steps read ----
         Bf.moff[:U + 1].copy_(h2d_i32(rt.moff_host, dev))
@@ -488,12 +544,19 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             mu = 0.0
         gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), lm_guard, tuple(k.data_ptr() for k in rt.kv_group), lam, mu if use_lm else 0.0,
                 float(len_weight), eos, blank, id(Bf), (U, len(groups), group_rows) if grid else None)
-        step_fn = "emoasr_joint_beam_grid_step" if grid else "emoasr_joint_beam_batch_step"
+        step_fn = ("emoasr_joint_beam_grid_step" if grid else "emoasr_joint_beam_batch_step") + ("_rnnlm" if rnn else "")
         if Bf.graphs is None or Bf.graphs[0] != gkey:
             dt_code = ops.dt(Bf.logits)
             ws_dec = torch.empty(lib.size_query("emoasr_decode_step_group_ws_bytes", dt_code, nb, dd, dh, F, V), device=dev, dtype=torch.uint8)
             ws_lm = torch.empty(lib.size_query("emoasr_decode_step_ws_bytes", dt_code, nb, max(ld, 8), max(lH, 1), max(lF, 8), V),
-                                device=dev, dtype=torch.uint8) if use_lm else None
+                                device=dev, dtype=torch.uint8) if (use_lm and not rnn) else None
+            if rnn:      # the stateful LM's step over the chain's rows: weight tables (host arrays of device pointers) and workspace
+                ws_lm = torch.empty(lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", dt_code, nb, lm.H), device=dev, dtype=torch.uint8)
+                ptrs = ctypes.c_void_p * lm.L
+                lm_w = [lm._w(l) for l in range(lm.L)]
+                lm_tabs = (ptrs(*[w[0].data_ptr() for w in lm_w]), ptrs(*[w[1].data_ptr() for w in lm_w]),
+                           ptrs(*[b.data_ptr() for b in lm._bias]))
+            rows = []
             pe_dec = eng._abs_table(Lmax, dev, dd)
             steps = []
             for cur in (0, 1):
@@ -519,7 +582,18 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 d.logits_last, d.ws, d.ws_bytes = Bf.logits.data_ptr(), ws_dec.data_ptr(), ws_dec.numel()
                 js.dec_k_prev, js.dec_v_prev = Bf.dec_k[prev].data_ptr(), Bf.dec_v[prev].data_ptr()
                 js.lm_nl = lnl if use_lm else 0
-                if use_lm:
+                if rnn:      # the even step reads half 1 of the pools and writes half 0, the odd step the reverse
+                    rl = lib.RnnlmRows()
+                    rl.L, rl.E, rl.H, rl.V, rl.R = lm.L, lm.E, lm.H, V, nb
+                    rl.emb = LA.w("lm.embed.weight").data_ptr()
+                    rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, ctypes.c_void_p) for t in lm_tabs)
+                    rl.w_out, rl.b_out = LA.w("lm.output.weight").data_ptr(), LA.p("lm.output.bias").data_ptr()
+                    rl.ph, rl.pc, rl.slots = Bf.lm_h.data_ptr(), Bf.lm_c.data_ptr(), 2 * nb
+                    rl.src_base, rl.dst_base = prev * nb, cur * nb
+                    rl.logits, rl.ldl = Bf.lm_logp.data_ptr(), V
+                    rl.ws, rl.ws_bytes = ws_lm.data_ptr(), ws_lm.numel()
+                    rows.append(rl)
+                elif use_lm:
                     js.lm_layers = lm_layers
                     l = js.lm
                     pre, cp = "lm.transformer.bert.", "lm.transformer.cls.predictions."
@@ -560,19 +634,23 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             # warm-up with every search marked finished (the bookkeeping returns at once, the networks run on valid rows):
             # every kernel's lazy one-time setup happens outside the capture.  Then each step is captured once: a linear
             # chain on one stream.
+            step_args = lambda k: (dt_code, ctypes.byref(steps[k])) + ((ctypes.byref(rows[k]),) if rnn else ()) + (ops._stream(),)
             reset(1)
             for k in (0, 1):
-                lib.call(step_fn, dt_code, ctypes.byref(steps[k]), ops._stream())
+                lib.call(step_fn, *step_args(k))
             torch.cuda.current_stream().synchronize()
             graphs = []
             for k in (0, 1):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
-                    lib.call(step_fn, dt_code, ctypes.byref(steps[k]), ops._stream())
+                    lib.call(step_fn, *step_args(k))
                 graphs.append(g)
-            Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group))
+            Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group, rows, lm_tabs if rnn else None))
         graphs = Bf.graphs[1]
         reset(0)
+        if rnn:       # (after the warm-up, whose steps write both halves) step 0 reads "previous" = half 1 at the search's row 0: zeros
+            Bf.lm_h[:, nb:].zero_()
+            Bf.lm_c[:, nb:].zero_()
         if use_ctc:   # (after the warm-up, whose steps write both halves of the scorer states)
             # step 0 reads "previous" = half 1 at (the search's row 0, candidate 0)
             if grid:
@@ -668,9 +746,10 @@ def joint_beam_search_device_batch(dec, eouts, elens, beam_width, len_weight=0, 
     use_lm = lm is not None and lm_weight > 0
     cw = min(dec.vocab_size, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if use_ctc else beam_width
     assert 1 <= beam_width <= 32 and 1 <= cw <= 32, "device beam bookkeeping handles up to 32 beams x 32 candidates"
-    assert not use_lm or hasattr(lm, "predict_device"), "the batched search fuses the Transformer LM only"
+    stateful = use_lm and rnnlm_on_device(dec, beam_width, lm, lm_weight, decode_ctc_weight)
+    assert not use_lm or stateful or hasattr(lm, "predict_device"), "the batched search fuses the Transformer LM, or the RNN LM by its switch"
     esz = 2 if eouts.dtype == torch.bfloat16 else 4
-    lnl, ld = (lm.params.num_layers, lm.params.hidden_size) if use_lm else (0, 0)
+    lnl, ld = (lm.params.num_layers, lm.params.hidden_size) if (use_lm and not stateful) else (0, 0)    # (a stateful LM: no K / V pools)
     cap = batch_chunk_capacity(beam_width, dec.max_decode_ylen + 1, eng.dnl, eng.dd, lnl, ld, esz)
     hyps, scores = [], []
     for b0 in range(0, B, cap):
@@ -778,7 +857,8 @@ def joint_beam_search_device_grid(dec, eouts, elens, beam_width, lm, lm_weights,
                 for i in range(len(n)):
                     found[b0 + i][k] = (h[i], s[i])
         if positive:
-            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, lm.params.num_layers, lm.params.hidden_size, esz)
+            lnl, ld = (0, 0) if getattr(lm, "stateful", False) else (lm.params.num_layers, lm.params.hidden_size)
+            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, lnl, ld, esz)
             for chunk in grid_chunk_plan(B, len(positive), cap):
                 utts = sorted({b for b, _, _ in chunk})
                 local = {b: i for i, b in enumerate(utts)}

@@ -3,6 +3,18 @@
     decoder(eouts, elens, eouts_inter, ys, ylens, ys_in, ys_out) -> (loss, loss_dict, logits)
     decoder(eouts, elens, ..., ys_in=ys_in, ys_out=None)         -> logits
     decoder.decode(eouts, elens, eouts_inter, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)
+
+Shallow fusion with a stateful LM (the RNN LM, lm_type "rnn") in the batched search -- several utterances, or one under
+joint_beam_impl = "batch" -- follows decoder.joint_rnnlm_impl:
+    "host"    (default) one joint_beam_search per utterance with the host bookkeeping: one lm.step, a few device-to-host copies and
+              a Python sort per output step and utterance;
+    "device"  the LM is stepped inside the captured chain of the batched device search (emoasr_rnnlm_step_rows over all S * W rows,
+              its state in slot pools addressed by the chain's own parent array); joint_beam_search_device_grid then searches every
+              distinct lm_weight of a fusion grid in one pass.  A configuration this form cannot take -- beam_search_device.
+              batch_rnnlm_why_not: another vocabulary or compute dtype than the model's, sizes outside the step kernel's plan, more than
+              32 beams or candidates, the switches that force the host bookkeeping -- is a ValueError naming the reason, never a quiet
+              detour through the host form.
+A Transformer LM is not touched by the switch.  Any other value is a ValueError.
 """
 import torch.nn as nn
 
@@ -33,6 +45,9 @@ class TransformerDecoder(nn.Module):
         # the joint search of ONE utterance: "single" (joint_beam_search) or "batch" (the batched device search with one search in it;
         # DESIGN.md section 21).  Several utterances always take the batched search.
         self.joint_beam_impl = "single"
+        # a stateful LM (the RNN LM) in the batched searches: "host" (one single search per utterance) or "device" (stepped inside the
+        # batched device search; see the module docstring).  A plain attribute: not a parameter, not saved.
+        self.joint_rnnlm_impl = "host"
         self._owner = None
 
     def forward(self, eouts, elens, eouts_inter=None, ys=None, ylens=None, ys_in=None, ys_out=None,
@@ -60,6 +75,8 @@ class TransformerDecoder(nn.Module):
         from .. import beam_search as bs
         if self.joint_beam_impl not in ("single", "batch"):
             raise ValueError(f"joint_beam_impl {self.joint_beam_impl!r}: 'single' or 'batch'")
+        if self.joint_rnnlm_impl not in ("host", "device"):
+            raise ValueError(f"emoasr_amd: joint_rnnlm_impl is 'host' or 'device', not {self.joint_rnnlm_impl!r}")
         B = eouts.shape[0]
         if B == 1 and self.joint_beam_impl == "single":
             return bs.joint_beam_search(self, eouts, elens, beam_width, len_weight, lm, lm_weight, decode_ctc_weight)

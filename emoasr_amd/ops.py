@@ -1734,6 +1734,38 @@ def rnnlm_step(W, nb, ids, ph, pc, src, dst, logp, row_dst=None):
              logp.shape[0], _p(row_dst), _p(W.ws), W.ws_bytes, _stream())
 
 
+def rnnlm_step_rows_supported(x, L, E, H):
+    """does emoasr_rnnlm_step_rows take an L-layer LSTM LM (embedding E, hidden H) in x's dtype?  (the step kernel's plan at 32 rows)"""
+    return lib.size_query("emoasr_rnnlm_step_rows_supported", dt(x), L, E, H) == 1
+
+
+def rnnlm_step_rows(W, R, ids, parent, ph, pc, src_base, dst_base, logits):
+    """the step for any R >= 1 rows in one call (csrc/rnnlm.hip): row r consumes ids[r] from the state in slot
+    src_base + parent[r] (a parent outside 0 .. R - 1: the zero state) and writes its new state to slot dst_base + r; ids / parent int32
+    [>= R] on the device; the two slot ranges lie inside ph / pc [L, slots, H] and do not overlap.  The RAW f32 logits of row r go to
+    logits[r] (f32 [>= R, >= V], row stride allowed).  W: RnnlmStepWeights"""
+    emb, _, _, _, w_out, b_out = W.tensors
+    L, slots, H = ph.shape
+    assert L == W.L and H == W.H and pc.shape == ph.shape and ph.is_contiguous() and pc.is_contiguous()
+    assert ph.dtype == emb.dtype and logits.stride(1) == 1 and logits.shape[1] >= W.V and logits.shape[0] >= R
+    for t in (ids, parent):
+        assert t.dtype == torch.int32 and t.numel() >= R and t.is_cuda
+    ws = getattr(W, "ws_rows", None)
+    need = lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", _DT[emb.dtype], R, H)
+    if ws is None or ws.numel() < need:
+        ws = W.ws_rows = torch.empty(need, device=emb.device, dtype=torch.uint8)
+    rl = lib.RnnlmRows()
+    rl.L, rl.E, rl.H, rl.V, rl.R = L, W.E, H, W.V, R
+    rl.emb = emb.data_ptr()
+    rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, c_void_p) for t in (W.p_ih, W.p_hh, W.p_b))
+    rl.w_out, rl.b_out = w_out.data_ptr(), b_out.data_ptr()
+    rl.ph, rl.pc, rl.slots = ph.data_ptr(), _chk(pc, torch.float32).data_ptr(), slots
+    rl.src_base, rl.dst_base = src_base, dst_base
+    rl.logits, rl.ldl = _chk(logits, torch.float32).data_ptr(), logits.stride(0)
+    rl.ws, rl.ws_bytes = ws.data_ptr(), ws.numel()
+    lib.call("emoasr_rnnlm_step_rows", dt(emb), ctypes.byref(rl), _p(ids), _p(parent), _stream())
+
+
 # ---- LAS decoder: location-aware attention, one position (csrc/las.hip) -------------------------------------------
 LAS_MAX_ATTN_DIM = 512
 

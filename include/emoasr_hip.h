@@ -736,6 +736,26 @@ int emoasr_rnnlm_step(int dtype, int nb, int L, int E, int H, int V, int slots, 
                       const void* const* w_ih, const void* const* w_hh, const float* const* bias, void* ph, float* pc,
                       const int* src, const int* dst, const void* w_out, const float* b_out, float* logp, long ldlogp,
                       int logp_rows, const int* row_dst, void* ws, long ws_bytes, void* stream);
+/* The same step for any R >= 1 rows in ONE call (L layer launches with the tiles of 32 rows on blockIdx.y, one emoasr_gemm_nt), addressed
+ * by the arrays of the batched joint search: row r reads the embedding of ids[r], the state at slot src_base +
+ * parent[r] (parent: GLOBAL rows, as emoasr_beam_update_batch writes n_parent; a parent outside 0 .. R - 1: the zero state) and writes
+ * the new state at slot dst_base + r.  The R source slots and the R destination slots lie inside the pools and do not overlap (the
+ * two halves of a double-buffered pool: src_base / dst_base in {0, R}, slots = 2 R).  Every row gets the bits emoasr_rnnlm_step
+ * gives it.  The RAW f32 logits output(h_top) + b_out go to logits [R][ldl] (no log-softmax: emoasr_beam_scores_topk forms it); ws:
+ * emoasr_rnnlm_step_rows_ws_bytes(dtype, R, H) bytes.  ids / parent are int32 DEVICE arrays [R], the weight tables HOST arrays of L
+ * device pointers; the call can be captured into a graph.  emoasr_rnnlm_step_rows_supported: emoasr_rnnlm_step_supported at 32 rows. */
+typedef struct emoasr_rnnlm_rows {
+  int L, E, H, V, R;
+  const void* emb;                               /* [V][E] */
+  const void* const* w_ih; const void* const* w_hh; const float* const* bias;
+  const void* w_out; const float* b_out;         /* [V][H], f32 [V] */
+  void* ph; float* pc; int slots, src_base, dst_base;
+  float* logits; long ldl;
+  void* ws; long ws_bytes;
+} emoasr_rnnlm_rows_t;
+int emoasr_rnnlm_step_rows_supported(int dtype, int L, int E, int H);
+long emoasr_rnnlm_step_rows_ws_bytes(int dtype, int R, int H);
+int emoasr_rnnlm_step_rows(int dtype, const emoasr_rnnlm_rows_t* rl, const int* ids, const int* parent, void* stream);
 
 /* ---- LAS decoder: location-aware additive attention, one decoder position (decoders/las.py:289-342; csrc/las.hip) ----
  *   f[t][c] = Conv1d(1, 10, 201, padding 100, no bias)(aw_prev)[c][t]
@@ -1248,6 +1268,12 @@ typedef struct emoasr_joint_grid_step {
   const float* mu; const float* mu_row;
 } emoasr_joint_grid_step_t;
 int emoasr_joint_beam_grid_step(int dtype, const emoasr_joint_grid_step_t* gs, void* stream);
+/* The two chains above with the stateful RNN LM in place of the Transformer LM: js.lm_nl must be 0 (js.lm and
+ * the LM's cache pointers are not read); emoasr_rnnlm_step_rows(rl, ids = js.dec.d.ids, parent = js.parent) takes the place of the
+ * LM's cache gather and emoasr_bert_lm_step, rl->logits (raw f32, rl->R = the chain's rows, rl->V = the decoder's V) is the `lm`
+ * operand of emoasr_beam_scores_topk (weight js.upd.u.mu) / _rows (weight gs->mu_row). */
+int emoasr_joint_beam_batch_step_rnnlm(int dtype, const emoasr_joint_batch_step_t* js, const emoasr_rnnlm_rows_t* rl, void* stream);
+int emoasr_joint_beam_grid_step_rnnlm(int dtype, const emoasr_joint_grid_step_t* gs, const emoasr_rnnlm_rows_t* rl, void* stream);
 
 /* ---- the LAS beam search for S utterances at once (csrc/las_beam.hip).  Rows as above: search s owns
  * rows s * W .. s * W + W - 1; `state` is the array emoasr_beam_update_batch keeps, `parent` its n_parent (GLOBAL rows).  A row at

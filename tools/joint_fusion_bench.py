@@ -17,7 +17,14 @@ The sizes of tools/joint_beam_bench.py: bench.py's config-4 model (`L3`: V = 100
       searches of the grid call's largest chunk;
   (e) the grid call with 1 .. 32 // W searches per attention workgroup, in one process, alternating (each timed call follows an untimed one with the same grouping, which re-captures the step graphs).
 
-The legs alternate repeat by repeat; the median is reported with minimum and maximum.  Prints one JSON line."""
+The legs alternate repeat by repeat; the median is reported with minimum and maximum.  Prints one JSON line.
+
+    python tools/joint_fusion_bench.py --lm rnn [--repeats 5] [--batch 16] [--beam 10] [--steps 36] [--out FILE]
+
+The same grid with the RNN LM of tools/rnnt_fusion_bench.py (2 layers, E = H = 512, bf16, random weights), on
+the same utterances in one process, alternating: (device) joint_beam_search_device_grid under decoder.joint_rnnlm_impl = "device" --
+one pass, the LM stepped inside the captured chain -- and (host) the same call under the default "host": one host search per utterance
+and distinct lm_weight."""
 import argparse
 import json
 import os
@@ -97,6 +104,7 @@ def main():
     ap.add_argument("--steps", type=int, default=36)
     ap.add_argument("--legs", type=str, default="a,b,c,d,e")
     ap.add_argument("--cells-per-group", type=int, default=None, help="searches per attention workgroup in (a); default: the library's")
+    ap.add_argument("--lm", type=str, default="transformer", choices=["transformer", "rnn"])
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
     import torch
@@ -114,7 +122,11 @@ def main():
     dev, sync = torch.device("cuda"), torch.cuda.synchronize
     torch.manual_seed(3)
     model = ASR(SimpleNamespace(**bench.L3), compute_dtype=torch.bfloat16).to(dev).eval()
-    lm = LM(SimpleNamespace(**bench.LM12), compute_dtype=torch.bfloat16).to(dev).eval()
+    if args.lm == "rnn":
+        lm = LM(SimpleNamespace(lm_type="rnn", vocab_size=bench.L3["vocab_size"], embedding_size=512, hidden_size=512, num_layers=2,
+                                dropout_rate=0.0, tie_weights=False), compute_dtype=torch.bfloat16).to(dev).eval()
+    else:
+        lm = LM(SimpleNamespace(**bench.LM12), compute_dtype=torch.bfloat16).to(dev).eval()
     model.engine().ensure_bound()
     dec = model.decoder
     dec.max_decode_ylen = args.steps
@@ -132,6 +144,40 @@ def main():
               "frames": "180..300", "B": B, "W": W, "decode_ctc_weight": lam, "max_decode_ylen": args.steps,
               "grid": f"{len(lm_w)} x {len(len_w)}", "cells_per_group": bsd.GRID_CELLS_PER_GROUP or max(1, 32 // W)}
     box = {}
+    if args.lm == "rnn":
+        why = bsd.batch_rnnlm_why_not(dec, W, lm, lam)
+        if why is not None:
+            raise SystemExit(f"joint_fusion_bench: the device form does not take this configuration: {why}")
+        result["model"] = "bench.py L3 (V=10000, dd=256, 4 heads, 6 layers) + RNN LM (2 layers, E=H=512), bf16, random weights"
+
+        def form(impl):
+            dec.joint_rnnlm_impl = impl
+            box[impl] = bsd.joint_beam_search_device_grid(dec, eouts, lens, W, lm, lm_w, len_w, lam)
+            dec.joint_rnnlm_impl = "host"
+
+        with torch.no_grad():
+            form("device"), form("host"), sync()        # warm-up: code objects, allocator, graph captures
+            samples = {"device": [], "host": []}
+            for _ in range(args.repeats):
+                for impl in ("device", "host"):
+                    sync()
+                    t0 = time.perf_counter()
+                    form(impl)
+                    sync()
+                    samples[impl].append(time.perf_counter() - t0)
+        result["device_grid_ms_per_utt"] = spread(samples["device"], 1e3 / B)
+        result["host_grid_ms_per_utt"] = spread(samples["host"], 1e3 / B)
+        result["host_over_device"] = statistics.median(samples["host"]) / statistics.median(samples["device"])
+        result["device_beyond_the_spread"] = max(samples["device"]) < min(samples["host"])
+        n_cells = len(lm_w) * len(len_w)
+        same = sum(1 for b in range(B) for c in range(n_cells) if box["device"][0][b][c][:1] == box["host"][0][b][c][:1])
+        result["cells_with_the_same_best_hypothesis"] = f"{same} / {B * n_cells}"
+        line = json.dumps(result)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     def grid():
         box["a"] = bsd.joint_beam_search_device_grid(dec, eouts, lens, W, lm, lm_w, len_w, lam)
