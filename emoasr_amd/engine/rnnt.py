@@ -326,6 +326,181 @@ class RNNTDecoder:
             aligns.append(align[:na].tolist())
         return hyps, aligns
 
+    # ---- the batched greedy search in lockstep (csrc/rnnt_greedy_batch.hip) -------------------------------
+    # joint rows per step: S K <= 1024, so a chunk holds 1024 // K searches (128 at K = 8).  What the cap implies at the L4 sizes
+    # (J = 512, V = 1000, bf16): 1 MB of joint rows, 2 MB of logits, 2 S state slots per layer (0.8 MB for two layers), and the
+    # stacked w_enc . eouts + b of the chunk, 1 KB per frame (39 MB for 128 utterances of 300 frames); twice that in f32.
+    _GREEDY_BATCH_ROWS = 1024
+    # frames_per_step and the steps between two reads of the live counter (once ceil(max(elens) / K) steps have run): the fastest
+    # of K = 1 / 2 / 4 / 8 at every batch size and dtype measured, and of blocks of 4 / 8 / 16 / 32
+    _GREEDY_BATCH_K = 8
+    _GREEDY_BATCH_POLL = 32
+
+    def rnnt_greedy_batch_why_not(self):
+        """why the batched greedy search cannot take this model (None: it can): nl >= 1 and the limits of
+        emoasr_rnnt_beam_lstm_rows / _joint_rows that rnnt_beam_device_ok checks for width 1 -- 16 rows of H floats in the joint
+        kernel's LDS, nin + H columns in the LSTM step's (the MFMA plan's 1904 in bf16, as rnnt_beam_lm_why_not) -- with the
+        kernels' vector widths.  rnnt_beam_device_ok's bound on the vocabulary belongs to the pick kernel, which keeps a row in
+        LDS; the greedy book kernel reads its rows from global memory, so any vocabulary of two labels or more is taken."""
+        A, H, nl = self.arena, self.r_H, self.r_nl
+        if self.dtype not in (torch.float32, torch.bfloat16):
+            return f"the compute dtype {self.dtype} is neither float32 nor bfloat16"
+        if nl < 1:
+            return "the prediction network has no LSTM layer"
+        V_ = A.w("decoder.output.weight").shape[0]
+        if V_ < 2:
+            return f"the vocabulary ({V_}) has no label beside blank"
+        vec, wide = (8, 1904) if self.dtype == torch.bfloat16 else (4, 2368)
+        nins = [A.w(f"decoder.rnns.{l}.weight_ih_l0").shape[1] for l in range(nl)]
+        if H % 8 or H % vec or any(n % vec for n in nins) or max(nins) + H > wide or 16 * H * 4 > 64 * 1024:
+            return (f"the prediction network's sizes (embedding {self.r_emb}, hidden {H}, layers {nl}) are outside "
+                    f"emoasr_rnnt_beam_lstm_rows' limits")
+        return None
+
+    def _rnnt_greedy_batch_graph(self, S, K, blank, eos, max_seq_len, total, longest):
+        """static buffers of S searches of K frames per step over <= st.rows frames in all, none longer than st.tmax, and ONE STEP
+        of all of them (LSTM layers on S rows, joint on S K rows, output product, book) captured as a HIP graph.  The warm-up runs
+        the body with every search finished (no frames): every row is inactive, no state is touched."""
+        from .. import lib
+        tab = self.__dict__.setdefault("_greedy_batch_static", {})
+        key = (S, K, blank, eos, max_seq_len)
+        st = tab.get(key)
+        if st is not None and st.rows >= total and st.tmax >= longest:
+            return st
+        A, J, H, nl = self.arena, self.r_J, self.r_H, self.r_nl
+        dev = A.flat.device
+        st = _Stash()
+        st.rows, st.tmax = 1024, 512
+        while st.rows < total:
+            st.rows *= 2
+        while st.tmax < longest:
+            st.tmax *= 2
+        R = st.R = S * K
+        st.nslots = 2 * S
+        st.ph = [torch.zeros(st.nslots, H, device=dev, dtype=self.dtype) for _ in range(nl)]
+        st.pc = [torch.zeros(st.nslots, H, device=dev, dtype=torch.float32) for _ in range(nl)]
+        st.e = torch.zeros(st.rows, J, device=dev, dtype=self.dtype)
+        st.hj = torch.zeros(R, J, device=dev, dtype=self.dtype)
+        st.row_off = torch.zeros(S + 1, device=dev, dtype=torch.int32)
+        st.ctl, st.state, st.hyp, st.align, st.lens, st.live = ops.rnnt_greedy_batch_buffers(S, K, max_seq_len, st.tmax, dev)
+        st.bias = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(nl)]   # (refreshed per search)
+
+        def launches():
+            """the step without its bookkeeping -> the logits [S K, V] of the rows of st.ctl"""
+            with self._scope():
+                dtc = ops.dt(st.ph[0])
+                l_lab, l_src, l_dst, l_act = (c_void_p(st.ctl.data_ptr() + 8 * S * i) for i in range(4))
+                j_dst, j_act, j_row = (c_void_p(st.ctl.data_ptr() + 8 * (4 * S + R * i)) for i in range(3))
+                emb = A.w("decoder.embed.weight")
+                xtab, ldx, nx, xidx = emb, emb.shape[1], emb.shape[0], l_lab
+                for l in range(nl):
+                    w_ih, w_hh = A.w(f"decoder.rnns.{l}.weight_ih_l0"), A.w(f"decoder.rnns.{l}.weight_hh_l0")
+                    lib.call("emoasr_rnnt_beam_lstm_rows", dtc, S, w_ih.shape[1], H, ops._p(xtab), ldx, nx, xidx, ops._p(w_ih),
+                             ops._p(w_hh), ops._p(st.bias[l]), ops._p(st.ph[l]), ops._p(st.pc[l]), st.nslots, l_src, l_dst, l_act,
+                             ops._stream())
+                    xtab, ldx, nx, xidx = st.ph[l], H, st.nslots, l_dst
+                lib.call("emoasr_rnnt_beam_joint_rows", dtc, R, H, J, st.rows, ops._p(st.ph[nl - 1]), st.nslots, j_dst, j_act,
+                         ops._p(A.w("decoder.w_dec.weight")), ops._p(A.p("decoder.w_dec.bias")), ops._p(st.e), j_row,
+                         ops._p(st.hj), ops._stream())
+                return ops.gemm_nt(st.hj, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"))
+
+        def body():
+            with self._scope():    # (the scope pins the stream the calls go to: the book kernel belongs to the capture as well)
+                logits = launches()
+                ops.rnnt_greedy_batch_book(st.row_off, K, blank, max_seq_len, logits, st.ctl, st.state, st.hyp, st.align, st.lens,
+                                           st.live)
+
+        st.launches = launches     # (tests run the same launches step by step and keep the books on the host)
+        ops.rnnt_greedy_batch_start(st.row_off, K, eos, max_seq_len, st.ctl, st.state, st.lens, st.live)   # (row_off all zero)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()   # warm-up outside the capture (allocator, lazy initialisation)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        st.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(st.graph):
+            body()
+        tab[key] = st
+        return st
+
+    def _rnnt_greedy_batch_load(self, eouts, elens, K, blank, eos, max_seq_len):
+        """one chunk's searches ready for their first step: the buffers and graph, w_enc . eouts + b stacked, the zero states, the
+        control words of step 0"""
+        A, nl = self.arena, self.r_nl
+        S, total, longest = len(elens), sum(elens), max(elens)
+        st = self._rnnt_greedy_batch_graph(S, K, blank, eos, max_seq_len, total, longest)
+        offs = [0]
+        for b in range(S):
+            # w_enc . eouts + b per utterance, as the per-utterance forms compute it (a row's bits then do not depend on the batch)
+            if elens[b]:
+                st.e[offs[-1]:offs[-1] + elens[b]].copy_(ops.gemm_nt(eouts[b, :elens[b]], A.w("decoder.w_enc.weight"),
+                                                                     bias=A.p("decoder.w_enc.bias")))
+            offs.append(offs[-1] + elens[b])
+        st.row_off.copy_(torch.tensor(offs, dtype=torch.int32))
+        for l in range(nl):
+            st.bias[l].copy_(self._lstm_bias(f"decoder.rnns.{l}"))
+            st.ph[l].view(S, 2, self.r_H)[:, 0].zero_()    # slot 2 s: the zero state search s starts from
+            st.pc[l].view(S, 2, self.r_H)[:, 0].zero_()
+        ops.rnnt_greedy_batch_start(st.row_off, K, eos, max_seq_len, st.ctl, st.state, st.lens, st.live)
+        return st
+
+    @staticmethod
+    def _rnnt_greedy_batch_read(st, S):
+        lens = st.lens.tolist()
+        hyp, align = st.hyp.cpu(), st.align.cpu()
+        return [hyp[s, :lens[s][0]].tolist() for s in range(S)], [align[s, :lens[s][1]].tolist() for s in range(S)]
+
+    def rnnt_greedy_batch(self, eouts, elens, blank, eos, max_seq_len=256, frames_per_step=None, poll_block=None):
+        """time-synchronous greedy search (rnn_transducer.py:194-240) of a BATCH in lockstep, the bookkeeping on the device
+        (csrc/rnnt_greedy_batch.hip): eouts [B, Tmax, d], utterance b is searched over its own elens[b] frames -> (hyps, aligns)
+        as rnnt_greedy returns them.  One step -- LSTM layers on S rows, joint and output product on S K rows (K =
+        frames_per_step consecutive frames of every live search against its current state), book -- is captured once per (S, K)
+        and replayed: ceil(max(elens) / K) times (no search can finish sooner), then in blocks of poll_block steps with one
+        4-byte read of the live counter after each, until it is zero; never more than max(elens) + max_seq_len + 1 steps.
+        Batches are searched in chunks of _GREEDY_BATCH_ROWS // K utterances.  A model outside the rows kernels' limits is a
+        ValueError naming the reason (rnnt_greedy_batch_why_not); rnnt_greedy takes any model.  self.rnnt_greedy_batch_stats:
+        the replays and counter reads of the last call."""
+        K = self._GREEDY_BATCH_K if frames_per_step is None else int(frames_per_step)
+        block = self._GREEDY_BATCH_POLL if poll_block is None else int(poll_block)
+        if not 1 <= K <= ops.RNNT_GREEDY_BATCH_MAX_FRAMES:
+            raise ValueError(f"rnnt_greedy_batch: frames_per_step {K} is outside 1..{ops.RNNT_GREEDY_BATCH_MAX_FRAMES}")
+        if block < 1:
+            raise ValueError(f"rnnt_greedy_batch: poll_block {block} is below 1")
+        elens = [int(v) for v in elens]
+        B = eouts.shape[0]
+        assert len(elens) == B and all(0 <= n <= eouts.shape[1] for n in elens), (elens, tuple(eouts.shape))
+        why = self.rnnt_greedy_batch_why_not()
+        if why is not None:
+            raise ValueError(f"rnnt_greedy_batch: {why}")
+        stats = self.rnnt_greedy_batch_stats = dict(steps=0, polls=0, bound=0)
+        hyps, aligns = [], []
+        cap = max(1, self._GREEDY_BATCH_ROWS // K)
+        with self._scope(), torch.no_grad():
+            self.arena.refresh_shadow()
+            for b0 in range(0, B, cap):
+                lens = elens[b0:b0 + cap]
+                st = self._rnnt_greedy_batch_load(eouts[b0:b0 + cap], lens, K, blank, eos, max_seq_len)
+                bound = max(lens) + max_seq_len + 1
+                steps, todo = 0, -(-max(lens) // K)
+                while True:
+                    for _ in range(todo):
+                        st.graph.replay()
+                    steps += todo
+                    live = int(st.live.item())
+                    stats["polls"] += 1
+                    if live == 0:
+                        break
+                    todo = min(block, bound - steps)
+                    if todo <= 0:
+                        raise RuntimeError(f"rnnt_greedy_batch: {live} searches still live after {steps} steps (bound {bound})")
+                stats["steps"] += steps
+                stats["bound"] += bound
+                h, a = self._rnnt_greedy_batch_read(st, len(lens))
+                hyps += h
+                aligns += a
+        return hyps, aligns
+
     def rnnt_beam_search(self, eouts, beam_width, blank, eos, num_expands=3, return_scores=False, lm=None, lm_weight=0,
                          len_weight=0):
         """alignment-length synchronous beam search for ONE utterance (rnn_transducer.py:242-325,348-359): the expansion round as a

@@ -340,6 +340,8 @@ SIGNATURES = {
     "emoasr_rnnt_beam_start": [I, I, I, I, I, P, P, P, L, P, P],
     "emoasr_rnnt_beam_book": [I, I, I, I, I, P, P, L, P, P, L, P, P],
     "emoasr_rnnt_beam_finish": [I, I, I, I, I, P, I, P, P, P, P, P, L, P, P],
+    "emoasr_rnnt_greedy_batch_start": [I, I, I, I, P, P, P, P, P, P],
+    "emoasr_rnnt_greedy_batch_book": [I, I, I, I, I, I, P, P, L, P, P, P, L, P, L, P, P, P],
     "emoasr_rnnt_beam_pick_lm": [I, I, I, I, I, I, I, P, L, P, L, P, P, P, L, P],
     "emoasr_rnnt_beam_gather_rows": [I, I, I, P, L, P, P, P, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],

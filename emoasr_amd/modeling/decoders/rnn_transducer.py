@@ -13,6 +13,10 @@ go to the batched search with the bookkeeping on the device (engine.rnnt_beam_se
 own elens[b] frames and the N-best lists come back with their scores; decoder.rnnt_beam_impl = "device" sends a single utterance
 there too (default "host": the search with the host bookkeeping, unchanged).
 
+Greedy search (beam_width <= 1): decoder.rnnt_greedy_impl = "utterance" (default: one search per utterance, unchanged) or "batch"
+(every utterance of the call in lockstep with the bookkeeping on the device, engine.rnnt_greedy_batch; a model
+that form cannot take is a ValueError naming the reason).  The return shapes are the same.
+
 Shallow fusion (the reference's search takes lm / lm_weight and never reads them): with lm is not None and
 lm_weight > 0 the non-blank candidates are ranked by log p_asr + lm_weight * log p_lm and a finished hypothesis' score gains
 len_weight * len(hyp).  Several utterances, or rnnt_beam_impl = "device", fuse the RNN LM on the device (returns as above);
@@ -66,6 +70,10 @@ class RNNTDecoder(nn.Module):
         # beam_width > 1 on ONE utterance: "host" (the expansion round on the device, the bookkeeping on the host; no scores) or
         # "device" (the batched search, which several utterances always take).  A plain attribute: not a parameter, not saved.
         self.rnnt_beam_impl = "host"
+        # beam_width <= 1: "utterance" (one search per utterance: the cooperative launch or the launch chain) or "batch" (every
+        # utterance of the call in lockstep with the bookkeeping on the device, engine.rnnt_greedy_batch; a model it cannot take
+        # is a ValueError).  A plain attribute as well.
+        self.rnnt_greedy_impl = "utterance"
         self._owner = None
 
     def prediction_stacked(self, ys_in_list, ylens_list):

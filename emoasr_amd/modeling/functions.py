@@ -624,7 +624,14 @@ def rnnt_forced_align_apply(log_probs, elens, ys, ylens, blank):
 
 
 def rnnt_greedy_apply(dec, eouts, elens):
+    """dec.rnnt_greedy_impl: "utterance" (one search per utterance, engine.rnnt_greedy) or "batch" (all utterances in lockstep,
+    engine.rnnt_greedy_batch; a model that form cannot take is a ValueError naming the reason -- no quiet detour)"""
+    impl = getattr(dec, "rnnt_greedy_impl", "utterance")
+    if impl not in ("utterance", "batch"):
+        raise ValueError(f"emoasr_amd: rnnt_greedy_impl is 'utterance' or 'batch', not {impl!r}")
     eng = _engine_of(dec)
+    if impl == "batch":    # (the engine refuses a model it cannot take: rnnt_greedy_batch_why_not)
+        return eng.rnnt_greedy_batch(eouts, _host_list(elens), dec.blank_id, dec.eos_id, dec.max_seq_len)
     return eng.rnnt_greedy(eouts, _host_list(elens), dec.blank_id, dec.eos_id, dec.max_seq_len)
 
 

@@ -2052,6 +2052,49 @@ def rnnt_beam_finish(row_off, W, num_expands, V, eos, Lmax, ws, status, ws_bytes
     return hyps, scores, n
 
 
+# ---- batched transducer greedy search in lockstep (csrc/rnnt_greedy_batch.hip) ------------------------------------------------------
+RNNT_GREEDY_BATCH_MAX_FRAMES = 16
+
+
+def rnnt_greedy_batch_buffers(S, K, max_seq_len, longest, device):
+    """the bookkeeping's buffers for S searches of K frames per step over utterances of at most `longest` frames ->
+    (ctl int64 [4 S + 3 S K], state int32 [S, 4], hyp int32 [S, max_seq_len + 1], align int32 [S, longest + max_seq_len + 1],
+    lens int32 [S, 2], live int32 [1])"""
+    z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, device=device, dtype=dtype)
+    return (z(4 * S + 3 * S * K, dtype=torch.int64), z(S, 4), z(S, max_seq_len + 1), z(S, longest + max_seq_len + 1), z(S, 2), z(1))
+
+
+def _rnnt_greedy_batch_chk(row_off, K, ctl, state, lens, live):
+    S = row_off.numel() - 1
+    if not 1 <= int(K) <= RNNT_GREEDY_BATCH_MAX_FRAMES:
+        raise ValueError(f"rnnt_greedy_batch: frames_per_step {K} is outside 1..{RNNT_GREEDY_BATCH_MAX_FRAMES}")
+    assert _chk(row_off, torch.int32).is_contiguous() and _chk(ctl, torch.int64).is_contiguous() and ctl.numel() == 4 * S + 3 * S * K
+    assert _chk(state, torch.int32).is_contiguous() and state.numel() == 4 * S and _chk(lens, torch.int32).is_contiguous()
+    assert lens.numel() == 2 * S and _chk(live, torch.int32).numel() == 1
+    return S
+
+
+def rnnt_greedy_batch_start(row_off, K, eos, max_seq_len, ctl, state, lens, live):
+    """every search of row_off (int32 [S + 1], device) before its first step: the control words of step 0 (<eos> from slot 2 s into
+    slot 2 s + 1, the rows at frames 0 .. K - 1), empty outputs, live = the searches with frames"""
+    S = _rnnt_greedy_batch_chk(row_off, K, ctl, state, lens, live)
+    with torch.cuda.device(ctl.device):
+        lib.call("emoasr_rnnt_greedy_batch_start", S, int(K), int(eos), int(max_seq_len), _p(row_off), _p(ctl), _p(state), _p(lens),
+                 _p(live), _stream())
+
+
+def rnnt_greedy_batch_book(row_off, K, blank, max_seq_len, logits, ctl, state, hyp, align, lens, live):
+    """one step's bookkeeping from the logits [S K, V] of the rows of ctl (compute dtype, as the output product stored them): the
+    reference's rule per search, the outputs, the next step's control words"""
+    S = _rnnt_greedy_batch_chk(row_off, K, ctl, state, lens, live)
+    assert logits.dim() == 2 and logits.shape[0] == S * K and logits.stride(1) == 1 and logits.dtype in _DT
+    assert _chk(hyp, torch.int32).shape[0] == S and hyp.stride(1) == 1 and _chk(align, torch.int32).shape[0] == S and align.stride(1) == 1
+    with torch.cuda.device(ctl.device):
+        lib.call("emoasr_rnnt_greedy_batch_book", dt(logits), S, int(K), logits.shape[1], int(blank), int(max_seq_len), _p(row_off),
+                 _p(logits), logits.stride(0), _p(ctl), _p(state), _p(hyp), hyp.stride(0), _p(align), align.stride(0), _p(lens),
+                 _p(live), _stream())
+
+
 # ---- RNN-LM shallow fusion inside the batched transducer search (csrc/rnnt_beam_lm.hip) -------------------------------------------
 def rnnt_beam_pick(logits, k, blank, out):
     """out[r] (f32, row stride >= 1 + 2 k) = { log_softmax(logits[r])[blank], the k best of log_softmax(logits[r])[1:], their indices

@@ -703,6 +703,28 @@ int emoasr_rnnt_beam_book(int S, int W, int num_expands, int V, int eos, const i
 int emoasr_rnnt_beam_finish(int S, int W, int num_expands, int V, int eos, const int* row_off, int Lmax, int* out_tok, int* out_len,
                             double* out_score, int* out_n, void* ws, long ws_bytes, int* status, void* stream);
 
+/* ---- batched transducer GREEDY search in lockstep, the bookkeeping on the device (csrc/rnnt_greedy_batch.hip;
+ * engine.rnnt_greedy_batch, rnn_transducer.py:194-240): S searches, each step scores up to K consecutive frames of every live search
+ * against its current decoder state (S K joint rows), no host round trip between steps.
+ * Control words ctl: int64 [4 S + 3 S K]: [4][S] for emoasr_rnnt_beam_lstm_rows (label, source slot, destination slot, active), then
+ * [3][S K] for emoasr_rnnt_beam_joint_rows (slot to read, active, row of the stacked [sum of T, J] matrix w_enc . eouts + b); an
+ * inactive row's words are zero.  Search s owns the slots 2 s and 2 s + 1 of the state pools; slot 2 s must hold the zero state
+ * when the search starts.  row_off: int32 [S + 1] as for the beam search.  state: int32 [S][4] (frame, current slot, finished, -).
+ *   emoasr_rnnt_greedy_batch_start: every search with frames consumes <eos> from slot 2 s into slot 2 s + 1 and points its rows at
+ *       the frames 0 .. K - 1 (rows past its last frame inactive); a search without frames is finished; *live = the others
+ *   emoasr_rnnt_greedy_batch_book : after the output product of a step (logits [S K][ldl] of the compute dtype): per search the
+ *       arg-max of every active row (the first maximum, as emoasr_argmax_rows), then the reference's rule -- first non-blank row k:
+ *       k blanks and the token to the alignment, the token to the hypothesis, frame += k, one LSTM step into the other slot; all
+ *       blank: the blanks, frame += active rows -- and the next step's words.  A search finishes at its last frame or once its
+ *       hypothesis is longer than max_len (max_len + 1 labels are kept); it then leaves its rows inactive and *live falls by one.
+ *       hyp int32 [S][ldh >= max_len + 1], align int32 [S][lda >= longest T + max_len + 1], lens int32 [S][2] = {len(hyp), len(align)}. */
+#define EMOASR_RNNT_GREEDY_BATCH_MAX_FRAMES 16
+int emoasr_rnnt_greedy_batch_start(int S, int K, int eos, int max_len, const int* row_off, long long* ctl, int* state, int* lens,
+                                   int* live, void* stream);
+int emoasr_rnnt_greedy_batch_book(int dtype, int S, int K, int V, int blank, int max_len, const int* row_off, const void* logits,
+                                  long ldl, long long* ctl, int* state, int* hyp, long ldh, int* align, long lda, int* lens, int* live,
+                                  void* stream);
+
 /* ---- RNN-LM shallow fusion inside the batched transducer search (csrc/rnnt_beam_lm.hip; engine.rnnt_beam_search_batch with lm=).
  * The LM's LSTM states live in pools beside ph / pc under the same slot numbers and are stepped by emoasr_rnnt_beam_lstm_rows under
  * the same control words; these two entry points are what a fused round adds.
