@@ -6,7 +6,10 @@
 //     weights of its PARENT row (the int32 global row emoasr_beam_update_batch leaves in n_parent): the gather of the largest
 //     state array happens inside the kernel.
 //   * emoasr_las_state_gather: parent row -> child row for the small state arrays of a step, through a pointer table, one launch.
-// Both read the update kernel's state array: a row at or past its search's n_alive, and every row of a finished search, is
+//   * emoasr_las_attend_cells: emoasr_las_attend_group for the fusion grid -- a search is an (utterance,
+//     lm_weight) pair, search s runs over the frames of utterance sutt[s], stored once per UTTERANCE.  The same kernels, compiled
+//     with the CELLS flag: a row gets the bits the group form gives it over replicated frames.
+// All read the update kernel's state array: a row at or past its search's n_alive, and every row of a finished search, is
 // skipped -- nothing of it is read, nothing is written for it.  Every index that comes from device memory (offsets, parents, the
 // live count) is range-checked before it addresses anything.
 #include <cfloat>
@@ -30,15 +33,22 @@ template <typename T> __device__ __forceinline__ float exp_t(float x) {
   if constexpr (sizeof(T) == 4) return expf(x); else return __expf(x);
 }
 
-// the live rows of search s and its frames; false: the search is skipped (finished, nothing alive, or offsets out of range)
-__device__ __forceinline__ bool las_search(const emoasr_beam_state_t* state, const int* moff, int s, int W, int Tmax, int rows,
-                                           int& na, long& r0, int& Ts) {
+// the live rows of search s and its frames; false: the search is skipped (finished, nothing alive, or offsets out of range).
+// CELLS: the frames are those of utterance sutt[s] of U (moff has U + 1 entries); a sutt[s] outside 0 .. U - 1 skips the search
+template <bool CELLS>
+__device__ __forceinline__ bool las_search(const emoasr_beam_state_t* state, const int* moff, const int* sutt, int U, int s, int W,
+                                           int Tmax, int rows, int& na, long& r0, int& Ts) {
   const emoasr_beam_state_t st = state[s];
   if (st.done) return false;
   na = min(st.n_alive, W);
   if (na < 1) return false;
-  r0 = moff[s];
-  Ts = moff[s + 1] - moff[s];
+  int u = s;
+  if constexpr (CELLS) {
+    u = sutt[s];
+    if (u < 0 || u >= U) return false;
+  }
+  r0 = moff[u];
+  Ts = moff[u + 1] - moff[u];
   return r0 >= 0 && Ts >= 1 && Ts <= Tmax && r0 + Ts <= (long)rows;
 }
 
@@ -47,8 +57,8 @@ __device__ __forceinline__ int las_parent(const int* parent, int R, int W, int w
   return (p >= R && p < R + W) ? p : R;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void las_group_score_kernel(const emoasr_las_attend_group_t a) {
+template <typename T, bool CELLS>
+__global__ __launch_bounds__(256) void las_group_score_kernel(const emoasr_las_attend_group_t a, const int* sutt, int U) {
   __shared__ float s_filt[LAS_C * LAS_K];
   __shared__ float s_strip[LAS_RB][LAS_SLD];
   __shared__ float s_feat[LAS_RB][LAS_TT * LAS_C];
@@ -57,7 +67,7 @@ __global__ __launch_bounds__(256) void las_group_score_kernel(const emoasr_las_a
   const int lane = tid & 63, wave = tid >> 6;
   int na, Ts;
   long r0;
-  if (!las_search(a.state, a.moff, s, a.W, a.Tmax, a.rows, na, r0, Ts)) return;   // (block-uniform)
+  if (!las_search<CELLS>(a.state, a.moff, sutt, U, s, a.W, a.Tmax, a.rows, na, r0, Ts)) return;   // (block-uniform)
   if (t0 >= Ts) return;
   const int R = s * a.W;
   for (int j = tid; j < LAS_C * LAS_K; j += 256) s_filt[j] = a.filt[j];
@@ -163,8 +173,8 @@ __global__ __launch_bounds__(256) void las_group_score_kernel(const emoasr_las_a
 }
 
 // WB: W rounded up to 8 / 16 / 24 / 32 -- the (row, column) accumulators of a thread have compile-time bounds
-template <typename T, int WB>
-__global__ __launch_bounds__(256) void las_group_ctx_kernel(const emoasr_las_attend_group_t a) {
+template <typename T, int WB, bool CELLS>
+__global__ __launch_bounds__(256) void las_group_ctx_kernel(const emoasr_las_attend_group_t a, const int* sutt, int U) {
   __shared__ float s_m[LAS_MAXW], s_inv[LAS_MAXW];
   __shared__ float s_w[WB][LAS_CH];
   __shared__ float s_acc[32][LAS_CTX_COLS + 1];
@@ -172,7 +182,7 @@ __global__ __launch_bounds__(256) void las_group_ctx_kernel(const emoasr_las_att
   const int lane = tid & 63, wave = tid >> 6;
   int na, Ts;
   long r0;
-  if (!las_search(a.state, a.moff, s, a.W, a.Tmax, a.rows, na, r0, Ts)) return;   // (block-uniform)
+  if (!las_search<CELLS>(a.state, a.moff, sutt, U, s, a.W, a.Tmax, a.rows, na, r0, Ts)) return;   // (block-uniform)
   const int R = s * a.W;
   // the soft-max statistics of every live row: one wave per row
   for (int w = wave; w < na; w += 4) {
@@ -260,32 +270,62 @@ __global__ __launch_bounds__(256) void las_state_gather_kernel(const emoasr_las_
 
 }  // namespace
 
-extern "C" int emoasr_las_attend_group(int dtype, const emoasr_las_attend_group_t* a, void* stream) {
-  EMO_CHECK(a, "las_attend_group: missing arguments");
-  EMO_CHECK(a->W >= 1 && a->W <= LAS_MAXW, "las_attend_group: group size %d outside 1..32", a->W);
-  EMO_CHECK(a->A > 0 && a->A % 8 == 0 && a->A <= LAS_MAX_A, "las_attend_group: attn_dim A=%d must be a multiple of 8, at most %d", a->A,
+namespace {
+
+// the argument checks and the two launches of emoasr_las_attend_group / _cells (`name` goes into the messages)
+template <bool CELLS>
+int las_attend_launch(const char* name, int dtype, const emoasr_las_attend_group_t* a, const int* sutt, int U, void* stream) {
+  EMO_CHECK(a->W >= 1 && a->W <= LAS_MAXW, "%s: group size %d outside 1..32", name, a->W);
+  EMO_CHECK(a->A > 0 && a->A % 8 == 0 && a->A <= LAS_MAX_A, "%s: attn_dim A=%d must be a multiple of 8, at most %d", name, a->A,
             LAS_MAX_A);
-  EMO_CHECK(a->D > 0 && a->D % 8 == 0, "las_attend_group: enc_hidden_size D=%d must be a multiple of 8", a->D);
-  EMO_CHECK(a->S >= 1 && a->S <= 65535, "las_attend_group: %d searches (1..65535)", a->S);
-  EMO_CHECK(a->Tmax >= 1 && a->rows >= 1, "las_attend_group: Tmax=%d, rows=%d", a->Tmax, a->rows);
+  EMO_CHECK(a->D > 0 && a->D % 8 == 0, "%s: enc_hidden_size D=%d must be a multiple of 8", name, a->D);
+  EMO_CHECK(a->S >= 1 && a->S <= 65535, "%s: %d searches (1..65535)", name, a->S);
+  EMO_CHECK(a->Tmax >= 1 && a->rows >= 1, "%s: Tmax=%d, rows=%d", name, a->Tmax, a->rows);
   EMO_CHECK(a->pk && a->eouts && a->moff && a->pq && a->aw_src && a->parent && a->state && a->filt && a->w_conv && a->b_conv &&
                 a->w_score && a->scores && a->aw_dst && a->ctx,
-            "las_attend_group: NULL operand");
-  EMO_CHECK(a->ctx_ld >= a->D && a->ctx_ld % 8 == 0, "las_attend_group: ctx_ld=%ld", a->ctx_ld);
+            "%s: NULL operand", name);
+  EMO_CHECK(a->ctx_ld >= a->D && a->ctx_ld % 8 == 0, "%s: ctx_ld=%ld", name, a->ctx_ld);
   EMO_CHECK((((size_t)a->pk | (size_t)a->eouts | (size_t)a->pq | (size_t)a->ctx) & 15) == 0,
-            "las_attend_group: pk, eouts, pq and ctx must be 16-byte aligned");
+            "%s: pk, eouts, pq and ctx must be 16-byte aligned", name);
   hipStream_t s = (hipStream_t)stream;
   const dim3 g1(cdiv(a->Tmax, LAS_TT), a->S), g2(cdiv(a->D, LAS_CTX_COLS), a->S);
-  EMO_DISPATCH(dtype, (las_group_score_kernel<T><<<g1, 256, 0, s>>>(*a)));
+  EMO_DISPATCH(dtype, (las_group_score_kernel<T, CELLS><<<g1, 256, 0, s>>>(*a, sutt, U)));
   EMO_LAUNCH_CHECK();
   const int wb = (a->W + 7) / 8;
   EMO_DISPATCH(dtype, {
-    if (wb == 1) las_group_ctx_kernel<T, 8><<<g2, 256, 0, s>>>(*a);
-    else if (wb == 2) las_group_ctx_kernel<T, 16><<<g2, 256, 0, s>>>(*a);
-    else if (wb == 3) las_group_ctx_kernel<T, 24><<<g2, 256, 0, s>>>(*a);
-    else las_group_ctx_kernel<T, 32><<<g2, 256, 0, s>>>(*a);
+    if (wb == 1) las_group_ctx_kernel<T, 8, CELLS><<<g2, 256, 0, s>>>(*a, sutt, U);
+    else if (wb == 2) las_group_ctx_kernel<T, 16, CELLS><<<g2, 256, 0, s>>>(*a, sutt, U);
+    else if (wb == 3) las_group_ctx_kernel<T, 24, CELLS><<<g2, 256, 0, s>>>(*a, sutt, U);
+    else las_group_ctx_kernel<T, 32, CELLS><<<g2, 256, 0, s>>>(*a, sutt, U);
   });
   EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int emoasr_las_attend_group(int dtype, const emoasr_las_attend_group_t* a, void* stream) {
+  EMO_CHECK(a, "las_attend_group: missing arguments");
+  return las_attend_launch<false>("las_attend_group", dtype, a, nullptr, 0, stream);
+}
+
+extern "C" int emoasr_las_attend_cells(int dtype, const emoasr_las_attend_cells_t* c, void* stream) {
+  EMO_CHECK(c && c->sutt, "las_attend_cells: missing arguments");
+  EMO_CHECK(c->U >= 1 && c->U <= c->g.S, "las_attend_cells: %d utterances for %d searches (1 .. searches)", c->U, c->g.S);
+  return las_attend_launch<true>("las_attend_cells", dtype, &c->g, c->sutt, c->U, stream);
+}
+
+/* host-side check of a search -> utterance map before it is uploaded: every entry inside 0 .. U - 1, the searches of one utterance
+ * consecutive and the utterances in order, every utterance searched at least once */
+extern "C" int emoasr_las_cells_check(int S, const int* sutt_host, int U) {
+  EMO_CHECK(sutt_host && S >= 1 && U >= 1 && U <= S, "las cells: missing map, or %d utterances for %d searches", U, S);
+  EMO_CHECK(sutt_host[0] == 0, "las cells: search 0 belongs to utterance %d (the map starts at utterance 0)", sutt_host[0]);
+  for (int s = 1; s < S; ++s) {
+    const int d = sutt_host[s] - sutt_host[s - 1];
+    EMO_CHECK(d == 0 || d == 1, "las cells: search %d belongs to utterance %d after utterance %d (searches of one utterance are "
+              "consecutive, utterances in order)", s, sutt_host[s], sutt_host[s - 1]);
+  }
+  EMO_CHECK(sutt_host[S - 1] == U - 1, "las cells: the map ends at utterance %d of %d", sutt_host[S - 1], U);
   return 0;
 }
 

@@ -4,10 +4,13 @@ Only layer 0 and the attention are sequential (the attention reads its own previ
 context).  Per position: one recurrent product of [ctx | h] against [W_ih[:, E:] | W_hh] with the hoisted embedding term as its
 residual, the cell kernel, the query projection, the attention step (csrc/las.hip).  Hoisted: the embedding gather and its input
 product, the key projection, LSTM layers 1.. as whole-sequence layers (recurrence.py), intermed + tanh and the vocabulary head.
-Time-major throughout; the logits are transposed to [B, L, V] at the end."""
+Time-major throughout; the logits are transposed to [B, L, V] at the end.
+The beam searches fuse a next-token LM on request: the host form calls it per step, the batched device form
+steps the RNN LM inside its captured chain, and the (lm_weight, len_weight) grid searches every distinct weight once."""
 import ctypes
 import gc
 
+import numpy as np
 import torch
 
 from .. import lib, ops
@@ -19,17 +22,26 @@ LAS_BEAM_MAX_ROWS = 1024            # S * W rows of one chunk of the batched sea
 LAS_BEAM_POOL_BUDGET_BYTES = 2 << 30    # the two attention-weight pools of one chunk
 
 
-def las_beam_pool_bytes(nb, Tmax):
-    """bytes of the attention-weight pools of nb rows: two halves (source / destination of a step), Tmax f32 per row"""
-    return 2 * nb * Tmax * 4
+def las_beam_pool_bytes(nb, Tmax, lm_row_bytes=0):
+    """bytes of the attention-weight pools of nb rows: two halves (source / destination of a step), Tmax f32 per row; a fused RNN
+    LM adds the two halves of its state pools, lm_row_bytes per row and half (las_lm_row_bytes)"""
+    return 2 * nb * (Tmax * 4 + lm_row_bytes)
 
 
-def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None):
+def las_lm_row_bytes(lm, esz):
+    """bytes of one row of one half of a fused RNN LM's state pools: h (compute dtype) and c (f32) of every layer; 0 without one"""
+    return 0 if lm is None else lm.L * lm.H * (esz + 4)
+
+
+def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None, lm_row_bytes=0):
     """S_max: the most searches of width W one chunk of las_beam_search_batch holds -- S_max * W <= LAS_BEAM_MAX_ROWS rows and
-    las_beam_pool_bytes(S_max * W, Tmax) <= LAS_BEAM_POOL_BUDGET_BYTES; never below one search"""
+    las_beam_pool_bytes(S_max * W, Tmax, lm_row_bytes) <= LAS_BEAM_POOL_BUDGET_BYTES; never below one search"""
     budget = LAS_BEAM_POOL_BUDGET_BYTES if budget is None else budget
     max_rows = LAS_BEAM_MAX_ROWS if max_rows is None else max_rows
-    return max(1, min(max_rows // W, budget // las_beam_pool_bytes(W, Tmax)))
+    return max(1, min(max_rows // W, budget // las_beam_pool_bytes(W, Tmax, lm_row_bytes)))
+
+
+LAS_BUFFER_SETS = 4    # buffer sets (each with its captured steps) the batched search keeps: (S, W, LM, grid) configurations
 
 
 class _LasBeamBuffers:
@@ -37,7 +49,7 @@ class _LasBeamBuffers:
     captured steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`, laid out
     as modeling/beam_search_device.py:batch_pack_sizes)."""
 
-    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, pack_sizes):
+    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, pack_sizes, V=0, rnn=None, grid=False):
         nb = S * W
         self.rows_cap, self.Tcap = rows_cap, Tcap
         i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
@@ -75,6 +87,12 @@ class _LasBeamBuffers:
         self.wcat = cdt(4 * H, D + H)
         self.bias = f32(NL, 4 * H)
         self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
+        if rnn:    # a fused RNN LM (rnn = (L, H, E); section 28): slot pools of two halves (source / destination of a step), raw logits
+            self.lm_h = torch.zeros(rnn[0], 2 * nb, rnn[1], device=dev, dtype=dt)
+            self.lm_c = f32(rnn[0], 2 * nb, rnn[1])
+            self.lm_logits = f32(nb, V)
+        if grid:   # the fusion grid: search -> utterance, the LM weight of every row
+            self.sutt, self.mu_row = i32(S), f32(nb)
         self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured steps point at)
 
 
@@ -247,12 +265,13 @@ class LASDecoder:
         return deouts.view(B, T, D)
 
     # ------------------------------------------------------------------ decoding
-    def las_step(self, S, ids, parents, first):
+    def las_step(self, S, ids, parents, first, lm_lp=None, mu=0.0):
         """one token for nb <= beam_width hypotheses of one utterance.  S: the utterance's state (las_beam_search): weights, the key
         projection, and two slot pools per state array -- [ctx | h0], c0, h / c of the layers above, the attention weights -- that
         take turns as source and destination.  ids int32 [nb] (device): the hypotheses' last tokens; parents int64 [nb] (device):
         the source slot of each; the new state of row k goes to slot k of the other pool.
-        -> (top log-probabilities f32 [nb, bw], their tokens int32 [nb, bw])"""
+        lm_lp f32 [nb, >= V] with mu > 0: the LM's next-token log-probabilities, the row becomes log_softmax(head) + mu * lm_lp[:, :V].
+        -> (top values of the row f32 [nb, bw], their tokens int32 [nb, bw])"""
         A, E, H, NL, I = self.arena, self.l_E, self.l_H, self.l_nl, self.l_I
         D, nb = S.D, ids.shape[0]
         src, dst = S.pools[S.cur], S.pools[1 - S.cur]
@@ -282,16 +301,21 @@ class LASDecoder:
         g = ops.gemm_nt(x, w_i[:, D:])
         hgen = ops.joint_tanh(e.view(nb, 1, I), g.view(nb, 1, I)).view(nb, I)
         logits = ops.gemm_nt(hgen, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"), out_f32=True)
-        vals, idx, _ = ops.topk(ops.log_softmax(logits), S.bw)
+        vals, idx, _ = ops.topk(ops.log_softmax(logits, add=lm_lp, mu=mu), S.bw)   # (the fused row is formed in f32)
         S.cur = 1 - S.cur
         return vals, idx
 
-    def las_beam_search(self, eouts, beam_width, len_weight, eos, max_len):
+    def las_beam_search(self, eouts, beam_width, len_weight, eos, max_len, lm=None, lm_weight=0):
         """LASDecoder.decode's search (las.py:196-287) for ONE utterance, eouts [1,T,D]: the device advances all live hypotheses by
         one token per las_step call; the host keeps the reference's bookkeeping literally -- every live beam expanded by its top
         beam_width tokens, all expansions sorted (stable), the best beam_width kept, ended beams with an empty stripped hypothesis
         dropped, final score + len_weight * len(hyp) with the leading <eos> counted, stop at beam_width results.
+        lm with lm_weight > 0: any next-token LM, fused as the reference's attention search fuses it
+        (decoders/transformer.py:217-226) -- one LM call per step over the live hypotheses, a stateful LM's state kept per
+        hypothesis in a slot pool as the host joint search keeps it; a live row is log_softmax(head) + lm_weight * log_softmax(LM).
+        Without one the launches and the results are today's.
         -> (hyps, scores), both empty when no hypothesis ever ends"""
+        use_lm = lm is not None and lm_weight > 0
         with torch.no_grad(), self._scope():
             A, E, H, NL, AD = self.arena, self.l_E, self.l_H, self.l_nl, self.l_A
             bw = int(beam_width)
@@ -317,18 +341,39 @@ class LASDecoder:
                 P.cu = torch.zeros(max(NL - 1, 1), bw, H, device=dev, dtype=torch.float32)
                 P.aw = torch.zeros(bw, T, device=dev, dtype=torch.float32)
                 S.pools.append(P)
-            beams = [{"hyp": [eos], "score": 0.0, "slot": 0}]
+            beams = [{"hyp": [eos], "score": 0.0, "slot": 0, "lm_slot": -1}]     # (-1: the LM's zero state)
+            stateful = use_lm and getattr(lm, "stateful", False)
+            if stateful:
+                lm_pools = lm.new_pools(2 * bw, bw)
+
+            def lm_rows(i):
+                """f32 [nb, >= V]: the LM's next-token log-probabilities after every live hypothesis"""
+                nb = len(beams)
+                if stateful:      # this step's half of the pool; the beams' slots are in the other one
+                    base = (i % 2) * bw
+                    ctl = h2d_i32([b["hyp"][-1] for b in beams] + [b["lm_slot"] for b in beams] + [base + m for m in range(nb)], dev)
+                    lm.step(lm_pools, nb, ctl[:nb], ctl[nb:2 * nb], ctl[2 * nb:])
+                    return lm_pools.logp[:nb]
+                ys_in = torch.tensor([b["hyp"] for b in beams], dtype=torch.int64)
+                if hasattr(lm, "predict_device"):     # (16 rows per call)
+                    rows = [lm.predict_device(ys_in[m:m + 16], [i + 1] * min(16, nb - m)) for m in range(0, nb, 16)]
+                    return rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+                return lm.predict(ys_in.to(dev), torch.tensor([i + 1] * nb), None)[0].to(torch.float32).contiguous()
+
             results = []
             for i in range(max_len):
                 ids, parents = h2d_pack([torch.tensor([b["hyp"][-1] for b in beams], dtype=torch.int32),
                                          torch.tensor([b["slot"] for b in beams], dtype=torch.int64)], dev)
-                vals, idx = self.las_step(S, ids, parents, i == 0)
+                if use_lm:
+                    vals, idx = self.las_step(S, ids, parents, i == 0, lm_rows(i), float(lm_weight))
+                else:
+                    vals, idx = self.las_step(S, ids, parents, i == 0)
                 vals, idx = vals.cpu(), idx.cpu()
                 new_beams = []
                 for k, beam in enumerate(beams):
                     for j in range(bw):
                         new_beams.append({"hyp": beam["hyp"] + [int(idx[k, j])], "score": beam["score"] + float(vals[k, j]),
-                                          "slot": k})
+                                          "slot": k, "lm_slot": (i % 2) * bw + k})
                 beams = sorted(new_beams, key=lambda x: x["score"], reverse=True)[:bw]
                 extend = []
                 for beam in beams:
@@ -348,10 +393,15 @@ class LASDecoder:
             return [r["hyp"] for r in results], [r["score"] for r in results]
 
     # ------------------------------------------------------------------ the same search for S utterances at once
-    def _las_batch_step(self, Bf, k, S, W, D, gather, upd):
+    def _las_batch_step(self, Bf, k, S, W, D, gather, upd, fuse=None):
         """one token for all S * W rows: pool k is the source, pool 1 - k the destination.  A linear chain of launches on the
         current stream, no host round trip: the state gather, the networks on the existing operators, the grouped attention,
-        log-softmax + top-W and the batched bookkeeping (emoasr_beam_update_batch, which writes the next step's ids / parents)."""
+        log-softmax + top-W and the batched bookkeeping (emoasr_beam_update_batch, which writes the next step's ids / parents).
+        fuse (section 28): the RNN LM's step over all rows (emoasr_rnnlm_step_rows with the search's own ids / parent; half k of
+        its pools is the source, half 1 - k the destination) and emoasr_beam_scores_topk in place of log-softmax + top-W -- the
+        head's f32 logits as `dec`, the LM's raw logits as `lm`, one weight (fuse.mu) or one per row (fuse.mu_row, the grid);
+        fuse.sutt: the searches share utterances (emoasr_las_attend_cells).  Dead rows and finished searches are computed by
+        the LM and ignored."""
         A, E, H, NL, I = self.arena, self.l_E, self.l_H, self.l_nl, self.l_I
         nb = S * W
         src, dst = Bf.pools[k], Bf.pools[1 - k]
@@ -362,8 +412,12 @@ class LASDecoder:
         h = dst.xc[:, D:]
         ops.lstm_cell_fwd(gates, Bf.g_c0, h, dst.c0, Bf.gact)
         pq = ops.gemm_nt(h, A.w("decoder.score.w_query.weight"), bias=A.p("decoder.score.w_query.bias"))
-        ops.las_attend_group(self._las_weights(), Bf.pk, Bf.eo, Bf.moff, pq, src.aw, Bf.parent, Bf.state, W, dst.aw, dst.xc[:, :D],
-                             Bf.scores)
+        if fuse is not None and fuse.sutt is not None:
+            ops.las_attend_cells(self._las_weights(), Bf.pk, Bf.eo, Bf.moff[:fuse.U + 1], fuse.sutt, pq, src.aw, Bf.parent, Bf.state,
+                                 W, dst.aw, dst.xc[:, :D], Bf.scores)
+        else:
+            ops.las_attend_group(self._las_weights(), Bf.pk, Bf.eo, Bf.moff, pq, src.aw, Bf.parent, Bf.state, W, dst.aw, dst.xc[:, :D],
+                                 Bf.scores)
         x = h
         for l in range(1, NL):
             name = f"decoder.rnns.{l}"
@@ -376,18 +430,37 @@ class LASDecoder:
         g = ops.gemm_nt(x, w_i[:, D:])
         hgen = ops.joint_tanh(e.view(nb, 1, I), g.view(nb, 1, I)).view(nb, I)
         logits = ops.gemm_nt(hgen, A.w("decoder.output.weight"), bias=A.p("decoder.output.bias"), out_f32=True)
-        logp = ops.log_softmax(logits)
-        V = logp.shape[1]
-        lib.call("emoasr_topk", nb, V, W, ops._p(logp), V, None, 0, ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
+        if fuse is None:
+            logp = ops.log_softmax(logits)
+            V = logp.shape[1]
+            lib.call("emoasr_topk", nb, V, W, ops._p(logp), V, None, 0, ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
+        else:
+            V = logits.shape[1]
+            lib.call("emoasr_rnnlm_step_rows", fuse.dt_code, ctypes.byref(fuse.rows[k]), ops._p(Bf.ids), ops._p(Bf.parent), ops._stream())
+            if fuse.mu_row is None:
+                lib.call("emoasr_beam_scores_topk", lib.F32, nb, V, W, ops._p(logits), V, ops._p(Bf.lm_logits), V, fuse.mu,
+                         ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
+            else:
+                lib.call("emoasr_beam_scores_topk_rows", lib.F32, nb, V, W, ops._p(logits), V, ops._p(Bf.lm_logits), V,
+                         ops._p(fuse.mu_row), ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
         lib.call("emoasr_beam_update_batch", ctypes.byref(upd), ops._stream())
 
-    def _las_beam_chunk(self, eouts, elens, W, len_weight, eos, max_len):
-        """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable)"""
+    def _las_beam_chunk(self, eouts, elens, W, len_weight, eos, max_len, lm=None, lm_weight=0, grid=None, sort=True):
+        """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable; sort=False:
+        in the order the search found them).  lm with lm_weight > 0: the RNN LM fused on the device (section 28).
+        grid = (sutt, mus): the fusion grid's chunk -- the U = len(elens) utterances' frames, key projection and eouts are stored
+        once, search s runs over utterance sutt[s] (consecutive per utterance) with the LM weight mus[s] > 0; lm_weight is not
+        read and len_weight must be 0."""
         from ..modeling import beam_search_device as bsd   # (imports this package: resolved at call time)
         A, E, H, NL, AD = self.arena, self.l_E, self.l_H, self.l_nl, self.l_A
         dev, dt = eouts.device, self.dtype
-        S, D = len(elens), eouts.shape[2]
+        U, D = len(elens), eouts.shape[2]
+        S = len(grid[0]) if grid else U
         nb = S * W
+        use_lm = lm is not None and (lm_weight > 0 or grid is not None)
+        if grid:
+            sutt, mus = grid
+            assert lm is not None and len(mus) == S and all(m > 0 for m in mus) and len_weight == 0
         V = A.p("decoder.output.bias").numel()
         bstream = getattr(self, "_beam_stream", None)   # its own stream: the legacy default stream cannot be captured
         if bstream is None:
@@ -399,16 +472,34 @@ class LASDecoder:
             total, longest = offs[-1], max(elens)
             rows_cap = (total + 1023) // 1024 * 1024
             Tcap = (longest + 63) // 64 * 64
-            key = (str(dev), dt, S, W, max_len, V, E, H, NL, D, AD)
-            cache = getattr(self, "_las_beam_bufs", None)
-            if cache is not None and cache[0] == key and cache[1].rows_cap >= rows_cap and cache[1].Tcap >= Tcap:
-                Bf = cache[1]
-            else:
-                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, bsd.batch_pack_sizes(S, W, max_len))
-                self._las_beam_bufs = (key, Bf)
+            rnn = lm_guard = None
+            if use_lm:
+                LA = lm._prepare()     # (arena bound, compute-dtype weights and the summed biases current: before the capture)
+                assert lm.V == V and LA.shadow.dtype == dt, "las_rnnlm_why_not decides what the device form can fuse"
+                rnn = (lm.L, lm.H, lm.E)
+                lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr()) + tuple(b.data_ptr() for b in lm._bias)
+            key = (str(dev), dt, S, W, max_len, V, E, H, NL, D, AD) + ((rnn, grid is not None) if use_lm else ())
+            # a few sets of buffers (with their captured steps) are kept, least recently used first: a grid alternates between its
+            # chunk shapes and the search without the LM, a caller between fused and unfused calls
+            sets = getattr(self, "_las_buf_sets", None)
+            if sets is None:
+                sets = self._las_buf_sets = {}
+            Bf = sets.pop(key, None)
+            if Bf is None or Bf.rows_cap < rows_cap or Bf.Tcap < Tcap:
+                Bf = None       # (drop the smaller set before the larger one is allocated)
+                while len(sets) >= LAS_BUFFER_SETS:
+                    sets.pop(next(iter(sets)))
+                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, bsd.batch_pack_sizes(S, W, max_len),
+                                     V, rnn, grid is not None)
+            sets[key] = Bf
+            self._las_beam_bufs = (key, Bf)      # the set of the last call
             # ---- this call's inputs, into the buffers the captured steps read ----
-            Bf.moff.copy_(moff)
-            mem = torch.cat([eouts[b, :elens[b]] for b in range(S)], 0).to(dt) if S > 1 else eouts[0, :elens[0]].to(dt).contiguous()
+            Bf.moff[:U + 1].copy_(moff)
+            if grid:
+                Bf.sutt.copy_(ops.las_cells_map(sutt, U, dev))
+                mu32 = np.asarray(mus, dtype=np.float32)        # rounded as emoasr_beam_scores_topk's one weight is
+                Bf.mu_row.copy_(torch.from_numpy(np.repeat(mu32, W)).to(dev))
+            mem = torch.cat([eouts[b, :elens[b]] for b in range(U)], 0).to(dt) if U > 1 else eouts[0, :elens[0]].to(dt).contiguous()
             Bf.eo[:total].copy_(mem)
             # the key projection: ONE product over all stacked frames
             ops.gemm_nt(mem, A.w("decoder.score.w_key.weight"), bias=A.p("decoder.score.w_key.bias"), out=Bf.pk[:total])
@@ -425,8 +516,12 @@ class LASDecoder:
                 Bf.score.zero_(); Bf.score_ctc.zero_()
                 P = Bf.pools[0]   # step 0 reads its parents' rows here: zeros, so the general step is the first step too
                 P.xc.zero_(); P.c0.zero_(); P.hu.zero_(); P.cu.zero_(); P.aw.zero_()
+                if use_lm:   # (the warm-up's steps write both halves) step 0 reads half 0 of the LM's pools at the search's row 0
+                    Bf.lm_h[:, :nb].zero_(); Bf.lm_c[:, :nb].zero_()
 
-            gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), float(len_weight), eos, id(Bf), ops.dt(Bf.pk))
+            mu = 0.0 if (grid or not use_lm) else float(np.float32(lm_weight))     # (the grid: the weights are device data)
+            gkey = (A.flat.data_ptr(), A.shadow.data_ptr(), float(len_weight), eos, id(Bf), ops.dt(Bf.pk), lm_guard, mu,
+                    U if grid else None)
             if Bf.graphs is None or Bf.graphs[0] != gkey:
                 ub = lib.BeamUpdateBatch()
                 ub.S, ub.max_pos, ub.pos, ub.ctl = S, max_len, Bf.pos.data_ptr(), Bf.ctl.data_ptr()
@@ -448,20 +543,43 @@ class LASDecoder:
                     for l in range(NL - 1):
                         pairs += [(P.hu[l], Bf.g_hu[l]), (P.cu[l], Bf.g_cu[l])]
                     gather.append(ops.las_state_gather_args(pairs, Bf.parent, Bf.state, W))
+                fuse = None
+                if use_lm:
+                    fuse = _Stash()
+                    fuse.dt_code, fuse.mu, fuse.mu_row = ops.dt(Bf.pk), mu, Bf.mu_row if grid else None
+                    fuse.sutt, fuse.U = (Bf.sutt, U) if grid else (None, U)
+                    fuse.ws = torch.empty(lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", fuse.dt_code, nb, lm.H), device=dev,
+                                          dtype=torch.uint8)
+                    ptrs = ctypes.c_void_p * lm.L
+                    lm_w = [lm._w(l) for l in range(lm.L)]
+                    fuse.tabs = (ptrs(*[w[0].data_ptr() for w in lm_w]), ptrs(*[w[1].data_ptr() for w in lm_w]),
+                                 ptrs(*[b.data_ptr() for b in lm._bias]))     # host arrays of device pointers
+                    fuse.rows = []
+                    for k in (0, 1):      # the even step reads half 0 of the pools and writes half 1, the odd step the reverse
+                        rl = lib.RnnlmRows()
+                        rl.L, rl.E, rl.H, rl.V, rl.R = lm.L, lm.E, lm.H, V, nb
+                        rl.emb = LA.w("lm.embed.weight").data_ptr()
+                        rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, ctypes.c_void_p) for t in fuse.tabs)
+                        rl.w_out, rl.b_out = LA.w("lm.output.weight").data_ptr(), LA.p("lm.output.bias").data_ptr()
+                        rl.ph, rl.pc, rl.slots = Bf.lm_h.data_ptr(), Bf.lm_c.data_ptr(), 2 * nb
+                        rl.src_base, rl.dst_base = k * nb, (1 - k) * nb
+                        rl.logits, rl.ldl = Bf.lm_logits.data_ptr(), V
+                        rl.ws, rl.ws_bytes = fuse.ws.data_ptr(), fuse.ws.numel()
+                        fuse.rows.append(rl)
                 # warm-up with every search marked finished (the new kernels and the bookkeeping return at once, the networks
                 # run on the rows as they are): every kernel's lazy one-time setup happens outside the capture.  Then each
                 # step is captured once: a linear chain on one stream.
                 reset(1)
                 for k in (0, 1):
-                    self._las_batch_step(Bf, k, S, W, D, gather, ub)
+                    self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse)
                 torch.cuda.current_stream().synchronize()
                 graphs = []
                 for k in (0, 1):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
-                        self._las_batch_step(Bf, k, S, W, D, gather, ub)
+                        self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse)
                     graphs.append(g)
-                Bf.graphs = (gkey, graphs, (ub, gather))
+                Bf.graphs = (gkey, graphs, (ub, gather, fuse))
             graphs = Bf.graphs[1]
             reset(0)
             mirror = Bf.mirror_host.numpy()
@@ -489,13 +607,20 @@ class LASDecoder:
             stats["steps"] += int(mirror[0]); stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
             host = Bf.pack.cpu().numpy()      # the one download
         caller.wait_stream(bstream)
-        return bsd.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len)
+        return bsd.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len, sort)
 
-    def las_beam_search_batch(self, eouts, elens, beam_width, len_weight, eos, max_len):
+    def las_beam_search_batch(self, eouts, elens, beam_width, len_weight, eos, max_len, lm=None, lm_weight=0, lm_weights=None,
+                              len_weights=None):
         """las_beam_search for every utterance of the batch: eouts [B, Tmax, D], utterance b over its own
         elens[b] >= 1 frames (frames past them are never read) -> (hyps, scores) with hyps[b] / scores[b] what las_beam_search
         returns for eouts[b:b+1, :elens[b]].  All searches of a chunk step in lockstep on the device: per step one captured chain
-        of launches, no host round trip, one download at the end.  Chunks hold at most las_beam_chunk_capacity searches."""
+        of launches, no host round trip, one download at the end.  Chunks hold at most las_beam_chunk_capacity searches.
+        lm with lm_weight > 0: the RNN LM fused inside the chain (section 28; modeling/functions.py:las_rnnlm_why_not says what it takes).
+        lm_weights / len_weights: the shallow-fusion grid instead -- (hyps[b][c], scores[b][c]) for the cells in lm_weight-outer,
+        len_weight-inner order; every distinct positive lm_weight of an utterance is searched once at len_weight 0 (the searches of
+        an utterance share its frames: emoasr_las_attend_cells), weights <= 0 fold into one search without the LM, and the
+        len_weights are expanded on the host in double (beam_search_device.expand_len_weights); len_weight and lm_weight are
+        not read."""
         W = int(beam_width)
         elens = [int(n) for n in elens]
         B, T = eouts.shape[0], eouts.shape[1]
@@ -503,11 +628,55 @@ class LASDecoder:
             raise ValueError(f"las_beam_search_batch: every utterance needs 1 <= elens[b] <= {T} frames, got elens {elens}")
         V = self.arena.p("decoder.output.bias").numel()
         assert 1 <= W <= 32 and W <= V, "the batched LAS search handles beams of 1..32 hypotheses, at most the vocabulary"
-        cap = las_beam_chunk_capacity(W, (max(elens) + 63) // 64 * 64)
+        Tcap = (max(elens) + 63) // 64 * 64
+        esz = 2 if self.dtype == torch.bfloat16 else 4
+        if lm_weights is not None:
+            return self._las_beam_grid(eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz)
+        if lm is None or lm_weight <= 0:
+            lm, lm_weight = None, 0
+        cap = las_beam_chunk_capacity(W, Tcap, lm_row_bytes=las_lm_row_bytes(lm, esz))
         hyps, scores = [], []
         for b0 in range(0, B, cap):
             n = elens[b0:b0 + cap]
-            h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len)
+            if lm is None:
+                h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len)
+            else:
+                h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len, lm, lm_weight)
             hyps += h
             scores += s
+        return hyps, scores
+
+    def _las_beam_grid(self, eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz):
+        """las_beam_search_batch's grid: the plan of beam_search_device.grid_cell_plan / grid_chunk_plan on the LAS chunks"""
+        from ..modeling import beam_search_device as bsd
+        lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
+        weights, cells = bsd.grid_cell_plan(lm_weights, len_weights, lm is not None)
+        B = len(elens)
+        found = [[None] * len(weights) for _ in range(B)]     # [b][k] -> (hyps, scores) of search k at len_weight 0
+        positive = [k for k, a in enumerate(weights) if a > 0]
+        if len(positive) < len(weights):      # the search without the LM: the batched search as it is, no LM launches
+            k = weights.index(0.0)
+            cap = las_beam_chunk_capacity(W, Tcap)
+            for b0 in range(0, B, cap):
+                n = elens[b0:b0 + cap]
+                h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, 0, eos, max_len, sort=False)
+                for i in range(len(n)):
+                    found[b0 + i][k] = (h[i], s[i])
+        if positive:
+            cap = las_beam_chunk_capacity(W, Tcap, lm_row_bytes=las_lm_row_bytes(lm, esz))
+            for chunk in bsd.grid_chunk_plan(B, len(positive), cap):
+                utts = sorted({b for b, _, _ in chunk})
+                local = {b: i for i, b in enumerate(utts)}
+                n = [elens[b] for b in utts]
+                sutt = [local[b] for b, _, cnt in chunk for _ in range(cnt)]
+                ks = [positive[k0 + j] for _, k0, cnt in chunk for j in range(cnt)]
+                sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
+                h, s = self._las_beam_chunk(sub, n, W, 0, eos, max_len, lm, 0, grid=(sutt, [weights[k] for k in ks]), sort=False)
+                for i, (u, k) in enumerate(zip(sutt, ks)):
+                    found[utts[u]][k] = (h[i], s[i])
+        hyps, scores = [], []
+        for b in range(B):
+            per_search = [bsd.expand_len_weights(h, s, len_weights) for h, s in found[b]]
+            hyps.append([per_search[k][j][0] for k, j in cells])
+            scores.append([per_search[k][j][1] for k, j in cells])
         return hyps, scores

@@ -15,8 +15,10 @@ Attention models (decoder_type == "transformer", any --decode_ctc_weight) go thr
 joint_beam_search_device_grid call per batch -- every distinct lm_weight is searched once, the len_weights are an expansion of the
 finished hypotheses' scores; with an RNN LM the tool sets decoder.joint_rnnlm_impl = "device", so that the LM is
 stepped inside that search (section 26).  Transducer models (decoder_type == "rnn_transducer") go through
-rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25).  The LAS
-search ignores the LM, in the reference and here: no grid for it.
+rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25).  LAS models
+(decoder_type == "las") go through las_fusion_grid: the reference's LAS search ignores the LM, the tool sets decoder.las_lm_fusion =
+"fuse" and the RNN LM is stepped inside the batched LAS search, one search per distinct lm_weight over frames stored once per
+utterance (section 28).  main dispatches "las" itself; grid_of keeps refusing it.
 """
 import argparse
 import logging
@@ -157,9 +159,49 @@ def rnnt_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_w
     return results, best
 
 
+def las_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                    texts_out=None):
+    """rnnt_fusion_grid for a LAS model (decoder_type == "las"): -> (results, best) with the same cell order and the same rule for
+    best.  One encoder pass and one functions.las_fusion_grid_apply call per batch: every distinct positive lm_weight of an
+    utterance is one search with the RNN LM stepped inside the chain, the searches of an utterance share its frames, the
+    len_weights are a host expansion.  decode_ctc_weight == 1 is greedy CTC whatever the weights."""
+    from .modeling.functions import las_fusion_grid_apply
+    kind = getattr(model, "decoder_type", None)
+    if kind != "las":
+        raise NotImplementedError(f"emoasr_amd.fusion_grid.las_fusion_grid handles decoder_type == 'las', not {kind!r}")
+    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+    hyps_of = [[] for _ in cells]
+    refs = []
+    with torch.no_grad():
+        for data in dataloader:
+            eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
+            if decode_ctc_weight == 1:
+                greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
+                best_of = lambda b, c: greedy[b]
+            else:
+                hyps, _ = las_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)
+                best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
+            for b, reftext in enumerate(data["texts"]):
+                refs.append(reftext.split())
+                for c in range(len(cells)):
+                    hyps_of[c].append(vocab.ids2text(strip_eos(best_of(b, c), eos_id)).split())
+    if texts_out is not None:
+        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
+    results = []
+    best = (0, 0, 100, "")
+    for c, (lm_weight, len_weight) in enumerate(cells):
+        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
+        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
+        results.append(row)
+        if wer < best[2]:
+            best = row
+    return results, best
+
+
 def grid_of(kind):
     """the grid function of a decoder type: "ctc" -> ctc_fusion_grid, "transformer" -> joint_fusion_grid, "rnn_transducer" ->
-    rnnt_fusion_grid; the LAS search ignores the LM in the reference and here (there is nothing to tune): refused"""
+    rnnt_fusion_grid.  "las" stays refused here: main sends it to las_fusion_grid before it asks (the reference's LAS search
+    ignores the LM; the fused one is this project's)"""
     if kind == "ctc":
         return ctc_fusion_grid
     if kind == "transformer":
@@ -168,6 +210,11 @@ def grid_of(kind):
         return rnnt_fusion_grid
     raise NotImplementedError(f"emoasr_amd.fusion_grid handles decoder_type 'ctc' and 'transformer' (and 'rnn_transducer'), "
                               f"not {kind!r}")
+
+
+def grid_for(kind):
+    """main's dispatch: "las" -> las_fusion_grid, decided before grid_of is asked (which refuses it); every other type: grid_of"""
+    return las_fusion_grid if kind == "las" else grid_of(kind)
 
 
 def set_joint_rnnlm_impl(decoder, beam_width, lm, decode_ctc_weight):
@@ -184,6 +231,17 @@ def set_joint_rnnlm_impl(decoder, beam_width, lm, decode_ctc_weight):
             logging.info(f"joint_rnnlm_impl stays 'host' (one host search per utterance and lm_weight): {why}")
     decoder.joint_rnnlm_impl = impl
     return impl
+
+
+def set_las_lm_fusion(decoder, beam_width, lm):
+    """a LAS model: decoder.las_lm_fusion = "fuse"; where functions.las_rnnlm_why_not gives a reason the grid runs one host search
+    per utterance and lm_weight, and that reason is logged.  -> the reason or None"""
+    from .modeling.functions import las_rnnlm_why_not
+    decoder.las_lm_fusion = "fuse"
+    why = las_rnnlm_why_not(decoder, beam_width, lm)
+    if why is not None:
+        logging.info(f"LAS fusion grid: the host form per utterance and lm_weight: {why}")
+    return why
 
 
 def log_results(results, best):
@@ -227,7 +285,7 @@ def main(args):
     from .rescore import load_config, model_path
     params = load_config(args.conf)
     kind = getattr(params, "decoder_type", None)
-    grid = grid_of(kind)
+    grid = grid_for(kind)
     if kind == "ctc":
         require_ctc(params, args.decode_ctc_weight)
     if not (args.lm_conf and args.lm_ep):
@@ -252,6 +310,8 @@ def main(args):
     beam_width = args.beam_width or params.beam_width
     if kind == "transformer":
         set_joint_rnnlm_impl(model.decoder, beam_width, lm, args.decode_ctc_weight)
+    if kind == "las":
+        set_las_lm_fusion(model.decoder, beam_width, lm)
     dataset = ASRDataset(params, data_path, phase="test")
     lm_weights, len_weights = weight_lists(args.lm_min, args.lm_max, args.lm_step, args.len_min, args.len_max, args.len_step)
     results, best = grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), beam_width,

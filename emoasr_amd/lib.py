@@ -233,6 +233,10 @@ class LasAttendGroup(Structure):
                 ("scores", c_void_p), ("aw_dst", c_void_p), ("ctx", c_void_p), ("ctx_ld", c_long)]
 
 
+class LasAttendCells(Structure):
+    _fields_ = [("g", LasAttendGroup), ("U", c_int), ("sutt", c_void_p)]
+
+
 LAS_GATHER_MAX = 16
 
 
@@ -350,6 +354,8 @@ SIGNATURES = {
     "emoasr_las_attend_bwd": [I, POINTER(LasAttend), P],
     "emoasr_las_dropmask": [POINTER(LasAttend), P, P],
     "emoasr_las_attend_group": [I, POINTER(LasAttendGroup), P],
+    "emoasr_las_attend_cells": [I, POINTER(LasAttendCells), P],
+    "emoasr_las_cells_check": [I, POINTER(c_int), I],
     "emoasr_las_state_gather": [POINTER(LasStateGather), P],
     "emoasr_mlm_expand": [I, I, I, P, P, P, I, I, I, I, P, P, P, P, P],
     "emoasr_sample_rows": [I, I, I, P, L, P, P, U64, L, P, P, P, P],

@@ -9,20 +9,35 @@ The sub-modules carry the reference's names (nn.LSTMCell `rnns`, `score.w_key / 
 csrc/las.hip.  As in the reference, the attention weights are dropped with p = 0.1 in train mode -- AttentionLoc's constructor
 default, which LASDecoder never overrides and no config field reaches (`decoder.score.dropout_attn_rate` is the attribute).
 
-decode(): `decode_ctc_weight == 1` is CTC greedy; otherwise the reference's beam search (las.py:176-287).  The
-reference's `lm`, `lm_weight` and intermediate `decode_ctc_weight` branches are `pass`: the arguments are accepted and their values
-ignored here too (as RNNTDecoder does with its LM arguments).  A search that never emits <eos> returns ([], [], None, None).
-The reference takes one utterance; here a batch of several returns (hyps[b], scores[b], None, None), utterance b searched over its
-own elens[b] frames -- N-best lists at every beam width, beam 1 included (one-element lists; [] / [] for a search that never
-ends).  `las_beam_impl`: "single" searches one utterance with the host bookkeeping (engine/las.py:las_beam_search) and a batch
-with the lockstep device search (las_beam_search_batch); "batch" sends one utterance there too.
+decode(): `decode_ctc_weight == 1` is CTC greedy; otherwise the reference's beam search (las.py:176-287).  The reference's
+intermediate `decode_ctc_weight` branch is `pass`: the value is accepted and ignored here too.  A search that never emits <eos>
+returns ([], [], None, None).  The reference takes one utterance; here a batch of several returns (hyps[b], scores[b], None, None),
+utterance b searched over its own elens[b] frames -- N-best lists at every beam width, beam 1 included (one-element lists; [] / []
+for a search that never ends).  `las_beam_impl`: "single" searches one utterance with the host bookkeeping
+(engine/las.py:las_beam_search) and a batch with the lockstep device search (las_beam_search_batch); "batch"
+sends one utterance there too.
+
+`lm` / `lm_weight` and the switch `las_lm_fusion`.  The reference's LM branch is `if lm_weight > 0: pass`
+(las.py:233): under the default "ignore" the arguments are accepted and their values not read, the search is the reference's bit for
+bit.  Under "fuse", with an LM and lm_weight > 0, the LM is fused the way the reference's own attention search fuses it at
+decode_ctc_weight == 0 (decoders/transformer.py:217-226, 246-286): the row of a live hypothesis is log_softmax(head)[v] + lm_weight *
+log_softmax(LM logits)[v] for v < V, its top beam_width are the expansions, the LM's input is the hypothesis's last token (<eos> at
+step 0) and its state follows the parent; a finished hypothesis gains len_weight * len(hyp) as before.  Routes under "fuse":
+    several utterances, or one under las_beam_impl == "batch"   the device form: the RNN LM stepped inside the captured chain
+    one utterance under "single"                                the host form: any next-token LM, the Transformer LM included
+    an LM the device form cannot take (functions.las_rnnlm_why_not: not lm_type "rnn", lm.V != V, another compute dtype or product
+        mode, sizes outside emoasr_rnnlm_step_rows' plan), beam_width > 32 or > V
+                                                                one host-form search per utterance, the reason logged once,
+                                                                the same return shape
+    a masked LM (BERT, ELECTRA, P2W, P-ELECTRA)                 refused with lm.require_next_token_lm's messages
+lm_weight <= 0 or lm None under "fuse" is the unfused search.
 
 Supported sizes (16-byte accesses): embedding_size, enc_hidden_size, dec_hidden_size, attn_dim and dec_intermediate_size are
 multiples of 8, attn_dim <= 512 (one 8-channel group per lane of the attention kernel); batch and lengths are free.
 """
 import torch.nn as nn
 
-from ..functions import las_beam_apply, las_beam_batch_apply, las_decoder_apply
+from ..functions import las_beam_apply, las_beam_batch_apply, las_decoder_apply, las_fusion_route
 from .ctc import CTCDecoder
 
 LAS_FIELDS = ("vocab_size", "embedding_size", "enc_hidden_size", "dec_hidden_size", "dec_num_layers", "attn_dim",
@@ -85,6 +100,7 @@ class LASDecoder(nn.Module):
         self.eos_id = params.eos_id
         self.max_decode_ylen = params.max_decode_ylen
         self.las_beam_impl = "single"   # "batch": one utterance goes through the batched device search too
+        self.las_lm_fusion = "ignore"   # "fuse": decode() fuses its lm / lm_weight arguments (the reference's branch is `pass`)
         self._owner = None
 
     def forward(self, eouts, elens, eouts_inter=None, ys=None, ylens=None, ys_in=None, ys_out=None, soft_labels=None,
@@ -105,10 +121,11 @@ class LASDecoder(nn.Module):
             return self.ctc.decode(eouts, elens, beam_width=1)
         if self.las_beam_impl not in ("single", "batch"):
             raise ValueError(f"las_beam_impl {self.las_beam_impl!r}: 'single' or 'batch'")
+        lm, lm_weight, _ = las_fusion_route(self, beam_width, lm, lm_weight)     # (None, 0, None) unless las_lm_fusion == "fuse"
         if eouts.size(0) == 1 and self.las_beam_impl == "single":   # las.py:196: the reference's one utterance, all its frames
-            hyps, scores = las_beam_apply(self, eouts, beam_width, len_weight)
+            hyps, scores = las_beam_apply(self, eouts, beam_width, len_weight, lm, lm_weight)
             return hyps, scores, None, None
-        hyps, scores = las_beam_batch_apply(self, eouts, elens, beam_width, len_weight)
+        hyps, scores = las_beam_batch_apply(self, eouts, elens, beam_width, len_weight, lm=lm, lm_weight=lm_weight)
         if eouts.size(0) == 1:   # one utterance through "batch": the single search's return shape
             return hyps[0], scores[0], None, None
         return hyps, scores, None, None

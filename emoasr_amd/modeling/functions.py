@@ -6,6 +6,8 @@ Parameter gradients are accumulated by the engine directly into the flat gradien
 (the parameters' .grad tensors are views of it); the Functions therefore return None for
 the parameter inputs.
 """
+import logging
+
 import torch
 
 from ..engine import h2d_i32
@@ -401,30 +403,124 @@ def las_decoder_apply(dec, eouts, elens, ys, ylens, ys_in, ys_out, soft_labels=N
                                ylens_host, ys_in, ys_out, dec.blank_id, soft, float(kd_weight), *eng.arena.params)
 
 
-def las_beam_apply(dec, eouts, beam_width, len_weight):
-    """LASDecoder.decode's beam search for one utterance -> (hyps, scores)"""
-    return _engine_of(dec).las_beam_search(eouts, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+def las_beam_apply(dec, eouts, beam_width, len_weight, lm=None, lm_weight=0):
+    """LASDecoder.decode's beam search for one utterance -> (hyps, scores); lm with lm_weight > 0: fused on the host form"""
+    eng = _engine_of(dec)
+    if lm is None or lm_weight <= 0:
+        return eng.las_beam_search(eouts, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+    return eng.las_beam_search(eouts, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen, lm=lm, lm_weight=lm_weight)
 
 
 LAS_BATCH_MAX_BEAM = 32   # rows of a search in csrc/las_beam.hip and in emoasr_beam_update_batch
+_LAS_FUSION_LOGGED = set()   # reasons already logged (las_fusion_route)
 
 
-def las_beam_batch_apply(dec, eouts, elens, beam_width, len_weight, batched=True):
-    """LASDecoder.decode's beam search for every utterance of the batch, utterance b over its own elens[b] frames
-    -> (hyps[b], scores[b]).  batched: all utterances in lockstep on the device (engine/las.py:las_beam_search_batch); beams wider
-    than 32 or than the vocabulary, and batched=False, run las_beam_search once per utterance."""
+def las_lm_fusion(dec):
+    """the decoder's switch for its LM arguments: "ignore" (default: accepted and not read, as the reference's `pass`) or "fuse";
+    anything else is refused"""
+    mode = getattr(dec, "las_lm_fusion", "ignore")
+    if mode not in ("ignore", "fuse"):
+        raise ValueError(f"emoasr_amd: las_lm_fusion is 'ignore' or 'fuse', not {mode!r}")
+    return mode
+
+
+def las_rnnlm_why_not(dec, beam_width, lm):
+    """why the batched LAS search cannot fuse this LM through emoasr_rnnlm_step_rows (None: it can; the twin
+    of beam_search_device.batch_rnnlm_why_not)"""
+    from .. import lib
+    if getattr(lm, "lm_type", None) != "rnn":
+        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
+    V = dec.vocab_size
+    if lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
+        return f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
     eng = _engine_of(dec)
+    if lm.compute_dtype != eng.dtype or bool(lm.f32_split) != bool(eng.split):
+        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
+    code = lib.F32X3 if lm.f32_split else {torch.float32: lib.F32, torch.bfloat16: lib.BF16}.get(lm.compute_dtype)
+    if code is None or lib.size_query("emoasr_rnnlm_step_rows_supported", code, lm.L, lm.E, lm.H) != 1:
+        return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnlm_step_rows' shape plan"
+    if not 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, V):
+        return f"beam_width {beam_width} (vocabulary {V}) is outside the device bookkeeping's {LAS_BATCH_MAX_BEAM} beams"
+    return None
+
+
+def las_fusion_route(dec, beam_width, lm, lm_weight):
+    """-> (lm, lm_weight, why): what LASDecoder.decode's search fuses.  (None, 0, None) under las_lm_fusion == "ignore", without an
+    LM or with lm_weight <= 0: today's search.  Under "fuse" a masked LM is refused (require_next_token_lm's messages); why is
+    None where the batched device form takes the LM, else las_rnnlm_why_not's reason -- logged once -- and the caller runs the
+    host form per utterance."""
+    if las_lm_fusion(dec) != "fuse" or lm is None or lm_weight <= 0:
+        return None, 0, None
+    from .lm import require_next_token_lm
+    require_next_token_lm(lm, lm_weight)
+    why = las_rnnlm_why_not(dec, beam_width, lm)
+    if why is not None and why not in _LAS_FUSION_LOGGED:
+        _LAS_FUSION_LOGGED.add(why)
+        logging.getLogger(__name__).info(f"LAS beam search: the LM is fused by one host search per utterance: {why}")
+    return lm, lm_weight, why
+
+
+def _las_check_elens(eouts, elens, what):
     elens = [int(n) for n in elens]
     B, T = eouts.shape[0], eouts.shape[1]
     if len(elens) != B or any(n < 1 or n > T for n in elens):
-        raise ValueError(f"LASDecoder.decode: every utterance needs 1 <= elens[b] <= {T} frames, got elens {elens}")
+        raise ValueError(f"{what}: every utterance needs 1 <= elens[b] <= {T} frames, got elens {elens}")
+    return elens
+
+
+def las_beam_batch_apply(dec, eouts, elens, beam_width, len_weight, batched=True, lm=None, lm_weight=0):
+    """LASDecoder.decode's beam search for every utterance of the batch, utterance b over its own elens[b] frames
+    -> (hyps[b], scores[b]).  batched: all utterances in lockstep on the device (engine/las.py:las_beam_search_batch); beams wider
+    than 32 or than the vocabulary, and batched=False, run las_beam_search once per utterance.  lm with lm_weight > 0 (already
+    routed: las_fusion_route): fused on the device where las_rnnlm_why_not has no objection, else by the host form per utterance."""
+    eng = _engine_of(dec)
+    elens = _las_check_elens(eouts, elens, "LASDecoder.decode")
+    B = eouts.shape[0]
+    fuse = lm is not None and lm_weight > 0
     if batched and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
-        return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+        if not fuse:
+            return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+        if las_rnnlm_why_not(dec, beam_width, lm) is None:
+            return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen, lm=lm,
+                                             lm_weight=lm_weight)
     hyps, scores = [], []
     for b in range(B):
-        h, s = eng.las_beam_search(eouts[b:b + 1, :elens[b]], beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
+        h, s = las_beam_apply(dec, eouts[b:b + 1, :elens[b]], beam_width, len_weight, lm if fuse else None, lm_weight if fuse else 0)
         hyps.append(h)
         scores.append(s)
+    return hyps, scores
+
+
+def las_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_weights):
+    """the LAS search of every utterance for every (lm_weight, len_weight) cell -> (hyps[b][cell][n], scores[b][cell][n]), cells in
+    lm_weight-outer, len_weight-inner order.  Where the device form takes the LM: ONE
+    las_beam_search_batch grid call.  Else (las_rnnlm_why_not's reason, logged once): one host-form search per utterance and
+    distinct lm_weight at len_weight 0, the len_weights expanded on the host as the device grid expands them."""
+    from . import beam_search_device as bsd
+    from .lm import require_next_token_lm
+    lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
+    eng = _engine_of(dec)
+    elens = _las_check_elens(eouts, elens, "las_fusion_grid")
+    weights, cells = bsd.grid_cell_plan(lm_weights, len_weights, lm is not None)
+    any_lm = max(weights) > 0
+    why = None
+    if any_lm:
+        require_next_token_lm(lm, max(weights))
+        why = las_rnnlm_why_not(dec, beam_width, lm)
+    if why is None and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
+        return eng.las_beam_search_batch(eouts, elens, beam_width, 0, dec.eos_id, dec.max_decode_ylen, lm=lm if any_lm else None,
+                                         lm_weights=lm_weights, len_weights=len_weights)
+    if why is not None and why not in _LAS_FUSION_LOGGED:
+        _LAS_FUSION_LOGGED.add(why)
+        logging.getLogger(__name__).info(f"LAS fusion grid: one host search per utterance and lm_weight: {why}")
+    hyps, scores = [], []
+    for b in range(len(elens)):
+        per_search = []
+        for a in weights:
+            h, s = las_beam_apply(dec, eouts[b:b + 1, :elens[b]], beam_width, 0, lm if a > 0 else None, a)
+            per_search.append(bsd.expand_len_weights(h, s, len_weights))
+        hyps.append([per_search[k][j][0] for k, j in cells])
+        scores.append([per_search[k][j][1] for k, j in cells])
     return hyps, scores
 
 

@@ -1862,9 +1862,10 @@ def las_group_offsets(elens, device):
     return t.pin_memory().to(device, non_blocking=True), offs
 
 
-def _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores):
+def _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores, a=None, S=None):
+    """a / S: the struct to fill and the number of searches where moff counts utterances (las_attend_cells)"""
     nb, A = pq.shape
-    S = moff.numel() - 1
+    S = moff.numel() - 1 if S is None else S
     rows, D = eouts.shape
     Tmax = aw_src.shape[1]
     assert nb == S * width and A == W.A and pk.shape == (rows, A) and pk.dtype == pq.dtype == eouts.dtype == ctx.dtype
@@ -1874,7 +1875,7 @@ def _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst
     assert _chk(parent, torch.int32).numel() == nb and _chk(moff, torch.int32).is_contiguous()
     assert _chk(state, torch.int32).is_contiguous() and state.numel() == 4 * S
     assert ctx.shape == (nb, D) and ctx.stride(1) == 1
-    a = lib.LasAttendGroup()
+    a = lib.LasAttendGroup() if a is None else a
     a.S, a.W, a.A, a.D, a.Tmax, a.rows = S, width, A, D, Tmax, rows
     a.pk, a.eouts, a.moff, a.pq = _chk(pk).data_ptr(), _chk(eouts).data_ptr(), moff.data_ptr(), _chk(pq).data_ptr()
     a.aw_src, a.parent, a.state = aw_src.data_ptr(), parent.data_ptr(), state.data_ptr()
@@ -1891,6 +1892,25 @@ def las_attend_group(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_ds
     scratch `scores` -- for the live rows only"""
     a = _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores)
     lib.call("emoasr_las_attend_group", dt(pq), byref(a), _stream())
+
+
+def las_cells_map(sutt, U, device):
+    """the search -> utterance map of las_attend_cells, checked on the host (emoasr_las_cells_check) -> int32 [S] on the device"""
+    sutt = [int(u) for u in sutt]
+    lib.call("emoasr_las_cells_check", len(sutt), (ctypes.c_int * len(sutt))(*sutt), int(U))
+    return torch.tensor(sutt, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
+def las_attend_cells(W, pk, eouts, moff, sutt, pq, aw_src, parent, state, width, aw_dst, ctx, scores):
+    """las_attend_group for searches that share utterances (emoasr_las_attend_cells_t): pk / eouts stacked over the U UTTERANCES,
+    moff int32 [U + 1], sutt int32 [S] (device, las_cells_map): search s runs over the frames of utterance sutt[s]; everything
+    else as las_attend_group, row for row the same bits"""
+    S = _chk(sutt, torch.int32).numel()
+    assert sutt.is_contiguous()
+    c = lib.LasAttendCells()
+    _las_group_args(W, pk, eouts, moff, pq, aw_src, parent, state, width, aw_dst, ctx, scores, a=c.g, S=S)
+    c.U, c.sutt = moff.numel() - 1, sutt.data_ptr()
+    lib.call("emoasr_las_attend_cells", dt(pq), byref(c), _stream())
 
 
 def las_state_gather_args(pairs, parent, state, width):

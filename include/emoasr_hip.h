@@ -1325,6 +1325,20 @@ typedef struct emoasr_las_attend_group {
   void* ctx; long ctx_ld;
 } emoasr_las_attend_group_t;
 int emoasr_las_attend_group(int dtype, const emoasr_las_attend_group_t* a, void* stream);
+/* emoasr_las_attend_group for the fusion grid: a search is an (utterance, lm_weight) pair.  g.S counts the
+ * SEARCHES, g.moff (device int32 [U + 1]) holds the first frames of the U UTTERANCES, whose pk / eouts rows are stored once;
+ * search s runs over the frames of utterance sutt[s] (device int32 [S], searches of one utterance consecutive).  The kernels are
+ * the group form's own, compiled with one more flag: a row gets the bits emoasr_las_attend_group gives it when run with one offset
+ * entry per search over replicated frames.  A search whose sutt[s] lies outside 0 .. U - 1 is skipped like a finished one.
+ * emoasr_las_cells_check verifies a HOST copy of the map (0 .. U - 1 in order, consecutive, every utterance present) before the
+ * upload. */
+typedef struct emoasr_las_attend_cells {
+  emoasr_las_attend_group_t g;
+  int U;
+  const int* sutt;
+} emoasr_las_attend_cells_t;
+int emoasr_las_attend_cells(int dtype, const emoasr_las_attend_cells_t* c, void* stream);
+int emoasr_las_cells_check(int S, const int* sutt_host, int U);
 /* Parent row -> child row for the small state arrays of a step, one launch: item k copies row_bytes (a multiple of 16, both
  * pointers 16-byte aligned) from src + parent[r] * row_bytes to dst + r * row_bytes for every live row r.  Exact copies. */
 #define EMOASR_LAS_GATHER_MAX 16
