@@ -8,12 +8,11 @@ Time-major throughout; the logits are transposed to [B, L, V] at the end.
 The beam searches fuse a next-token LM on request: the host form calls it per step, the batched device form
 steps the RNN LM inside its captured chain, and the (lm_weight, len_weight) grid searches every distinct weight once."""
 import ctypes
-import gc
 
 import numpy as np
 import torch
 
-from .. import lib, ops
+from .. import lib, lockstep, ops
 from ..recurrence import lstm_stack_bwd, lstm_stack_fwd
 from .arena import _Stash, _cfg, h2d_i32, h2d_pack
 
@@ -44,33 +43,16 @@ def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None, lm_row_bytes=0)
 LAS_BUFFER_SETS = 4    # buffer sets (each with its captured steps) the batched search keeps: (S, W, LM, grid) configurations
 
 
-class _LasBeamBuffers:
-    """device buffers of one (S, W, max_len, frame capacities) configuration of the batched search, reused across calls: the
-    captured steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`, laid out
-    as modeling/beam_search_device.py:batch_pack_sizes)."""
+class _LasBeamBuffers(lockstep.BookBuffers):
+    """lockstep.BookBuffers of one (S, W, max_len, frame capacities) configuration of the batched search, with the LAS search's own
+    pools: the stacked frames and keys, the decoder state and attention weights of two halves, the gathered parents' rows"""
 
-    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, pack_sizes, V=0, rnn=None, grid=False):
+    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, V=0, rnn=None, grid=False):
+        super().__init__(dev, dt, S, W, W, Lmax, V, rnn, grid)      # (rnn = (L, H, E) of a fused RNN LM; section 28)
         nb = S * W
         self.rows_cap, self.Tcap = rows_cap, Tcap
-        i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         cdt = lambda *s: torch.zeros(*s, device=dev, dtype=dt)
-        self.pack = i32(sum(pack_sizes))
-        o = [0]
-        for v in pack_sizes:
-            o.append(o[-1] + v)
-        self.pack_off = o
-        part = lambda k: self.pack[o[k]:o[k + 1]]
-        self.res_score = part(0).view(torch.float64)
-        self.state, self.res_step, self.res_parent = part(1).view(S, 4), part(2), part(3)
-        self.hist_parent, self.hist_token = part(4).view(Lmax, nb), part(5).view(Lmax, nb)
-        self.pos, self.ctl = i32(1), i32(1)
-        self.ids, self.parent, self.pcand = i32(nb), i32(nb), i32(nb)
-        self.last, self.outlen, self.klens = i32(nb), i32(nb), i32(nb)
-        self.score = torch.zeros(nb, device=dev, dtype=torch.float64)
-        self.score_ctc = f32(nb)
-        self.vals, self.cands = f32(nb, W), i32(nb, W)
-        self.moff = i32(S + 1)
         self.pk, self.eo = cdt(rows_cap, AD), cdt(rows_cap, D)
         nu = max(NL - 1, 1)
         self.pools = []
@@ -86,14 +68,6 @@ class _LasBeamBuffers:
         self.scores = f32(nb, Tcap)
         self.wcat = cdt(4 * H, D + H)
         self.bias = f32(NL, 4 * H)
-        self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
-        if rnn:    # a fused RNN LM (rnn = (L, H, E); section 28): slot pools of two halves (source / destination of a step), raw logits
-            self.lm_h = torch.zeros(rnn[0], 2 * nb, rnn[1], device=dev, dtype=dt)
-            self.lm_c = f32(rnn[0], 2 * nb, rnn[1])
-            self.lm_logits = f32(nb, V)
-        if grid:   # the fusion grid: search -> utterance, the LM weight of every row
-            self.sutt, self.mu_row = i32(S), f32(nb)
-        self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured steps point at)
 
 
 class LASDecoder:
@@ -451,7 +425,6 @@ class LASDecoder:
         grid = (sutt, mus): the fusion grid's chunk -- the U = len(elens) utterances' frames, key projection and eouts are stored
         once, search s runs over utterance sutt[s] (consecutive per utterance) with the LM weight mus[s] > 0; lm_weight is not
         read and len_weight must be 0."""
-        from ..modeling import beam_search_device as bsd   # (imports this package: resolved at call time)
         A, E, H, NL, AD = self.arena, self.l_E, self.l_H, self.l_nl, self.l_A
         dev, dt = eouts.device, self.dtype
         U, D = len(elens), eouts.shape[2]
@@ -489,8 +462,7 @@ class LASDecoder:
                 Bf = None       # (drop the smaller set before the larger one is allocated)
                 while len(sets) >= LAS_BUFFER_SETS:
                     sets.pop(next(iter(sets)))
-                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, bsd.batch_pack_sizes(S, W, max_len),
-                                     V, rnn, grid is not None)
+                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, V, rnn, grid is not None)
             sets[key] = Bf
             self._las_beam_bufs = (key, Bf)      # the set of the last call
             # ---- this call's inputs, into the buffers the captured steps read ----
@@ -508,12 +480,7 @@ class LASDecoder:
                 Bf.bias[l].copy_(self._las_bias(l))
 
             def reset(done):
-                Bf.state.copy_(h2d_i32([[0, 1, 0, done]] * S, dev))
-                Bf.pos.zero_(); Bf.ctl.fill_(done)
-                Bf.ids.fill_(eos); Bf.last.fill_(eos)
-                Bf.parent.copy_(torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(W) * W)
-                Bf.pcand.zero_(); Bf.outlen.zero_(); Bf.klens.fill_(1)
-                Bf.score.zero_(); Bf.score_ctc.zero_()
+                lockstep.reset_book(Bf, S, W, eos, done)
                 P = Bf.pools[0]   # step 0 reads its parents' rows here: zeros, so the general step is the first step too
                 P.xc.zero_(); P.c0.zero_(); P.hu.zero_(); P.cu.zero_(); P.aw.zero_()
                 if use_lm:   # (the warm-up's steps write both halves) step 0 reads half 0 of the LM's pools at the search's row 0
@@ -524,18 +491,7 @@ class LASDecoder:
                     U if grid else None)
             if Bf.graphs is None or Bf.graphs[0] != gkey:
                 ub = lib.BeamUpdateBatch()
-                ub.S, ub.max_pos, ub.pos, ub.ctl = S, max_len, Bf.pos.data_ptr(), Bf.ctl.data_ptr()
-                u = ub.u
-                u.bw, u.cw, u.eos = W, W, eos                  # attention only: psi and lm_at stay NULL
-                u.one_minus_lam, u.lam, u.mu, u.len_weight = 1.0, 0.0, 0.0, float(len_weight)
-                u.vals, u.cands = Bf.vals.data_ptr(), Bf.cands.data_ptr()
-                u.score, u.score_ctc = Bf.score.data_ptr(), Bf.score_ctc.data_ptr()
-                u.n_ids, u.n_parent, u.n_pcand = Bf.ids.data_ptr(), Bf.parent.data_ptr(), Bf.pcand.data_ptr()
-                u.n_last, u.n_outlen, u.n_klens = Bf.last.data_ptr(), Bf.outlen.data_ptr(), Bf.klens.data_ptr()
-                u.hist_parent, u.hist_token = Bf.hist_parent.data_ptr(), Bf.hist_token.data_ptr()
-                u.res_score, u.res_step, u.res_parent = Bf.res_score.data_ptr(), Bf.res_step.data_ptr(), Bf.res_parent.data_ptr()
-                u.state = Bf.state.data_ptr()
-                u.host_mirror = Bf.mirror_host.data_ptr()      # pinned: the tail kernel writes it, the host polls it
+                lockstep.fill_beam_update(ub, Bf, S, W, W, eos, max_len, len_weight)     # attention only: psi and lm_at stay NULL
                 gather = []
                 for k in (0, 1):
                     P = Bf.pools[k]
@@ -548,66 +504,14 @@ class LASDecoder:
                     fuse = _Stash()
                     fuse.dt_code, fuse.mu, fuse.mu_row = ops.dt(Bf.pk), mu, Bf.mu_row if grid else None
                     fuse.sutt, fuse.U = (Bf.sutt, U) if grid else (None, U)
-                    fuse.ws = torch.empty(lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", fuse.dt_code, nb, lm.H), device=dev,
-                                          dtype=torch.uint8)
-                    ptrs = ctypes.c_void_p * lm.L
-                    lm_w = [lm._w(l) for l in range(lm.L)]
-                    fuse.tabs = (ptrs(*[w[0].data_ptr() for w in lm_w]), ptrs(*[w[1].data_ptr() for w in lm_w]),
-                                 ptrs(*[b.data_ptr() for b in lm._bias]))     # host arrays of device pointers
-                    fuse.rows = []
-                    for k in (0, 1):      # the even step reads half 0 of the pools and writes half 1, the odd step the reverse
-                        rl = lib.RnnlmRows()
-                        rl.L, rl.E, rl.H, rl.V, rl.R = lm.L, lm.E, lm.H, V, nb
-                        rl.emb = LA.w("lm.embed.weight").data_ptr()
-                        rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, ctypes.c_void_p) for t in fuse.tabs)
-                        rl.w_out, rl.b_out = LA.w("lm.output.weight").data_ptr(), LA.p("lm.output.bias").data_ptr()
-                        rl.ph, rl.pc, rl.slots = Bf.lm_h.data_ptr(), Bf.lm_c.data_ptr(), 2 * nb
-                        rl.src_base, rl.dst_base = k * nb, (1 - k) * nb
-                        rl.logits, rl.ldl = Bf.lm_logits.data_ptr(), V
-                        rl.ws, rl.ws_bytes = fuse.ws.data_ptr(), fuse.ws.numel()
-                        fuse.rows.append(rl)
-                # warm-up with every search marked finished (the new kernels and the bookkeeping return at once, the networks
-                # run on the rows as they are): every kernel's lazy one-time setup happens outside the capture.  Then each
-                # step is captured once: a linear chain on one stream.
-                reset(1)
-                for k in (0, 1):
-                    self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse)
-                torch.cuda.current_stream().synchronize()
-                graphs = []
-                for k in (0, 1):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
-                        self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse)
-                    graphs.append(g)
+                    # the even step reads half 0 of the LM's pools and writes half 1, the odd step the reverse
+                    fuse.rows, fuse.tabs, fuse.ws = lockstep.rnnlm_rows_pair(lm, LA, Bf, nb, V, fuse.dt_code, even_src=0)
+                graphs = lockstep.capture_two_steps(lambda k: self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse), reset)
                 Bf.graphs = (gkey, graphs, (ub, gather, fuse))
-            graphs = Bf.graphs[1]
             reset(0)
-            mirror = Bf.mirror_host.numpy()
-            mirror[:] = (0, 0)
-            main = torch.cuda.current_stream()
-            main.synchronize()     # (the mirror is host memory: the reset above must not race the first step's store)
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record(main)
-            gc_was_on = gc.isenabled()
-            gc.disable()           # (a collection in the middle of the loop stalls a step for milliseconds)
-            try:
-                # steps are issued one ahead of the mirror they depend on: a step replayed after the end changes nothing
-                for i in range(max_len):
-                    graphs[i & 1].replay()
-                    if i >= 1 and bsd.batch_step_reported(mirror, i, S, main):
-                        break
-                ev1.record(main)
-                main.synchronize()
-            finally:
-                if gc_was_on:
-                    gc.enable()
-            stats = getattr(self, "_las_beam_stats", None)   # running totals for tools/las_beam_bench.py
-            if stats is None:
-                stats = self._las_beam_stats = {"steps": 0, "loop_s": 0.0, "utts": 0, "calls": 0}
-            stats["steps"] += int(mirror[0]); stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
-            host = Bf.pack.cpu().numpy()      # the one download
+            host = lockstep.replay_until_done(Bf.graphs[1], Bf, max_len, S, self, "_las_beam_stats")   # (totals: tools/las_beam_bench.py)
         caller.wait_stream(bstream)
-        return bsd.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len, sort)
+        return lockstep.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len, sort)
 
     def las_beam_search_batch(self, eouts, elens, beam_width, len_weight, eos, max_len, lm=None, lm_weight=0, lm_weights=None,
                               len_weights=None):
@@ -647,36 +551,28 @@ class LASDecoder:
         return hyps, scores
 
     def _las_beam_grid(self, eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz):
-        """las_beam_search_batch's grid: the plan of beam_search_device.grid_cell_plan / grid_chunk_plan on the LAS chunks"""
-        from ..modeling import beam_search_device as bsd
+        """las_beam_search_batch's grid: lockstep.run_fusion_grid on the LAS chunks"""
         lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
-        weights, cells = bsd.grid_cell_plan(lm_weights, len_weights, lm is not None)
         B = len(elens)
-        found = [[None] * len(weights) for _ in range(B)]     # [b][k] -> (hyps, scores) of search k at len_weight 0
-        positive = [k for k, a in enumerate(weights) if a > 0]
-        if len(positive) < len(weights):      # the search without the LM: the batched search as it is, no LM launches
-            k = weights.index(0.0)
+
+        def search_plain():      # the search without the LM: the batched search as it is, no LM launches
             cap = las_beam_chunk_capacity(W, Tcap)
+            hyps, scores = [], []
             for b0 in range(0, B, cap):
                 n = elens[b0:b0 + cap]
                 h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, 0, eos, max_len, sort=False)
-                for i in range(len(n)):
-                    found[b0 + i][k] = (h[i], s[i])
-        if positive:
+                hyps += h
+                scores += s
+            return hyps, scores
+
+        def search_fused(positive, weights, found):
             cap = las_beam_chunk_capacity(W, Tcap, lm_row_bytes=las_lm_row_bytes(lm, esz))
-            for chunk in bsd.grid_chunk_plan(B, len(positive), cap):
-                utts = sorted({b for b, _, _ in chunk})
-                local = {b: i for i, b in enumerate(utts)}
-                n = [elens[b] for b in utts]
-                sutt = [local[b] for b, _, cnt in chunk for _ in range(cnt)]
-                ks = [positive[k0 + j] for _, k0, cnt in chunk for j in range(cnt)]
+            for utts, n, sutt, k_local in lockstep.grid_chunks(B, len(positive), cap, elens):
+                ks = [positive[j] for j in k_local]
                 sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
                 h, s = self._las_beam_chunk(sub, n, W, 0, eos, max_len, lm, 0, grid=(sutt, [weights[k] for k in ks]), sort=False)
                 for i, (u, k) in enumerate(zip(sutt, ks)):
                     found[utts[u]][k] = (h[i], s[i])
-        hyps, scores = [], []
-        for b in range(B):
-            per_search = [bsd.expand_len_weights(h, s, len_weights) for h, s in found[b]]
-            hyps.append([per_search[k][j][0] for k, j in cells])
-            scores.append([per_search[k][j][1] for k, j in cells])
-        return hyps, scores
+
+        return lockstep.run_fusion_grid(B, lm_weights, len_weights, lm is not None, search_plain, search_fused,
+                                        lambda f, a: lockstep.expand_len_weights(*f, len_weights))

@@ -5,7 +5,7 @@ from ctypes import c_void_p
 
 import torch
 
-from .. import ops
+from .. import lockstep, ops
 from ..recurrence import lstm_stack_bwd, lstm_stack_fwd
 from .arena import _Stash, _cfg, h2d_i32
 
@@ -788,29 +788,24 @@ class RNNTDecoder:
         return hyps, scores
 
     def _rnnt_beam_search_grid(self, eouts, elens, W, blank, eos, E, lm, lm_weights, len_weights):
-        """rnnt_beam_search_batch with lm_weights: plan the searches, run them in chunks, expand the cells"""
-        from ..modeling.beam_search_device import grid_cell_plan
+        """rnnt_beam_search_batch with lm_weights: lockstep.run_fusion_grid over (utterance, weight) pairs in chunks; the fused
+        searches' results are expanded by rnnt_len_expand, the search without the LM does not read the len_weights"""
         from ..modeling.lm import require_next_token_lm
+        lm_weights = [float(a) for a in lm_weights]
         len_weights = [0.0] if len_weights is None else [float(v) for v in len_weights]
-        weights, cells = grid_cell_plan([float(a) for a in lm_weights], len_weights, lm is not None)
-        require_next_token_lm(lm, max(weights))
+        require_next_token_lm(lm, max(lockstep.grid_cell_plan(lm_weights, len_weights, lm is not None)[0]))
         B = len(elens)
-        found = [[None] * len(weights) for _ in range(B)]      # [b][k] -> (hyps, scores) of search k, before the len_weight
-        positive = [k for k, a in enumerate(weights) if a > 0]
-        if len(positive) < len(weights):                       # the search without the LM: the call as it was
-            k = weights.index(0.0)
-            h, s = self.rnnt_beam_search_batch(eouts, elens, W, blank, eos, E)
-            for b in range(B):
-                found[b][k] = (h[b], s[b])
-        if positive and not self.rnnt_beam_device_ok(W, E, lm):
-            for b in range(B):
-                for k in positive:
-                    if elens[b] == 0:
-                        found[b][k] = ([[eos]], [0.0])
-                    else:
-                        h, s = self._rnnt_beam_search_chain(eouts[b:b + 1, :elens[b]], W, blank, eos, E, True, lm, weights[k], 0)
-                        found[b][k] = (h, [float(v) for v in s])
-        elif positive:
+
+        def search_fused(positive, weights, found):
+            if not self.rnnt_beam_device_ok(W, E, lm):      # the host chain, utterance by utterance
+                for b in range(B):
+                    for k in positive:
+                        if elens[b] == 0:
+                            found[b][k] = ([[eos]], [0.0])
+                        else:
+                            h, s = self._rnnt_beam_search_chain(eouts[b:b + 1, :elens[b]], W, blank, eos, E, True, lm, weights[k], 0)
+                            found[b][k] = (h, [float(v) for v in s])
+                return
             pairs = [(b, k) for b in range(B) for k in positive]
             cap = self.rnnt_beam_chunk_capacity(W, E, lm)
             for p0 in range(0, len(pairs), cap):
@@ -819,12 +814,10 @@ class RNNTDecoder:
                                                      [b for b, _ in chunk])
                 for i, (b, k) in enumerate(chunk):
                     found[b][k] = (h[i], s[i])
-        hyps, scores = [], []
-        for b in range(B):
-            per_cell = [self.rnnt_len_expand(*found[b][k], len_weights[j]) if weights[k] > 0 else found[b][k] for k, j in cells]
-            hyps.append([c[0] for c in per_cell])
-            scores.append([c[1] for c in per_cell])
-        return hyps, scores
+
+        return lockstep.run_fusion_grid(B, lm_weights, len_weights, lm is not None,
+                                        lambda: self.rnnt_beam_search_batch(eouts, elens, W, blank, eos, E), search_fused,
+                                        lambda f, a: [self.rnnt_len_expand(*f, w) if a > 0 else f for w in len_weights])
 
     def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total, lm=None):
         """static buffers of S searches of width W over <= st.rows frames in all, and ONE FRAME of all of them (E rounds of

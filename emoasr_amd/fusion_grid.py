@@ -48,60 +48,20 @@ def require_ctc(model, decode_ctc_weight=0):
                                   "not built; CTC models only")
 
 
-def ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
-                    texts_out=None):
-    """-> (results, best): results = [(lm_weight, len_weight, wer, wer_info)] over lm_weights x len_weights (lm_weights outer), best =
-    (lm_weight, len_weight, wer, wer_info) of the first cell with strictly smaller WER, from (0, 0, 100, "") as the reference starts.
-    One pass over the loader: every batch is encoded once, all cells are searched in one call, a cell with lm_weight <= 0 is the search
-    without an LM (it adds nothing).  texts_out: a list that receives, per cell in the order of results, the 1-best texts."""
-    from .modeling.ctc_beam_search import ctc_prefix_beam_search_batch_lm
-    require_ctc(model, decode_ctc_weight)
-    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
-    hyps_of = [[] for _ in cells]
-    refs = []
-    with torch.no_grad():
-        for data in dataloader:
-            eouts, elens, _ = model.encoder(data["xs"].to(device), data["xlens"])
-            hyps, _, _ = ctc_prefix_beam_search_batch_lm(model.decoder, eouts, elens, beam_width, lm, cells)
-            for b, reftext in enumerate(data["texts"]):
-                refs.append(reftext.split())
-                for c in range(len(cells)):
-                    best_hyp = hyps[b][c][0] if hyps[b][c] else []
-                    hyps_of[c].append(vocab.ids2text(strip_eos(best_hyp, eos_id)).split())
-    if texts_out is not None:
-        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
-    results = []
-    best = (0, 0, 100, "")
-    for c, (lm_weight, len_weight) in enumerate(cells):
-        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
-        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
-        results.append(row)
-        if wer < best[2]:
-            best = row
-    return results, best
-
-
-def joint_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
-                      texts_out=None):
-    """ctc_fusion_grid for an attention model (decoder_type == "transformer"): -> (results, best) with the same cell order and the
-    same rule for best.  One encoder pass and one joint_beam_search_device_grid call per batch; decode_ctc_weight == 1 is greedy
-    CTC whatever the weights: decoded once per batch, every cell gets that result."""
-    from .modeling.beam_search_device import joint_beam_search_device_grid
-    kind = getattr(model, "decoder_type", None)
-    if kind != "transformer":
-        raise NotImplementedError(f"emoasr_amd.fusion_grid.joint_fusion_grid handles decoder_type == 'transformer', not {kind!r}")
-    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+def _grid_pass(model, dataloader, vocab, cells, search_batch, device, eos_id, decode_ctc_weight, texts_out, greedy_at_one):
+    """one pass over the loader -> (results, best): every batch is encoded once, search_batch(eouts, elens) -> hyps[b][c] searches
+    all cells of it (greedy_at_one and decode_ctc_weight == 1: greedy CTC whatever the weights, decoded once per batch for every
+    cell), every cell is scored with compute_wers; best = the first cell with strictly smaller WER, from (0, 0, 100, "")"""
     hyps_of = [[] for _ in cells]
     refs = []
     with torch.no_grad():
         for data in dataloader:
             eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
-            if decode_ctc_weight == 1:
+            if greedy_at_one and decode_ctc_weight == 1:
                 greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
                 best_of = lambda b, c: greedy[b]
             else:
-                hyps, _ = joint_beam_search_device_grid(model.decoder, eouts, elens, beam_width, lm, [a for a in lm_weights],
-                                                        [b for b in len_weights], decode_ctc_weight)
+                hyps = search_batch(eouts, elens)
                 best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
             for b, reftext in enumerate(data["texts"]):
                 refs.append(reftext.split())
@@ -118,6 +78,42 @@ def joint_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_
         if wer < best[2]:
             best = row
     return results, best
+
+
+def _cells(lm_weights, len_weights):
+    return [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
+
+
+def _require_kind(model, kind, name):
+    got = getattr(model, "decoder_type", None)
+    if got != kind:
+        raise NotImplementedError(f"emoasr_amd.fusion_grid.{name} handles decoder_type == {kind!r}, not {got!r}")
+
+
+def ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                    texts_out=None):
+    """-> (results, best): results = [(lm_weight, len_weight, wer, wer_info)] over lm_weights x len_weights (lm_weights outer), best =
+    (lm_weight, len_weight, wer, wer_info) of the first cell with strictly smaller WER, from (0, 0, 100, "") as the reference starts.
+    One pass over the loader: every batch is encoded once, all cells are searched in one call, a cell with lm_weight <= 0 is the search
+    without an LM (it adds nothing).  texts_out: a list that receives, per cell in the order of results, the 1-best texts."""
+    from .modeling.ctc_beam_search import ctc_prefix_beam_search_batch_lm
+    require_ctc(model, decode_ctc_weight)
+    cells = _cells(lm_weights, len_weights)
+    search = lambda eouts, elens: ctc_prefix_beam_search_batch_lm(model.decoder, eouts, elens, beam_width, lm, cells)[0]
+    return _grid_pass(model, dataloader, vocab, cells, search, device, eos_id, decode_ctc_weight, texts_out, False)
+
+
+def joint_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
+                      texts_out=None):
+    """ctc_fusion_grid for an attention model (decoder_type == "transformer"): -> (results, best) with the same cell order and the
+    same rule for best.  One encoder pass and one joint_beam_search_device_grid call per batch; decode_ctc_weight == 1 is greedy
+    CTC whatever the weights: decoded once per batch, every cell gets that result."""
+    from .modeling.beam_search_device import joint_beam_search_device_grid
+    _require_kind(model, "transformer", "joint_fusion_grid")
+    search = lambda eouts, elens: joint_beam_search_device_grid(model.decoder, eouts, elens, beam_width, lm, [a for a in lm_weights],
+                                                                [b for b in len_weights], decode_ctc_weight)[0]
+    return _grid_pass(model, dataloader, vocab, _cells(lm_weights, len_weights), search, device, eos_id, decode_ctc_weight, texts_out,
+                      True)
 
 
 def rnnt_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
@@ -127,36 +123,10 @@ def rnnt_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_w
     lm_weight of an utterance is one search with the RNN LM stepped beside the prediction network, the len_weights are a host
     expansion.  decode_ctc_weight == 1 is greedy CTC whatever the weights, as in joint_fusion_grid."""
     from .modeling.functions import rnnt_fusion_grid_apply
-    kind = getattr(model, "decoder_type", None)
-    if kind != "rnn_transducer":
-        raise NotImplementedError(f"emoasr_amd.fusion_grid.rnnt_fusion_grid handles decoder_type == 'rnn_transducer', not {kind!r}")
-    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
-    hyps_of = [[] for _ in cells]
-    refs = []
-    with torch.no_grad():
-        for data in dataloader:
-            eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
-            if decode_ctc_weight == 1:
-                greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
-                best_of = lambda b, c: greedy[b]
-            else:
-                hyps, _ = rnnt_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)
-                best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
-            for b, reftext in enumerate(data["texts"]):
-                refs.append(reftext.split())
-                for c in range(len(cells)):
-                    hyps_of[c].append(vocab.ids2text(strip_eos(best_of(b, c), eos_id)).split())
-    if texts_out is not None:
-        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
-    results = []
-    best = (0, 0, 100, "")
-    for c, (lm_weight, len_weight) in enumerate(cells):
-        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
-        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
-        results.append(row)
-        if wer < best[2]:
-            best = row
-    return results, best
+    _require_kind(model, "rnn_transducer", "rnnt_fusion_grid")
+    search = lambda eouts, elens: rnnt_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)[0]
+    return _grid_pass(model, dataloader, vocab, _cells(lm_weights, len_weights), search, device, eos_id, decode_ctc_weight, texts_out,
+                      True)
 
 
 def las_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device, eos_id=2, decode_ctc_weight=0,
@@ -166,36 +136,10 @@ def las_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_we
     utterance is one search with the RNN LM stepped inside the chain, the searches of an utterance share its frames, the
     len_weights are a host expansion.  decode_ctc_weight == 1 is greedy CTC whatever the weights."""
     from .modeling.functions import las_fusion_grid_apply
-    kind = getattr(model, "decoder_type", None)
-    if kind != "las":
-        raise NotImplementedError(f"emoasr_amd.fusion_grid.las_fusion_grid handles decoder_type == 'las', not {kind!r}")
-    cells = [(np.float64(a), np.float64(b)) for a in lm_weights for b in len_weights]
-    hyps_of = [[] for _ in cells]
-    refs = []
-    with torch.no_grad():
-        for data in dataloader:
-            eouts, elens, eouts_inter = model.encoder(data["xs"].to(device), data["xlens"])
-            if decode_ctc_weight == 1:
-                greedy = model.decoder.decode(eouts, elens, eouts_inter, 1, decode_ctc_weight=1)[0]
-                best_of = lambda b, c: greedy[b]
-            else:
-                hyps, _ = las_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)
-                best_of = lambda b, c: hyps[b][c][0] if hyps[b][c] else []
-            for b, reftext in enumerate(data["texts"]):
-                refs.append(reftext.split())
-                for c in range(len(cells)):
-                    hyps_of[c].append(vocab.ids2text(strip_eos(best_of(b, c), eos_id)).split())
-    if texts_out is not None:
-        texts_out += [[" ".join(words) for words in cell] for cell in hyps_of]
-    results = []
-    best = (0, 0, 100, "")
-    for c, (lm_weight, len_weight) in enumerate(cells):
-        wer, wer_dict = compute_wers(hyps_of[c], refs, device=device)
-        row = (lm_weight, len_weight, wer, wer_summary(wer, wer_dict))
-        results.append(row)
-        if wer < best[2]:
-            best = row
-    return results, best
+    _require_kind(model, "las", "las_fusion_grid")
+    search = lambda eouts, elens: las_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)[0]
+    return _grid_pass(model, dataloader, vocab, _cells(lm_weights, len_weights), search, device, eos_id, decode_ctc_weight, texts_out,
+                      True)
 
 
 def grid_of(kind):

@@ -21,13 +21,13 @@ import time
 import numpy as np
 import torch
 
-from .. import lib, ops
+from .. import lib, lockstep, ops
 from ..decode_rt import DecoderStepRuntime, LMStepRuntime, _lin, _ln
 from ..engine import h2d_i32
+from ..lockstep import (_STEP_DEADLINE_S, _yield, batch_nbest_from_pack, batch_pack_sizes, batch_step_reported,  # noqa: F401
+                        expand_len_weights, grid_cell_plan, grid_chunk_plan)
 from .functions import _engine_of
 from .lm import require_next_token_lm
-
-_STEP_DEADLINE_S = 30.0   # a search step takes ~0.5 ms; this only bounds the wait for a launch that will never report
 
 CTC_BEAM_WIDTH_RATIO = 1.5
 
@@ -56,9 +56,6 @@ class _Buffers:
         self.lm_v = torch.zeros_like(self.lm_k)
         # the flag the host polls: a pinned copy of `state`
         self.state_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-
-
-_yield = os.sched_yield if os.environ.get("EMOASR_BEAM_YIELD", "1") != "0" else (lambda: None)
 
 
 def joint_beam_search_device(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
@@ -349,17 +346,10 @@ def joint_rnnlm_impl(dec):
 
 def batch_rnnlm_why_not(dec, beam_width, lm, decode_ctc_weight):
     """why the batched device search cannot fuse this LM through emoasr_rnnlm_step_rows (None: it can)"""
-    if getattr(lm, "lm_type", None) != "rnn":
-        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
     V = dec.vocab_size
-    if lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
-        return f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
-    eng = _engine_of(dec)
-    if lm.compute_dtype != eng.dtype or bool(lm.f32_split) != bool(eng.split):
-        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
-    code = lib.F32X3 if lm.f32_split else {torch.float32: lib.F32, torch.bfloat16: lib.BF16}.get(lm.compute_dtype)
-    if code is None or lib.size_query("emoasr_rnnlm_step_rows_supported", code, lm.L, lm.E, lm.H) != 1:
-        return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnlm_step_rows' shape plan"
+    why = lockstep.rnnlm_rows_why_not(_engine_of(dec), V, lm)
+    if why is not None:
+        return why
     cw = min(V, int(beam_width * CTC_BEAM_WIDTH_RATIO)) if decode_ctc_weight > 0 else beam_width
     if not (1 <= beam_width <= 32 and 1 <= cw <= 32 and beam_width <= V):
         return f"beam_width {beam_width} (candidate width {cw}, vocabulary {V}) is outside the device bookkeeping's 32 beams x 32 candidates"
@@ -395,49 +385,27 @@ def batch_device_ok(dec, beam_width, lm, lm_weight, decode_ctc_weight):
     return lm is None or lm_weight <= 0 or hasattr(lm, "predict_device")
 
 
-class _BatchBuffers:
-    """device buffers of one (S, W, cw, Lmax, model sizes, frame capacities) configuration, reused across calls: the captured
-    steps point into them.  Everything the host reads back at the end lives in ONE int32 allocation (`pack`)."""
+class _BatchBuffers(lockstep.BookBuffers):
+    """lockstep.BookBuffers of one (S, W, cw, Lmax, model sizes, frame capacities) configuration, with the joint search's own pools:
+    the decoder's (and a Transformer LM's) self-attention caches of two halves, the CTC scorer's frames and states"""
 
     def __init__(self, dev, dtype, S, W, cw, Lmax, V, dnl, dd, lnl, ld, rows_cap, Tcap, use_ctc, grid=False, rnn=None):
+        super().__init__(dev, dtype, S, W, cw, Lmax, V, rnn, grid)     # (rnn = (L, H): a stateful LM has slot pools, no K / V pools)
         nb = S * W
         self.rows_cap, self.Tcap = rows_cap, Tcap
         i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
-        # pack: res_score (double [nb]) | state [S, 4] | res_step [nb] | res_parent [nb] | hist_parent [Lmax, nb] | hist_token [Lmax, nb]
-        n = batch_pack_sizes(S, W, Lmax)
-        self.pack = i32(sum(n))
-        o = [0]
-        for v in n:
-            o.append(o[-1] + v)
-        self.pack_off = o
-        part = lambda k: self.pack[o[k]:o[k + 1]]
-        self.res_score = part(0).view(torch.float64)
-        self.state, self.res_step, self.res_parent = part(1).view(S, 4), part(2), part(3)
-        self.hist_parent, self.hist_token = part(4).view(Lmax, nb), part(5).view(Lmax, nb)
-        self.pos, self.ctl = i32(1), i32(1)
-        self.ids, self.parent, self.pcand = i32(nb), i32(nb), i32(nb)
-        self.last, self.outlen, self.klens = i32(nb), i32(nb), i32(nb)
-        self.score = torch.zeros(nb, device=dev, dtype=torch.float64)
-        self.score_ctc = f32(nb)
-        self.vals, self.cands, self.lm_at, self.psi = f32(nb, cw), i32(nb, cw), f32(nb, cw), f32(nb, cw)
+        self.lm_at, self.psi = f32(nb, cw), f32(nb, cw)
         self.logits = torch.zeros(nb, V, device=dev, dtype=dtype)
-        self.lm_logp = f32(nb, V) if (lnl or rnn) else None
-        # a stateful LM (rnn = (L, H); section 26): slot pools of two halves (previous / current step), no K / V pools
-        self.lm_h = torch.zeros(rnn[0], 2 * nb, rnn[1], device=dev, dtype=dtype) if rnn else None
-        self.lm_c = f32(rnn[0], 2 * nb, rnn[1]) if rnn else None
+        self.lm_logp = self.lm_logits if rnn else (f32(nb, V) if lnl else None)    # (what either LM's step writes)
         self.dec_k = torch.zeros(2, dnl, nb, Lmax, dd, device=dev, dtype=dtype)
         self.dec_v = torch.zeros_like(self.dec_k)
         self.lm_k = torch.zeros(2, max(lnl, 1), nb, Lmax, max(ld, 1), device=dev, dtype=dtype) if lnl else None
         self.lm_v = torch.zeros_like(self.lm_k) if lnl else None
-        self.moff = i32(S + 1)
         self.ctc_x = f32(rows_cap, V) if use_ctc else None
         self.states = f32(2, nb, cw, Tcap, 2) if use_ctc else None
-        self.mirror_host = torch.zeros(2, dtype=torch.int32).pin_memory()   # {position, finished searches}
-        if grid:   # the fusion grid: search -> utterance, the LM weight of every search / row, the attention's row groups [<= S, 3]
-            self.sutt, self.groups = i32(S), i32(3 * S)
-            self.mu, self.mu_row = f32(S), f32(nb)
-        self.graphs = None    # (key, [graph of the even steps, graph of the odd steps], what the captured structs point at)
+        if grid:   # the LM weight of every search, the attention's row groups [<= S, 3]
+            self.groups, self.mu = i32(3 * S), f32(S)
 
 
 def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, decode_ctc_weight, grid=None, sort=True):
@@ -531,14 +499,7 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             ctc_logits = eng.head_logits(mem.unsqueeze(0), "decoder.ctc.output")
             Bf.ctc_x[:total].copy_(ops.log_softmax(ctc_logits.view(total, V)))
 
-        def reset(done):
-            Bf.state.copy_(h2d_i32([[0, 1, 0, done]] * S, dev))
-            Bf.pos.zero_(); Bf.ctl.fill_(done)
-            Bf.ids.fill_(eos); Bf.last.fill_(eos)
-            Bf.parent.copy_(torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(W) * W)
-            Bf.pcand.zero_(); Bf.outlen.zero_(); Bf.klens.fill_(1)
-            Bf.score.zero_(); Bf.score_ctc.zero_()
-
+        reset = lambda done: lockstep.reset_book(Bf, S, W, eos, done)
         lam, mu = float(decode_ctc_weight), float(lm_weight)
         if grid:    # the weights are device data; the groups' count and width are part of the captured launches
             mu = 0.0
@@ -550,13 +511,9 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
             ws_dec = torch.empty(lib.size_query("emoasr_decode_step_group_ws_bytes", dt_code, nb, dd, dh, F, V), device=dev, dtype=torch.uint8)
             ws_lm = torch.empty(lib.size_query("emoasr_decode_step_ws_bytes", dt_code, nb, max(ld, 8), max(lH, 1), max(lF, 8), V),
                                 device=dev, dtype=torch.uint8) if (use_lm and not rnn) else None
-            if rnn:      # the stateful LM's step over the chain's rows: weight tables (host arrays of device pointers) and workspace
-                ws_lm = torch.empty(lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", dt_code, nb, lm.H), device=dev, dtype=torch.uint8)
-                ptrs = ctypes.c_void_p * lm.L
-                lm_w = [lm._w(l) for l in range(lm.L)]
-                lm_tabs = (ptrs(*[w[0].data_ptr() for w in lm_w]), ptrs(*[w[1].data_ptr() for w in lm_w]),
-                           ptrs(*[b.data_ptr() for b in lm._bias]))
-            rows = []
+            rows, lm_tabs = [], None
+            if rnn:      # the stateful LM's step over the chain's rows: the even step reads half 1 of the pools and writes half 0
+                rows, lm_tabs, ws_lm = lockstep.rnnlm_rows_pair(lm, LA, Bf, nb, V, dt_code, even_src=1)
             pe_dec = eng._abs_table(Lmax, dev, dd)
             steps = []
             for cur in (0, 1):
@@ -582,18 +539,7 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 d.logits_last, d.ws, d.ws_bytes = Bf.logits.data_ptr(), ws_dec.data_ptr(), ws_dec.numel()
                 js.dec_k_prev, js.dec_v_prev = Bf.dec_k[prev].data_ptr(), Bf.dec_v[prev].data_ptr()
                 js.lm_nl = lnl if use_lm else 0
-                if rnn:      # the even step reads half 1 of the pools and writes half 0, the odd step the reverse
-                    rl = lib.RnnlmRows()
-                    rl.L, rl.E, rl.H, rl.V, rl.R = lm.L, lm.E, lm.H, V, nb
-                    rl.emb = LA.w("lm.embed.weight").data_ptr()
-                    rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, ctypes.c_void_p) for t in lm_tabs)
-                    rl.w_out, rl.b_out = LA.w("lm.output.weight").data_ptr(), LA.p("lm.output.bias").data_ptr()
-                    rl.ph, rl.pc, rl.slots = Bf.lm_h.data_ptr(), Bf.lm_c.data_ptr(), 2 * nb
-                    rl.src_base, rl.dst_base = prev * nb, cur * nb
-                    rl.logits, rl.ldl = Bf.lm_logp.data_ptr(), V
-                    rl.ws, rl.ws_bytes = ws_lm.data_ptr(), ws_lm.numel()
-                    rows.append(rl)
-                elif use_lm:
+                if use_lm and not rnn:
                     js.lm_layers = lm_layers
                     l = js.lm
                     pre, cp = "lm.transformer.bert.", "lm.transformer.cls.predictions."
@@ -613,40 +559,16 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 if use_ctc:
                     js.ctc_x = Bf.ctc_x.data_ptr()
                     js.states_prev, js.states_cur = Bf.states[prev].data_ptr(), Bf.states[cur].data_ptr()
-                ub = js.upd
-                ub.S, ub.max_pos, ub.pos, ub.ctl = S, max_steps, Bf.pos.data_ptr(), Bf.ctl.data_ptr()
-                u = ub.u
-                u.bw, u.cw, u.eos = W, cw, eos
+                lockstep.fill_beam_update(js.upd, Bf, S, W, cw, eos, max_steps, len_weight)
+                u = js.upd.u
                 u.one_minus_lam, u.lam = float(np.float32(1 - lam)), float(np.float32(lam))
                 u.mu = float(np.float32(mu)) if use_lm else 0.0      # (the grid: mu[s] on the device)
-                u.len_weight = float(len_weight)
-                u.vals, u.cands = Bf.vals.data_ptr(), Bf.cands.data_ptr()
                 u.lm_at = Bf.lm_at.data_ptr() if (use_lm and use_ctc) else None
                 u.psi = Bf.psi.data_ptr() if use_ctc else None
-                u.score, u.score_ctc = Bf.score.data_ptr(), Bf.score_ctc.data_ptr()
-                u.n_ids, u.n_parent, u.n_pcand = Bf.ids.data_ptr(), Bf.parent.data_ptr(), Bf.pcand.data_ptr()
-                u.n_last, u.n_outlen, u.n_klens = Bf.last.data_ptr(), Bf.outlen.data_ptr(), Bf.klens.data_ptr()
-                u.hist_parent, u.hist_token = Bf.hist_parent.data_ptr(), Bf.hist_token.data_ptr()
-                u.res_score, u.res_step, u.res_parent = Bf.res_score.data_ptr(), Bf.res_step.data_ptr(), Bf.res_parent.data_ptr()
-                u.state = Bf.state.data_ptr()
-                u.host_mirror = Bf.mirror_host.data_ptr()
                 steps.append(gs if grid else js)
-            # warm-up with every search marked finished (the bookkeeping returns at once, the networks run on valid rows):
-            # every kernel's lazy one-time setup happens outside the capture.  Then each step is captured once: a linear
-            # chain on one stream.
             step_args = lambda k: (dt_code, ctypes.byref(steps[k])) + ((ctypes.byref(rows[k]),) if rnn else ()) + (ops._stream(),)
-            reset(1)
-            for k in (0, 1):
-                lib.call(step_fn, *step_args(k))
-            torch.cuda.current_stream().synchronize()
-            graphs = []
-            for k in (0, 1):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="relaxed"), ops.stream_scope():
-                    lib.call(step_fn, *step_args(k))
-                graphs.append(g)
-            Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group, rows, lm_tabs if rnn else None))
-        graphs = Bf.graphs[1]
+            graphs = lockstep.capture_two_steps(lambda k: lib.call(step_fn, *step_args(k)), reset)
+            Bf.graphs = (gkey, graphs, (steps, ws_dec, ws_lm, pe_dec, dec_layers, rt.kv_group, rows, lm_tabs))
         reset(0)
         if rnn:       # (after the warm-up, whose steps write both halves) step 0 reads "previous" = half 1 at the search's row 0: zeros
             Bf.lm_h[:, nb:].zero_()
@@ -657,79 +579,9 @@ def _batch_search_chunk(dec, eng, eouts, elens, bw, len_weight, lm, lm_weight, d
                 ops.ctc_prefix_init_cells(Bf.ctc_x, Bf.moff[:U + 1], Bf.sutt, blank, Bf.states[1], W * cw * Tcap * 2)
             else:
                 ops.ctc_prefix_init_ragged(Bf.ctc_x, Bf.moff, blank, Bf.states[1], W * cw * Tcap * 2)
-        mirror = Bf.mirror_host.numpy()
-        mirror[:] = (0, 0)
-        main = torch.cuda.current_stream()
-        main.synchronize()     # (the mirror is host memory: the reset above must not race the first step's store)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(main)
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            # steps are issued one ahead of the mirror they depend on: a step replayed after the end changes nothing
-            for i in range(max_steps):
-                graphs[i & 1].replay()
-                if i >= 1 and batch_step_reported(mirror, i, S, main):
-                    break
-            ev1.record(main)
-            main.synchronize()
-        finally:
-            if gc_was_on:
-                gc.enable()
-        n_done = int(mirror[0])
-        stats = getattr(eng, "_beam_batch_stats", None)   # running totals for tools/joint_beam_bench.py
-        if stats is None:
-            stats = eng._beam_batch_stats = {"steps": 0, "loop_s": 0.0, "utts": 0, "calls": 0}
-        stats["steps"] += n_done; stats["loop_s"] += 1e-3 * ev0.elapsed_time(ev1); stats["utts"] += S; stats["calls"] += 1
-        host = Bf.pack.cpu().numpy()      # the one download
+        host = lockstep.replay_until_done(Bf.graphs[1], Bf, max_steps, S, eng, "_beam_batch_stats")   # (totals: tools/joint_beam_bench.py)
     caller.wait_stream(bstream)
     return batch_nbest_from_pack(host, Bf.pack_off, S, W, Lmax, sort)
-
-
-def batch_pack_sizes(S, W, Lmax):
-    """int32 words of the parts of the ONE allocation the host reads back after a batched search: res_score (double [nb]) |
-    state [S, 4] | res_step [nb] | res_parent [nb] | hist_parent [Lmax, nb] | hist_token [Lmax, nb]"""
-    nb = S * W
-    return [2 * nb, 4 * S, nb, nb, Lmax * nb, Lmax * nb]
-
-
-def batch_step_reported(mirror, i, S, main):
-    """wait until emoasr_beam_update_batch's pinned mirror {position, finished searches} shows step i - 1 -> whether every search
-    has finished"""
-    spins, t_wait = 0, None
-    while mirror[0] < i and mirror[1] < S:
-        _yield()
-        spins += 1
-        if spins & 0xFFF == 0:   # a lost launch / a faulted device must surface, not spin forever
-            now = time.perf_counter()
-            t_wait = now if t_wait is None else t_wait
-            if now - t_wait > _STEP_DEADLINE_S:
-                raise RuntimeError(f"batched beam search: step {i - 1} did not report within {_STEP_DEADLINE_S:.0f} s "
-                                   f"(stream idle: {main.query()}; last library error: {lib.load().emoasr_last_error().decode()!r})")
-    return mirror[1] >= S
-
-
-def batch_nbest_from_pack(host, o, S, W, Lmax, sort=True):
-    """the downloaded pack (batch_pack_sizes; o: the parts' offsets) -> (hyps[s], scores[s]): the token sequences rebuilt from
-    the (parent, token) history, each search's results sorted by score (stable); sort=False: in the order they were found"""
-    rs = host[o[0]:o[1]].view(np.float64)
-    state = host[o[1]:o[2]].reshape(S, 4)
-    rstep, rpar = host[o[2]:o[3]], host[o[3]:o[4]]
-    hp, ht = host[o[4]:o[5]].reshape(Lmax, S, W), host[o[5]:o[6]].reshape(Lmax, S, W)
-    hyps, scores = [], []
-    for s in range(S):
-        results = []
-        for k in range(int(state[s, 2])):
-            toks, slot = [], int(rpar[s * W + k])
-            for p in range(int(rstep[s * W + k]) - 1, -1, -1):
-                toks.append(int(ht[p, s, slot]))
-                slot = int(hp[p, s, slot])
-            results.append((toks[::-1], float(rs[s * W + k])))
-        if sort:
-            results = sorted(results, key=lambda r: r[1], reverse=True)
-        hyps.append([r[0] for r in results])
-        scores.append([r[1] for r in results])
-    return hyps, scores
 
 
 def joint_beam_search_device_batch(dec, eouts, elens, beam_width, len_weight=0, lm=None, lm_weight=0, decode_ctc_weight=0):
@@ -771,108 +623,53 @@ def joint_beam_search_device_batch(dec, eouts, elens, beam_width, len_weight=0, 
 GRID_CELLS_PER_GROUP = 1
 
 
-def grid_cell_plan(lm_weights, len_weights, has_lm=True):
-    """-> (search_weights, cells): search_weights the distinct lm_weights to search in order of first appearance, every weight
-    <= 0 (and every weight without an LM) folded into ONE entry 0.0, the search without the LM; cells[c] = (index into
-    search_weights, index into len_weights) for the cells in lm_weight-outer, len_weight-inner order.  Weights are compared as
-    doubles, unrounded: 0.30000000000000004 and 0.3 are two searches."""
-    search_weights, index, cells = [], {}, []
-    for a in lm_weights:
-        a = float(a)
-        a = a if (has_lm and a > 0) else 0.0
-        if a not in index:
-            index[a] = len(search_weights)
-            search_weights.append(a)
-        cells += [(index[a], j) for j in range(len(len_weights))]
-    return search_weights, cells
-
-
-def grid_chunk_plan(n_utts, n_weights, cap):
-    """chunks of at most cap searches for n_utts utterances of n_weights searches each -> [[(utterance, first weight, count)]]:
-    whole utterances per chunk while an utterance fits a chunk; an utterance with more searches than a chunk is cut into
-    pieces of cap (each piece forms that utterance's memory projection again)"""
-    assert n_weights >= 1 and cap >= 1
-    chunks, cur, room = [], [], cap
-    for b in range(n_utts):
-        k0 = 0
-        while k0 < n_weights:
-            left = n_weights - k0
-            if left > room and (cur and (left <= cap or k0 == 0)):   # does not fit behind what the chunk holds: a new chunk
-                chunks.append(cur)
-                cur, room = [], cap
-            n = min(left, room)
-            cur.append((b, k0, n))
-            k0 += n
-            room -= n
-            if room == 0:
-                chunks.append(cur)
-                cur, room = [], cap
-    if cur:
-        chunks.append(cur)
-    return chunks
-
-
-def expand_len_weights(hyps, scores, len_weights):
-    """the results of ONE search at len_weight 0 in the order the search found them -> per len_weight w (hyps, scores): every score
-    + w * (len(hyp) + 2) in double -- what emoasr_beam_update_batch writes as cscore + len_weight * (double)(pos + 2), the library
-    being compiled without contraction of the multiply-add -- sorted by score with the stable order of batch_nbest_from_pack"""
-    out = []
-    for w in len_weights:
-        w = float(w)
-        sc = [float(s) + w * float(len(h) + 2) for h, s in zip(hyps, scores)]
-        order = sorted(range(len(sc)), key=lambda i: sc[i], reverse=True)
-        out.append(([hyps[i] for i in order], [sc[i] for i in order]))
-    return out
-
-
 def joint_beam_search_device_grid(dec, eouts, elens, beam_width, lm, lm_weights, len_weights, decode_ctc_weight=0):
     """the joint search of every utterance for every (lm_weight, len_weight) cell -> (hyps, scores): hyps[b][c] / scores[b][c] what
     joint_beam_search_device_batch returns for utterance b with cell c's weights (cells in lm_weight-outer, len_weight-inner
-    order).  Distinct lm_weights are searched once, at len_weight 0; weights <= 0 are one search without the LM."""
+    order).  Distinct lm_weights are searched once, at len_weight 0; weights <= 0 are one search without the LM
+    (lockstep.run_fusion_grid)."""
     lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
-    weights, cells = grid_cell_plan(lm_weights, len_weights, lm is not None)
-    require_next_token_lm(lm, max(weights))
+    top = max(grid_cell_plan(lm_weights, len_weights, lm is not None)[0])
+    require_next_token_lm(lm, top)
     elens = [int(n) for n in elens]
     B = eouts.shape[0]
     if len(elens) != B or any(n < 1 for n in elens):
         raise ValueError(f"joint_beam_search_device_grid: every utterance needs at least one frame, got elens {elens}")
-    found = [[None] * len(weights) for _ in range(B)]     # [b][k] -> (hyps, scores) of search k at len_weight 0
-    if not batch_device_ok(dec, beam_width, lm, max(weights), decode_ctc_weight):
+    expand = lambda f, a: expand_len_weights(*f, len_weights)
+    if not batch_device_ok(dec, beam_width, lm, top, decode_ctc_weight):
         from .beam_search import joint_beam_search_batch
-        for k, a in enumerate(weights):
-            h, s = joint_beam_search_batch(dec, eouts, elens, beam_width, 0, lm, a, decode_ctc_weight)[:2]
-            for b in range(B):
-                found[b][k] = (h[b], s[b])
-    else:
-        eng = _engine_of(dec)
-        esz = 2 if eouts.dtype == torch.bfloat16 else 4
-        Lmax = dec.max_decode_ylen + 1
-        positive = [k for k, a in enumerate(weights) if a > 0]
-        if len(positive) < len(weights):      # the search without the LM: the batched search as it is, no LM launches
-            k = weights.index(0.0)
-            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, 0, 0, esz)
-            for b0 in range(0, B, cap):
-                n = elens[b0:b0 + cap]
-                h, s = _batch_search_chunk(dec, eng, eouts[b0:b0 + cap, :max(n)], n, beam_width, 0, None, 0, decode_ctc_weight, sort=False)
-                for i in range(len(n)):
-                    found[b0 + i][k] = (h[i], s[i])
-        if positive:
-            lnl, ld = (0, 0) if getattr(lm, "stateful", False) else (lm.params.num_layers, lm.params.hidden_size)
-            cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, lnl, ld, esz)
-            for chunk in grid_chunk_plan(B, len(positive), cap):
-                utts = sorted({b for b, _, _ in chunk})
-                local = {b: i for i, b in enumerate(utts)}
-                n = [elens[b] for b in utts]
-                sutt = [local[b] for b, _, cnt in chunk for _ in range(cnt)]
-                ks = [positive[k0 + j] for _, k0, cnt in chunk for j in range(cnt)]
-                sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
-                h, s = _batch_search_chunk(dec, eng, sub, n, beam_width, 0, lm, 0, decode_ctc_weight,
-                                           grid=(sutt, [weights[k] for k in ks], GRID_CELLS_PER_GROUP), sort=False)
-                for i, (u, k) in enumerate(zip(sutt, ks)):
-                    found[utts[u]][k] = (h[i], s[i])
-    hyps, scores = [], []
-    for b in range(B):
-        per_search = [expand_len_weights(h, s, len_weights) for h, s in found[b]]
-        hyps.append([per_search[k][j][0] for k, j in cells])
-        scores.append([per_search[k][j][1] for k, j in cells])
-    return hyps, scores
+        host = lambda a: joint_beam_search_batch(dec, eouts, elens, beam_width, 0, lm, a, decode_ctc_weight)[:2]
+
+        def host_fused(positive, weights, found):
+            for k in positive:
+                h, s = host(weights[k])
+                for b in range(B):
+                    found[b][k] = (h[b], s[b])
+
+        return lockstep.run_fusion_grid(B, lm_weights, len_weights, lm is not None, lambda: host(0.0), host_fused, expand)
+    eng = _engine_of(dec)
+    esz = 2 if eouts.dtype == torch.bfloat16 else 4
+    Lmax = dec.max_decode_ylen + 1
+
+    def search_plain():      # the search without the LM: the batched search as it is, no LM launches
+        cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, 0, 0, esz)
+        hyps, scores = [], []
+        for b0 in range(0, B, cap):
+            n = elens[b0:b0 + cap]
+            h, s = _batch_search_chunk(dec, eng, eouts[b0:b0 + cap, :max(n)], n, beam_width, 0, None, 0, decode_ctc_weight, sort=False)
+            hyps += h
+            scores += s
+        return hyps, scores
+
+    def search_fused(positive, weights, found):
+        lnl, ld = (0, 0) if getattr(lm, "stateful", False) else (lm.params.num_layers, lm.params.hidden_size)
+        cap = batch_chunk_capacity(beam_width, Lmax, eng.dnl, eng.dd, lnl, ld, esz)
+        for utts, n, sutt, k_local in lockstep.grid_chunks(B, len(positive), cap, elens):
+            ks = [positive[j] for j in k_local]
+            sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
+            h, s = _batch_search_chunk(dec, eng, sub, n, beam_width, 0, lm, 0, decode_ctc_weight,
+                                       grid=(sutt, [weights[k] for k in ks], GRID_CELLS_PER_GROUP), sort=False)
+            for i, (u, k) in enumerate(zip(sutt, ks)):
+                found[utts[u]][k] = (h[i], s[i])
+
+    return lockstep.run_fusion_grid(B, lm_weights, len_weights, lm is not None, search_plain, search_fused, expand)

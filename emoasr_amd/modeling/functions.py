@@ -10,6 +10,7 @@ import logging
 
 import torch
 
+from .. import lockstep
 from ..engine import h2d_i32
 
 
@@ -412,7 +413,7 @@ def las_beam_apply(dec, eouts, beam_width, len_weight, lm=None, lm_weight=0):
 
 
 LAS_BATCH_MAX_BEAM = 32   # rows of a search in csrc/las_beam.hip and in emoasr_beam_update_batch
-_LAS_FUSION_LOGGED = set()   # reasons already logged (las_fusion_route)
+_LAS_FUSION_LOGGED = lockstep._LOGGED   # what log_once has emitted (las_fusion_route, las_fusion_grid_apply)
 
 
 def las_lm_fusion(dec):
@@ -425,20 +426,12 @@ def las_lm_fusion(dec):
 
 
 def las_rnnlm_why_not(dec, beam_width, lm):
-    """why the batched LAS search cannot fuse this LM through emoasr_rnnlm_step_rows (None: it can; the twin
-    of beam_search_device.batch_rnnlm_why_not)"""
-    from .. import lib
-    if getattr(lm, "lm_type", None) != "rnn":
-        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
+    """why the batched LAS search cannot fuse this LM through emoasr_rnnlm_step_rows (None: it can):
+    lockstep.rnnlm_rows_why_not's reasons, then the beam width"""
     V = dec.vocab_size
-    if lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
-        return f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
-    eng = _engine_of(dec)
-    if lm.compute_dtype != eng.dtype or bool(lm.f32_split) != bool(eng.split):
-        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
-    code = lib.F32X3 if lm.f32_split else {torch.float32: lib.F32, torch.bfloat16: lib.BF16}.get(lm.compute_dtype)
-    if code is None or lib.size_query("emoasr_rnnlm_step_rows_supported", code, lm.L, lm.E, lm.H) != 1:
-        return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnlm_step_rows' shape plan"
+    why = lockstep.rnnlm_rows_why_not(_engine_of(dec), V, lm)
+    if why is not None:
+        return why
     if not 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, V):
         return f"beam_width {beam_width} (vocabulary {V}) is outside the device bookkeeping's {LAS_BATCH_MAX_BEAM} beams"
     return None
@@ -454,9 +447,8 @@ def las_fusion_route(dec, beam_width, lm, lm_weight):
     from .lm import require_next_token_lm
     require_next_token_lm(lm, lm_weight)
     why = las_rnnlm_why_not(dec, beam_width, lm)
-    if why is not None and why not in _LAS_FUSION_LOGGED:
-        _LAS_FUSION_LOGGED.add(why)
-        logging.getLogger(__name__).info(f"LAS beam search: the LM is fused by one host search per utterance: {why}")
+    if why is not None:
+        lockstep.log_once(logging.getLogger(__name__), f"LAS beam search: the LM is fused by one host search per utterance: {why}")
     return lm, lm_weight, why
 
 
@@ -496,32 +488,36 @@ def las_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_wei
     lm_weight-outer, len_weight-inner order.  Where the device form takes the LM: ONE
     las_beam_search_batch grid call.  Else (las_rnnlm_why_not's reason, logged once): one host-form search per utterance and
     distinct lm_weight at len_weight 0, the len_weights expanded on the host as the device grid expands them."""
-    from . import beam_search_device as bsd
     from .lm import require_next_token_lm
     lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
     eng = _engine_of(dec)
     elens = _las_check_elens(eouts, elens, "las_fusion_grid")
-    weights, cells = bsd.grid_cell_plan(lm_weights, len_weights, lm is not None)
-    any_lm = max(weights) > 0
+    weights = lockstep.grid_cell_plan(lm_weights, len_weights, lm is not None)[0]
+    top = max(weights)
     why = None
-    if any_lm:
-        require_next_token_lm(lm, max(weights))
+    if top > 0:
+        require_next_token_lm(lm, top)
         why = las_rnnlm_why_not(dec, beam_width, lm)
     if why is None and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
-        return eng.las_beam_search_batch(eouts, elens, beam_width, 0, dec.eos_id, dec.max_decode_ylen, lm=lm if any_lm else None,
+        return eng.las_beam_search_batch(eouts, elens, beam_width, 0, dec.eos_id, dec.max_decode_ylen, lm=lm if top > 0 else None,
                                          lm_weights=lm_weights, len_weights=len_weights)
-    if why is not None and why not in _LAS_FUSION_LOGGED:
-        _LAS_FUSION_LOGGED.add(why)
-        logging.getLogger(__name__).info(f"LAS fusion grid: one host search per utterance and lm_weight: {why}")
-    hyps, scores = [], []
-    for b in range(len(elens)):
-        per_search = []
-        for a in weights:
-            h, s = las_beam_apply(dec, eouts[b:b + 1, :elens[b]], beam_width, 0, lm if a > 0 else None, a)
-            per_search.append(bsd.expand_len_weights(h, s, len_weights))
-        hyps.append([per_search[k][j][0] for k, j in cells])
-        scores.append([per_search[k][j][1] for k, j in cells])
-    return hyps, scores
+    if why is not None:
+        lockstep.log_once(logging.getLogger(__name__), f"LAS fusion grid: one host search per utterance and lm_weight: {why}")
+    # utterance by utterance, every search weight of one before the next; the driver assembles the cells
+    per = [[las_beam_apply(dec, eouts[b:b + 1, :elens[b]], beam_width, 0, lm if a > 0 else None, a) for a in weights]
+           for b in range(len(elens))]
+
+    def search_plain():
+        k = weights.index(0.0)
+        return [p[k][0] for p in per], [p[k][1] for p in per]
+
+    def search_fused(positive, weights, found):
+        for b, p in enumerate(per):
+            for k in positive:
+                found[b][k] = p[k]
+
+    return lockstep.run_fusion_grid(len(elens), lm_weights, len_weights, lm is not None, search_plain, search_fused,
+                                    lambda f, a: lockstep.expand_len_weights(*f, len_weights))
 
 
 class _CMLMDecoderFn(torch.autograd.Function):

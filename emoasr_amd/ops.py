@@ -1754,16 +1754,25 @@ def rnnlm_step_rows(W, R, ids, parent, ph, pc, src_base, dst_base, logits):
     need = lib.size_query("emoasr_rnnlm_step_rows_ws_bytes", _DT[emb.dtype], R, H)
     if ws is None or ws.numel() < need:
         ws = W.ws_rows = torch.empty(need, device=emb.device, dtype=torch.uint8)
-    rl = lib.RnnlmRows()
-    rl.L, rl.E, rl.H, rl.V, rl.R = L, W.E, H, W.V, R
-    rl.emb = emb.data_ptr()
-    rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, c_void_p) for t in (W.p_ih, W.p_hh, W.p_b))
-    rl.w_out, rl.b_out = w_out.data_ptr(), b_out.data_ptr()
-    rl.ph, rl.pc, rl.slots = ph.data_ptr(), _chk(pc, torch.float32).data_ptr(), slots
-    rl.src_base, rl.dst_base = src_base, dst_base
-    rl.logits, rl.ldl = _chk(logits, torch.float32).data_ptr(), logits.stride(0)
-    rl.ws, rl.ws_bytes = ws.data_ptr(), ws.numel()
+    rl = rnnlm_rows_fill(R, W.V, emb, (W.p_ih, W.p_hh, W.p_b), w_out, b_out, ph, _chk(pc, torch.float32), src_base, dst_base,
+                         _chk(logits, torch.float32), ws)
     lib.call("emoasr_rnnlm_step_rows", dt(emb), ctypes.byref(rl), _p(ids), _p(parent), _stream())
+
+
+def rnnlm_rows_fill(R, V, emb, tabs, w_out, b_out, ph, pc, src_base, dst_base, logits, ws):
+    """-> lib.RnnlmRows for R rows: tabs = (w_ih, w_hh, bias) per-layer pointer tables (host arrays of device pointers, which the
+    caller keeps alive), ph / pc [L, slots, H] the state pools, logits f32 [>= R, >= V] (row stride allowed), ws the workspace"""
+    rl = lib.RnnlmRows()
+    L, slots, H = ph.shape
+    rl.L, rl.E, rl.H, rl.V, rl.R = L, emb.shape[1], H, V, R
+    rl.emb = emb.data_ptr()
+    rl.w_ih, rl.w_hh, rl.bias = (ctypes.cast(t, c_void_p) for t in tabs)
+    rl.w_out, rl.b_out = w_out.data_ptr(), b_out.data_ptr()
+    rl.ph, rl.pc, rl.slots = ph.data_ptr(), pc.data_ptr(), slots
+    rl.src_base, rl.dst_base = src_base, dst_base
+    rl.logits, rl.ldl = logits.data_ptr(), logits.stride(0)
+    rl.ws, rl.ws_bytes = ws.data_ptr(), ws.numel()
+    return rl
 
 
 # ---- LAS decoder: location-aware attention, one position (csrc/las.hip) -------------------------------------------

@@ -261,6 +261,32 @@ def test_chunking(dev, monkeypatch):
         assert _close(a, c), (a, c)
 
 
+def test_replayed_graphs_outlive_a_collection(dev):
+    """the fused chunk of B = 3, elens (9, 4, 2), W = 4 is captured on one set of frames; after gc.collect() the same graphs are
+    replayed on other frames of the same shape and return exactly what a fresh engine, which captures anew, returns for them:
+    everything the captured launches point at (structs, pointer tables, workspaces) is still alive"""
+    import gc
+    from emoasr_amd.modeling import beam_search_device as bsd
+    from emoasr_amd.modeling.asr import ASR
+    model, lm, _ = _models(torch.float32, dev)
+    five, five_lens = _five(torch.float32, dev)
+    elens = [9, 4, 2]
+    assert min(five_lens[:2]) >= 9 and five_lens[3] >= 2
+    first, second = five[[0, 1, 2], :9].contiguous(), five[[1, 0, 3], :9].contiguous()
+    run = lambda dec, frames: bsd._batch_search_chunk(dec, bsd._engine_of(dec), frames, elens, 4, 0.0, lm, 0.3, 0.3)
+    run(model.decoder, first)
+    eng = bsd._engine_of(model.decoder)
+    graphs = eng._beam_batch_bufs[1].graphs[1]
+    gc.collect()
+    got = run(model.decoder, second)
+    assert eng._beam_batch_bufs[1].graphs[1] is graphs, "the second call replays the first call's graphs"
+    fresh = ASR(SimpleNamespace(**CONFIGS["l3_tiny"]), compute_dtype=torch.float32)
+    fresh.load_state_dict(load_golden("l3_tiny")[1])
+    want = run(fresh.to(dev).eval().decoder, second)
+    assert got == want, (got, want)
+    assert all(len(h) >= 1 for h in got[0]) and got != run(model.decoder, first)
+
+
 @pytest.mark.parametrize("ctc_weight,W,lm_weights,len_weights", [(0.3, 4, [0.0, 0.3], [0.0, 0.1, 0.3]), (0.0, 3, [0.5], [0.0, 0.2, 0.3])])
 def test_grid(dev, ctc_weight, W, lm_weights, len_weights, monkeypatch):
     """every cell of joint_beam_search_device_grid equals the batched device search run with that cell's weights (hypotheses exact,

@@ -144,17 +144,23 @@ def _las():
 def _model(dev, mode):
     """the las_tiny model (eval mode) and the rnnlm_tiny LM in the same compute dtype, one pair per dtype for the module"""
     if mode not in _CACHE:
-        from emoasr_amd.modeling.asr import ASR
         from emoasr_amd.modeling.lm import LM
-        cfg, sd, _ = _las()
-        torch.manual_seed(0)
-        model = ASR(SimpleNamespace(**las_ref.las_asr_config(cfg)), compute_dtype=mode)
-        model.load_state_dict(sd, strict=False)
-        model.decoder.score.dropout_attn_rate = 0.0
+        model = _asr(dev, mode)
         lm = LM(SimpleNamespace(**RNNLM_CFG), compute_dtype=mode)
         lm.load_state_dict(rnnlm_state(rnnlm_golden()))
-        _CACHE[mode] = (model.to(dev).eval(), lm.to(dev).eval())
+        _CACHE[mode] = (model, lm.to(dev).eval())
     return _CACHE[mode]
+
+
+def _asr(dev, mode):
+    """a las_tiny model of its own (eval mode): its engine has captured nothing yet"""
+    from emoasr_amd.modeling.asr import ASR
+    cfg, sd, _ = _las()
+    torch.manual_seed(0)
+    model = ASR(SimpleNamespace(**las_ref.las_asr_config(cfg)), compute_dtype=mode)
+    model.load_state_dict(sd, strict=False)
+    model.decoder.score.dropout_attn_rate = 0.0
+    return model.to(dev).eval()
 
 
 @pytest.fixture
@@ -233,6 +239,29 @@ def test_first_position_of_the_fused_step(dev, fused, monkeypatch):
         assert hi[0].tolist() == cands[b].tolist(), (b, hi, cands[b])
         assert (hv[0] - vals[b]).abs().max().item() < 1e-4, (b, hv, vals[b])
     assert len(seen) == 3
+
+
+def test_replayed_graphs_outlive_a_collection(dev, fused):
+    """the fused chunk of B = 3, elens (9, 4, 2), W = 4 is captured on one set of frames; after gc.collect() the same graphs are
+    replayed on other frames of the same shape and return exactly what a fresh engine, which captures anew, returns for them:
+    everything the captured launches point at (structs, pointer tables, workspace) is still alive"""
+    import gc
+    from emoasr_amd.modeling.functions import _engine_of
+    model, lm = fused
+    first, elens = _padded([(0, 9), (1, 4), (2, 2)], dev)
+    second, _ = _padded([(1, 9), (2, 4), (0, 2)], dev)
+    assert elens == [9, 4, 2]
+    dec = model.decoder
+    run = lambda eng, frames: eng._las_beam_chunk(frames, elens, 4, 0.0, dec.eos_id, dec.max_decode_ylen, lm, 0.3)
+    eng = _engine_of(dec)
+    run(eng, first)
+    graphs = eng._las_beam_bufs[1].graphs[1]
+    gc.collect()
+    got = run(eng, second)
+    assert eng._las_beam_bufs[1].graphs[1] is graphs, "the second call replays the first call's graphs"
+    want = run(_engine_of(_asr(dev, torch.float32).decoder), second)
+    assert got == want, (got, want)
+    assert all(len(h) >= 1 for h in got[0]) and got != run(eng, first)
 
 
 _E2E = [(a, W, lw) for a, W in U.CASES for lw in U.LEN_WEIGHTS]
