@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libemoasr_hip.so")
 SOURCES = ["api.hip", "gemm.hip", "layernorm.hip", "elementwise.hip", "convmodule.hip",
-           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "decode_batch.hip", "decode_grid.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_greedy_batch.hip", "rnnt_beam.hip", "rnnt_beam_book.hip", "rnnt_beam_lm.hip", "rnnlm.hip", "ctc_beam_host.hip", "ctc_beam.hip", "ctc_beam_lm.hip", "mlm.hip", "electra.hip", "correct.hip", "las.hip", "las_beam.hip", "rescore.hip"]
+           "subsample.hip", "ctc.hip", "attention.hip", "optim.hip", "feats.hip", "decoder.hip", "rnnt.hip", "layer.hip", "decode_rt.hip", "decode_batch.hip", "decode_grid.hip", "distill.hip", "gemm_big.hip", "gemm_big_tn.hip", "convfused.hip", "rowlin.hip", "decode_coop.hip", "lstm_coop.hip", "bilstm.hip", "rnnt_greedy.hip", "rnnt_greedy_batch.hip", "rnnt_beam.hip", "rnnt_beam_book.hip", "rnnt_beam_lm.hip", "lm_tree.hip", "rnnlm.hip", "ctc_beam_host.hip", "ctc_beam.hip", "ctc_beam_lm.hip", "mlm.hip", "electra.hip", "correct.hip", "las.hip", "las_beam.hip", "rescore.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-Wno-unused-value", "-Wno-comment",
          "-ffp-contract=off"]
 

@@ -719,6 +719,51 @@ class RNNTDecoder:
             return f"the LM's vocabulary ({lm.V}) is smaller than the model's ({V_})"
         return None
 
+    _TLM_POOL_BUDGET = 8 << 30     # bytes of K / V node pools one chunk of Transformer-LM fused searches may hold (the joint search's
+                                   # cache budget, not the 256 MB of the LSTM pools: a node is layers x d x 2 values)
+
+    def rnnt_beam_tlm_why_not(self, lm):
+        """why the batched device search cannot fuse this LM over the prefix tree (None: it can).  The LM's step
+        is emoasr_lm_tree_step (csrc/lm_tree.hip) beside the prediction network's launches: a causal Transformer LM (lm_type ==
+        "transformer") of the engine's compute dtype and product mode, its vocabulary at least the model's, its heads and its longest
+        prefix inside emoasr_lm_tree_attn's plan.  rnnt_beam_lm_why_not keeps answering for the RNN form."""
+        from .. import lm_tree
+        if getattr(lm, "lm_type", None) != "transformer":
+            return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'transformer'"
+        if not getattr(lm, "causal", False):
+            return "there is no causal LM (the prefix tree steps p(next token | prefix))"
+        if lm.compute_dtype != self.dtype or lm.compute_dtype not in (torch.float32, torch.bfloat16) or bool(lm.f32_split) != bool(self.split):
+            return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {self.dtype} ({bool(self.split)})"
+        P = lm.params
+        V_ = self.arena.w("decoder.output.weight").shape[0]
+        if P.vocab_size < V_:
+            return f"the LM's vocabulary ({P.vocab_size}) is smaller than the model's ({V_})"
+        if not lm_tree.head_ok(P.hidden_size, P.num_attention_heads):
+            return (f"the LM's heads ({P.hidden_size} over {P.num_attention_heads}) are outside emoasr_lm_tree_attn's plan "
+                    f"(8 .. 128 wide, a multiple of 8)")
+        if lm_tree.attn_lds_bytes(P.max_seq_len) > lm_tree.LDS_BYTES:
+            return (f"max_seq_len {P.max_seq_len} needs {lm_tree.attn_lds_bytes(P.max_seq_len)} bytes of LDS in emoasr_lm_tree_attn "
+                    f"({lm_tree.LDS_BYTES} at most)")
+        return None
+
+    @staticmethod
+    def _tlm_frames(longest):
+        """the frame capacity the tree's buffers are sized for: the longest utterance, rounded up to 64 frames"""
+        return max(64, -(-int(longest) // 64) * 64)
+
+    def rnnt_beam_tlm_chunk_capacity(self, W, E, lm, longest):
+        """searches per launch chain with the Transformer LM: _BEAM_BATCH_CAP, and no more than hold their tree -- W (E - 1) frames + 1
+        nodes per search (the worst case: every fused round steps W rows) of (K, V) x layers x d values, the lists of its (E + 1) W
+        slots and the prediction network's pools -- inside _TLM_POOL_BUDGET; never below one"""
+        from .. import lm_tree
+        P = lm.params
+        esz = 2 if self.dtype == torch.bfloat16 else 4
+        frames = self._tlm_frames(longest)
+        nodes, Lcap = lm_tree.node_cap(W, E, frames), lm_tree.list_cap(E, frames, P.max_seq_len)
+        per_search = (2 * P.num_layers * nodes * P.hidden_size * esz + (E + 1) * W * (Lcap + 1) * 4
+                      + (E + 1) * W * (esz + 4) * self.r_nl * self.r_H)
+        return max(1, min(self._BEAM_BATCH_CAP, self._TLM_POOL_BUDGET // per_search))
+
     def rnnt_beam_device_ok(self, beam_width, num_expands=3, lm=None):
         """does the model fit the batched search's round kernels?  (the limits of the fused round, _rnnt_beam_round_graph, and of
         the bookkeeping kernel: beam_width <= 16, beam_width <= V - 1; with an LM to fuse, rnnt_beam_lm_why_not as well)"""
@@ -748,7 +793,8 @@ class RNNTDecoder:
         order = sorted(range(len(sc)), key=lambda i: -sc[i])
         return [hyps[i] for i in order], [sc[i] for i in order]
 
-    def rnnt_beam_search_batch(self, eouts, elens, beam_width, blank, eos, num_expands=3, lm=None, lm_weights=None, len_weights=None):
+    def rnnt_beam_search_batch(self, eouts, elens, beam_width, blank, eos, num_expands=3, lm=None, lm_weights=None, len_weights=None,
+                               tlm_fusion="host"):
         """alignment-length synchronous beam search for a BATCH (rnn_transducer.py:242-325 per utterance; the reference asserts a
         batch of one): eouts [B, Tmax, d], utterance b is searched over its own elens[b] frames -> (hyps[b][n], scores[b][n]),
         best first, hypotheses with the leading <sos>, float64 scores.  The bookkeeping runs on the device
@@ -762,14 +808,23 @@ class RNNTDecoder:
         is an (utterance, lm_weight) pair: every distinct positive lm_weight of an utterance is searched once with the LM's LSTM
         stepped beside the prediction network's, all weights <= 0 (or no LM) are ONE search on the chain above.  The len_weights
         are a host expansion of a fused search's results (rnnt_len_expand); the search without the LM does not read them.  An LM
-        or a width the device form cannot take is searched utterance by utterance through the host form."""
+        or a width the device form cannot take is searched utterance by utterance through the host form.
+
+        tlm_fusion ("host", the default: everything above, unchanged; or "device"; decoder.rnnt_tlm_fusion): with "device" a
+        Transformer LM is fused on the device too, stepped over a prefix tree of K / V nodes in chunks of
+        rnnt_beam_tlm_chunk_capacity searches; an LM or a width that form cannot take is then a ValueError naming the reason, and a
+        search that outgrows the LM's positions or its node pool a RuntimeError naming the search.  self.rnnt_tlm_stats: the nodes
+        every search of the last such call took, and their bound."""
+        if tlm_fusion not in ("host", "device"):
+            raise ValueError(f"emoasr_amd: rnnt_tlm_fusion is 'host' or 'device', not {tlm_fusion!r}")
         elens = [int(v) for v in elens]
         B = eouts.shape[0]
         assert len(elens) == B and all(0 <= n <= eouts.shape[1] for n in elens), (elens, tuple(eouts.shape))
         with self._scope():
             self.arena.refresh_shadow()
         if lm_weights is not None:
-            return self._rnnt_beam_search_grid(eouts, elens, beam_width, blank, eos, num_expands, lm, lm_weights, len_weights)
+            return self._rnnt_beam_search_grid(eouts, elens, beam_width, blank, eos, num_expands, lm, lm_weights, len_weights,
+                                               tlm_fusion)
         hyps, scores = [], []
         if not self.rnnt_beam_device_ok(beam_width, num_expands):
             for b in range(B):
@@ -787,17 +842,26 @@ class RNNTDecoder:
             scores += s
         return hyps, scores
 
-    def _rnnt_beam_search_grid(self, eouts, elens, W, blank, eos, E, lm, lm_weights, len_weights):
+    def _rnnt_beam_search_grid(self, eouts, elens, W, blank, eos, E, lm, lm_weights, len_weights, tlm_fusion="host"):
         """rnnt_beam_search_batch with lm_weights: lockstep.run_fusion_grid over (utterance, weight) pairs in chunks; the fused
-        searches' results are expanded by rnnt_len_expand, the search without the LM does not read the len_weights"""
+        searches' results are expanded by rnnt_len_expand, the search without the LM does not read the len_weights.  tlm_fusion ==
+        "device" sends a Transformer LM through the same chunks over the prefix tree instead of the host chain."""
         from ..modeling.lm import require_next_token_lm
         lm_weights = [float(a) for a in lm_weights]
         len_weights = [0.0] if len_weights is None else [float(v) for v in len_weights]
         require_next_token_lm(lm, max(lockstep.grid_cell_plan(lm_weights, len_weights, lm is not None)[0]))
         B = len(elens)
 
+        tlm = tlm_fusion == "device" and getattr(lm, "lm_type", None) == "transformer"
+        if tlm and any(a > 0 for a in lm_weights):      # asked for by name: no quiet detour through the host chain
+            why = self.rnnt_beam_tlm_why_not(lm)
+            if why is None and not self.rnnt_beam_device_ok(W, E):
+                why = f"the model, beam_width {W} or num_expands {E} is outside the batched device search's limits"
+            if why is not None:
+                raise ValueError(f"emoasr_amd: rnnt_tlm_fusion = 'device' cannot fuse this LM: {why}")
+
         def search_fused(positive, weights, found):
-            if not self.rnnt_beam_device_ok(W, E, lm):      # the host chain, utterance by utterance
+            if not tlm and not self.rnnt_beam_device_ok(W, E, lm):      # the host chain, utterance by utterance
                 for b in range(B):
                     for k in positive:
                         if elens[b] == 0:
@@ -807,7 +871,11 @@ class RNNTDecoder:
                             found[b][k] = (h, [float(v) for v in s])
                 return
             pairs = [(b, k) for b in range(B) for k in positive]
-            cap = self.rnnt_beam_chunk_capacity(W, E, lm)
+            if tlm:
+                cap = self.rnnt_beam_tlm_chunk_capacity(W, E, lm, max(elens, default=0))
+                self.rnnt_tlm_stats = dict(nodes=[], node_cap=0, lcap=0)
+            else:
+                cap = self.rnnt_beam_chunk_capacity(W, E, lm)
             for p0 in range(0, len(pairs), cap):
                 chunk = pairs[p0:p0 + cap]
                 h, s = self._rnnt_beam_search_device(eouts, elens, W, blank, eos, E, lm, [weights[k] for _, k in chunk],
@@ -819,23 +887,34 @@ class RNNTDecoder:
                                         lambda: self.rnnt_beam_search_batch(eouts, elens, W, blank, eos, E), search_fused,
                                         lambda f, a: [self.rnnt_len_expand(*f, w) if a > 0 else f for w in len_weights])
 
-    def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total, lm=None):
+    def _rnnt_beam_frame_graph(self, S, W, blank, eos, E, total, lm=None, longest=0):
         """static buffers of S searches of width W over <= st.rows frames in all, and ONE FRAME of all of them (E rounds of
         LSTM layers, joint, output product, pick, book) captured as a HIP graph.  The warm-up runs the body with every search
         finished (no frames): every row is inactive, no state is touched.
         lm (an RNN LM that rnnt_beam_lm_why_not passes, _prepare()d by the caller): the fused frame -- every round but the last runs
         the LM's LSTM layers under the same control words on pools lh / lc beside ph / pc, gathers the top layer's h, forms the LM's
         logits and ranks the candidates with emoasr_rnnt_beam_pick_lm under the per-search weights st.mu; the last round of a frame
-        grows no candidate and stays the chain without the LM.  Keyed by the LM's identity, sizes and parameter addresses."""
+        grows no candidate and stays the chain without the LM.  Keyed by the LM's identity, sizes and parameter addresses.
+        lm a Transformer LM that rnnt_beam_tlm_why_not passes, longest = the chunk's longest utterance: the
+        same fused rounds with emoasr_lm_tree_advance + emoasr_lm_tree_step (csrc/lm_tree.hip) in place of the LSTM layers, gather and
+        head product: the tree state st.tree and the node pools of st.tstep beside ph / pc under the same slot numbers, sized for
+        st.tmax >= longest frames."""
         from .. import lib
         tab = self.__dict__.setdefault("_beam_batch_static", {})
         key = (S, W, blank, eos, E)
-        if lm is not None:
+        tlm = lm is not None and getattr(lm, "lm_type", None) == "transformer"
+        if tlm:
+            LA, P = lm._arena, lm.params
+            key += ("tlm", id(lm), P.vocab_size, P.hidden_size, P.num_attention_heads, P.intermediate_size, P.num_layers,
+                    P.max_seq_len, LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._pe.data_ptr())
+        elif lm is not None:
             LA = lm._arena
             key += (id(lm), lm.V, lm.E, lm.H, lm.L, LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._bias[0].data_ptr())
         st = tab.get(key)
-        if st is not None and st.rows >= total:
+        if st is not None and st.rows >= total and (not tlm or st.tmax >= longest):
             return st
+        if st is not None:
+            del tab[key], st       # (the pools of the outgrown record are released before the larger ones are taken)
         A, J, H, nl = self.arena, self.r_J, self.r_H, self.r_nl
         dev = A.flat.device
         V_ = A.w("decoder.output.weight").shape[0]
@@ -855,7 +934,21 @@ class RNNTDecoder:
         st.ws = torch.empty(lib.size_query("emoasr_rnnt_beam_ws_bytes", S, st.rows, W, E), device=dev, dtype=torch.uint8)
         st.status = torch.zeros(1, device=dev, dtype=torch.int32)
         st.bias = [self._lstm_bias(f"decoder.rnns.{l}").contiguous() for l in range(nl)]   # (refreshed per search)
-        if lm is not None:
+        if tlm:
+            from .. import lm_tree
+            st.tmax = self._tlm_frames(longest)
+            # the node pools of ALL kept records stay inside the budget: the oldest records go first (a chunk of another size,
+            # another width or another LM left them behind)
+            st.tbytes = (2 * P.num_layers * S * lm_tree.node_cap(W, E, st.tmax) * P.hidden_size
+                         * (2 if self.dtype == torch.bfloat16 else 4))
+            held = [k for k, v in tab.items() if getattr(v, "tbytes", 0)]
+            while held and sum(tab[k].tbytes for k in held) + st.tbytes > self._TLM_POOL_BUDGET:
+                del tab[held.pop(0)]
+            st.tree = lm_tree.TreeState(S, W, st.nslots, lm_tree.list_cap(E, st.tmax, lm.params.max_seq_len),
+                                        lm_tree.node_cap(W, E, st.tmax), dev)
+            st.tstep = lm_tree.TreeStep(lm, st.tree, c_void_p(st.ctl.data_ptr()), c_void_p(st.ctl.data_ptr() + 8 * R * 2))
+            st.mu = torch.zeros(S, device=dev, dtype=torch.float32)
+        elif lm is not None:
             st.lh = [torch.zeros(st.nslots, lm.H, device=dev, dtype=self.dtype) for _ in range(lm.L)]
             st.lc = [torch.zeros(st.nslots, lm.H, device=dev, dtype=torch.float32) for _ in range(lm.L)]
             st.lmh = torch.zeros(R, lm.H, device=dev, dtype=self.dtype)
@@ -879,7 +972,12 @@ class RNNTDecoder:
                 for v in range(E):
                     fuse = lm is not None and v < E - 1
                     lstm_layers(dtc, emb, weights, st.bias, st.ph, st.pc, H, p_lab, p_src, p_dst, p_act)
-                    if fuse:
+                    if fuse and tlm:
+                        # the lists of the destination slots, a node per live row; like the LSTM rows kernel this relies on the book
+                        # kernel's mark and sweep: no live row's source slot is a destination slot of the same round
+                        st.tree.advance(p_src, p_dst, p_act)
+                        lm_logits = st.tstep()
+                    elif fuse:
                         LA = lm._arena
                         lstm_layers(dtc, LA.w("lm.embed.weight"), [lm._w(l) for l in range(lm.L)], lm._bias, st.lh, st.lc, lm.H,
                                     p_lab, p_src, p_dst, p_act)
@@ -888,10 +986,11 @@ class RNNTDecoder:
                              ops._p(st.hj), ops._stream())
                     logits = ops.gemm_nt(st.hj, w_out, bias=b_out)
                     if fuse:
-                        lib.call("emoasr_rnnt_beam_gather_rows", dtc, R, lm.H, ops._p(st.lh[lm.L - 1]), st.nslots, p_dst, p_act,
-                                 ops._p(st.lmh), ops._stream())
-                        lm_logits = ops.gemm_nt(st.lmh, LA.w("lm.output.weight"), bias=LA.p("lm.output.bias"))
-                        lib.call("emoasr_rnnt_beam_pick_lm", dtc, R, V_, lm.V, W, blank, W, ops._p(logits), logits.stride(0),
+                        if not tlm:
+                            lib.call("emoasr_rnnt_beam_gather_rows", dtc, R, lm.H, ops._p(st.lh[lm.L - 1]), st.nslots, p_dst, p_act,
+                                     ops._p(st.lmh), ops._stream())
+                            lm_logits = ops.gemm_nt(st.lmh, LA.w("lm.output.weight"), bias=LA.p("lm.output.bias"))
+                        lib.call("emoasr_rnnt_beam_pick_lm", dtc, R, V_, lm_logits.shape[1], W, blank, W, ops._p(logits), logits.stride(0),
                                  ops._p(lm_logits), lm_logits.stride(0), ops._p(st.mu), p_act, ops._p(st.rec), st.rec.stride(0),
                                  ops._stream())
                     else:
@@ -923,10 +1022,11 @@ class RNNTDecoder:
             lens = [elens[b] for b in sutt]
             S, total, longest = len(lens), sum(lens), max(lens)
             V_ = A.w("decoder.output.weight").shape[0]
+            tlm = lm is not None and getattr(lm, "lm_type", None) == "transformer"
             if lm is not None:
-                assert len(mus) == S and self.rnnt_beam_lm_why_not(lm) is None
-                lm._prepare()      # (compute-dtype weights current, bias_ih + bias_hh rebuilt in place)
-            st = self._rnnt_beam_frame_graph(S, W, blank, eos, E, total, lm)
+                assert len(mus) == S and (self.rnnt_beam_tlm_why_not(lm) if tlm else self.rnnt_beam_lm_why_not(lm)) is None
+                lm._prepare()      # (compute-dtype weights current, bias_ih + bias_hh / the position table rebuilt in place)
+            st = self._rnnt_beam_frame_graph(S, W, blank, eos, E, total, lm, longest)
             offs, rows_of = [0], {}
             for b in sutt:
                 # w_enc . eouts + b per utterance, as the single-utterance forms compute it (a row's bits then do not depend on
@@ -943,6 +1043,9 @@ class RNNTDecoder:
                 st.pc[l].view(S, -1, self.r_H)[:, 0].zero_()
             if lm is not None:
                 st.mu.copy_(torch.tensor([float(m) for m in mus], dtype=torch.float32))
+            if tlm:
+                st.tree.reset()    # llen = 0 in every slot (a search's first slot is its zero state), no node taken, no bit raised
+            elif lm is not None:
                 for l in range(lm.L):
                     st.lh[l].view(S, -1, lm.H)[:, 0].zero_()
                     st.lc[l].view(S, -1, lm.H)[:, 0].zero_()
@@ -950,6 +1053,12 @@ class RNNTDecoder:
             ops.rnnt_beam_start(st.row_off, W, E, V_, eos, st.ctl, st.ws, st.status)
             for _ in range(longest):
                 st.graph.replay()
+            if tlm:    # a raised bit is an error naming the search and the limit, as the host form's max_seq_len assertion is
+                st.tree.raise_for_status("rnnt_beam_search_batch (Transformer-LM fusion)",
+                                         [f"search {s} (utterance {b}, lm_weight {float(mus[s]):g})" for s, b in enumerate(sutt)])
+                stats = self.rnnt_tlm_stats = getattr(self, "rnnt_tlm_stats", None) or dict(nodes=[], node_cap=0, lcap=0)
+                stats["nodes"] += st.tree.nnodes.tolist()
+                stats["node_cap"], stats["lcap"] = st.tree.node_cap, st.tree.Lcap
             hyps, scores, _ = ops.rnnt_beam_finish(st.row_off, W, E, V_, eos, longest * (E - 1), st.ws, st.status)
             return hyps, scores
 

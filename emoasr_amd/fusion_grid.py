@@ -15,7 +15,9 @@ Attention models (decoder_type == "transformer", any --decode_ctc_weight) go thr
 joint_beam_search_device_grid call per batch -- every distinct lm_weight is searched once, the len_weights are an expansion of the
 finished hypotheses' scores; with an RNN LM the tool sets decoder.joint_rnnlm_impl = "device", so that the LM is
 stepped inside that search (section 26).  Transducer models (decoder_type == "rnn_transducer") go through
-rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25).  LAS models
+rnnt_fusion_grid: the RNN LM is fused inside the batched device search, one search per distinct lm_weight (section 25); with a
+Transformer LM the tool sets decoder.rnnt_tlm_fusion = "device" and the LM is stepped there over a prefix tree (section 30; where
+that form cannot take the LM the reason is logged and the host form runs).  LAS models
 (decoder_type == "las") go through las_fusion_grid: the reference's LAS search ignores the LM, the tool sets decoder.las_lm_fusion =
 "fuse" and the RNN LM is stepped inside the batched LAS search, one search per distinct lm_weight over frames stored once per
 utterance (section 28).  main dispatches "las" itself; grid_of keeps refusing it.
@@ -124,7 +126,10 @@ def rnnt_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_w
     expansion.  decode_ctc_weight == 1 is greedy CTC whatever the weights, as in joint_fusion_grid."""
     from .modeling.functions import rnnt_fusion_grid_apply
     _require_kind(model, "rnn_transducer", "rnnt_fusion_grid")
-    search = lambda eouts, elens: rnnt_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights)[0]
+    # decoder.rnnt_tlm_fusion = "device" (set_rnnt_tlm_fusion): a Transformer LM is stepped on the device over a prefix tree
+    # (DESIGN.md section 30); "host", the default, is the call as it always was
+    kw = {"tlm_fusion": "device"} if getattr(model.decoder, "rnnt_tlm_fusion", "host") == "device" else {}
+    search = lambda eouts, elens: rnnt_fusion_grid_apply(model.decoder, eouts, elens, beam_width, lm, lm_weights, len_weights, **kw)[0]
     return _grid_pass(model, dataloader, vocab, _cells(lm_weights, len_weights), search, device, eos_id, decode_ctc_weight, texts_out,
                       True)
 
@@ -174,6 +179,26 @@ def set_joint_rnnlm_impl(decoder, beam_width, lm, decode_ctc_weight):
         else:
             logging.info(f"joint_rnnlm_impl stays 'host' (one host search per utterance and lm_weight): {why}")
     decoder.joint_rnnlm_impl = impl
+    return impl
+
+
+def set_rnnt_tlm_fusion(decoder, beam_width, lm):
+    """a transducer model with a Transformer LM: decoder.rnnt_tlm_fusion = "device", every distinct lm_weight of an utterance is one
+    search with the LM stepped on the device over a prefix tree -- unless engine.rnnt_beam_tlm_why_not or the
+    device search's limits give a reason: that reason is logged and the switch stays "host" (one host search per utterance and
+    weight).  -> the value set"""
+    from .modeling.functions import _engine_of
+    impl = "host"
+    if getattr(lm, "lm_type", None) == "transformer":
+        eng = _engine_of(decoder)
+        why = eng.rnnt_beam_tlm_why_not(lm)
+        if why is None and not eng.rnnt_beam_device_ok(beam_width):
+            why = f"the model or beam_width {beam_width} is outside the batched device search's limits"
+        if why is None:
+            impl = "device"
+        else:
+            logging.info(f"rnnt_tlm_fusion stays 'host' (one host search per utterance and lm_weight): {why}")
+    decoder.rnnt_tlm_fusion = impl
     return impl
 
 
@@ -256,6 +281,8 @@ def main(args):
         set_joint_rnnlm_impl(model.decoder, beam_width, lm, args.decode_ctc_weight)
     if kind == "las":
         set_las_lm_fusion(model.decoder, beam_width, lm)
+    if kind == "rnn_transducer":
+        set_rnnt_tlm_fusion(model.decoder, beam_width, lm)
     dataset = ASRDataset(params, data_path, phase="test")
     lm_weights, len_weights = weight_lists(args.lm_min, args.lm_max, args.lm_step, args.len_min, args.len_max, args.len_step)
     results, best = grid(model, _loader(dataset, GRID_BATCH), Vocab(params.vocab_path), beam_width,

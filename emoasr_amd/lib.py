@@ -114,6 +114,22 @@ class BertStep(Structure):
                 ("ws", c_void_p), ("ws_bytes", ctypes.c_size_t)]
 
 
+class LmTree(Structure):
+    _fields_ = [("S", c_int), ("W", c_int), ("nslots", c_int), ("Lcap", c_int), ("node_cap", c_int),
+                ("llen", c_void_p), ("lanc", c_void_p), ("nnodes", c_void_p), ("row_node", c_void_p), ("row_pos", c_void_p),
+                ("status", c_void_p)]
+
+
+class LmTreeStep(Structure):
+    _fields_ = [("d", c_int), ("H", c_int), ("F", c_int), ("V", c_int), ("n_emb", c_int), ("lab", c_void_p), ("dst", c_void_p),
+                ("word_emb", c_void_p), ("pe", c_void_p), ("ln_emb", LnP), ("kpool", c_void_p), ("vpool", c_void_p),
+                ("transform", Lin), ("ln_transform", LnP), ("out_bias", c_void_p), ("logits", c_void_p),
+                ("ws", c_void_p), ("ws_bytes", ctypes.c_size_t)]
+
+
+LM_TREE_OVERLEN, LM_TREE_POOL_FULL = 1, 2
+
+
 class BeamUpdate(Structure):
     _fields_ = [("bw", c_int), ("cw", c_int), ("eos", c_int), ("one_minus_lam", c_float), ("lam", c_float), ("mu", c_float),
                 ("len_weight", ctypes.c_double), ("vals", c_void_p), ("cands", c_void_p), ("lm_at", c_void_p), ("psi", c_void_p),
@@ -348,6 +364,9 @@ SIGNATURES = {
     "emoasr_rnnt_greedy_batch_book": [I, I, I, I, I, I, P, P, L, P, P, P, L, P, L, P, P, P],
     "emoasr_rnnt_beam_pick_lm": [I, I, I, I, I, I, I, P, L, P, L, P, P, P, L, P],
     "emoasr_rnnt_beam_gather_rows": [I, I, I, P, L, P, P, P, P],
+    "emoasr_lm_tree_advance": [POINTER(LmTree), P, P, P, P],
+    "emoasr_lm_tree_attn": [I, POINTER(LmTree), I, I, P, P, P, P, P, P],
+    "emoasr_lm_tree_step": [I, I, POINTER(BertLayer), POINTER(LmTree), POINTER(LmTreeStep), P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
     "emoasr_rnnlm_step_rows": [I, POINTER(RnnlmRows), P, P, P],
     "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],

@@ -1,0 +1,130 @@
+"""Python side of the prefix-tree Transformer-LM step (csrc/lm_tree.hip): the kernels' plan (what an LM must
+look like), the tree state of a chunk of transducer searches (lists and lengths per state slot, node counters, status words, the K / V
+node pools) and the step's parameter record.  engine.rnnt_beam_search_batch drives it under decoder.rnnt_tlm_fusion = "device"."""
+import ctypes
+
+import torch
+
+from . import lib, ops
+
+LDS_BYTES, ATTN_LDS_FIXED = 64 * 1024, 1536      # emoasr_lm_tree_attn: 8 Lcap bytes (scores + node list) + q, k, v of one head
+OVERLEN, POOL_FULL = lib.LM_TREE_OVERLEN, lib.LM_TREE_POOL_FULL
+STATUS = {OVERLEN: "a hypothesis outgrew the prefix capacity", POOL_FULL: "the node pool is full"}
+
+
+def head_ok(d, H):
+    """the attention kernel's plan for the heads: d / H in 8 .. 128, a multiple of 8 (as emoasr_attn_step)"""
+    return H >= 1 and d % H == 0 and (d // H) % 8 == 0 and 8 <= d // H <= 128
+
+
+def attn_lds_bytes(Lcap):
+    return 8 * int(Lcap) + ATTN_LDS_FIXED
+
+
+def list_cap(E, longest, max_seq_len):
+    """Lcap: the longest prefix a slot may hold -- <sos> and E - 1 labels per frame, never more than the LM's positions"""
+    return max(1, min(1 + (E - 1) * longest, int(max_seq_len)))
+
+
+def node_cap(W, E, longest):
+    """nodes per search, worst case: every fused round (E - 1 per frame) steps W rows, + 1 so that the capacity is never zero"""
+    return W * (E - 1) * longest + 1
+
+
+def _ptr(x):
+    return ops._p(x) if torch.is_tensor(x) else x
+
+
+class TreeState:
+    """the tree of S searches of width W: llen / lanc per state slot, nnodes / status per search, (node, position) per row"""
+
+    def __init__(self, S, W, nslots, Lcap, node_cap, device):
+        z = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.int32)
+        self.S, self.W, self.nslots, self.Lcap, self.node_cap = int(S), int(W), int(nslots), int(Lcap), int(node_cap)
+        self.nodes = self.S * self.node_cap
+        self.llen, self.lanc, self.nnodes, self.status = z(nslots), z(nslots, Lcap), z(S), z(S)
+        self.row_node, self.row_pos = torch.full((S * W,), -1, device=device, dtype=torch.int32), z(S * W)
+        c = self.c = lib.LmTree()
+        c.S, c.W, c.nslots, c.Lcap, c.node_cap = self.S, self.W, self.nslots, self.Lcap, self.node_cap
+        c.llen, c.lanc, c.nnodes = self.llen.data_ptr(), self.lanc.data_ptr(), self.nnodes.data_ptr()
+        c.row_node, c.row_pos, c.status = self.row_node.data_ptr(), self.row_pos.data_ptr(), self.status.data_ptr()
+
+    def reset(self):
+        """before a search: every slot holds the empty prefix (a search's first slot is the zero state it starts from), no node is
+        taken, no bit is raised"""
+        self.llen.zero_()
+        self.nnodes.zero_()
+        self.status.zero_()
+
+    def pools(self, layers, d, dtype):
+        """-> (K, V) node pools [layers, nodes, d] of the compute dtype"""
+        return tuple(torch.zeros(layers, self.nodes, d, device=self.llen.device, dtype=dtype) for _ in range(2))
+
+    def advance(self, src, dst, active):
+        """emoasr_lm_tree_advance under the control words src / dst / active (int64 [S W] tensors or device addresses)"""
+        lib.call("emoasr_lm_tree_advance", ctypes.byref(self.c), _ptr(src), _ptr(dst), _ptr(active), ops._stream())
+
+    def attn(self, qkv, kpool, vpool, dst, H, out=None):
+        """emoasr_lm_tree_attn on ONE layer's pools [nodes, d]: qkv [S W, 3 d] -> out [S W, d] (rows without a node are not written)"""
+        R, d = self.S * self.W, qkv.shape[1] // 3
+        assert tuple(qkv.shape) == (R, 3 * d) and ops._chk(qkv).is_contiguous()
+        for pool in (kpool, vpool):
+            assert tuple(pool.shape) == (self.nodes, d) and ops._chk(pool, qkv.dtype).is_contiguous()
+        if out is None:
+            out = torch.zeros(R, d, device=qkv.device, dtype=qkv.dtype)
+        assert tuple(out.shape) == (R, d) and ops._chk(out, qkv.dtype).is_contiguous()
+        lib.call("emoasr_lm_tree_attn", ops.dt(qkv), ctypes.byref(self.c), d, int(H), ops._p(qkv), ops._p(kpool), ops._p(vpool),
+                 _ptr(dst), ops._p(out), ops._stream())
+        return out
+
+    def raise_for_status(self, who, names=None):
+        """a raised bit is reported, not swallowed: RuntimeError naming the searches and the limit they met"""
+        bits = self.status.tolist()
+        if not any(bits):
+            return
+        parts = []
+        for s, b in enumerate(bits):
+            if b:
+                name = names[s] if names is not None else f"search {s}"
+                why = []
+                if b & OVERLEN:
+                    why.append(f"{STATUS[OVERLEN]} of {self.Lcap} tokens")
+                if b & POOL_FULL:
+                    why.append(f"{STATUS[POOL_FULL]} ({self.node_cap} nodes per search)")
+                parts.append(f"{name}: " + " and ".join(why))
+        raise RuntimeError(f"{who}: " + "; ".join(parts))
+
+
+class TreeStep:
+    """emoasr_lm_tree_step of a Transformer LM (modeling/lm.py, lm_type "transformer") on a TreeState: raw logits [S W, V] of the
+    compute dtype for the rows of the control words lab / dst.  The parameter addresses are read when it is built (after
+    lm._prepare()): build it anew when the arena moved."""
+
+    def __init__(self, lm, tree, lab, dst):
+        from .decode_rt import LMStepRuntime, _lin, _ln
+        P = lm.params
+        A, self.layers = LMStepRuntime(lm)._params()
+        d, H, F, V, nl = P.hidden_size, P.num_attention_heads, P.intermediate_size, P.vocab_size, P.num_layers
+        dev, dtype = A.flat.device, A.shadow.dtype
+        assert lm._pe.shape[0] >= tree.Lcap and lm._pe.dtype == torch.float32, (tuple(lm._pe.shape), tree.Lcap)
+        self.tree, self.nl, self.R, self.V = tree, nl, tree.S * tree.W, V
+        self.kpool, self.vpool = tree.pools(nl, d, dtype)
+        self.logits = torch.zeros(self.R, V, device=dev, dtype=dtype)
+        code = lib.BF16 if dtype == torch.bfloat16 else lib.F32
+        self.ws = torch.zeros(lib.size_query("emoasr_lm_tree_step_ws_bytes", code, self.R, d, F), device=dev, dtype=torch.uint8)
+        pre, cp = "lm.transformer.bert.", "lm.transformer.cls.predictions."
+        io = self.io = lib.LmTreeStep()
+        io.d, io.H, io.F, io.V, io.n_emb = d, H, F, V, V
+        io.lab, io.dst = _ptr(lab), _ptr(dst)
+        io.word_emb, io.pe = A.w(pre + "embeddings.word_embeddings.weight").data_ptr(), lm._pe.data_ptr()
+        _ln(io.ln_emb, A.p(pre + "embeddings.LayerNorm.weight"), A.p(pre + "embeddings.LayerNorm.bias"))
+        io.kpool, io.vpool = self.kpool.data_ptr(), self.vpool.data_ptr()
+        _lin(io.transform, A.w(cp + "transform.dense.weight"), A.p(cp + "transform.dense.bias"))
+        _ln(io.ln_transform, A.p(cp + "transform.LayerNorm.weight"), A.p(cp + "transform.LayerNorm.bias"))
+        io.out_bias, io.logits = A.p(cp + "bias").data_ptr(), self.logits.data_ptr()
+        io.ws, io.ws_bytes = self.ws.data_ptr(), self.ws.numel()
+
+    def __call__(self):
+        lib.call("emoasr_lm_tree_step", ops.dt(self.logits), self.nl, self.layers, ctypes.byref(self.tree.c), ctypes.byref(self.io),
+                 ops._stream())
+        return self.logits

@@ -22,10 +22,15 @@ lm_weight > 0 the non-blank candidates are ranked by log p_asr + lm_weight * log
 len_weight * len(hyp).  Several utterances, or rnnt_beam_impl = "device", fuse the RNN LM on the device (returns as above);
 one utterance with "host" takes the host form (any next-token LM; no scores).  "device" with an LM the device form cannot take is a
 ValueError.  Without an LM, or with lm_weight <= 0, neither weight is read.
+
+decoder.rnnt_tlm_fusion = "host" (the default: everything above) or "device": a Transformer LM is then fused on the device as well,
+stepped over a prefix tree of K / V nodes -- for several utterances, and for one under rnnt_beam_impl =
+"device"; an LM that form cannot take is a ValueError carrying engine.rnnt_beam_tlm_why_not's reason.
 """
 import torch.nn as nn
 
-from ..functions import rnnt_apply, rnnt_beam_apply, rnnt_beam_batch_apply, rnnt_greedy_apply, rnnt_prediction_stacked
+from ..functions import (rnnt_apply, rnnt_beam_apply, rnnt_beam_batch_apply, rnnt_greedy_apply, rnnt_prediction_stacked,
+                         rnnt_tlm_fusion_of)
 from ...criteria import RNNTAlignDistillLoss, RNNTWordDistillLoss
 from ..lm import require_next_token_lm
 from .ctc import CTCDecoder
@@ -74,6 +79,10 @@ class RNNTDecoder(nn.Module):
         # utterance of the call in lockstep with the bookkeeping on the device, engine.rnnt_greedy_batch; a model it cannot take
         # is a ValueError).  A plain attribute as well.
         self.rnnt_greedy_impl = "utterance"
+        # shallow fusion of a TRANSFORMER LM in the batched search: "host" (one host search per utterance, the LM re-run on every
+        # prefix) or "device" (the LM stepped on the device over a prefix tree; an LM it cannot take is a ValueError).  A plain
+        # attribute as well.
+        self.rnnt_tlm_fusion = "host"
         self._owner = None
 
     def prediction_stacked(self, ys_in_list, ylens_list):
@@ -104,13 +113,18 @@ class RNNTDecoder(nn.Module):
             if self.rnnt_beam_impl == "device" and beam_width > 16:   # (asked for by name: no quiet detour through the host forms)
                 raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' takes beam_width <= 16, not {beam_width}")
             fuse = lm is not None and lm_weight > 0    # shallow fusion; without it lm_weight and len_weight are not read
+            tlm = rnnt_tlm_fusion_of(self) == "device" and getattr(lm, "lm_type", None) == "transformer"
             if fuse:
                 require_next_token_lm(lm, lm_weight)
-                if self.rnnt_beam_impl == "device" and getattr(lm, "lm_type", None) != "rnn":   # (by name: no quiet detour)
+                if self.rnnt_beam_impl == "device" and getattr(lm, "lm_type", None) != "rnn" and not tlm:   # (by name: no quiet detour)
                     raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' fuses the RNN LM (lm_type 'rnn') only, not lm_type "
                                      f"{getattr(lm, 'lm_type', None)!r}; rnnt_beam_impl = 'host' takes any next-token LM")
             if eouts.size(0) > 1 or self.rnnt_beam_impl == "device":
-                if fuse:
+                if fuse and tlm:      # the prefix-tree form: the engine refuses, by name, an LM it cannot take
+                    hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width, lm, [float(lm_weight)], [float(len_weight)],
+                                                         require_device=self.rnnt_beam_impl == "device", tlm_fusion="device")
+                    hyps, scores = [h[0] for h in hyps], [s[0] for s in scores]
+                elif fuse:
                     hyps, scores = rnnt_beam_batch_apply(self, eouts, elens, beam_width, lm, [float(lm_weight)], [float(len_weight)],
                                                          require_device=self.rnnt_beam_impl == "device")
                     hyps, scores = [h[0] for h in hyps], [s[0] for s in scores]

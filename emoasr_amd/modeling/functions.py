@@ -732,20 +732,38 @@ def rnnt_beam_apply(dec, eouts, beam_width, lm=None, lm_weight=0, len_weight=0):
                                             len_weight=len_weight)
 
 
-def rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm=None, lm_weights=None, len_weights=None, require_device=False):
+def rnnt_tlm_fusion_of(dec):
+    """the decoder's rnnt_tlm_fusion: "host" (the default; a Transformer LM is fused utterance by utterance on the host, as ever) or
+    "device" (fused on the device over the prefix tree); anything else is a ValueError"""
+    impl = getattr(dec, "rnnt_tlm_fusion", "host")
+    if impl not in ("host", "device"):
+        raise ValueError(f"emoasr_amd: rnnt_tlm_fusion is 'host' or 'device', not {impl!r}")
+    return impl
+
+
+def rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm=None, lm_weights=None, len_weights=None, require_device=False,
+                          tlm_fusion="host"):
     """-> (hyps[b][n], scores[b][n]): every utterance searched over its own elens[b] frames; with lm_weights the shallow-fusion
     grid (hyps[b][cell][n], scores[b][cell][n]: engine.rnnt_beam_search_batch).  require_device: a ValueError naming the reason
-    where the device form cannot fuse this LM, instead of the host form"""
+    where the device form cannot fuse this LM, instead of the host form.  tlm_fusion = "device": a Transformer LM is fused on the
+    device over the prefix tree (the engine refuses, by name, an LM that form cannot take)"""
+    if tlm_fusion not in ("host", "device"):
+        raise ValueError(f"emoasr_amd: rnnt_tlm_fusion is 'host' or 'device', not {tlm_fusion!r}")
     eng = _engine_of(dec)
-    if require_device and lm is not None and lm_weights is not None and any(float(a) > 0 for a in lm_weights):
+    tlm = tlm_fusion == "device" and getattr(lm, "lm_type", None) == "transformer"
+    if require_device and not tlm and lm is not None and lm_weights is not None and any(float(a) > 0 for a in lm_weights):
         why = eng.rnnt_beam_lm_why_not(lm)
         if why is not None:
             raise ValueError(f"emoasr_amd: rnnt_beam_impl = 'device' cannot fuse this LM: {why}")
+    if tlm_fusion == "host":      # today's call, unchanged
+        return eng.rnnt_beam_search_batch(eouts, _host_list(elens), beam_width, dec.blank_id, dec.eos_id, lm=lm, lm_weights=lm_weights,
+                                          len_weights=len_weights)
     return eng.rnnt_beam_search_batch(eouts, _host_list(elens), beam_width, dec.blank_id, dec.eos_id, lm=lm, lm_weights=lm_weights,
-                                      len_weights=len_weights)
+                                      len_weights=len_weights, tlm_fusion=tlm_fusion)
 
 
-def rnnt_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_weights):
+def rnnt_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_weights, tlm_fusion="host"):
     """the transducer search of every utterance for every (lm_weight, len_weight) cell -> (hyps[b][cell][n], scores[b][cell][n]),
     cells in lm_weight-outer, len_weight-inner order"""
-    return rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm, [float(a) for a in lm_weights], [float(b) for b in len_weights])
+    return rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm, [float(a) for a in lm_weights], [float(b) for b in len_weights],
+                                 tlm_fusion=tlm_fusion)

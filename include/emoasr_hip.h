@@ -1147,6 +1147,54 @@ int emoasr_attn_step(int nb, int d, int H, int Lmax, const void* qkv, void* kcac
  * none of its grid barriers ever gave up waiting, 1 otherwise (results of that step are then undefined), -1 on a runtime error.
  * Synchronises the device. */
 long emoasr_decode_coop_status(void);
+
+/* ---- Transformer-LM shallow fusion inside the batched transducer search, over a PREFIX TREE (csrc/lm_tree.hip;
+ * engine.rnnt_beam_search_batch with a Transformer LM under decoder.rnnt_tlm_fusion = "device").  Every token a hypothesis appends is
+ * one NODE whose key / value rows are written once and never copied; a state slot (the slot numbers of the prediction network's
+ * pools) holds the node ids of its prefix: llen int32 [nslots] (prefix length; 0 in a search's zero-state slot), lanc int32
+ * [nslots][Lcap] (node ids, oldest first).  Search s owns the nodes s * node_cap .. (s + 1) * node_cap - 1 of the pools (compute
+ * dtype [nl][nodes][d], K and V separately, nodes = S * node_cap) and has taken nnodes[s] of them so far.
+ *   emoasr_lm_tree_advance: one launch per round, one wave per search, no atomics.  Row i = s W + w of the control words
+ *       emoasr_rnnt_beam_book wrote (source slot, destination slot, active; int64 [R = S W] each) is LIVE when active[i] != 0 and both
+ *       slots lie in 0 .. nslots - 1 and 0 <= p = llen[src[i]].  A live row whose prefix would exceed Lcap (p >= Lcap) raises
+ *       EMOASR_LM_TREE_OVERLEN in status[s]; the live rows left take the nodes s * node_cap + nnodes[s] + 0, 1, ... in row order
+ *       (inactive rows take none) until the search's node_cap is used up, every row past that raises EMOASR_LM_TREE_POOL_FULL.  A row
+ *       that got a node copies lanc[src][:p] to lanc[dst], appends the node, sets llen[dst] = p + 1 and records row_node[i] = node,
+ *       row_pos[i] = p; every other row records row_node[i] = -1 and changes nothing else.  No live row's source slot may be another
+ *       row's destination in the same launch (the book kernel's mark and sweep guarantees it).
+ *   emoasr_lm_tree_attn: single-query attention GATHERED through the lists, one wave per (row, head): a row with row_node[i] >= 0
+ *       writes k / v (row i of qkv [R, 3d] = q | k | v) at its node of this layer's pools, then out[i] = softmax(q . K[lanc[dst[i]]
+ *       [0 .. p]]^T / sqrt(dk)) . V[...] with f32 accumulation (p + 1 = llen[dst[i]] keys, the new one last).  dk = d / H in 8 .. 128,
+ *       a multiple of 8; 8 Lcap + 1536 bytes of LDS (<= 64 KB).  A row with row_node[i] < 0, a slot or a length out of range writes
+ *       nothing; node ids read from a list are clamped into the pool.
+ *   emoasr_lm_tree_step: the launch chain of emoasr_bert_lm_step for R rows of any count -- embedding of label lab[i] (int64 control
+ *       words; clamped into the table) + pe[row_pos[i]], LayerNorm, per layer (qkv product, emoasr_lm_tree_attn, output product,
+ *       LayerNorm, feed-forward, LayerNorm), the prediction head -> RAW logits [R, V] of the compute dtype (emoasr_rnnt_beam_pick_lm
+ *       takes its own log-softmax).  No host input between the launches.  Rows with row_node[i] < 0 carry zeros / stale values. */
+#define EMOASR_LM_TREE_OVERLEN 1
+#define EMOASR_LM_TREE_POOL_FULL 2
+typedef struct emoasr_lm_tree {
+  int S, W, nslots, Lcap, node_cap;
+  int* llen; int* lanc; int* nnodes;            /* [nslots], [nslots][Lcap], [S] */
+  int* row_node; int* row_pos;                  /* [S W] each, written by advance */
+  int* status;                                  /* [S], bits are only ever raised */
+} emoasr_lm_tree_t;
+typedef struct emoasr_lm_tree_step {
+  int d, H, F, V, n_emb;
+  const long long* lab; const long long* dst;   /* control words, [S W] each */
+  const void* word_emb; const float* pe; emoasr_lnp_t ln_emb;     /* word_emb [n_emb, d]; pe f32 [>= Lcap, d] */
+  void* kpool; void* vpool;                     /* compute dtype [nl][S node_cap][d] */
+  emoasr_lin_t transform; emoasr_lnp_t ln_transform; const float* out_bias;
+  void* logits;                                 /* compute dtype [S W, V] */
+  void* ws; size_t ws_bytes;                    /* emoasr_lm_tree_step_ws_bytes() */
+} emoasr_lm_tree_step_t;
+int emoasr_lm_tree_advance(const emoasr_lm_tree_t* t, const long long* src, const long long* dst, const long long* active,
+                           void* stream);
+int emoasr_lm_tree_attn(int dtype, const emoasr_lm_tree_t* t, int d, int H, const void* qkv, void* kpool, void* vpool,
+                        const long long* dst, void* out, void* stream);
+size_t emoasr_lm_tree_step_ws_bytes(int dtype, int R, int d, int F);
+int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
+                        const emoasr_lm_tree_step_t* io, void* stream);
 /* times the cooperative step kernel of a chain (0 decoder, 1 LM) was enqueued or captured since the library was loaded */
 long emoasr_decode_coop_launches(int chain);
 int emoasr_beam_cache_gather(int dtype, int nl, int nb, int Lmax, int d, const void* src_k, const void* src_v, void* dst_k,
