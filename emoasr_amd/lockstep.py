@@ -3,7 +3,9 @@ of every per-hypothesis array and step together, one captured step serving them 
 Here: the bookkeeping buffers and their reset, the fillers of the update and RNN-LM structs, the capture of the two steps, the replay
 loop with its one download, the admission checks of emoasr_rnnlm_step_rows, and the driver of the (lm_weight, len_weight) grids.
 What belongs to one decoder -- the staging of its inputs, its step, its cache key and its buffer-cache policy -- stays with it:
-modeling/beam_search_device.py (joint CTC / attention), engine/las.py (LAS), engine/rnnt.py (the transducer: the grid driver only)."""
+modeling/beam_search_device.py (joint CTC / attention), engine/las.py (LAS), engine/rnnt_search.py (the transducer, whose books are
+rnnt_beam_book / rnnt_greedy_batch_book: of this module it takes the grid driver, the capture after a warm-up, the LM admission checks
+and the length expansion)."""
 import ctypes
 import gc
 import os
@@ -137,6 +139,22 @@ def capture_two_steps(step, reset):
     return graphs
 
 
+def capture_after_warmup(body, device, warm=None):
+    """-> (graph, what the captured body() returned): body's launches captured as a HIP graph with the DEFAULT capture mode (not
+    capture_two_steps' relaxed one), after a warm-up outside the capture (allocator, lazy initialisation, per-stream scratch) on a
+    fresh side stream.  warm: the warm-up, when it is more than one run of body."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        (warm or body)()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    return graph, out
+
+
 def batch_step_reported(mirror, i, S, main):
     """wait until emoasr_beam_update_batch's pinned mirror {position, finished searches} shows step i - 1 -> whether every search
     has finished"""
@@ -206,15 +224,30 @@ def batch_nbest_from_pack(host, o, S, W, Lmax, sort=True):
     return hyps, scores
 
 
+def lm_type_why_not(lm, lm_type):
+    """the first admission check of every fused device search: the LM is of the type whose state the search can hold"""
+    if getattr(lm, "lm_type", None) != lm_type:
+        note = " (no per-hypothesis state the slot pools could hold)" if lm_type == "rnn" else ""
+        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not {lm_type!r}{note}"
+    return None
+
+
+def lm_compute_why_not(eng, lm, dtypes=None):
+    """the LM computes as the engine does: the same dtype (one of dtypes, when the kernels take no other), the same product mode"""
+    if lm.compute_dtype != eng.dtype or (dtypes is not None and lm.compute_dtype not in dtypes) or bool(lm.f32_split) != bool(eng.split):
+        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
+    return None
+
+
 def rnnlm_rows_why_not(eng, V, lm):
     """why emoasr_rnnlm_step_rows cannot step this LM inside a lockstep chain of an engine with vocabulary V (None: it can): the
     reasons the searches share; each adds its own (beam and candidate widths, environment switches)"""
-    if getattr(lm, "lm_type", None) != "rnn":
-        return f"lm_type {getattr(lm, 'lm_type', None)!r} is not 'rnn' (no per-hypothesis state the slot pools could hold)"
-    if lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
-        return f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
-    if lm.compute_dtype != eng.dtype or bool(lm.f32_split) != bool(eng.split):
-        return f"the LM computes in {lm.compute_dtype} (split products: {bool(lm.f32_split)}), the model in {eng.dtype} ({bool(eng.split)})"
+    why = lm_type_why_not(lm, "rnn")
+    if why is None and lm.V != V:   # the scores kernel soft-maxes the first V columns; the reference soft-maxes all of the LM's, then slices
+        why = f"the LM's vocabulary ({lm.V}) is not the model's ({V})"
+    why = why or lm_compute_why_not(eng, lm)
+    if why is not None:
+        return why
     code = lib.F32X3 if lm.f32_split else {torch.float32: lib.F32, torch.bfloat16: lib.BF16}.get(lm.compute_dtype)
     if code is None or lib.size_query("emoasr_rnnlm_step_rows_supported", code, lm.L, lm.E, lm.H) != 1:
         return f"the LM's sizes (embedding {lm.E}, hidden {lm.H}, layers {lm.L}) are outside emoasr_rnnlm_step_rows' shape plan"
@@ -276,14 +309,15 @@ def grid_chunks(B, n_positive, cap, elens):
                [k0 + j for _, k0, cnt in chunk for j in range(cnt)])
 
 
-def expand_len_weights(hyps, scores, len_weights):
+def expand_len_weights(hyps, scores, len_weights, offset=2):
     """the results of ONE search at len_weight 0 in the order the search found them -> per len_weight w (hyps, scores): every score
-    + w * (len(hyp) + 2) in double -- what emoasr_beam_update_batch writes as cscore + len_weight * (double)(pos + 2), the library
-    being compiled without contraction of the multiply-add -- sorted by score with the stable order of batch_nbest_from_pack"""
+    + w * (len(hyp) + offset) in double -- what emoasr_beam_update_batch writes as cscore + len_weight * (double)(pos + 2), the
+    library being compiled without contraction of the multiply-add; the transducer, whose hypotheses keep their leading <sos>, passes
+    offset 0 -- sorted by score with the stable order of batch_nbest_from_pack"""
     out = []
     for w in len_weights:
         w = float(w)
-        sc = [float(s) + w * float(len(h) + 2) for h, s in zip(hyps, scores)]
+        sc = [float(s) + w * float(len(h) + offset) for h, s in zip(hyps, scores)]
         order = sorted(range(len(sc)), key=lambda i: sc[i], reverse=True)
         out.append(([hyps[i] for i in order], [sc[i] for i in order]))
     return out

@@ -50,7 +50,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import lockstep, ops
 from ..engine import ParamArena, _Stash, h2d_i32
 from ..ops import ACT_GELU
 from .blocks import _Holder
@@ -687,15 +687,7 @@ class LM(_StackOps, nn.Module):
                 with ops.stream_scope(split):
                     return self._forward_rows(g.ids, g.klens, g.idx, Bp, Np)
 
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                body()   # warm-up outside the capture (allocator, lazy initialisation, per-stream scratch)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g.graph):
-                g.out = body()
+            g.graph, g.out = lockstep.capture_after_warmup(body, dev)
             graphs[(Bp, Np)] = g
         n_ids = Bp * Np
         h = g.host

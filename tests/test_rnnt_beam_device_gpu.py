@@ -170,6 +170,27 @@ def test_batch_f32_returns_the_golden_hypotheses(dev):
         assert hyps[0] == [[dec.eos_id]] and scores[0] == [0.0] and hyps[1] == want[2][1]
 
 
+def test_round_graph_with_the_unfused_body(dev, monkeypatch):
+    """EMOASR_RNNT_BEAM_FUSED=0, set before a fresh model's engine builds its record: the replayed round captures the launch chain
+    with explicit copies (also the fall-back when a fused kernel refuses in the warm-up) -- the reference's hypotheses for every
+    golden utterance, scores within 1e-4 of the chain form's (the bar tests/test_l4_gpu.py sets between two forms of the round)"""
+    monkeypatch.setenv("EMOASR_RNNT_BEAM_FUSED", "0")
+    model, g = _build(torch.float32, dev)
+    want = load_rnnt_beam_golden()
+    eouts, elens = _encode_alone(model, g, dev)
+    eng, dec = model.engine(), model.decoder
+    assert getattr(eng, "_beam_static", None) is None
+    with torch.no_grad():
+        for bw in RNNT_BEAM_WIDTHS:
+            for b, n in enumerate(elens):
+                h_g, s_g = eng._rnnt_beam_search_graph(eouts[b:b + 1, :n], bw, dec.blank_id, dec.eos_id, return_scores=True)
+                h_c, s_c = eng._rnnt_beam_search_chain(eouts[b:b + 1, :n], bw, dec.blank_id, dec.eos_id, return_scores=True)
+                print(bw, b, max(abs(a - c) for a, c in zip(s_g, s_c)))
+                assert h_g == want[bw][b] and h_c == h_g, (b, bw, h_g, want[bw][b])
+                assert max(abs(a - c) for a, c in zip(s_g, s_c)) < 1e-4, (b, bw, s_g, s_c)
+                assert eng._beam_static.zero_copy is False
+
+
 def test_batch_bf16_agrees_with_the_graph_form(dev):
     """bf16 at width 4 against the graph form: token agreement above 0.9 (the bar of
     tests/test_l4_gpu.py::test_beam_search_bf16_fused_round_agrees_with_the_chain)"""
