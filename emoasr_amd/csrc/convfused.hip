@@ -15,9 +15,13 @@
 // of its two channels from the ring.  The arithmetic, its order and every rounding to bf16 are those of the separate kernels
 // (convmodule.hip, elementwise.hip): c, the BatchNorm partials (one pair per 32-frame tile at the tile's table position) and
 // dg are bit-identical to the unfused sequence for every S.  The weight-gradient sums stay in registers across the strip: the
-// dense entry point flushes them per tile (the unfused kernel's table, bit-identical dw / dbias), the stacked one per strip
-// into a compact table with one row per live strip -- no zero rows for the grid's empty corners, under 1024 rows for the
-// benchmark's steps, so emo_dwconv_bwd_w_reduce runs as one slice without float atomics (run-to-run deterministic).
+// dense entry point flushes them per tile (the unfused kernel's table: bit-identical dw / dbias BELOW 1024 TILES, B cdiv(T, 32)
+// < 1024 -- from 1024 rows on emo_dwconv_bwd_w_reduce folds the table in four slices that meet in float atomics, where
+// emoasr_dwconv_bwd_w always folds in one: dw / dbias are then the same sums in another order, within the order-independent f32
+// bound of an f64 reference and not run-to-run deterministic; measured at 32 x 1024 frames, tests/test_conv_kernels_gpu.py), the
+// stacked one per strip into a compact table with one row per live strip -- no zero rows for the grid's empty corners, under
+// 1024 rows for the benchmark's steps, so emo_dwconv_bwd_w_reduce runs as one slice without float atomics (run-to-run
+// deterministic).
 // S: option "conv_strip" (strip_tiles below).  Step of bench.py, parent 25.02 ms: S = 1 24.71, 2 24.74, 3 24.63, 4 24.63,
 // 8 25.40, the rule 24.66 (profiles/conv_strip_step.txt); per-kernel times not measured yet.
 // Registers (gfx950): backward 208, forward 209 (GLU) / 196, no scratch; 70 KB / 48 KB LDS: two workgroups per CU.
@@ -194,7 +198,8 @@ __global__ __launch_bounds__(CF_CB) void cf_dwconv_kernel(int Tn, int C, int K, 
 // tot: [2][C] means from the BatchNorm fold (emoasr_bn_swish_bwd_sums).
 // The weight-gradient sums stay in registers and are flushed
 //   per_tile = 1: after every tile, to row (utterance * tiles + tile): the [tile][K+1][C] table of the unfused kernel, so the
-//                 reduce adds the same numbers in the same order (dense entry point; bit-identical dw / dbias);
+//                 reduce adds the same numbers in the same order (dense entry point; bit-identical dw / dbias below 1024 tiles,
+//                 where the reduce is one slice);
 //   per_tile = 0: once per strip, in frame order over the strip's tiles, to a COMPACT table: row = strips of the earlier
 //                 segments + utterance-in-segment * strips-per-utterance + strip.  Only live strips have a row; a workgroup
 //                 without frames writes nothing.

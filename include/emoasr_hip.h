@@ -356,7 +356,9 @@ int emoasr_bn_swish_bwd(int dtype, int M, int C, const void* dz, const void* y, 
                         const float* var, const float* gamma, const float* beta, float eps, void* dy,
                         float* dgamma, float* dbeta, float* scratch, void* stream);
 /* ---- fused convolution-module kernels (csrc/convfused.hip; bf16, K <= 31, C % 8 == 0): bit-identical to the separate
- * launches they replace (every intermediate is rounded to bf16 at the same point).
+ * launches they replace (every intermediate is rounded to bf16 at the same point); dw / dbias of emoasr_conv_bwd_fused below
+ * 1024 tiles (B * ceil(Tn / 32) < 1024) -- from there on they are folded in four slices that meet in float atomics: the same sums
+ * in another order, not run-to-run deterministic.
  * emoasr_glu_dwconv_fwd: c = depthwise_conv(GLU(g)), g [B*T, 2C]; part (may be NULL) receives the per-block BatchNorm
  *   partial statistics of emoasr_dwconv_fwd_stats.  conformer.py:126-131.
  * emoasr_bn_swish_bwd_sums: passes 1-2 of emoasr_bn_swish_bwd (dgamma / dbeta accumulated; *tot_out = the [2][C] means

@@ -2,7 +2,9 @@
 consecutive 32-frame tiles of one utterance and keeps the halo rows in an LDS ring.
 
 Dense entry points: for every strip length all outputs are EQUAL to the unfused launch sequence (the construction of
-test_ops_gpu.py::test_fused_conv_module_kernels_are_bit_identical).  Stacked entry points (several segments of unequal length
+test_ops_gpu.py::test_fused_conv_module_kernels_are_bit_identical); for the depthwise weight / bias gradient that holds below
+1024 tiles (B cdiv(T, 32) < 1024, every shape here) -- from 1024 on the fused entry folds its partials in four slices that meet in
+float atomics (tests/test_conv_kernels_gpu.py::test_weight_gradient_fold_at_1024_tiles).  Stacked entry points (several segments of unequal length
 in one launch): everything but the depthwise weight / bias gradient is EQUAL to the dense entry points called once per
 segment; those two are f32 sums in another order (one partial row per strip) and are held to an f64 reference with the unfused
 kernels' own error as the yardstick."""
