@@ -1255,6 +1255,7 @@ extern "C" int emoasr_conv2_fwd(int dtype, int B, int T1, int F1, int C, const v
   EMO_CHECK(T1 >= 3 && F1 >= 3, "conv2: input too small (T1=%d F1=%d)", T1, F1);
   const int T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
   EMO_CHECK(C % 32 == 0, "conv2: C must be a multiple of 32");
+  if (B == 0) return 0;   // (no rows: an empty grid is a launch error)
   // bias (+ ReLU) only, bf16, C % 256 == 0: the large-tile kernel (gemm_big.hip)
   if (dtype == EMO_BF16 && C % 256 == 0 && g_opt.conv_big && ep->alpha == 1.f && !ep->residual && !ep->dact_pre &&
       !ep->pre_out && ep->drop_p == 0.f && !ep->out_f32 && (ep->act == EMO_ACT_NONE || ep->act == EMO_ACT_RELU))
@@ -1274,6 +1275,7 @@ extern "C" int emoasr_conv2_dgrad(int dtype, int B, int T1, int F1, int C, const
   SplitScope split_scope(dtype);
   EMO_CHECK(T1 >= 3 && F1 >= 3, "conv2_dgrad: input too small (T1=%d F1=%d)", T1, F1);
   EMO_CHECK(C % 64 == 0, "conv2_dgrad: C must be a multiple of 64");
+  if (B == 0) return 0;
   const int T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
   for (int pt = 0; pt < 2; ++pt)
     for (int pf = 0; pf < 2; ++pf) {
@@ -1311,6 +1313,7 @@ extern "C" int emoasr_conv2_wgrad(int dtype, int B, int T1, int F1, int C, const
     hipMemsetAsync(dw, 0, sizeof(float) * (size_t)C * 9 * C, (hipStream_t)stream);
     if (dbias) hipMemsetAsync(dbias, 0, sizeof(float) * C, (hipStream_t)stream);
   }
+  if (B == 0) return 0;   // (an empty reduction: launch_tn would divide by its zero k-tiles)
   TnArgs a{};
   a.N1 = C; a.N2 = 9 * C; a.K = B * T2 * F2; a.A = dy2; a.lda = C; a.B = y1; a.ldb = 0; a.C = dw;
   a.ldc = 9 * C; a.alpha = 1.f; a.colsum = dbias; a.colsum_scale = 1.f;

@@ -1207,6 +1207,7 @@ extern "C" int emoasr_conv2_dgrad_kc(int dtype, int B, int T1, int F1, int C, co
   EMO_CHECK(dtype == EMO_BF16, "conv2_dgrad_kc: bf16 only");
   EMO_CHECK(T1 >= 3 && F1 >= 3, "conv2_dgrad_kc: input too small (T1=%d F1=%d)", T1, F1);
   EMO_CHECK(C % 256 == 0, "conv2_dgrad_kc: C must be a multiple of 256");
+  if (B == 0) return 0;
   EMO_CHECK((long)B * T1 * F1 * C * 2 < (1L << 32), "conv2_dgrad_kc: tensors must be < 4 GiB");
   BigArgs a{};
   const int bm = dgrad_plan(B, T1, F1, C, a);

@@ -135,7 +135,10 @@ int emoasr_colsum(int dtype, int M, int N, const void* X, long ldx, float* out, 
 
 /* ---- Conv2d subsampling front-end (asr/modeling/encoders/conv.py:5-28) ------
  * x f32 [B,T,F] -> y1 T [B,T1,F1,C] (channels-last), T1=(T-3)/2+1, F1=(F-3)/2+1
- * w1 f32 [C,9], b1 f32 [C]; ReLU fused. */
+ * w1 f32 [C,9], b1 f32 [C]; ReLU fused.
+ * B == 0 is an empty call on every entry of this section: nothing is launched; the weight-gradient entries (conv1_wgrad,
+ * conv2_wgrad, conv2_dgrad_w1) zero their outputs when accumulate == 0 and leave them alone otherwise.  (A segment of
+ * emoasr_conv2_wgrad_seg must have B > 0.) */
 int emoasr_conv1_fwd(int dtype, int B, int T, int F, int C, const float* x, const float* w1,
                      const float* b1, void* y1, void* stream);
 /* dw1[C,9], db1[C] (+)= from dy1 (gradient w.r.t. the pre-ReLU conv1 output);
