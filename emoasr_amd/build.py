@@ -30,7 +30,7 @@ def build(force=False, verbose=True, variant=None, defines=()):
     headers = [os.path.join(CSRC, h) for h in ("common.h", "mma.h", "lds_dma.h", "gemm_big_tn.h", "lstm_step.h", "gumbel.h",
                                                   "ctc_beam_step.h", "attn_group.h", "attn_group_body.h",
                                                   "beam_score_step.h", "beam_scores_topk_body.h", "ctc_prefix_body.h", "beam_update_batch.h",
-                                                  "beam_update_batch_body.h")]
+                                                  "beam_update_batch_body.h", "log_softmax_body.h")]
     headers.append(os.path.join(HERE, "..", "include", "emoasr_hip.h"))
     sources = SOURCES
     flags = FLAGS + ["-D" + d for d in defines]

@@ -126,13 +126,7 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(int V, const T* __rest
   __shared__ float red[16];
   const long m = blockIdx.x;
   const T* row = x + m * ldx;
-  float mx = -INFINITY;
-  for (int v = threadIdx.x; v < V; v += 256) mx = fmaxf(mx, to_f32(row[v]));
-  mx = block_max(mx, red);
-  float se = 0.f;
-  for (int v = threadIdx.x; v < V; v += 256) se += expf(to_f32(row[v]) - mx);
-  se = block_sum(se, red);
-  const float lse = mx + logf(se);
+#include "log_softmax_body.h"
   for (int v = threadIdx.x; v < V; v += 256) {
     float r = to_f32(row[v]) - lse;
     if (add) r += mu * add[m * lda + v];

@@ -12,6 +12,15 @@
 //   emoasr_lm_tree_step      the launch chain of emoasr_bert_lm_step (csrc/decode_rt.hip) for R rows: per-row positions, the kernel
 //                            above in place of the cache append + dense attention, raw logits in the compute dtype
 //
+// The fused CTC search (csrc/ctc_beam_lm.hip) drives the same tree under decoder.ctc_tlm_fusion = "device" (DESIGN.md section 32): its
+// pool rows are the slots, its record list (one record per new prefix) the rows of a step:
+//
+//   emoasr_lm_tree_advance_rec    advance from the record list and its count as they lie on the device: one wave per record, a node
+//                                 per record by atomicAdd on the search's counter, the control words lab / dst for the two kernels above
+//   emoasr_lm_tree_attn_rows / emoasr_lm_tree_step_rows    the two kernels above over the first R rows (they are these with R = S W)
+//   emoasr_log_softmax_rows_to    the step's raw logits, normalised over the LM's whole vocabulary by the body of emoasr_log_softmax
+//                                 (csrc/log_softmax_body.h), scattered into the f32 pool rows the next frame reads
+//
 // Bounds: every slot number, length, label and node id that arrives through device memory is checked or clamped before it is used as
 // an index; a row that fails a check writes nothing.
 #include <math.h>
@@ -61,6 +70,75 @@ __global__ __launch_bounds__(64) void lm_tree_advance_kernel(const emoasr_lm_tre
     t.nnodes[s] = base + taken;
     if (bits) t.status[s] |= bits;                  // (one writer per word: this wave)
   }
+}
+
+// The advance step under the RECORD LIST of the fused CTC search (csrc/ctc_beam_lm.hip): one wave per record,
+// lanes striding the list copy.  The records of one search lie anywhere in the list, so a node is taken with one atomicAdd on the
+// search's counter (which names the node, nothing else) and a bit is raised with atomicOr.  A share that is used up is put back by
+// the wave that overdrew it: the counter never ends above node_cap, and no wave that reads it at or above node_cap takes a node.
+__global__ __launch_bounds__(256) void lm_tree_advance_rec_kernel(const emoasr_lm_tree_t t, const int* __restrict__ rec, int rec_cap,
+                                                                  const int* __restrict__ rec_count,
+                                                                  const double* __restrict__ lm_weight,
+                                                                  long long* __restrict__ lab, long long* __restrict__ dstw) {
+  const int lane = threadIdx.x & 63, Lcap = t.Lcap;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rec_cap) return;                         // (uniform over the wave)
+  const int n = min(max(rec_count[0], 0), rec_cap);
+  const int per = t.nslots / t.S;                   // slots of one search's share
+  int node = -1, p = 0, sl = -1, dl = -1;
+  long long token = 0;
+  if (r < n) {
+    const int s = rec[r];
+    token = rec[3 * (long)rec_cap + r];
+    sl = rec[4 * (long)rec_cap + r];
+    dl = rec[5 * (long)rec_cap + r];
+    const bool in_share = s >= 0 && s < t.S && dl >= s * per && dl < (s + 1) * per && (sl < 0 || (sl >= s * per && sl < (s + 1) * per));
+    if (in_share && !(lm_weight && !(lm_weight[s] > 0.0))) {      // (a search that fuses nothing takes no node)
+      p = sl < 0 ? 0 : t.llen[sl];
+      if (p < 0) {
+        p = 0;                                      // a slot that holds no prefix: no effect
+      } else if (p >= Lcap) {
+        if (lane == 0) atomicOr(&t.status[s], EMOASR_LM_TREE_OVERLEN);
+      } else {
+        int got = -1;
+        if (lane == 0) {
+          const int old = atomicAdd(&t.nnodes[s], 1);
+          if (old >= 0 && old < t.node_cap) got = s * t.node_cap + old;
+          else { atomicSub(&t.nnodes[s], 1); atomicOr(&t.status[s], EMOASR_LM_TREE_POOL_FULL); }
+        }
+        node = __shfl(got, 0, 64);
+      }
+    }
+  }
+  if (node >= 0) {
+    // no record's source slot is a destination slot of this launch (the frame kernel frees the row of a prefix that left the
+    // beam only at the start of the next frame), so the copies of different waves do not overlap and need no order
+    const long so = (long)sl * Lcap, dn = (long)dl * Lcap;
+    for (int i = lane; i < p; i += 64) t.lanc[dn + i] = t.lanc[so + i];
+    if (lane == 0) { t.lanc[dn + p] = node; t.llen[dl] = p + 1; }
+  }
+  if (lane == 0) {
+    t.row_node[r] = node;
+    t.row_pos[r] = node >= 0 ? p : 0;
+    lab[r] = node >= 0 ? token : 0;
+    dstw[r] = node >= 0 ? dl : -1;
+  }
+}
+
+// pool[row_dst[r]][:V] = log_softmax(x[r, :V_lm])[:V] for the rows r < n that row_ok admits (NULL: all): the body of
+// log_softmax_kernel (csrc/decoder.hip), so a row is bit-equal to emoasr_log_softmax's.  A row whose destination lies outside the
+// pool is dropped.
+template <typename T>
+__global__ __launch_bounds__(256) void log_softmax_rows_to_kernel(int V, int Vout, const T* __restrict__ x, long ldx,
+                                                                  const int* __restrict__ row_dst, const int* __restrict__ row_ok,
+                                                                  float* __restrict__ out, long ldo, int out_rows) {
+  __shared__ float red[16];
+  const long m = blockIdx.x;
+  const int o = row_dst[m];
+  if (o < 0 || o >= out_rows || (row_ok && row_ok[m] < 0)) return;      // (uniform over the workgroup)
+  const T* row = x + m * ldx;
+#include "log_softmax_body.h"
+  for (int v = threadIdx.x; v < Vout; v += 256) out[o * ldo + v] = to_f32(row[v]) - lse;
 }
 
 struct TreeAttnArgs {
@@ -177,12 +255,13 @@ int tree_ok(const emoasr_lm_tree_t* t, const char* who) {
   return 0;
 }
 
-int tree_attn(int dtype, const emoasr_lm_tree_t* t, int d, int H, const void* qkv, void* kpool, void* vpool, const long long* dst,
-              void* out, void* stream) {
+int tree_attn(int dtype, const emoasr_lm_tree_t* t, int R, int d, int H, const void* qkv, void* kpool, void* vpool,
+              const long long* dst, void* out, void* stream) {
+  if (R == 0) return 0;
   EMO_CHECK(H >= 1 && d % H == 0 && (d / H) % 8 == 0 && d / H <= 128, "lm_tree_attn: d=%d H=%d unsupported (heads of 8 .. 128 in multiples of 8)", d, H);
   const size_t lds = (size_t)t->Lcap * 8;
   EMO_CHECK(lds + 1536 <= 64 * 1024, "lm_tree_attn: Lcap=%d needs %zu bytes of LDS (64 KB at most)", t->Lcap, lds + 1536);
-  TreeAttnArgs a{t->S * t->W, d, d / H, t->nslots, t->Lcap, (long)t->S * t->node_cap, qkv, kpool, vpool, t->llen, t->lanc,
+  TreeAttnArgs a{R, d, d / H, t->nslots, t->Lcap, (long)t->S * t->node_cap, qkv, kpool, vpool, t->llen, t->lanc,
                  t->row_node, dst, 1.f / sqrtf((float)(d / H)), out};
   dim3 grid(a.R, H);
   EMO_DISPATCH(dtype, (lm_tree_attn_kernel<T><<<grid, 64, lds, (hipStream_t)stream>>>(a)));
@@ -201,11 +280,38 @@ extern "C" int emoasr_lm_tree_advance(const emoasr_lm_tree_t* t, const long long
   return 0;
 }
 
+extern "C" int emoasr_lm_tree_advance_rec(const emoasr_lm_tree_t* t, const int* rec, int rec_cap, const int* rec_count,
+                                          const double* lm_weight, long long* lab, long long* dst, void* stream) {
+  if (tree_ok(t, "lm_tree_advance_rec")) return 1;
+  EMO_CHECK(rec && rec_count && lab && dst && rec_cap >= 1, "lm_tree_advance_rec: missing records or control words (rec_cap=%d)", rec_cap);
+  EMO_CHECK(t->nslots % t->S == 0, "lm_tree_advance_rec: %d slots do not divide into %d searches' shares", t->nslots, t->S);
+  lm_tree_advance_rec_kernel<<<cdiv(rec_cap, 4), 256, 0, (hipStream_t)stream>>>(*t, rec, rec_cap, rec_count, lm_weight, lab, dst);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_log_softmax_rows_to(int dtype, int n, int V_lm, int V, const void* x, long ldx, const int* row_dst,
+                                          const int* row_ok, float* out, long ld_lm, int out_rows, void* stream) {
+  if (n == 0) return 0;
+  EMO_CHECK(n > 0 && V >= 1 && V_lm >= V && ldx >= V_lm && ld_lm >= V && out_rows >= 1 && x && row_dst && out,
+            "log_softmax_rows_to: n=%d V_lm=%d V=%d ldx=%ld ld_lm=%ld out_rows=%d", n, V_lm, V, ldx, ld_lm, out_rows);
+  EMO_DISPATCH(dtype, (log_softmax_rows_to_kernel<T><<<n, 256, 0, (hipStream_t)stream>>>(V_lm, V, (const T*)x, ldx, row_dst, row_ok,
+                                                                                        out, ld_lm, out_rows)));
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_lm_tree_attn_rows(int dtype, const emoasr_lm_tree_t* t, int R, int d, int H, const void* qkv, void* kpool,
+                                        void* vpool, const long long* dst, void* out, void* stream) {
+  if (tree_ok(t, "lm_tree_attn")) return 1;
+  EMO_CHECK(R >= 0 && qkv && kpool && vpool && dst && out, "lm_tree_attn: missing arguments (R=%d)", R);
+  return tree_attn(dtype, t, R, d, H, qkv, kpool, vpool, dst, out, stream);
+}
+
 extern "C" int emoasr_lm_tree_attn(int dtype, const emoasr_lm_tree_t* t, int d, int H, const void* qkv, void* kpool, void* vpool,
                                    const long long* dst, void* out, void* stream) {
   if (tree_ok(t, "lm_tree_attn")) return 1;
-  EMO_CHECK(qkv && kpool && vpool && dst && out, "lm_tree_attn: missing arguments");
-  return tree_attn(dtype, t, d, H, qkv, kpool, vpool, dst, out, stream);
+  return emoasr_lm_tree_attn_rows(dtype, t, t->S * t->W, d, H, qkv, kpool, vpool, dst, out, stream);
 }
 
 extern "C" size_t emoasr_lm_tree_step_ws_bytes(int dtype, int R, int d, int F) {
@@ -214,12 +320,15 @@ extern "C" size_t emoasr_lm_tree_step_ws_bytes(int dtype, int R, int d, int F) {
   return (size_t)R * esz * ((size_t)5 * d + 3 * d + F) + 8 * 256;
 }
 
-extern "C" int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
-                                   const emoasr_lm_tree_step_t* io, void* stream) {
+// R rows: the first R of the control words, of (row_node, row_pos) and of the logits; the cost follows R, not the capacity
+extern "C" int emoasr_lm_tree_step_rows(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
+                                        const emoasr_lm_tree_step_t* io, int R, void* stream) {
   if (tree_ok(t, "lm_tree_step")) return 1;
   EMO_CHECK(layers && io && io->ws && io->logits && io->kpool && io->vpool && io->lab && io->dst && io->word_emb && io->pe,
             "lm_tree_step: missing arguments");
-  const int R = t->S * t->W, d = io->d, H = io->H, F = io->F, V = io->V;
+  EMO_CHECK(R >= 0, "lm_tree_step: R=%d", R);
+  if (R == 0) return 0;
+  const int d = io->d, H = io->H, F = io->F, V = io->V;
   EMO_CHECK(nl >= 1 && d >= 1 && H >= 1 && d % H == 0 && F >= 1 && V >= 1 && io->n_emb >= 1, "lm_tree_step: bad dims nl=%d d=%d H=%d F=%d V=%d", nl, d, H, F, V);
   const size_t esz = dtype == EMO_BF16 ? 2 : 4;
   hipStream_t s = (hipStream_t)stream;
@@ -243,7 +352,7 @@ extern "C" int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t*
     char* kp = (char*)io->kpool + li * layer_bytes;
     char* vp = (char*)io->vpool + li * layer_bytes;
     if (linear(dtype, R, 3 * d, d, x, Ly.qkv, qkv, EMOASR_ACT_NONE, nullptr, stream)) return 1;
-    if (tree_attn(dtype, t, d, H, qkv, kp, vp, io->dst, o, stream)) return 1;
+    if (tree_attn(dtype, t, R, d, H, qkv, kp, vp, io->dst, o, stream)) return 1;
     if (linear(dtype, R, d, d, o, Ly.attn_out, y, EMOASR_ACT_NONE, x, stream)) return 1;
     if (emoasr_layernorm_fwd(dtype, R, d, y, Ly.ln_attn.g, Ly.ln_attn.b, 1e-12f, x, nullptr, nullptr, stream)) return 1;
     if (linear(dtype, R, F, d, x, Ly.inter, act, 3 /* GELU */, nullptr, stream)) return 1;
@@ -254,4 +363,10 @@ extern "C" int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t*
   if (emoasr_layernorm_fwd(dtype, R, d, t1, io->ln_transform.g, io->ln_transform.b, 1e-12f, t2, nullptr, nullptr, stream)) return 1;
   emoasr_lin_t tied{io->word_emb, io->out_bias};
   return linear(dtype, R, V, d, t2, tied, io->logits, EMOASR_ACT_NONE, nullptr, stream);
+}
+
+extern "C" int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
+                                   const emoasr_lm_tree_step_t* io, void* stream) {
+  if (tree_ok(t, "lm_tree_step")) return 1;
+  return emoasr_lm_tree_step_rows(dtype, nl, layers, t, io, t->S * t->W, stream);
 }

@@ -3,7 +3,9 @@
 The reference decodes the test set once per (lm_weight, len_weight) cell, 11 x 6 = 66 full decodes in 66 host processes.  Encoder,
 head, soft-max and top-k do not depend on the cell, and the searches of all cells of a batch are independent: here every batch is
 encoded once and all cells are searched in one call of ctc_prefix_beam_search_batch_lm (csrc/ctc_beam_lm.hip), each cell scored with
-metrics.compute_wers on the device.
+metrics.compute_wers on the device.  With a Transformer LM the tool sets decoder.ctc_tlm_fusion = "device" (set_ctc_tlm_fusion): the LM is
+stepped over a prefix tree on the device (where that form cannot take the LM the reason is logged and the
+per-frame lm.predict runs).
 
     results, best = ctc_fusion_grid(model, dataloader, vocab, beam_width, lm, lm_weights, len_weights, device)
     python -m emoasr_amd.fusion_grid -conf asr.yaml -ep 40 --data test.tsv --beam_width 10 --lm_conf lm.yaml --lm_ep 20
@@ -202,6 +204,22 @@ def set_rnnt_tlm_fusion(decoder, beam_width, lm):
     return impl
 
 
+def set_ctc_tlm_fusion(decoder, lm):
+    """a CTC model with a Transformer LM: decoder.ctc_tlm_fusion = "device", the LM is stepped on the device over a prefix tree
+     -- unless functions.ctc_tlm_why_not gives a reason: that reason is logged and the switch stays "host"
+    (one lm.predict over the new prefixes per frame).  -> the value set"""
+    from .modeling.functions import ctc_tlm_why_not
+    impl = "host"
+    if getattr(lm, "lm_type", None) == "transformer":
+        why = ctc_tlm_why_not(decoder, lm)
+        if why is None:
+            impl = "device"
+        else:
+            logging.info(f"ctc_tlm_fusion stays 'host' (one lm.predict over the new prefixes per frame): {why}")
+    decoder.ctc_tlm_fusion = impl
+    return impl
+
+
 def set_las_lm_fusion(decoder, beam_width, lm):
     """a LAS model: decoder.las_lm_fusion = "fuse"; where functions.las_rnnlm_why_not gives a reason the grid runs one host search
     per utterance and lm_weight, and that reason is logged.  -> the reason or None"""
@@ -277,6 +295,8 @@ def main(args):
     lm.load_state_dict(torch.load(model_path(args.lm_conf, args.lm_ep), map_location="cpu"))
     lm.to(device).eval()
     beam_width = args.beam_width or params.beam_width
+    if kind == "ctc":
+        set_ctc_tlm_fusion(model.decoder, lm)
     if kind == "transformer":
         set_joint_rnnlm_impl(model.decoder, beam_width, lm, args.decode_ctc_weight)
     if kind == "las":

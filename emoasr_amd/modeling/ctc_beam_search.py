@@ -32,7 +32,8 @@ emoasr_ctc_beam_batch; beam_width <= 32), with the same hypotheses in the same o
 With an LM, ctc_prefix_beam_search_batch_lm runs the searches of a whole batch -- and of all (lm_weight, len_weight) cells of a
 fusion grid over that batch -- frame by frame on the device (csrc/ctc_beam_lm.hip: one launch moves every search one frame and lists
 the prefixes that are new; one batched LM call scores them into a pool of rows the next launch reads).  Nothing but the record
-count (and, for a stateless LM, the records) comes to the host per frame.
+count (and, for a stateless LM, the records) comes to the host per frame.  decoder.ctc_tlm_fusion = "device" steps the Transformer LM
+over a prefix tree instead (_TreePass; csrc/lm_tree.hip): the records stay on the device and no prefix is re-run.
 """
 import math
 import os
@@ -292,11 +293,11 @@ def _check_width(beam_width):
         raise ValueError(f"device CTC beam search: beam width {beam_width} is outside 1..{ops.CTC_BEAM_MAX_WIDTH}")
 
 
-def _chunks(dec, eouts, elens, k, admits=lambda n: True):
+def _chunks(dec, eouts, elens, k, admits=lambda n, longest: True):
     """the acoustic side of the device searches, chunk by chunk -> (b0, b1, row_off, logits, logp, top) per chunk of utterances
     b0 .. b1: row_off the host list of their row offsets, logits [rows, V] of the head over their valid frames only (the rows of
     all of them stacked), logp its log-soft-max, top int32 [rows, k] its top-k: one launch each.  The next utterance joins the
-    chunk while the chunk's rows x V stay within CTC_BEAM_BATCH_BUDGET and admits(utterances the chunk would then hold); an
+    chunk while the chunk's rows x V stay within CTC_BEAM_BATCH_BUDGET and admits(utterances the chunk would then hold, its longest); an
     utterance that breaks either bound on its own goes alone."""
     eng = _engine_of(dec)
     V = dec.vocab_size
@@ -305,9 +306,10 @@ def _chunks(dec, eouts, elens, k, admits=lambda n: True):
     assert len(lens) == B
     b0 = 0
     while b0 < B:
-        b1, rows = b0 + 1, lens[b0]
-        while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET and admits(b1 + 1 - b0):
+        b1, rows, longest = b0 + 1, lens[b0], lens[b0]
+        while b1 < B and (rows + lens[b1]) * V <= CTC_BEAM_BATCH_BUDGET and admits(b1 + 1 - b0, max(longest, lens[b1])):
             rows += lens[b1]
+            longest = max(longest, lens[b1])
             b1 += 1
         row_off = [0]
         for n in lens[b0:b1]:
@@ -417,10 +419,59 @@ class _StatelessPass:
         self.logp.index_copy_(0, st.rec[5, :n].long(), rows[:, : self.logp.shape[1]].float())
 
 
-def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weights):
+tree_stats = None              # of the last chunk searched over the prefix tree: nodes taken per search, the capacities, the longest list
+_TLM_POOL_BUDGET = 8 << 30     # bytes of K / V node pools and lists one chunk of tree-fused searches may hold (as engine/rnnt_search.py)
+
+
+def _tree_bytes(lm, W, max_frames):
+    """bytes of one search's share of the tree: its K / V nodes over all layers and the lists of its 2 W + 2 slots"""
+    from .. import lm_tree
+    P = lm.params
+    esz = 2 if lm.compute_dtype == torch.bfloat16 else 4
+    return (2 * P.num_layers * lm_tree.ctc_node_cap(W, max_frames) * P.hidden_size * esz
+            + ops.ctc_beam_lm_slots(W) * (lm_tree.ctc_list_cap(max_frames, P.max_seq_len) + 1) * 4)
+
+
+class _TreePass:
+    """LM pass of the Transformer LM under decoder.ctc_tlm_fusion = "device" (DESIGN.md section 32): the pool rows are the slots of a
+    prefix tree (lm_tree.TreeState), a record is one new node.  Per call emoasr_lm_tree_advance_rec reads the record list where the
+    frame kernel left it, emoasr_lm_tree_step_rows steps the n new prefixes by ONE token against their parents' keys / values, and
+    emoasr_log_softmax_rows_to puts the normalised rows into the pool.  No host work beyond the count the caller read, no record
+    comes to the host, no prefix is re-run.  A search with lm_weight <= 0 takes no node (its rows are never read)."""
+
+    def __init__(self, lm, S, W, slots, V, max_frames, lm_weight, device):
+        from .. import lm_tree
+        lm._prepare()
+        P = lm.params
+        self.V, self.lm_weight, self.split = V, lm_weight, lm._split()
+        self.tree = lm_tree.TreeState(S, W, S * slots, lm_tree.ctc_list_cap(max_frames, P.max_seq_len),
+                                      lm_tree.ctc_node_cap(W, max_frames), device, rows=max(S * W, 1))
+        self.tree.reset()
+        with ops.stream_scope(self.split):
+            self.step = lm_tree.TreeStep(lm, self.tree)
+        self.logp = torch.zeros(S * slots, V, device=device, dtype=torch.float32)
+
+    def __call__(self, st, n):
+        n = min(n, self.tree.rows)
+        if not n:
+            return
+        with ops.stream_scope(self.split):
+            self.tree.advance_records(st.rec, st.rec_count, self.lm_weight)
+            logits = self.step(n)
+            ops.log_softmax_rows_to(logits, n, st.rec[5], self.logp, self.V, row_ok=self.tree.row_node)
+
+    def finish(self, names):
+        global tree_stats
+        tree_stats = {"nodes": self.tree.nnodes.tolist(), "node_cap": self.tree.node_cap, "lcap": self.tree.Lcap,
+                      "longest_prefix": int(self.tree.llen.max())}
+        self.tree.raise_for_status("ctc_prefix_beam_search_batch_lm (ctc_tlm_fusion = 'device')", names, tags=True)
+
+
+def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weights, tree=False, first=0):
     """the frame loop over csrc/ctc_beam_lm.hip for the utterances of row_off x the weight pairs -> (hyps, scores), each
     [utterance][pair].  init, an LM pass over the root records, then per frame one launch, one small download (the record count;
-    the stateless pass also takes the records) and one LM pass; finish and ONE download of the results."""
+    the stateless pass also takes the records) and one LM pass; finish and ONE download of the results.  tree: the Transformer LM
+    over the prefix tree (_TreePass; a limit it met is a RuntimeError naming the search, `first` the chunk's first utterance)."""
     dev = logp.device
     B, C, W = len(row_off_host) - 1, len(weights), beam_width
     S, V = B * C, logp.shape[1]
@@ -430,12 +481,17 @@ def _search_device_lm(logp, top, row_off_host, beam_width, blank, eos, lm, weigh
     wt = torch.tensor([[float(a) for a, _ in weights] * B, [float(b) for _, b in weights] * B], dtype=torch.float64).to(dev)
     st = ops.ctc_beam_lm_init(row_off, utt, W, eos, max_frames)
     rows = S * st.slots
-    lm_pass = _StatefulPass(lm, rows, V) if getattr(lm, "stateful", False) else _StatelessPass(lm, rows, V, dev)
+    if tree:
+        lm_pass = _TreePass(lm, S, W, st.slots, V, max_frames, wt[0], dev)
+    else:
+        lm_pass = _StatefulPass(lm, rows, V) if getattr(lm, "stateful", False) else _StatelessPass(lm, rows, V, dev)
     lm_pass(st, int(st.rec_count.item()))
     for t in range(max_frames):
         ops.ctc_beam_lm_frame(st, t, logp, top, wt[0], wt[1], blank, lm_pass.logp)
         lm_pass(st, int(st.rec_count.item()))
     hyps, scores = _download(*ops.ctc_beam_lm_finish(st), st.status, "emoasr_ctc_beam_lm refused a search")
+    if tree:
+        lm_pass.finish([f"search {s} (utterance {first + s // C}, weights {weights[s % C]})" for s in range(S)])
     return [hyps[b * C:(b + 1) * C] for b in range(B)], [scores[b * C:(b + 1) * C] for b in range(B)]
 
 
@@ -450,7 +506,12 @@ def ctc_prefix_beam_search_batch_lm(dec, eouts, elens, beam_width, lm, weights):
     frames, one log-soft-max, one top-k.  Utterances are taken in chunks: the next utterance joins the chunk while (a) the chunk's
     rows x V stay within CTC_BEAM_BATCH_BUDGET = 2^27 elements (512 MiB of f32 log-probabilities) and (b) its searches' LM pool,
     utterances x pairs x (2 beam_width + 2) rows x V, stays within CTC_BEAM_LM_POOL_BUDGET = 2^30 elements (4 GiB); an utterance
-    that breaks either bound on its own goes alone."""
+    that breaks either bound on its own goes alone.
+
+    decoder.ctc_tlm_fusion = "device" with a causal Transformer LM (functions.ctc_tlm_why_not passes it; otherwise a ValueError
+    carrying the reason): the LM is stepped over a prefix tree on the device (_TreePass), and (c) the searches' node pools and
+    lists, sized for the chunk's longest utterance, stay within _TLM_POOL_BUDGET = 8 GiB.  An RNN LM ignores the switch."""
+    from .functions import ctc_tlm_fusion_of, ctc_tlm_why_not
     require_next_token_lm(lm, max([float(a) for a, _ in weights] + [0.0]))
     if lm is None:
         raise ValueError("ctc_prefix_beam_search_batch_lm needs an LM (without one: ctc_prefix_beam_search_batch)")
@@ -459,5 +520,20 @@ def ctc_prefix_beam_search_batch_lm(dec, eouts, elens, beam_width, lm, weights):
     assert weights, "at least one (lm_weight, len_weight) pair"
     blank, eos, V = dec.blank_id, dec.eos_id, dec.vocab_size
     per_utt = len(weights) * ops.ctc_beam_lm_slots(beam_width) * V          # pool elements one utterance's searches need
-    return _search_chunks(_chunks(dec, eouts, elens, min(beam_width, V), lambda n: n * per_utt <= CTC_BEAM_LM_POOL_BUDGET),
-                          lambda logp, top, row_off: _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights))
+    tree = ctc_tlm_fusion_of(dec) == "device" and getattr(lm, "lm_type", None) == "transformer" and any(a > 0 for a, _ in weights)
+    if not tree:
+        return _search_chunks(_chunks(dec, eouts, elens, min(beam_width, V), lambda n, longest: n * per_utt <= CTC_BEAM_LM_POOL_BUDGET),
+                              lambda logp, top, row_off: _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights))
+    why = ctc_tlm_why_not(dec, lm)
+    if why is not None:
+        raise ValueError(f"emoasr_amd: ctc_tlm_fusion = 'device' cannot fuse this LM: {why}")
+    admits = lambda n, longest: (n * per_utt <= CTC_BEAM_LM_POOL_BUDGET
+                                 and n * len(weights) * _tree_bytes(lm, beam_width, longest) <= _TLM_POOL_BUDGET)
+    first = [0]
+
+    def search(logp, top, row_off):
+        out = _search_device_lm(logp, top, row_off, beam_width, blank, eos, lm, weights, tree=True, first=first[0])
+        first[0] += len(row_off) - 1
+        return out
+
+    return _search_chunks(_chunks(dec, eouts, elens, min(beam_width, V), admits), search)

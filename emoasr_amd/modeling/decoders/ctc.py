@@ -6,7 +6,8 @@
     (beam_width <= 1: greedy; > 1: CTC prefix beam search with optional LM fusion, ctc.py:203-344)
     beam_width > 1 without an LM on a batch of several utterances: the batched device search (csrc/ctc_beam.hip) -> hyps, scores
     and logits are lists with one entry per utterance.  decoder.ctc_beam_impl = "device" sends a single utterance there too, and
-    sends every search WITH an LM (lm_weight > 0, any number of utterances) to the batched fused search (csrc/ctc_beam_lm.hip).
+    sends every search WITH an LM (lm_weight > 0, any number of utterances) to the batched fused search (csrc/ctc_beam_lm.hip);
+    there decoder.ctc_tlm_fusion = "device" steps a Transformer LM over a prefix tree on the device (csrc/lm_tree.hip).
 
 With every auxiliary weight at 0 (the L-series configs) the head GEMM, CTC lattice and gradient run as one
 fused autograd node.  Knowledge distillation (kd_weight, ctc.py:117-127), the phone-level CTC
@@ -59,6 +60,10 @@ class CTCDecoder(nn.Module):
         # "host": one utterance (with or without an LM) through csrc/ctc_beam_host.hip, an LM with several utterances is refused;
         # "device": one utterance without an LM through csrc/ctc_beam.hip too, any search with an LM through csrc/ctc_beam_lm.hip
         self.ctc_beam_impl = "host"
+        # "host": the fused device search scores a Transformer LM's new prefixes with one lm.predict per frame; "device": it steps the
+        # LM over a prefix tree on the device.  Only under ctc_beam_impl = "device" with lm_weight > 0 and a
+        # causal Transformer LM; an LM that form cannot take is a ValueError carrying functions.ctc_tlm_why_not's reason
+        self.ctc_tlm_fusion = "host"
         self._prefix = prefix  # parameter-name prefix of this module inside the owning ASR model
         self._owner = None
 
@@ -126,6 +131,8 @@ class CTCDecoder(nn.Module):
         from ..ctc_beam_search import ctc_prefix_beam_search, ctc_prefix_beam_search_batch
         if self.ctc_beam_impl not in ("host", "device"):
             raise ValueError(f"emoasr_amd: ctc_beam_impl is 'host' or 'device', not {self.ctc_beam_impl!r}")
+        from ..functions import ctc_tlm_fusion_of
+        ctc_tlm_fusion_of(self)      # (anything but 'host' / 'device' is a ValueError, whichever path the search takes)
         no_lm = lm is None or lm_weight <= 0
         if not no_lm and self.ctc_beam_impl == "device":
             from ..ctc_beam_search import ctc_prefix_beam_search_batch_lm

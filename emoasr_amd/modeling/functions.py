@@ -741,6 +741,40 @@ def rnnt_tlm_fusion_of(dec):
     return impl
 
 
+def ctc_tlm_fusion_of(dec):
+    """the decoder's ctc_tlm_fusion: "host" (the default; the fused CTC search scores a Transformer LM's new prefixes with one
+    lm.predict per frame, as ever) or "device" (stepped on the device over the prefix tree); anything else is
+    a ValueError.  It matters only under ctc_beam_impl = "device" with lm_weight > 0 and a causal Transformer LM."""
+    impl = getattr(dec, "ctc_tlm_fusion", "host")
+    if impl not in ("host", "device"):
+        raise ValueError(f"emoasr_amd: ctc_tlm_fusion is 'host' or 'device', not {impl!r}")
+    return impl
+
+
+def ctc_tlm_why_not(dec, lm):
+    """why the fused CTC search cannot step this LM over the prefix tree (None: it can): a causal Transformer
+    LM in f32 or bf16 (its own compute dtype: the pool rows are f32 either way), its vocabulary at least the CTC head's, its heads
+    and its longest prefix inside emoasr_lm_tree_attn's plan"""
+    from .. import lm_tree, lockstep
+    why = lockstep.lm_type_why_not(lm, "transformer")
+    if why is None and not getattr(lm, "causal", False):
+        why = "there is no causal LM (the prefix tree steps p(next token | prefix))"
+    if why is None and getattr(lm, "compute_dtype", None) not in (torch.float32, torch.bfloat16):
+        why = f"the LM computes in {getattr(lm, 'compute_dtype', None)} (emoasr_lm_tree_step takes f32 or bf16)"
+    if why is not None:
+        return why
+    P = lm.params
+    if P.vocab_size < dec.vocab_size:
+        return f"the LM's vocabulary ({P.vocab_size}) is smaller than the model's ({dec.vocab_size})"
+    if not lm_tree.head_ok(P.hidden_size, P.num_attention_heads):
+        return (f"the LM's heads ({P.hidden_size} over {P.num_attention_heads}) are outside emoasr_lm_tree_attn's plan "
+                f"(8 .. 128 wide, a multiple of 8)")
+    if lm_tree.attn_lds_bytes(P.max_seq_len) > lm_tree.LDS_BYTES:
+        return (f"max_seq_len {P.max_seq_len} needs {lm_tree.attn_lds_bytes(P.max_seq_len)} bytes of LDS in emoasr_lm_tree_attn "
+                f"({lm_tree.LDS_BYTES} at most)")
+    return None
+
+
 def rnnt_beam_batch_apply(dec, eouts, elens, beam_width, lm=None, lm_weights=None, len_weights=None, require_device=False,
                           tlm_fusion="host"):
     """-> (hyps[b][n], scores[b][n]): every utterance searched over its own elens[b] frames; with lm_weights the shallow-fusion

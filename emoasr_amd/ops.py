@@ -1126,6 +1126,21 @@ def log_softmax(x, add=None, mu=0.0):
     return out
 
 
+def log_softmax_rows_to(x, n, row_dst, pool, V, row_ok=None):
+    """emoasr_log_softmax_rows_to: row r < n of the raw logits x [R, V_lm] (f32 or bf16; row stride allowed) is normalised over all
+    V_lm columns, its first V columns go to row row_dst[r] (int32 [>= n]) of the f32 pool [rows, >= V]; a row with row_ok[r] < 0
+    (int32, optional) or a destination outside the pool is dropped.  Bit-equal to log_softmax(x)[r, :V]."""
+    R, V_lm, ld = _rows(_chk(x))
+    n, V = int(n), int(V)
+    assert 0 <= n <= R and 1 <= V <= V_lm and _chk(pool, torch.float32).dim() == 2 and pool.stride(1) == 1 and pool.shape[1] >= V
+    assert _chk(row_dst, torch.int32).dim() == 1 and row_dst.is_contiguous() and row_dst.numel() >= n
+    assert row_ok is None or (_chk(row_ok, torch.int32).is_contiguous() and row_ok.numel() >= n)
+    if n:
+        lib.call("emoasr_log_softmax_rows_to", dt(x), n, V_lm, V, _p(x), ld, _p(row_dst), _p(row_ok), _p(pool),
+                 pool.stride(0) if pool.shape[0] > 1 else pool.shape[1], pool.shape[0], _stream())
+    return pool
+
+
 def topk(x, k, aux=None):
     """x f32 [M,V] -> (vals [M,k], idx int32 [M,k], aux gathered [M,k] | None)"""
     M, V, ld = _rows(_chk(x, torch.float32))

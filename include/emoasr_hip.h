@@ -1200,6 +1200,32 @@ int emoasr_lm_tree_attn(int dtype, const emoasr_lm_tree_t* t, int d, int H, cons
 size_t emoasr_lm_tree_step_ws_bytes(int dtype, int R, int d, int F);
 int emoasr_lm_tree_step(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
                         const emoasr_lm_tree_step_t* io, void* stream);
+/* The same tree under the fused CTC search (csrc/ctc_beam_lm.hip; decoder.ctc_tlm_fusion = "device"): the tree's slots are the rows of
+ * the LM pool (search s owns the slots s * nslots / S .. and the nodes s * node_cap ..), the rows of a step are the frame's RECORDS.
+ *   emoasr_lm_tree_advance_rec: rec int32 [6][rec_cap] (search, node id, parent id, token, src row, dst row) and rec_count int32 [1]
+ *       as emoasr_ctc_beam_lm_frame left them on the device; row_node, row_pos, lab and dst hold rec_cap entries.  Record r <
+ *       *rec_count with src < 0 starts from the empty prefix (p = 0), otherwise p = llen[src]; it takes one node of its search's share
+ *       (one atomicAdd: which record gets which node is not defined, nothing else depends on the order of the records), copies
+ *       lanc[src][:p] to lanc[dst], appends the node, sets llen[dst] = p + 1, row_node[r] = node, row_pos[r] = p and the control words
+ *       lab[r] = token, dst[r] = dst row, which emoasr_lm_tree_attn / _step read.  p >= Lcap raises EMOASR_LM_TREE_OVERLEN in
+ *       status[search], a share that is used up EMOASR_LM_TREE_POOL_FULL; such a row, a row r >= *rec_count, a record that names a
+ *       search outside 0 .. S - 1 or a slot outside that search's share, and (lm_weight f64 [S] given) a record of a search with
+ *       lm_weight <= 0 get row_node[r] = -1, lab[r] = 0, dst[r] = -1 and change nothing else.  No record's src row may be another
+ *       record's dst row in the same launch (the frame kernel frees a row one frame after its prefix left the beam).
+ *   emoasr_lm_tree_attn_rows / emoasr_lm_tree_step_rows: emoasr_lm_tree_attn / _step over the first R rows (R >= 0; the entry points
+ *       above are these with R = S W): launches and products are sized by R, rows >= R are neither read nor written.
+ *   emoasr_log_softmax_rows_to: row r < n of x [n, V_lm] (compute dtype, row stride ldx) is normalised over all V_lm columns with the
+ *       body of emoasr_log_softmax, its first V columns go to row row_dst[r] of the f32 pool out (row stride ld_lm, out_rows rows):
+ *       bit-equal to emoasr_log_softmax of the same row.  A row with row_dst outside the pool or (row_ok given) row_ok[r] < 0 is
+ *       dropped; columns >= V and every other row of the pool are not touched. */
+int emoasr_lm_tree_advance_rec(const emoasr_lm_tree_t* t, const int* rec, int rec_cap, const int* rec_count, const double* lm_weight,
+                               long long* lab, long long* dst, void* stream);
+int emoasr_lm_tree_attn_rows(int dtype, const emoasr_lm_tree_t* t, int R, int d, int H, const void* qkv, void* kpool, void* vpool,
+                             const long long* dst, void* out, void* stream);
+int emoasr_lm_tree_step_rows(int dtype, int nl, const emoasr_bert_layer_t* layers, const emoasr_lm_tree_t* t,
+                             const emoasr_lm_tree_step_t* io, int R, void* stream);
+int emoasr_log_softmax_rows_to(int dtype, int n, int V_lm, int V, const void* x, long ldx, const int* row_dst, const int* row_ok,
+                               float* out, long ld_lm, int out_rows, void* stream);
 /* times the cooperative step kernel of a chain (0 decoder, 1 LM) was enqueued or captured since the library was loaded */
 long emoasr_decode_coop_launches(int chain);
 int emoasr_beam_cache_gather(int dtype, int nl, int nb, int Lmax, int d, const void* src_k, const void* src_v, void* dst_k,
