@@ -21,6 +21,13 @@
 //   emoasr_log_softmax_rows_to    the step's raw logits, normalised over the LM's whole vocabulary by the body of emoasr_log_softmax
 //                                 (csrc/log_softmax_body.h), scattered into the f32 pool rows the next frame reads
 //
+// The batched LAS search (engine/las.py) drives it under decoder.las_tlm_fusion = "device" (DESIGN.md section 33): the search is
+// label-synchronous, a row of a step is its parent's prefix plus one token, and the slots are two halves of S W rows:
+//
+//   emoasr_lm_tree_advance_beam   advance from the lockstep book (ids, parent, state): one wave per search, nodes by ballot, the
+//                                 control words lab / dst for the step; emoasr_log_softmax_rows_to then fills the f32 rows the score
+//                                 kernel reads
+//
 // Bounds: every slot number, length, label and node id that arrives through device memory is checked or clamped before it is used as
 // an index; a row that fails a check writes nothing.
 #include <math.h>
@@ -122,6 +129,58 @@ __global__ __launch_bounds__(256) void lm_tree_advance_rec_kernel(const emoasr_l
     t.row_pos[r] = node >= 0 ? p : 0;
     lab[r] = node >= 0 ? token : 0;
     dstw[r] = node >= 0 ? dl : -1;
+  }
+}
+
+// The advance step under the LOCKSTEP BOOK of the batched LAS search (emoasr_beam_update_batch's ids / parent / state; DESIGN.md
+// section 33): one wave per search, lane w < W owns row s W + w, nodes by ballot as in lm_tree_advance_kernel.  The slots are two
+// halves of S W: row r reads slot src_base + parent' (its parent's row of the previous step) and writes slot dst_base + r.  Which
+// rows are live is csrc/las_beam.hip's rule: the search is not done, w < n_alive, a parent outside the search's rows reads row 0.
+__global__ __launch_bounds__(64) void lm_tree_advance_beam_kernel(const emoasr_lm_tree_t t, const int* __restrict__ ids,
+                                                                  const int* __restrict__ parent,
+                                                                  const emoasr_beam_state_t* __restrict__ state, int src_base,
+                                                                  int dst_base, long long* __restrict__ lab,
+                                                                  long long* __restrict__ dstw) {
+  const int s = blockIdx.x, lane = threadIdx.x, W = t.W, Lcap = t.Lcap, R = s * W;
+  const emoasr_beam_state_t st = state[s];
+  const int na = st.done ? 0 : min(max(st.n_alive, 0), W);
+  int sl = -1, dl = -1, p = -1;
+  bool live = lane < na;                            // (nothing of a skipped row is read)
+  if (live) {
+    const int pr = parent[R + lane];
+    sl = src_base + ((pr >= R && pr < R + W) ? pr : R);       // (the host checked both halves against nslots)
+    dl = dst_base + R + lane;
+    p = t.llen[sl];
+    live = p >= 0;
+  }
+  const bool over = live && p >= Lcap;              // the prefix would exceed Lcap
+  const bool want = live && !over;
+  const unsigned long long wants = __ballot(want);
+  const int rank = __popcll(wants & ((1ull << lane) - 1ull));
+  const int base = min(max(t.nnodes[s], 0), t.node_cap);
+  const bool full = want && base + rank >= t.node_cap;
+  const bool ok = want && !full;
+  const int node = ok ? s * t.node_cap + base + rank : -1;
+  const int bits = (__ballot(over) ? EMOASR_LM_TREE_OVERLEN : 0) | (__ballot(full) ? EMOASR_LM_TREE_POOL_FULL : 0);
+  const int taken = __popcll(__ballot(ok));
+  if (lane < W) {
+    t.row_node[R + lane] = node;
+    t.row_pos[R + lane] = ok ? p : 0;
+    lab[R + lane] = ok ? (long long)ids[R + lane] : 0;
+    dstw[R + lane] = ok ? (long long)dl : -1;
+  }
+  // the lists, row after row: sources lie in one half of the slots, destinations in the other, so no copy reads what another writes
+  for (int w = 0; w < W; ++w) {
+    const int nd = __shfl(node, w, 64);
+    if (nd < 0) continue;                           // (uniform over the wave)
+    const int ss = __shfl(sl, w, 64), ds = __shfl(dl, w, 64), pw = __shfl(p, w, 64);
+    const long so = (long)ss * Lcap, dn = (long)ds * Lcap;
+    for (int i = lane; i < pw; i += 64) t.lanc[dn + i] = t.lanc[so + i];
+    if (lane == 0) { t.lanc[dn + pw] = nd; t.llen[ds] = pw + 1; }
+  }
+  if (lane == 0) {
+    t.nnodes[s] = base + taken;
+    if (bits) t.status[s] |= bits;                  // (one writer per word: this wave)
   }
 }
 
@@ -286,6 +345,20 @@ extern "C" int emoasr_lm_tree_advance_rec(const emoasr_lm_tree_t* t, const int* 
   EMO_CHECK(rec && rec_count && lab && dst && rec_cap >= 1, "lm_tree_advance_rec: missing records or control words (rec_cap=%d)", rec_cap);
   EMO_CHECK(t->nslots % t->S == 0, "lm_tree_advance_rec: %d slots do not divide into %d searches' shares", t->nslots, t->S);
   lm_tree_advance_rec_kernel<<<cdiv(rec_cap, 4), 256, 0, (hipStream_t)stream>>>(*t, rec, rec_cap, rec_count, lm_weight, lab, dst);
+  EMO_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int emoasr_lm_tree_advance_beam(const emoasr_lm_tree_t* t, const int* ids, const int* parent,
+                                           const emoasr_beam_state_t* state, int src_base, int dst_base, long long* lab,
+                                           long long* dst, void* stream) {
+  if (tree_ok(t, "lm_tree_advance_beam")) return 1;
+  EMO_CHECK(ids && parent && state && lab && dst, "lm_tree_advance_beam: missing book or control words");
+  const long nb = (long)t->S * t->W;
+  EMO_CHECK(src_base >= 0 && dst_base >= 0 && src_base + nb <= t->nslots && dst_base + nb <= t->nslots &&
+            (src_base + nb <= dst_base || dst_base + nb <= src_base),
+            "lm_tree_advance_beam: halves at %d and %d of %ld rows do not lie apart inside %d slots", src_base, dst_base, nb, t->nslots);
+  lm_tree_advance_beam_kernel<<<t->S, 64, 0, (hipStream_t)stream>>>(*t, ids, parent, state, src_base, dst_base, lab, dst);
   EMO_LAUNCH_CHECK();
   return 0;
 }

@@ -6,7 +6,8 @@ residual, the cell kernel, the query projection, the attention step (csrc/las.hi
 product, the key projection, LSTM layers 1.. as whole-sequence layers (recurrence.py), intermed + tanh and the vocabulary head.
 Time-major throughout; the logits are transposed to [B, L, V] at the end.
 The beam searches fuse a next-token LM on request: the host form calls it per step, the batched device form
-steps the RNN LM inside its captured chain, and the (lm_weight, len_weight) grid searches every distinct weight once."""
+steps the RNN LM inside its captured chain, and the (lm_weight, len_weight) grid searches every distinct weight once.  A Transformer
+LM is stepped there too, over the prefix tree of csrc/lm_tree.hip, under decoder.las_tlm_fusion = "device" (section 33)."""
 import ctypes
 
 import numpy as np
@@ -32,12 +33,40 @@ def las_lm_row_bytes(lm, esz):
     return 0 if lm is None else lm.L * lm.H * (esz + 4)
 
 
-def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None, lm_row_bytes=0):
+def las_tlm_dims(lm, W, max_len):
+    """(Lcap, node_cap) of the prefix tree a fused Transformer LM steps over (section 33): lm_tree.las_list_cap / las_node_cap"""
+    from .. import lm_tree
+    return lm_tree.las_list_cap(max_len, lm.params.max_seq_len), lm_tree.las_node_cap(W, max_len)
+
+
+def las_tlm_search_bytes(lm, W, max_len, V):
+    """bytes of one search's share of a fused Transformer LM's prefix tree (lm_tree.las_search_bytes); 0 without one"""
+    if lm is None:
+        return 0
+    from .. import lm_tree
+    P = lm.params
+    Lcap, node_cap = las_tlm_dims(lm, W, max_len)
+    return lm_tree.las_search_bytes(W, Lcap, node_cap, P.num_layers, P.hidden_size, V, 2 if lm.compute_dtype == torch.bfloat16 else 4)
+
+
+def las_beam_chunk_capacity(W, Tmax, budget=None, max_rows=None, lm_row_bytes=0, tree_bytes=0):
     """S_max: the most searches of width W one chunk of las_beam_search_batch holds -- S_max * W <= LAS_BEAM_MAX_ROWS rows and
-    las_beam_pool_bytes(S_max * W, Tmax, lm_row_bytes) <= LAS_BEAM_POOL_BUDGET_BYTES; never below one search"""
+    las_beam_pool_bytes(S_max * W, Tmax, lm_row_bytes) + S_max * tree_bytes <= LAS_BEAM_POOL_BUDGET_BYTES (tree_bytes: a fused
+    Transformer LM's prefix tree per search, las_tlm_search_bytes); never below one search"""
     budget = LAS_BEAM_POOL_BUDGET_BYTES if budget is None else budget
     max_rows = LAS_BEAM_MAX_ROWS if max_rows is None else max_rows
-    return max(1, min(max_rows // W, budget // las_beam_pool_bytes(W, Tmax, lm_row_bytes)))
+    return max(1, min(max_rows // W, budget // (las_beam_pool_bytes(W, Tmax, lm_row_bytes) + tree_bytes)))
+
+
+def _is_tlm(lm):
+    return getattr(lm, "lm_type", None) == "transformer"
+
+
+def _las_lm_cost(lm, esz, W, max_len, V):
+    """las_beam_chunk_capacity's keywords for a fused LM: the RNN LM's state pools per row, a Transformer LM's tree per search"""
+    if _is_tlm(lm):
+        return dict(tree_bytes=las_tlm_search_bytes(lm, W, max_len, V))
+    return dict(lm_row_bytes=las_lm_row_bytes(lm, esz))
 
 
 LAS_BUFFER_SETS = 4    # buffer sets (each with its captured steps) the batched search keeps: (S, W, LM, grid) configurations
@@ -47,9 +76,15 @@ class _LasBeamBuffers(lockstep.BookBuffers):
     """lockstep.BookBuffers of one (S, W, max_len, frame capacities) configuration of the batched search, with the LAS search's own
     pools: the stacked frames and keys, the decoder state and attention weights of two halves, the gathered parents' rows"""
 
-    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, V=0, rnn=None, grid=False):
+    def __init__(self, dev, dt, S, W, Lmax, E, H, NL, D, AD, rows_cap, Tcap, V=0, rnn=None, grid=False, tlm=None):
         super().__init__(dev, dt, S, W, W, Lmax, V, rnn, grid)      # (rnn = (L, H, E) of a fused RNN LM; section 28)
         nb = S * W
+        self.tree = None
+        if tlm is not None:      # tlm = (Lcap, node_cap) of a fused Transformer LM's prefix tree (section 33): two halves of nb slots
+            from .. import lm_tree
+            self.tree = lm_tree.TreeState(S, W, 2 * nb, tlm[0], tlm[1], dev)
+            self.lm_logits = torch.zeros(nb, V, device=dev, dtype=torch.float32)     # the LM's log-probabilities, row for row
+            self.row_id = torch.arange(nb, device=dev, dtype=torch.int32)
         self.rows_cap, self.Tcap = rows_cap, Tcap
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         cdt = lambda *s: torch.zeros(*s, device=dev, dtype=dt)
@@ -375,7 +410,10 @@ class LASDecoder:
         its pools is the source, half 1 - k the destination) and emoasr_beam_scores_topk in place of log-softmax + top-W -- the
         head's f32 logits as `dec`, the LM's raw logits as `lm`, one weight (fuse.mu) or one per row (fuse.mu_row, the grid);
         fuse.sutt: the searches share utterances (emoasr_las_attend_cells).  Dead rows and finished searches are computed by
-        the LM and ignored."""
+        the LM and ignored.
+        fuse.tstep (section 33): a Transformer LM instead -- emoasr_lm_tree_advance_beam from the same ids / parent / state,
+        emoasr_lm_tree_step on the S W rows, emoasr_log_softmax_rows_to into the f32 rows the score kernel reads; dead rows and
+        finished searches take no node and are not computed."""
         A, E, H, NL, I = self.arena, self.l_E, self.l_H, self.l_nl, self.l_I
         nb = S * W
         src, dst = Bf.pools[k], Bf.pools[1 - k]
@@ -410,7 +448,16 @@ class LASDecoder:
             lib.call("emoasr_topk", nb, V, W, ops._p(logp), V, None, 0, ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
         else:
             V = logits.shape[1]
-            lib.call("emoasr_rnnlm_step_rows", fuse.dt_code, ctypes.byref(fuse.rows[k]), ops._p(Bf.ids), ops._p(Bf.parent), ops._stream())
+            if fuse.tstep is not None:
+                # the Transformer LM over the prefix tree (section 33): half k of the slots is the source, half 1 - k the destination;
+                # a row without a node keeps its stale (finite) f32 row, which the update never reads
+                ops.split_products(fuse.split)
+                Bf.tree.advance_beam(Bf.ids, Bf.parent, Bf.state, k * nb, (1 - k) * nb)
+                ops.log_softmax_rows_to(fuse.tstep(), nb, Bf.row_id, Bf.lm_logits, V, row_ok=Bf.tree.row_node)
+                ops.split_products(self.split)
+            else:
+                lib.call("emoasr_rnnlm_step_rows", fuse.dt_code, ctypes.byref(fuse.rows[k]), ops._p(Bf.ids), ops._p(Bf.parent),
+                         ops._stream())
             if fuse.mu_row is None:
                 lib.call("emoasr_beam_scores_topk", lib.F32, nb, V, W, ops._p(logits), V, ops._p(Bf.lm_logits), V, fuse.mu,
                          ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
@@ -419,9 +466,11 @@ class LASDecoder:
                          ops._p(fuse.mu_row), ops._p(Bf.vals), ops._p(Bf.cands), None, ops._stream())
         lib.call("emoasr_beam_update_batch", ctypes.byref(upd), ops._stream())
 
-    def _las_beam_chunk(self, eouts, elens, W, len_weight, eos, max_len, lm=None, lm_weight=0, grid=None, sort=True):
+    def _las_beam_chunk(self, eouts, elens, W, len_weight, eos, max_len, lm=None, lm_weight=0, grid=None, sort=True, first=0):
         """S = len(elens) searches in lockstep -> (hyps[s], scores[s]): each search's results sorted by score (stable; sort=False:
-        in the order the search found them).  lm with lm_weight > 0: the RNN LM fused on the device (section 28).
+        in the order the search found them).  lm with lm_weight > 0: the RNN LM fused on the device (section 28), or a Transformer
+        LM over the prefix tree (section 33; a search past the tree's limits is a RuntimeError naming it, `first` being the
+        chunk's first utterance).
         grid = (sutt, mus): the fusion grid's chunk -- the U = len(elens) utterances' frames, key projection and eouts are stored
         once, search s runs over utterance sutt[s] (consecutive per utterance) with the LM weight mus[s] > 0; lm_weight is not
         read and len_weight must be 0."""
@@ -445,13 +494,21 @@ class LASDecoder:
             total, longest = offs[-1], max(elens)
             rows_cap = (total + 1023) // 1024 * 1024
             Tcap = (longest + 63) // 64 * 64
-            rnn = lm_guard = None
+            rnn = tlm = lm_guard = None
             if use_lm:
                 LA = lm._prepare()     # (arena bound, compute-dtype weights and the summed biases current: before the capture)
+            if use_lm and _is_tlm(lm):
+                P = lm.params
+                assert P.vocab_size == V, "las_tlm_why_not decides what the prefix tree can fuse"
+                tlm = las_tlm_dims(lm, W, max_len)
+                sizes = ("tlm", P.num_layers, P.hidden_size, P.num_attention_heads, P.intermediate_size, P.vocab_size,
+                         LA.shadow.dtype) + tlm
+                lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr(), lm._pe.data_ptr())
+            elif use_lm:
                 assert lm.V == V and LA.shadow.dtype == dt, "las_rnnlm_why_not decides what the device form can fuse"
-                rnn = (lm.L, lm.H, lm.E)
+                sizes = rnn = (lm.L, lm.H, lm.E)
                 lm_guard = (LA.flat.data_ptr(), LA.shadow.data_ptr()) + tuple(b.data_ptr() for b in lm._bias)
-            key = (str(dev), dt, S, W, max_len, V, E, H, NL, D, AD) + ((rnn, grid is not None) if use_lm else ())
+            key = (str(dev), dt, S, W, max_len, V, E, H, NL, D, AD) + ((sizes, grid is not None) if use_lm else ())
             # a few sets of buffers (with their captured steps) are kept, least recently used first: a grid alternates between its
             # chunk shapes and the search without the LM, a caller between fused and unfused calls
             sets = getattr(self, "_las_buf_sets", None)
@@ -462,7 +519,7 @@ class LASDecoder:
                 Bf = None       # (drop the smaller set before the larger one is allocated)
                 while len(sets) >= LAS_BUFFER_SETS:
                     sets.pop(next(iter(sets)))
-                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, V, rnn, grid is not None)
+                Bf = _LasBeamBuffers(dev, dt, S, W, max_len, E, H, NL, D, AD, rows_cap, Tcap, V, rnn, grid is not None, tlm)
             sets[key] = Bf
             self._las_beam_bufs = (key, Bf)      # the set of the last call
             # ---- this call's inputs, into the buffers the captured steps read ----
@@ -483,7 +540,9 @@ class LASDecoder:
                 lockstep.reset_book(Bf, S, W, eos, done)
                 P = Bf.pools[0]   # step 0 reads its parents' rows here: zeros, so the general step is the first step too
                 P.xc.zero_(); P.c0.zero_(); P.hu.zero_(); P.cu.zero_(); P.aw.zero_()
-                if use_lm:   # (the warm-up's steps write both halves) step 0 reads half 0 of the LM's pools at the search's row 0
+                if tlm:      # every slot the empty prefix, no node taken, no bit raised: step 0 reads slot s W of half 0
+                    Bf.tree.reset()
+                elif use_lm:   # (the warm-up's steps write both halves) step 0 reads half 0 of the LM's pools at the search's row 0
                     Bf.lm_h[:, :nb].zero_(); Bf.lm_c[:, :nb].zero_()
 
             mu = 0.0 if (grid or not use_lm) else float(np.float32(lm_weight))     # (the grid: the weights are device data)
@@ -504,12 +563,24 @@ class LASDecoder:
                     fuse = _Stash()
                     fuse.dt_code, fuse.mu, fuse.mu_row = ops.dt(Bf.pk), mu, Bf.mu_row if grid else None
                     fuse.sutt, fuse.U = (Bf.sutt, U) if grid else (None, U)
-                    # the even step reads half 0 of the LM's pools and writes half 1, the odd step the reverse
-                    fuse.rows, fuse.tabs, fuse.ws = lockstep.rnnlm_rows_pair(lm, LA, Bf, nb, V, fuse.dt_code, even_src=0)
+                    fuse.tstep = None
+                    if tlm:      # the step's record holds the parameter addresses of this arena (lm_guard is in the key)
+                        from .. import lm_tree
+                        fuse.split = lm._split()
+                        ops.split_products(fuse.split)
+                        fuse.tstep = lm_tree.TreeStep(lm, Bf.tree)
+                        ops.split_products(self.split)
+                    else:
+                        # the even step reads half 0 of the LM's pools and writes half 1, the odd step the reverse
+                        fuse.rows, fuse.tabs, fuse.ws = lockstep.rnnlm_rows_pair(lm, LA, Bf, nb, V, fuse.dt_code, even_src=0)
                 graphs = lockstep.capture_two_steps(lambda k: self._las_batch_step(Bf, k, S, W, D, gather, ub, fuse), reset)
                 Bf.graphs = (gkey, graphs, (ub, gather, fuse))
             reset(0)
             host = lockstep.replay_until_done(Bf.graphs[1], Bf, max_len, S, self, "_las_beam_stats")   # (totals: tools/las_beam_bench.py)
+            if tlm:      # a raised bit is an error naming the search and the limit, as the host form's max_seq_len assertion is
+                names = ([f"utterance {first + u} at lm_weight {float(m):g}" for u, m in zip(sutt, mus)] if grid
+                         else [f"utterance {first + s}" for s in range(S)])
+                Bf.tree.raise_for_status("las_beam_search_batch (las_tlm_fusion = 'device')", names, tags=True)
         caller.wait_stream(bstream)
         return lockstep.batch_nbest_from_pack(host, Bf.pack_off, S, W, max_len, sort)
 
@@ -535,22 +606,24 @@ class LASDecoder:
         Tcap = (max(elens) + 63) // 64 * 64
         esz = 2 if self.dtype == torch.bfloat16 else 4
         if lm_weights is not None:
-            return self._las_beam_grid(eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz)
+            return self._las_beam_grid(eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz, V)
         if lm is None or lm_weight <= 0:
             lm, lm_weight = None, 0
-        cap = las_beam_chunk_capacity(W, Tcap, lm_row_bytes=las_lm_row_bytes(lm, esz))
+        cap = las_beam_chunk_capacity(W, Tcap, **_las_lm_cost(lm, esz, W, max_len, V))
         hyps, scores = [], []
         for b0 in range(0, B, cap):
             n = elens[b0:b0 + cap]
             if lm is None:
                 h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len)
+            elif _is_tlm(lm):
+                h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len, lm, lm_weight, first=b0)
             else:
                 h, s = self._las_beam_chunk(eouts[b0:b0 + cap, :max(n)], n, W, len_weight, eos, max_len, lm, lm_weight)
             hyps += h
             scores += s
         return hyps, scores
 
-    def _las_beam_grid(self, eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz):
+    def _las_beam_grid(self, eouts, elens, W, eos, max_len, lm, lm_weights, len_weights, Tcap, esz, V):
         """las_beam_search_batch's grid: lockstep.run_fusion_grid on the LAS chunks"""
         lm_weights, len_weights = [float(a) for a in lm_weights], [float(b) for b in len_weights]
         B = len(elens)
@@ -566,11 +639,12 @@ class LASDecoder:
             return hyps, scores
 
         def search_fused(positive, weights, found):
-            cap = las_beam_chunk_capacity(W, Tcap, lm_row_bytes=las_lm_row_bytes(lm, esz))
+            cap = las_beam_chunk_capacity(W, Tcap, **_las_lm_cost(lm, esz, W, max_len, V))
             for utts, n, sutt, k_local in lockstep.grid_chunks(B, len(positive), cap, elens):
                 ks = [positive[j] for j in k_local]
                 sub = eouts[utts[0]:utts[-1] + 1, :max(n)]      # (a chunk's utterances are consecutive)
-                h, s = self._las_beam_chunk(sub, n, W, 0, eos, max_len, lm, 0, grid=(sutt, [weights[k] for k in ks]), sort=False)
+                more = dict(first=utts[0]) if _is_tlm(lm) else {}
+                h, s = self._las_beam_chunk(sub, n, W, 0, eos, max_len, lm, 0, grid=(sutt, [weights[k] for k in ks]), sort=False, **more)
                 for i, (u, k) in enumerate(zip(sutt, ks)):
                     found[utts[u]][k] = (h[i], s[i])
 

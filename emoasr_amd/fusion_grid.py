@@ -22,7 +22,9 @@ Transformer LM the tool sets decoder.rnnt_tlm_fusion = "device" and the LM is st
 that form cannot take the LM the reason is logged and the host form runs).  LAS models
 (decoder_type == "las") go through las_fusion_grid: the reference's LAS search ignores the LM, the tool sets decoder.las_lm_fusion =
 "fuse" and the RNN LM is stepped inside the batched LAS search, one search per distinct lm_weight over frames stored once per
-utterance (section 28).  main dispatches "las" itself; grid_of keeps refusing it.
+utterance (section 28); with a Transformer LM it also sets decoder.las_tlm_fusion = "device" and the LM is stepped there over a prefix
+tree (section 33; where that form cannot take the LM the reason is logged and the host form runs).  main dispatches "las" itself;
+grid_of keeps refusing it.
 """
 import argparse
 import logging
@@ -223,8 +225,16 @@ def set_ctc_tlm_fusion(decoder, lm):
 def set_las_lm_fusion(decoder, beam_width, lm):
     """a LAS model: decoder.las_lm_fusion = "fuse"; where functions.las_rnnlm_why_not gives a reason the grid runs one host search
     per utterance and lm_weight, and that reason is logged.  -> the reason or None"""
-    from .modeling.functions import las_rnnlm_why_not
+    from .modeling.functions import las_rnnlm_why_not, las_tlm_why_not
     decoder.las_lm_fusion = "fuse"
+    if getattr(lm, "lm_type", None) == "transformer":
+        # a Transformer LM: decoder.las_tlm_fusion = "device", the LM is stepped inside the batched search over the prefix tree
+        # (DESIGN.md section 33) -- unless las_tlm_why_not gives a reason: it is logged and the switch stays "host"
+        why = las_tlm_why_not(decoder, beam_width, lm)
+        decoder.las_tlm_fusion = "device" if why is None else "host"
+        if why is None:
+            return None
+        logging.info(f"las_tlm_fusion stays 'host': {why}")
     why = las_rnnlm_why_not(decoder, beam_width, lm)
     if why is not None:
         logging.info(f"LAS fusion grid: the host form per utterance and lm_weight: {why}")

@@ -371,6 +371,7 @@ SIGNATURES = {
     "emoasr_lm_tree_attn_rows": [I, POINTER(LmTree), I, I, I, P, P, P, P, P, P],
     "emoasr_lm_tree_step_rows": [I, I, POINTER(BertLayer), POINTER(LmTree), POINTER(LmTreeStep), I, P],
     "emoasr_log_softmax_rows_to": [I, I, I, I, P, L, P, P, P, L, I, P],
+    "emoasr_lm_tree_advance_beam": [POINTER(LmTree), P, P, P, I, I, P, P, P],
     "emoasr_rnnlm_step": [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, P, L, P],
     "emoasr_rnnlm_step_rows": [I, POINTER(RnnlmRows), P, P, P],
     "emoasr_las_attend_fwd": [I, POINTER(LasAttend), P],

@@ -44,6 +44,22 @@ def ctc_node_cap(W, max_frames):
     return int(W) * int(max_frames) + 1
 
 
+def las_list_cap(max_len, max_seq_len):
+    """Lcap of the fused LAS search (section 33): one token per step (<eos> first), never more than the LM's positions"""
+    return max(1, min(int(max_len), int(max_seq_len)))
+
+
+def las_node_cap(W, max_len):
+    """nodes per LAS search, worst case: W live rows on every step, + 1 so that the capacity is never zero"""
+    return int(W) * int(max_len) + 1
+
+
+def las_search_bytes(W, Lcap, node_cap, layers, d, V, esz):
+    """bytes of one LAS search's share of the tree: its node_cap nodes in both pools (K and V) of every layer, the lists and
+    lengths of its 2 W slots, the step's logits (LM dtype) and the f32 rows the score kernel reads"""
+    return 2 * layers * int(node_cap) * d * esz + 2 * int(W) * (int(Lcap) + 1) * 4 + int(W) * V * (esz + 4)
+
+
 def _ptr(x):
     return ops._p(x) if torch.is_tensor(x) else x
 
@@ -97,6 +113,18 @@ class TreeState:
         ctl = self.control_words()
         lib.call("emoasr_lm_tree_advance_rec", ctypes.byref(self.c), ops._p(rec), self.rows, ops._p(rec_count), ops._p(lm_weight),
                  ops._p(ctl[0]), ops._p(ctl[1]), ops._stream())
+
+    def advance_beam(self, ids, parent, state, src_base, dst_base):
+        """emoasr_lm_tree_advance_beam under the lockstep book of the batched LAS search (section 33): ids / parent int32 [S W],
+        state int32 [S, 4]; row r reads slot src_base + its parent's row and writes slot dst_base + r.  The control words are
+        the tree's own (control_words)."""
+        nb = self.S * self.W
+        for x in (ids, parent):
+            assert ops._chk(x, torch.int32).numel() == nb and x.is_contiguous(), (tuple(x.shape), nb)
+        assert tuple(ops._chk(state, torch.int32).shape) == (self.S, 4) and state.is_contiguous()
+        ctl = self.control_words()
+        lib.call("emoasr_lm_tree_advance_beam", ctypes.byref(self.c), ops._p(ids), ops._p(parent), ops._p(state), int(src_base),
+                 int(dst_base), ops._p(ctl[0]), ops._p(ctl[1]), ops._stream())
 
     def attn(self, qkv, kpool, vpool, dst, H, out=None, n=None):
         """emoasr_lm_tree_attn on ONE layer's pools [nodes, d]: qkv [S W, 3 d] -> out [S W, d] (rows without a node are not written);

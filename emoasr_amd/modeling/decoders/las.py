@@ -25,6 +25,12 @@ log_softmax(LM logits)[v] for v < V, its top beam_width are the expansions, the 
 step 0) and its state follows the parent; a finished hypothesis gains len_weight * len(hyp) as before.  Routes under "fuse":
     several utterances, or one under las_beam_impl == "batch"   the device form: the RNN LM stepped inside the captured chain
     one utterance under "single"                                the host form: any next-token LM, the Transformer LM included
+    a Transformer LM under las_tlm_fusion = "device"            the device form over the prefix tree of csrc/lm_tree.hip (DESIGN.md
+        (default "host": the row below)                         section 33), for several utterances and for one under "batch"; an
+                                                                LM the tree cannot take (functions.las_tlm_why_not: not causal,
+                                                                not f32 / bf16, lm V != V, heads or prefix length outside
+                                                                emoasr_lm_tree_attn's plan, beam_width > 32 or > V) is a
+                                                                ValueError with the reason, before any search
     an LM the device form cannot take (functions.las_rnnlm_why_not: not lm_type "rnn", lm.V != V, another compute dtype or product
         mode, sizes outside emoasr_rnnlm_step_rows' plan), beam_width > 32 or > V
                                                                 one host-form search per utterance, the reason logged once,
@@ -101,6 +107,7 @@ class LASDecoder(nn.Module):
         self.max_decode_ylen = params.max_decode_ylen
         self.las_beam_impl = "single"   # "batch": one utterance goes through the batched device search too
         self.las_lm_fusion = "ignore"   # "fuse": decode() fuses its lm / lm_weight arguments (the reference's branch is `pass`)
+        self.las_tlm_fusion = "host"    # "device": under "fuse", a Transformer LM is stepped inside the batched search (section 33)
         self._owner = None
 
     def forward(self, eouts, elens, eouts_inter=None, ys=None, ylens=None, ys_in=None, ys_out=None, soft_labels=None,

@@ -437,15 +437,69 @@ def las_rnnlm_why_not(dec, beam_width, lm):
     return None
 
 
+def las_tlm_fusion_of(dec):
+    """the decoder's las_tlm_fusion: "host" (the default; a Transformer LM is fused by one host search per utterance, as ever) or
+    "device" (stepped inside the batched search over the prefix tree); anything else is a ValueError.  It
+    matters only under las_lm_fusion = "fuse" with lm_weight > 0 and a Transformer LM."""
+    impl = getattr(dec, "las_tlm_fusion", "host")
+    if impl not in ("host", "device"):
+        raise ValueError(f"emoasr_amd: las_tlm_fusion is 'host' or 'device', not {impl!r}")
+    return impl
+
+
+def las_tlm_why_not(dec, beam_width, lm):
+    """why the batched LAS search cannot step this LM over the prefix tree (None: it can): ctc_tlm_why_not's
+    reasons -- a causal Transformer LM in f32 or bf16 (its own compute dtype: the score kernel reads f32 rows either way), its heads
+    inside emoasr_lm_tree_attn's plan -- with the LDS bound taken on the search's own longest prefix Lcap = min(max_decode_ylen,
+    max_seq_len) and the LM's vocabulary EQUAL to the model's (emoasr_beam_scores_topk soft-maxes the first V columns, the rule
+    of the RNN form), then the beam width"""
+    from .. import lm_tree
+    why = lockstep.lm_type_why_not(lm, "transformer")
+    if why is None and not getattr(lm, "causal", False):
+        why = "there is no causal LM (the prefix tree steps p(next token | prefix))"
+    if why is None and getattr(lm, "compute_dtype", None) not in (torch.float32, torch.bfloat16):
+        why = f"the LM computes in {getattr(lm, 'compute_dtype', None)} (emoasr_lm_tree_step takes f32 or bf16)"
+    if why is not None:
+        return why
+    P, V = lm.params, dec.vocab_size
+    if P.vocab_size != V:
+        return f"the LM's vocabulary ({P.vocab_size}) is not the model's ({V})"
+    if not lm_tree.head_ok(P.hidden_size, P.num_attention_heads):
+        return (f"the LM's heads ({P.hidden_size} over {P.num_attention_heads}) are outside emoasr_lm_tree_attn's plan "
+                f"(8 .. 128 wide, a multiple of 8)")
+    Lcap = lm_tree.las_list_cap(dec.max_decode_ylen, P.max_seq_len)
+    if lm_tree.attn_lds_bytes(Lcap) > lm_tree.LDS_BYTES:
+        return (f"prefixes of {Lcap} tokens need {lm_tree.attn_lds_bytes(Lcap)} bytes of LDS in emoasr_lm_tree_attn "
+                f"({lm_tree.LDS_BYTES} at most)")
+    if not 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, V):
+        return f"beam_width {beam_width} (vocabulary {V}) is outside the device bookkeeping's {LAS_BATCH_MAX_BEAM} beams"
+    return None
+
+
+def _las_tlm_on_device(dec, lm):
+    """a Transformer LM under las_tlm_fusion = "device": the prefix tree's route (the switch is not read for another LM)"""
+    return getattr(lm, "lm_type", None) == "transformer" and las_tlm_fusion_of(dec) == "device"
+
+
+def _las_tlm_require(dec, beam_width, lm):
+    why = las_tlm_why_not(dec, beam_width, lm)
+    if why is not None:
+        raise ValueError(f"emoasr_amd: las_tlm_fusion = 'device' cannot fuse this LM: {why}")
+
+
 def las_fusion_route(dec, beam_width, lm, lm_weight):
     """-> (lm, lm_weight, why): what LASDecoder.decode's search fuses.  (None, 0, None) under las_lm_fusion == "ignore", without an
     LM or with lm_weight <= 0: today's search.  Under "fuse" a masked LM is refused (require_next_token_lm's messages); why is
     None where the batched device form takes the LM, else las_rnnlm_why_not's reason -- logged once -- and the caller runs the
-    host form per utterance."""
+    host form per utterance.  A Transformer LM under las_tlm_fusion = "device" goes to the prefix tree: why is None, and an LM
+    the tree cannot take (las_tlm_why_not) is a ValueError here, before any search."""
     if las_lm_fusion(dec) != "fuse" or lm is None or lm_weight <= 0:
         return None, 0, None
     from .lm import require_next_token_lm
     require_next_token_lm(lm, lm_weight)
+    if _las_tlm_on_device(dec, lm):
+        _las_tlm_require(dec, beam_width, lm)
+        return lm, lm_weight, None
     why = las_rnnlm_why_not(dec, beam_width, lm)
     if why is not None:
         lockstep.log_once(logging.getLogger(__name__), f"LAS beam search: the LM is fused by one host search per utterance: {why}")
@@ -464,7 +518,8 @@ def las_beam_batch_apply(dec, eouts, elens, beam_width, len_weight, batched=True
     """LASDecoder.decode's beam search for every utterance of the batch, utterance b over its own elens[b] frames
     -> (hyps[b], scores[b]).  batched: all utterances in lockstep on the device (engine/las.py:las_beam_search_batch); beams wider
     than 32 or than the vocabulary, and batched=False, run las_beam_search once per utterance.  lm with lm_weight > 0 (already
-    routed: las_fusion_route): fused on the device where las_rnnlm_why_not has no objection, else by the host form per utterance."""
+    routed: las_fusion_route): fused on the device where las_rnnlm_why_not (a Transformer LM under las_tlm_fusion = "device":
+    las_tlm_why_not) has no objection, else by the host form per utterance."""
     eng = _engine_of(dec)
     elens = _las_check_elens(eouts, elens, "LASDecoder.decode")
     B = eouts.shape[0]
@@ -472,7 +527,7 @@ def las_beam_batch_apply(dec, eouts, elens, beam_width, len_weight, batched=True
     if batched and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
         if not fuse:
             return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen)
-        if las_rnnlm_why_not(dec, beam_width, lm) is None:
+        if (las_tlm_why_not if _las_tlm_on_device(dec, lm) else las_rnnlm_why_not)(dec, beam_width, lm) is None:
             return eng.las_beam_search_batch(eouts, elens, beam_width, len_weight, dec.eos_id, dec.max_decode_ylen, lm=lm,
                                              lm_weight=lm_weight)
     hyps, scores = [], []
@@ -497,7 +552,10 @@ def las_fusion_grid_apply(dec, eouts, elens, beam_width, lm, lm_weights, len_wei
     why = None
     if top > 0:
         require_next_token_lm(lm, top)
-        why = las_rnnlm_why_not(dec, beam_width, lm)
+        if _las_tlm_on_device(dec, lm):      # the prefix tree (section 33), or a ValueError with its reason
+            _las_tlm_require(dec, beam_width, lm)
+        else:
+            why = las_rnnlm_why_not(dec, beam_width, lm)
     if why is None and 1 <= beam_width <= min(LAS_BATCH_MAX_BEAM, dec.vocab_size):
         return eng.las_beam_search_batch(eouts, elens, beam_width, 0, dec.eos_id, dec.max_decode_ylen, lm=lm if top > 0 else None,
                                          lm_weights=lm_weights, len_weights=len_weights)

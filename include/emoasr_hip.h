@@ -1429,6 +1429,17 @@ typedef struct emoasr_las_state_gather {
   emoasr_las_gather_item_t item[EMOASR_LAS_GATHER_MAX];
 } emoasr_las_state_gather_t;
 int emoasr_las_state_gather(const emoasr_las_state_gather_t* g, void* stream);
+/* The prefix tree of csrc/lm_tree.hip under this search (decoder.las_tlm_fusion = "device"), advanced from the
+ * lockstep book: ids / parent (device int32 [S W]: emoasr_beam_update_batch's n_ids / n_parent) and `state`.  One launch per step, one
+ * wave per search, no atomics.  The tree's slots are two halves of S W (nslots >= 2 S W): row r = s W + w reads slot src_base + parent'
+ * and writes slot dst_base + r, (src_base, dst_base) = (0, S W) on even steps and (S W, 0) on odd ones; the two ranges must lie apart
+ * inside the slots.  Rows are live and parents corrected by the rule above; a live row with p = llen[src] >= Lcap raises
+ * EMOASR_LM_TREE_OVERLEN in status[s], the live rows left take the nodes s * node_cap + nnodes[s] + 0, 1, ... in row order until the
+ * share is used up (then EMOASR_LM_TREE_POOL_FULL).  A row that got a node copies lanc[src][:p] to lanc[dst], appends the node, sets
+ * llen[dst] = p + 1, row_node[r] = node, row_pos[r] = p, lab[r] = ids[r], dst[r] = its slot; every other row records row_node[r] = -1,
+ * row_pos[r] = 0, lab[r] = 0, dst[r] = -1 and changes nothing else.  lab / dst: the int64 control words of emoasr_lm_tree_step. */
+int emoasr_lm_tree_advance_beam(const emoasr_lm_tree_t* t, const int* ids, const int* parent, const emoasr_beam_state_t* state,
+                                int src_base, int dst_base, long long* lab, long long* dst, void* stream);
 
 /* ---- optimizer (asr/train_asr.py:84-92, torch.optim.Adam semantics) ---------- */
 /* out[0] += sum x^2 */
